@@ -27,6 +27,7 @@ os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md "Chip-level parameters")
 FP32_MFMA_PEAK_TF = 157.3
+DUMP_MAX_BYTES = 48 << 20  # --dump-outputs: all arrays together
 
 
 def synth_batch(rng, B, N, C=4):
@@ -398,6 +399,19 @@ def _print_last(line):
     print(line, flush=True)
 
 
+def dump_outputs(out_dir, arrays, seed=0):
+    """--dump-outputs: every array, flattened, as out_dir/<name>.npy in float32.  Above DUMP_MAX_BYTES in all, each array
+    keeps the same seeded sample of flat indices (ascending), so that two runs or two builds compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    flat = {k: np.ascontiguousarray(a, np.float32).ravel() for k, a in arrays.items()}
+    keep = DUMP_MAX_BYTES // (4 * len(flat))
+    sample = 4 * sum(a.size for a in flat.values()) > DUMP_MAX_BYTES
+    for name, a in flat.items():
+        if sample and a.size > keep:
+            a = a[np.sort(np.random.default_rng(seed).choice(a.size, size=keep, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main_rl(args):
     """--workload cfg0: BASELINE configs[0] (default Sim_Config: 4 links, 16 features, batch 256, gamma 0.2, episodes of 20
     train steps), on the engine and -- as cpu_baseline, kind "port" -- on the CPU oracle behind the same agent.
@@ -543,8 +557,13 @@ def build_parser():
     ap.add_argument("--no-fast-path", "--no-edge-gather", dest="no_fast_path", action="store_true",
                     help="skip the second timed pass with the complement aggregation (the fast path for complete-minus-few "
                          "graphs) that is printed beside the headline; the headline itself runs the general edge-index gather")
-    ap.add_argument("--min-seconds", type=float, default=6.0,
-                    help="the timed region is extended to at least this long (more steps than --steps if needed)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="extend the timed region to at least this long (more steps than --steps if needed; the fast-path and "
+                         "weak passes to at most 2 s of it); 0, the default: the timed region runs exactly --steps steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed region, write what its last fit step left as DIR/<name>.npy (float32): the weights, "
+                         "the gradient and Adam's two moments (a fixed, seeded sample of each when they exceed %d MB in all)"
+                         % (DUMP_MAX_BYTES >> 20))
     ap.add_argument("--nodes", type=int, default=20)
     ap.add_argument("--feat", type=int, default=64)
     ap.add_argument("--layers", type=int, default=2)
@@ -781,6 +800,12 @@ def run_workload(args, ctx, light=False):
     ms_per_step = 1e3 * elapsed / steps
     n_counted = B_local if args.shard_of > 1 else n_global          # --shard-of: only this shard's graphs were processed
     value = n_counted * steps / elapsed
+
+    # ---- what the last timed step left, before any later pass touches the engine (the moments' gather is collective)
+    if args.dump_outputs and not light:
+        m, v, _ = trainer.gather_optimizer_state() if trainer is not None else eng.get_optimizer_state()
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"params": eng.get_flat(), "grads": eng.get_grad_flat(), "adam_m": m, "adam_v": v})
 
     # ---- the fast path beside it: the same steps with the complement aggregation (when the batch qualifies)
     fast = None
@@ -1087,6 +1112,8 @@ def summary(out, others, dropin, cpu):
 def main():
     args = build_parser().parse_args()
     if args.workload in ("cfg0", "cfg2loop"):
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: fit-step workloads only (cfg2, cfg4, cfg5)")
         return main_rl(args)
     args = resolve_workload(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:          # no launcher around us: start the ranks ourselves
@@ -1116,8 +1143,8 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     ctx = Ctx(world, rank, local, dist, force_dp)
 
-    # Order of a default run: CPU legs first, then every GPU pass, the contract's timed region (>= --min-seconds) last but
-    # for its own fast-path / weak companions -- the stretch a 5-s utilisation sampler sees is the one that is reported.
+    # Order of a default run: CPU legs first, then every GPU pass, the contract's timed region (--steps steps) last but
+    # for its own fast-path / weak companions.
     ragged = args.ragged is not None
     solo = rank == 0 and world == 1 and args.shard_of == 1
     cpu = None

@@ -338,6 +338,34 @@ def test_rccl_path_single_rank(tmp_path):
         assert r2["config"]["launch"] == name and r2["config"]["launch_probe_ms"] is None, r2["config"]
 
 
+def test_bench_runs_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --steps K` times exactly K fit steps and reports ms_per_step for them; --dump-outputs writes the weights,
+    gradient and Adam moments the last timed step left, and two runs with the same arguments write the same arrays (whichever
+    launch form --launch auto picks in each: test_graph_replay_matches_eager_bitwise)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    res = []
+    for d in ("run1", "run2"):
+        cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3", "--no-cpu-baseline",
+               "--no-dropin", "--no-other-workloads", "--no-fast-path", "--dump-outputs", str(tmp_path / d)]
+        out = subprocess.run(cmd, cwd=root, capture_output=True, text=True, timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res.append(json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1]))
+    r = res[0]
+    assert r["steps"] == r["steps_requested"] == 7 and r["ms_per_step"] > 0
+    assert abs(7 * r["ms_per_step"] - 1e3 * r["timed_seconds"]) <= 0.06      # (timed_seconds: 4 decimals)
+    n = r["config"]["n_params"]
+    arrays = {}
+    for name in ("params", "grads", "adam_m", "adam_v"):
+        a, b = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("run1", "run2"))
+        assert a.dtype == np.float32 and a.shape == (n,) and np.all(np.isfinite(a)), name
+        assert np.array_equal(a, b), name              # seeded inputs, fixed-order reductions: the same bits
+        arrays[name] = a
+    assert np.abs(arrays["grads"]).max() > 0 and np.all(arrays["adam_v"] >= 0)
+
+
 def test_ragged_large_batch_loss_is_split_reduced():
     """> 16k node rows with one Huber mean: the loss reduction is cut into ranges combined by the last workgroup.
     Checked against numpy on the engine's own q, twice (the arrival counter must re-arm itself)."""

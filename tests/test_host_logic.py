@@ -474,3 +474,23 @@ def test_bench_gpus_2_without_a_launcher_starts_two_ranks():
     assert out.stderr.count("bench.py needs a GPU") >= 1, out.stderr[-2000:]
     assert "local_rank" in out.stderr or "ChildFailedError" in out.stderr, out.stderr[-2000:]     # torch.distributed.run's report
     assert "launch with torch.distributed.run" not in out.stderr
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_to_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: arrays under the budget are written whole; above it every array keeps the same seeded sample
+    of flat indices (so two runs compare element for element) and the files stay within the budget."""
+    import bench
+    a = np.arange(1000, dtype=np.float64)
+    bench.dump_outputs(str(tmp_path / "whole"), {"a": a, "b": a.reshape(10, 100) * 2})
+    got = np.load(str(tmp_path / "whole" / "a.npy"))
+    assert got.dtype == np.float32 and np.array_equal(got, a)
+    assert np.array_equal(np.load(str(tmp_path / "whole" / "b.npy")), 2 * a)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 2400)
+    for d in ("s1", "s2"):
+        bench.dump_outputs(str(tmp_path / d), {"a": a, "b": 2 * a, "c": np.arange(50.0)})
+    sa, sb, sc = (np.load(str(tmp_path / "s1" / (n + ".npy"))) for n in "abc")
+    assert sa.size == sb.size == 200 and np.array_equal(sb, 2 * sa)        # 2400 B / (4 B x 3 arrays) each, same indices
+    assert np.all(np.diff(sa) > 0) and np.array_equal(sc, np.arange(50.0))  # ascending sample; a small array stays whole
+    assert 4 * (sa.size + sb.size + sc.size) <= 2400
+    for n in "abc":
+        assert np.array_equal(np.load(str(tmp_path / "s1" / (n + ".npy"))), np.load(str(tmp_path / "s2" / (n + ".npy"))))
