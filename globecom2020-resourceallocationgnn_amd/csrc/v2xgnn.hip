@@ -2129,6 +2129,11 @@ bool wide_adam_fusable(const v2x_model* m, const DevBatch& d) {
 
 }  // namespace
 
+// the v2x_last_error(NULL) text, for the entry points of the other translation units (v2xopt.hip)
+namespace v2x {
+void set_global_error(const char* text) { g_err = text; }
+}
+
 // ======================================================================================= C ABI
 extern "C" {
 

@@ -42,6 +42,13 @@ class Feed(C.Structure):
                 ("nbr", C.POINTER(C.c_void_p)), ("is_f64", C.POINTER(C.c_uint8)), ("adjacency", C.c_void_p)]
 
 
+class OptProblem(C.Structure):
+    """v2x_opt_problem of include/v2xgnn.h"""
+    _fields_ = [("E", C.c_int32), ("n", C.c_int32), ("rb", C.c_int32), ("pad_", C.c_int32),
+                ("v2v_ff", C.c_void_p), ("v2i_ff", C.c_void_p), ("v2i_abs", C.c_void_p), ("dest", C.c_void_p)] + \
+        [(k, C.c_double) for k in ("p_v2v", "p_v2i", "veh_gain", "bs_gain", "bs_nf", "veh_nf", "sig2", "w_v2v", "w_v2i")]
+
+
 # every symbol include/v2xgnn.h declares: (name, restype, argtypes)
 _P, _I, _L, _F = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = [
@@ -90,6 +97,9 @@ SYMBOLS = [
     ("v2x_profile_enable", C.c_int, [_P, C.c_int]),
     ("v2x_path_info", C.c_int, [_P, _P, C.c_char_p, C.c_int]),
     ("v2x_profile_read", C.c_int, [_P, C.c_char_p, C.c_int, C.POINTER(C.c_double), C.POINTER(_L), C.c_int]),
+    ("v2x_opt_workspace_bytes", _L, [C.POINTER(OptProblem)]),
+    ("v2x_opt_search", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P]),
+    ("v2x_opt_rewards", C.c_int, [C.POINTER(OptProblem), _P, _L, _L, _P, _P]),
 ]
 
 

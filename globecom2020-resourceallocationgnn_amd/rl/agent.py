@@ -24,6 +24,14 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 
 
+OPT_BACKENDS = ('host', 'device')
+
+
+def _check_opt_backend(opt_backend):
+    if opt_backend not in OPT_BACKENDS:
+        raise ValueError("opt_backend must be one of %s, got %r" % (OPT_BACKENDS, opt_backend))
+
+
 def _random_channels(n, nn, n_ch):
     """The reference draws `np.random.choice(range(0, n_ch), nn)` once per link (BS_brain.py:322-324, :1015-1017): with
     replace=True and no probabilities that IS `randint(0, n_ch, nn)`, element by element on the process-wide numpy
@@ -782,11 +790,34 @@ class Agent(object):
         best = int(np.argmax(rewards))
         return best, float(rewards[best]), res[best]
 
-    def test_run(self, num_episodes, num_test_step, opt_flag=False):
+    def _brute_force_device(self, opt):
+        """_brute_force on the GPU (rl/optimum.py): the kernel picks the index, the numpy reward of the decoded joint action
+        gives the recorded rates and the reward the `reward > 0` rule sees, as on the host path."""
+        index, _ = opt.search(self.env, self.v2v_weight, self.v2i_weight)
+        best = int(index[0])
+        res = self.dump_act(opt.decode(best, self.num_D2D, self.num_CH).reshape(self.num_D2D, 1))
+        return best, float(self.v2v_weight * np.sum(res[0]) + self.v2i_weight * np.sum(res[1])), res
+
+    def _optimum_search(self, opt_backend):
+        """-> a callable () -> (index, reward, rates) of the optimum of the CURRENT simulator state.  opt_backend 'host':
+        _brute_force over _joint_actions() (C^N <= 65536); 'device': the exhaustive search in HIP (C^N <= 2^36)."""
+        _check_opt_backend(opt_backend)
+        if opt_backend == 'host':
+            joint = self._joint_actions()
+            return lambda: self._brute_force(joint)
+        from .optimum import OptimalAllocation
+        OptimalAllocation.check_size(self.num_D2D, self.num_CH)
+        if self.num_Neighbor != 1:
+            raise ValueError("opt_backend='device' supports one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor)
+        opt = OptimalAllocation()
+        return lambda: self._brute_force_device(opt)
+
+    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host'):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
-        :1071-1078; here any N with C^N <= 65536).  Same return tuple as the reference: 15 arrays with opt_flag,
-        10 without."""
+        :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
+        rl/optimum.py).  Same return tuple as the reference: 15 arrays with opt_flag, 10 without."""
+        _check_opt_backend(opt_backend)
         n, C = self.num_D2D, self.num_CH
         self.num_Episodes, self.num_Test_Step = num_episodes, num_test_step
         w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
@@ -804,13 +835,13 @@ class Agent(object):
 
         rl, ra, opt = book(), book(), book()
         if opt_flag:
-            joint = self._joint_actions()
+            optimum = self._optimum_search(opt_backend)
         for ep in range(num_episodes):
             self.env.new_random_game(self.num_D2D)
             for st in range(num_test_step):
                 record(ra, ep, st, *self.dump_act(self.select_action_random(None)))
                 if opt_flag:
-                    best, reward, res = self._brute_force(joint)
+                    best, reward, res = optimum()
                     if reward > 0:                                                        # at least one feasible solution
                         record(opt, ep, st, *res)
                 d2d_state, adj = self.observe()
@@ -826,15 +857,16 @@ class Agent(object):
         return os.path.join(root if root is not None else os.getcwd(), name)
 
     def evaluate_training_diff_trials(self, num_episodes, num_test_step, opt_flag, fixed_epsilon, num_evaluate_trials,
-                                      model_dir=None, num_train_steps=20, load=True):
+                                      model_dir=None, num_train_steps=20, load=True, opt_backend='host'):
         """Evaluation of the TRAINING PROCESS (BS_brain.py:1164-1451): for every saved checkpoint (one per 5 training
         episodes, :1218,:1228) and every trial, an episode under a FIXED epsilon-greedy policy (:1376-1397) next to the
         random-action baseline (:1330-1338) and -- per step of the first checkpoint -- the brute-force optimum (:1282-
         1328); with opt_flag also the optimum of every step (:1340-1374).  Trial t re-seeds the Python / numpy RNGs with
         t + 1 before every episode (:1262-1265).  Same return tuples as the reference: 9 arrays with opt_flag, 5 without.
         model_dir: checkpoint folder (default: checkpoint_dir()); load=False evaluates the weights already in the brain
-        for every checkpoint (tests with a recording brain)."""
+        for every checkpoint (tests with a recording brain).  opt_backend: where the optimum is searched, as in test_run."""
         import random
+        _check_opt_backend(opt_backend)
         n, C, nn = self.num_D2D, self.num_CH, self.num_Neighbor
         self.num_Episodes = int(num_episodes // 5)
         self.num_Test_Step = num_test_step
@@ -847,7 +879,7 @@ class Agent(object):
             opt_return, opt_reward = np.zeros((n_tr, n_ep)), np.zeros((n_tr, n_ep, n_st))
             opt_v2v, opt_v2i, opt_intf = np.zeros((n_tr, n_ep, n_st, n)), np.zeros((n_tr, n_ep, n_st, C)), np.zeros((n_tr, n_ep, n_st, C))
         ret, rew = np.zeros((n_tr, n_ep)), np.zeros((n_tr, n_ep, n_st))
-        joint = self._joint_actions()
+        optimum = self._optimum_search(opt_backend)
         for trial in range(n_tr):
             for ep in range(n_ep):
                 if load:
@@ -859,7 +891,7 @@ class Agent(object):
                 self.env.new_random_game(self.num_D2D)
                 for st in range(n_st):
                     if ep == 0:                                  # ground truth once per trial (:1282)
-                        _, reward, _ = self._brute_force(joint)
+                        _, reward, _ = optimum()
                         if reward > 0:
                             ev_opt_reward[trial, st] = reward
                             ev_opt_return[trial] += reward
@@ -867,7 +899,7 @@ class Agent(object):
                     ra_reward[trial, ep, st] = w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i)
                     ra_return[trial, ep] += ra_reward[trial, ep, st]
                     if opt_flag:
-                        _, reward, (v2v, v2i, intf) = self._brute_force(joint)
+                        _, reward, (v2v, v2i, intf) = optimum()
                         if reward > 0:
                             opt_reward[trial, ep, st] = reward
                             opt_return[trial, ep] += reward

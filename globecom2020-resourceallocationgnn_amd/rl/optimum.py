@@ -1,0 +1,172 @@
+"""Optimal channel allocation of a simulator state on the GPU: the brute-force baseline of the evaluation drivers
+(BS_brain.py:1060-1100, :1286-1330, :1339-1380) as an exhaustive fp64 search in HIP (csrc/v2xopt.hip, the v2x_opt_*
+entry points of include/v2xgnn.h).
+
+Every joint action a in [0, C)^N of a state with N links (one receiver each, every link active) is scored with the reward
+of `compute_reward_with_channel_selection` -- w_v2v * sum of the V2V rates + w_v2i * sum of the V2I rates -- and the
+best one is returned as its index  idx = sum_l a_l * C^(N-1-l)  (link 0 most significant: itertools.product order);
+among exactly equal rewards the lowest index wins, like np.argmax.
+
+    opt = OptimalAllocation()
+    index, reward = opt.search(env, agent.v2v_weight, agent.v2i_weight)      # env: Environ (E = 1) or BatchedEnviron
+    actions = opt.decode(index, n, C)                                          # [E, N]
+"""
+import ctypes as C
+
+import numpy as np
+
+from ..lib import OptProblem, check, load_library
+
+MAX_SEARCH = 1 << 36                 # joint actions per state the search accepts (v2x_opt_search)
+MAX_INDEX = 1 << 62                  # ... and the reward range (v2x_opt_rewards)
+HOST_S_PER_ACTION = 57e-6            # one numpy reward of the host path (Agent._brute_force)
+DEVICE_S_PER_ACTION = 2e-10          # search kernel time per joint action at 16 links on one MI355X: the estimate in errors
+
+
+def decode(index, n, rb):
+    """index [E] (or a scalar) -> int64 actions [E, n]: digit l of the index in base rb, link 0 most significant."""
+    idx = np.atleast_1d(np.asarray(index, dtype=np.int64))
+    out = np.empty((idx.size, n), np.int64)
+    rest = idx.copy()
+    for l in range(n - 1, -1, -1):
+        out[:, l] = rest % rb
+        rest //= rb
+    return out
+
+
+def _seconds(s):
+    if s < 120:
+        return "%.3g s" % s
+    if s < 2 * 86400:
+        return "%.3g h" % (s / 3600.0)
+    return "%.3g days" % (s / 86400.0)
+
+
+def _sizes(env):
+    return (env.n_Veh if hasattr(env, 'E') else len(env.vehicles)), env.n_RB
+
+
+def problem_arrays(env):
+    """-> (v2v_ff [E,n,n,rb], v2i_ff [E,n,rb], v2i_abs [E,n], dest [E,n] int64, constants dict) of a simulator, after the
+    checks the search needs (ValueError: more than one receiver per link, an inactive link)."""
+    if hasattr(env, 'E'):                                           # BatchedEnviron (rl/batched_env.py)
+        env.finish_step()                                           # as its reward does: a pending step lands first
+        n, rb = env.n_Veh, env.n_RB
+        v2v = np.asarray(env.V2V_channels_with_fastfading, np.float64).reshape(env.E, n, n, rb)
+        v2i = np.asarray(env.V2I_channels_with_fastfading, np.float64).reshape(env.E, n, rb)
+        v2i_abs = np.asarray(env.V2I_channels_abs, np.float64).reshape(env.E, n)
+        dest = np.asarray(env.dest, np.int64).reshape(env.E, n)
+    else:
+        n, rb = len(env.vehicles), env.n_RB
+        v2v = np.asarray(env.V2V_channels_with_fastfading, np.float64).reshape(1, n, n, rb)
+        v2i = np.asarray(env.V2I_channels_with_fastfading, np.float64).reshape(1, n, rb)
+        v2i_abs = np.asarray(env.V2I_channels_abs, np.float64)[:n].reshape(1, n)
+        dest = None
+    if env.n_Neighbor != 1:
+        raise ValueError("the optimal-allocation search supports one receiver per link (n_Neighbor = 1), got %d"
+                         % env.n_Neighbor)
+    active = np.asarray(getattr(env, 'activate_links', True))
+    if not np.all(active):
+        raise ValueError("the optimal-allocation search needs every link active (activate_links has %d inactive)"
+                         % int(np.size(active) - np.count_nonzero(active)))
+    if dest is None:
+        dest = np.array([[v.destinations[0] for v in env.vehicles]], np.int64)
+    if dest.min() < 0 or dest.max() >= n:
+        raise ValueError("receiver index outside [0, %d)" % n)
+    const = dict(p_v2v=float(env.V2V_power_dB_List[env.fixed_v2v_power_index]), p_v2i=float(env.V2I_power_dB),
+                 veh_gain=float(env.vehAntGain), bs_gain=float(env.bsAntGain), bs_nf=float(env.bsNoiseFigure),
+                 veh_nf=float(env.vehNoiseFigure), sig2=float(env.sig2))
+    return v2v, v2i, v2i_abs, dest, const
+
+
+class OptimalAllocation(object):
+    """Owns the device workspace (grown on demand) and issues the search on torch's current stream of `device`.  The
+    argument checks (ValueError) come before any device work."""
+
+    def __init__(self, device=0):
+        self.device_index = int(device)
+        self.torch = None
+        self._ws = None
+        self._keep = None
+
+    def _init_device(self):
+        if self.torch is None:
+            import torch
+            if not torch.cuda.is_available():
+                raise RuntimeError("OptimalAllocation needs a GPU (there is no CPU fallback; the host path is "
+                                   "Agent._brute_force)")
+            self.torch = torch
+            self.device = torch.device('cuda', self.device_index)
+            self._lib = load_library()
+
+    @staticmethod
+    def check_size(n, rb, limit=MAX_SEARCH):
+        if not 1 <= n <= 32 or not 2 <= rb <= 16:
+            raise ValueError("the optimal-allocation search supports 1..32 links and 2..16 channels, got %d x %d" % (n, rb))
+        total = rb ** n
+        if total > limit:
+            raise ValueError("the optimal-allocation search over %d^%d = %.3g joint actions exceeds the limit of 2^%d "
+                             "(estimated %s per state on the GPU, %s on the host)"
+                             % (rb, n, float(total), limit.bit_length() - 1, _seconds(total * DEVICE_S_PER_ACTION),
+                                _seconds(total * HOST_S_PER_ACTION)))
+
+    def _setup(self, env, v2v_weight, v2i_weight, limit):
+        v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
+        E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
+        self.check_size(n, rb, limit)
+        self._init_device()
+        t = self.torch
+        dev = [t.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (v2v, v2i, v2i_abs, dest)]
+        prob = OptProblem(E=E, n=n, rb=rb, pad_=0, v2v_ff=dev[0].data_ptr(), v2i_ff=dev[1].data_ptr(),
+                          v2i_abs=dev[2].data_ptr(), dest=dev[3].data_ptr(), w_v2v=float(v2v_weight),
+                          w_v2i=float(v2i_weight), **const)
+        need = int(self._lib.v2x_opt_workspace_bytes(C.byref(prob)))
+        if need < 0:
+            check(self._lib, need)
+        if self._ws is None or self._ws.numel() < need:
+            self._ws = t.empty(max(need, 1 << 20), dtype=t.uint8, device=self.device)
+        self._keep = dev                                  # inputs stay alive until the next call (the launches are async)
+        return prob, E, n, rb
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def search_device(self, env, v2v_weight, v2i_weight):
+        """search() with the results left on the device: (index int64 [E], reward float64 [E]) torch tensors."""
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_SEARCH)
+        t = self.torch
+        index = t.empty(E, dtype=t.int64, device=self.device)
+        reward = t.empty(E, dtype=t.float64, device=self.device)
+        check(self._lib, self._lib.v2x_opt_search(C.byref(prob), self._ws.data_ptr(), index.data_ptr(), reward.data_ptr(),
+                                                  self._stream()))
+        return index, reward
+
+    def search(self, env, v2v_weight, v2i_weight):
+        """-> (index int64 [E], reward float64 [E]) host arrays: the optimum of every state of the simulator."""
+        index, reward = self.search_device(env, v2v_weight, v2i_weight)
+        return index.cpu().numpy(), reward.cpu().numpy()
+
+    def rewards_device(self, env, v2v_weight, v2i_weight, first=0, count=None):
+        """The reward of every joint action index in [first, first + count) of every state: float64 [E, count] torch
+        tensor on the device (count None: to the last index)."""
+        n, rb = _sizes(env)
+        self.check_size(n, rb, MAX_INDEX)
+        total = rb ** n
+        first = int(first)
+        count = total - first if count is None else int(count)
+        if first < 0 or count < 1 or first + count > total:
+            raise ValueError("index range [%d, %d) outside [0, %d)" % (first, first + count, total))
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX)
+        t = self.torch
+        out = t.empty((E, count), dtype=t.float64, device=self.device)
+        check(self._lib, self._lib.v2x_opt_rewards(C.byref(prob), self._ws.data_ptr(), first, count, out.data_ptr(),
+                                                   self._stream()))
+        return out
+
+    def rewards(self, env, v2v_weight, v2i_weight, first=0, count=None):
+        """rewards_device() copied to the host: float64 [E, count] (the reference's Curr_Feasible_Reward vector)."""
+        return self.rewards_device(env, v2v_weight, v2i_weight, first, count).cpu().numpy()
+
+    @staticmethod
+    def decode(index, n, rb):
+        return decode(index, n, rb)

@@ -4,7 +4,7 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device]
 """
 import argparse
 import json
@@ -33,9 +33,10 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
     return agent
 
 
-def run_test(cfg, agent):
-    """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme."""
-    out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag)
+def run_test(cfg, agent, opt_backend='host'):
+    """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme.  opt_backend: where the
+    optimum is searched ('host': numpy over every joint action; 'device': the GPU search of rl/optimum.py)."""
+    out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend)
     names = ['Expect_Return', 'Reward', 'Per_V2V_Rate', 'Per_V2I_Rate', 'Per_V2B_Interference']
     res = {}
     for prefix, chunk in zip(('', 'RA_', 'Opt_'), (out[0:5], out[5:10], out[10:15])):
@@ -56,6 +57,8 @@ def main(argv=None):
     ap.add_argument("--test-episodes", type=int, default=10)
     ap.add_argument("--test-steps", type=int, default=50)
     ap.add_argument("--opt", action="store_true", help="also run the brute-force optimum (C^N joint actions)")
+    ap.add_argument("--opt-backend", choices=("host", "device"), default="host",
+                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU (C^N <= 2^36)")
     ap.add_argument("--seed", type=int, default=11)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
@@ -70,7 +73,7 @@ def main(argv=None):
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = start_env(args.links)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed)
-    res = run_test(cfg, agent)
+    res = run_test(cfg, agent, opt_backend=args.opt_backend)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,
                "mean_reward_gnn": float(res['Reward'].mean()), "mean_reward_random": float(res['RA_Reward'].mean())}
     if args.opt:

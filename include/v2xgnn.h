@@ -269,6 +269,32 @@ void* v2x_debug_exchange_counters(v2x_model* m);
  * launch of the model): tests push one out of step on purpose.                                                                    */
 void* v2x_debug_split_counters(v2x_model* m, int32_t* n_tiles);
 
+/* ---- optimal channel allocation (csrc/v2xopt.hip) ---------------------------------------------------------------
+ * The brute-force baseline of the evaluation drivers (BS_brain.py:1060-1100, :1286-1330, :1339-1380): for each of E
+ * simulator states (one receiver per link, every link active), the joint action a[0..n) in [0, rb)^n with the largest
+ *   w_v2v * sum_l log2(1 + signal_l / I_l) + w_v2i * sum_{r < min(rb, n)} log2(1 + V2I signal_r / (BS_r + sig2))
+ * in fp64 (the rates of compute_reward_with_channel_selection, rl/environment.py).  Joint action index
+ * idx = sum_l a_l * rb^(n-1-l): link 0 most significant, the order of itertools.product(range(rb), repeat=n).  Among exact
+ * ties the lowest index wins (np.argmax).  Limits: 1 <= n <= 32, 2 <= rb <= 16, E <= 65535; the search takes
+ * rb^n <= 2^36, the reward range rb^n <= 2^62.  All pointers [dev]; the dB inputs are the simulator's own arrays.
+ * Every call is asynchronous on `stream` (no allocation, no synchronisation: capturable).  Error text: v2x_last_error(NULL). */
+typedef struct v2x_opt_problem {
+  int32_t E, n, rb, pad_;
+  const double* v2v_ff;    /* [E][n][n][rb] dB, V2V_channels_with_fastfading                                         */
+  const double* v2i_ff;    /* [E][n][rb]    dB, V2I_channels_with_fastfading                                         */
+  const double* v2i_abs;   /* [E][n]        dB, V2I_channels_abs                                                     */
+  const int64_t* dest;     /* [E][n]        receiver of link l (destinations[0]); outside [0, n): that link's rewards NaN */
+  double p_v2v, p_v2i, veh_gain, bs_gain, bs_nf, veh_nf, sig2, w_v2v, w_v2i;
+} v2x_opt_problem;
+/* bytes of the workspace both calls below need (tables of all E states + the search's partial results); < 0 on a bad
+ * problem */
+int64_t v2x_opt_workspace_bytes(const v2x_opt_problem* p);
+/* best_index[E], best_reward[E]: the optimum of every state */
+int  v2x_opt_search(const v2x_opt_problem* p, void* workspace, int64_t* best_index, double* best_reward, void* stream);
+/* out[E][count]: the reward of every index in [first, first + count) (the reference's Curr_Feasible_Reward vector); the
+ * same device arithmetic as the search, so out[best_index - first] == best_reward bit for bit */
+int  v2x_opt_rewards(const v2x_opt_problem* p, void* workspace, int64_t first, int64_t count, double* out, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */
