@@ -1233,7 +1233,8 @@ bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x) {
   return mlp_wg_split(x.n_idx, x.grid_y).tiles_per_wg <= max_tiles;
 }
 
-// all GNN stages (needs dpre[0..L]) in ceil((L+1)/4) launches
+// all GNN stages (needs dpre[0..L]): one launch when the embed rides on the stage roles (embed_rides), else
+// ceil((L+1)/WG_MAX_ROLES) launches of at most WG_MAX_ROLES stage roles -- one up to L = 7, two at L = 8
 int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch& d) {
   if (is_wide(m)) {
     if (m->wide_merge_now) m->wide_roles = &m->wide_roles_buf;          // collect: L + 1 graph layers (+ Dense-0), one grid

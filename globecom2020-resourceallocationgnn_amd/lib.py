@@ -16,6 +16,10 @@ class V2XError(RuntimeError):
     pass
 
 
+class V2XInvalidArgument(V2XError, ValueError):
+    """V2X_EINVAL: a library error (V2XError) and the exception class Keras raises on bad inputs (ValueError)."""
+
+
 class Config(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_channels", C.c_int32), ("feat_dim", C.c_int32),
                 ("n_mp_layers", C.c_int32), ("share_weights", C.c_int32), ("variable_graphs", C.c_int32),
@@ -143,5 +147,5 @@ def check(lib, rc, handle=None):
         msg = lib.v2x_last_error(handle)
         text = msg.decode() if msg else "unknown error"
         if rc == -1:
-            raise ValueError(text)          # V2X_EINVAL: same exception class Keras raises on bad inputs
+            raise V2XInvalidArgument(text)      # V2X_EINVAL
         raise V2XError("v2xgnn error %d: %s" % (rc, text))

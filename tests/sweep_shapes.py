@@ -3,8 +3,8 @@ run on a GPU box:
     python tests/sweep_shapes.py [n_cases]
 Every case is one seeded draw, judged exactly as tests/test_gpu_shapes.py judges its permanent subset: plain rounding
 tolerances, ReLU gates at fp32 rounding distance of 0 identified explicitly and taken the kernels' way (tests/util.py),
-nothing redrawn.  The grid: 7 link counts x 4 feature widths x 3 depths x shared / per-node weights x 3 batch sizes = 504
-shapes, reference topology or a random adjacency."""
+nothing redrawn.  The grid: 7 link counts x 4 feature widths x 5 depths (1, 2, 4, 6, 8) x shared / per-node weights x
+3 batch sizes = 840 shapes, reference topology or a random adjacency."""
 import itertools, os, sys, traceback
 import numpy as np
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
@@ -14,7 +14,7 @@ from oracle import compact as oc
 from util import f32_params, random_inputs, oracle_step, assert_fwd_close, assert_close, assert_grads_match_oracle
 
 rng = np.random.default_rng(7)
-cases = list(itertools.product([1, 2, 3, 7, 20, 33, 40], [16, 32, 64, 128], [1, 2, 4], [False, True], [1, 17, 130]))
+cases = list(itertools.product([1, 2, 3, 7, 20, 33, 40], [16, 32, 64, 128], [1, 2, 4, 6, 8], [False, True], [1, 17, 130]))
 rng.shuffle(cases)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 bad = flips = 0
@@ -31,7 +31,8 @@ for (N, F, L, shared, B) in cases[:n]:
         eng.set_weights(oc.params_to_list(P))
         graph = ((np.arange(B + 1) * N).astype(np.int32), pb.row_ptr, pb.col_idx)
         q = eng.forward(pb)
-        y = (q + rng.normal(0, 1.2, size=q.shape)).astype(np.float32)
+        # (the spread grows with |q|: deep models reach |q| ~ 1e9, where q + N(0, 1.2) rounds back to q in fp32)
+        y = (q + rng.normal(0, 1.2, size=q.shape) * np.maximum(1.0, 1e-3 * np.abs(q))).astype(np.float32)
         step = oracle_step(spec, P, x.reshape(B * N, -1), e.reshape(B * N, -1), graph, y, q_at=q)
         assert_fwd_close(q, step['q'], "forward")
         loss = eng.forward_backward(pb, y)

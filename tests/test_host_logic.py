@@ -494,3 +494,66 @@ def test_bench_dump_outputs_writes_float32_and_samples_to_the_budget(tmp_path, m
     assert 4 * (sa.size + sb.size + sc.size) <= 2400
     for n in "abc":
         assert np.array_equal(np.load(str(tmp_path / "s1" / (n + ".npy"))), np.load(str(tmp_path / "s2" / (n + ".npy"))))
+
+
+@pytest.mark.parametrize("kw,message", [
+    (dict(n_mp_layers=0), r"n_mp_layers must be in \[1,8\]"),
+    (dict(n_mp_layers=9), r"n_mp_layers must be in \[1,8\]"),
+    (dict(feat_dim=48), r"feat_dim must be 16, 32, 64, 128 or 256 in this build \(got 48\)"),
+    (dict(feat_dim=512), r"feat_dim must be 16, 32, 64, 128 or 256 in this build \(got 512\)"),
+    (dict(n_channels=5), r"n_channels must be 4 in this build \(got 5\)"),
+    (dict(variable_graphs=True, n_nodes=1), r"variable_graphs requires share_weights"),
+])
+def test_create_rejects_sizes_outside_the_domain(kw, message):
+    """v2x_create checks its configuration before it looks for a device: the same error with and without a GPU.  Invalid
+    arguments are library errors (V2XError) and ValueError, the class Keras raises on bad inputs."""
+    with pytest.raises(vlib.V2XError, match=message) as exc:
+        v2xgnn.GnnEngine(GnnSpec(**kw))
+    assert isinstance(exc.value, ValueError)
+
+
+@pytest.mark.parametrize("shared", [False, True])
+def test_create_accepts_eight_layers(shared):
+    """n_mp_layers = 8 (FZ_MAXL, the deepest the kernels are sized for) passes validation: without a GPU the error is the
+    missing device, with one the model is created."""
+    import torch
+    spec = GnnSpec(n_nodes=6, feat_dim=32, n_mp_layers=8, share_weights=shared)
+    if not torch.cuda.is_available():
+        with pytest.raises(vlib.V2XError, match="no CPU fallback"):
+            v2xgnn.GnnEngine(spec)
+        return
+    eng = v2xgnn.GnnEngine(spec)
+    assert eng.n_params == spec.n_params
+    eng.close()
+
+
+@pytest.mark.parametrize("L,shared", [(1, False), (1, True), (8, False), (8, True)])
+def test_weight_layout_at_depth(L, shared):
+    """keras_list_to_flat / flat_to_keras_list, the parameter count and the Keras layer table at the shallowest and the
+    deepest model v2x_create accepts."""
+    from v2xgnn.bs_brain import GnnQModel
+    N, F = 5, 32
+    spec = GnnSpec(n_nodes=N, feat_dim=F, n_mp_layers=L, share_weights=shared)
+    S = 1 if shared else N
+    embed = (9 + 4 + F) * F + F                              # [x | e | nbr] -> F
+    stage = (F + 9 + 4 + F) * F + F                          # [h | x | e | agg] -> F
+    dense = (9 + 2 * F) * 80 + 80 + 80 * 40 + 40 + 40 * 20 + 20 + 20 * 4 + 4
+    assert spec.n_params == S * (embed + L * stage + dense)
+    shapes = v2xgnn.keras_list_shapes(spec)
+    assert len(shapes) == S * (4 * (L + 1) + 2 * 4)
+    assert sum(int(np.prod(s)) for s in shapes) == spec.n_params
+    rng = np.random.default_rng(L)
+    ws = [rng.normal(size=s).astype(np.float32) for s in shapes]
+    flat = v2xgnn.keras_list_to_flat(spec, ws)
+    assert flat.shape == (spec.n_params,) and np.array_equal(np.sort(flat), np.sort(np.concatenate([w.ravel() for w in ws])))
+    assert all(np.array_equal(a, b) for a, b in zip(ws, v2xgnn.flat_to_keras_list(spec, flat)))
+    # the last stage's bias of slot S - 1 sits right before Dense-0 (stage-major, slot-minor layout)
+    off = S * (embed + L * stage)
+    assert np.array_equal(flat[off - F:off], ws[4 * S * (L + 1) - 1])
+    m = GnnQModel.__new__(GnnQModel)
+    m.spec, m.model_index = spec, 0
+    table = m.keras_layer_table()
+    assert sum(len(w) for _, w in table) == len(shapes)
+    assert len({ln for ln, _ in table}) == len(table)
+    names = [w for _, ws_ in table for w in ws_]
+    assert len(set(names)) == len(names)
