@@ -6,11 +6,14 @@ feat_dim 64, 2 message-passing layers, batch 4096 per GPU (BASELINE.json configs
     python bench.py --gpus 1 --steps 200 --warmup 20
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0.  A plain run does only what the headline needs: it sets up, picks the launch form
+(--launch auto), warms up, times the steps, writes --dump-outputs and prints the line.  With --full the line also carries
   roofline     -- the dominant kernel's algorithmic bytes / its average launch duration, measured live
                   with HIP events around every launch of an instrumented (eager) pass of the same steps
   cpu_baseline -- the CPU oracle (a numpy restatement of the reference formulation's math, NOT
                   Keras/TF1) timed on this box's host cores on a bounded sample of the same workload
+and the complement fast path, the weak-scaling pass (N > 1), the drop-in boundary leg, the other workloads' passes and
+a summary of them all (each of them can still be skipped with its --no-* option).
 """
 import argparse
 import json
@@ -414,7 +417,7 @@ def dump_outputs(out_dir, arrays, seed=0):
 
 def main_rl(args):
     """--workload cfg0: BASELINE configs[0] (default Sim_Config: 4 links, 16 features, batch 256, gamma 0.2, episodes of 20
-    train steps), on the engine and -- as cpu_baseline, kind "port" -- on the CPU oracle behind the same agent.
+    train steps), on the engine and (--full) -- as cpu_baseline, kind "port" -- on the CPU oracle behind the same agent.
     --workload cfg2loop: configs[2] on one GPU (20 links, 64 features, replay batch 4096, HBM-resident replay)."""
     import torch
     links, feat, batch, gamma = (4, 16, 256, 0.2) if args.workload == "cfg0" else (20, 64, 4096, 0.5)
@@ -423,7 +426,7 @@ def main_rl(args):
     with ctx:
         gpu = rl_episode(links, feat, batch, gamma, steps, 1001, use_graph=not args.no_graph and args.launch != "eager", envs=args.envs, episodes=episodes)
     cpu = None
-    if args.workload == "cfg0" and not args.no_cpu_baseline:
+    if args.workload == "cfg0" and args.full and not args.no_cpu_baseline:
         from oracle.engine import OracleEngine
         r = rl_episode(links, feat, batch, gamma, steps, 1001, engine_factory=lambda spec: OracleEngine(spec, dtype=np.float32),
                        envs=args.envs, episodes=1)
@@ -555,7 +558,7 @@ def build_parser():
     ap.add_argument("--envs", type=int, default=0, help="cfg0 / cfg2loop: number of simulators stepped as arrays (0 = the single one)")
     ap.add_argument("--episodes", type=int, default=5, help="cfg0 / cfg2loop: timed episodes of 20 train steps")
     ap.add_argument("--no-fast-path", "--no-edge-gather", dest="no_fast_path", action="store_true",
-                    help="skip the second timed pass with the complement aggregation (the fast path for complete-minus-few "
+                    help="--full: skip the second timed pass with the complement aggregation (the fast path for complete-minus-few "
                          "graphs) that is printed beside the headline; the headline itself runs the general edge-index gather")
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="extend the timed region to at least this long (more steps than --steps if needed; the fast-path and "
@@ -573,15 +576,21 @@ def build_parser():
                     help="how a fit step reaches the GPU: one hipGraph replay + the Adam launch, or five eager launches; auto (default) "
                          "times 200 steps of each after the warm-up and keeps the faster (round 6: on ROCm 7.2 a graph replay costs "
                          "3.6-5 us per step more than the eager launches it replaces whenever the host runs ahead of the GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, run every other leg of the benchmark: the CPU baselines, the per-kernel roofline "
+                         "pass, the complement fast path, the weak-scaling pass (N > 1), the drop-in boundary leg and the other "
+                         "workloads' passes (the --no-* options below skip one of them); a plain run does none of these")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in boundary leg (dict API at the reference's configuration)")
+    ap.add_argument("--no-roofline", action="store_true",
+                    help="skip the pass of 55 fit steps before the timed region (instrumented with --full, for the roofline; plain "
+                         "otherwise, so that the timed steps start where those of a --full run do)")
+    ap.add_argument("--no-dropin", action="store_true", help="--full: skip the drop-in boundary leg (dict API at the reference's configuration)")
     ap.add_argument("--no-other-workloads", action="store_true",
-                    help="skip the short passes of configs[3] / configs[4] at their per-GPU shares (config.other_workloads)")
+                    help="--full: skip the short passes of configs[3] / configs[4] at their per-GPU shares (config.other_workloads)")
     ap.add_argument("--other-kernels", action="store_true",
                     help="config.other_workloads in its long form (workload prose, kernel path, per-kernel HIP-event times); the default "
                          "line is kept under 8 KB so that a record that keeps only a tail of stdout keeps all of it")
-    ap.add_argument("--no-weak-pass", action="store_true", help="N > 1: skip the second timed pass at --batch graphs PER GPU (config.weak)")
+    ap.add_argument("--no-weak-pass", action="store_true", help="--full, N > 1: skip the second timed pass at --batch graphs PER GPU (config.weak)")
     ap.add_argument("--cpu-seconds", type=float, default=30.0)
     ap.add_argument("--workload", choices=["cfg2", "cfg4", "cfg5", "cfg0", "cfg2loop"], default="cfg2",
                     help="BASELINE.json configs[1] (default, the metric's configuration), [3] (100 links x 256 features x "
@@ -776,21 +785,26 @@ def run_workload(args, ctx, light=False):
     args = argparse.Namespace(**dict(vars(args), no_graph=launch == "eager"))      # (the fast-path engine below follows the choice)
 
     # ---- per-kernel roofline: an instrumented (eager, HIP events around every launch) pass of the same steps, BEFORE the
-    # timed region so that the timed region is the last and longest stretch of GPU work of the run
+    # timed region so that the timed region is the last and longest stretch of GPU work of the run.  Its fit steps train the
+    # engine, so a plain run takes the same steps uninstrumented: the timed region starts from the same weights and Adam
+    # moments either way (an instrumented step is an eager step, bitwise equal to a replayed one)
     roofline, kernels, prof = None, None, None
     if rank == 0 and not args.no_roofline:
-        eng.profile(True)
+        if args.full:
+            eng.profile(True)
         with torch.cuda.stream(stream):
             for _ in range(5):
                 eng.train_step(db, yd, n_global=n_denom, want_loss=False)
             torch.cuda.synchronize()
-            eng.profile_read()
+            if args.full:
+                eng.profile_read()
             n_prof = 50 if not light else 20
             for _ in range(n_prof):
                 eng.train_step(db, yd, n_global=n_denom, want_loss=False)
             torch.cuda.synchronize()
-        prof = eng.profile_read()
-        eng.profile(False)
+        if args.full:
+            prof = eng.profile_read()
+            eng.profile(False)
     if dist is not None:
         dist.barrier()
 
@@ -809,7 +823,7 @@ def run_workload(args, ctx, light=False):
 
     # ---- the fast path beside it: the same steps with the complement aggregation (when the batch qualifies)
     fast = None
-    if not explicit and not args.no_fast_path and not light and str(path.get("graph_layers")).startswith("fused"):
+    if args.full and not explicit and not args.no_fast_path and not light and str(path.get("graph_layers")).startswith("fused"):
         eng2 = make_engine(spec, ctx, args, edge_gather=False)
         p2 = eng2.path_info(db)
         if p2.get("aggregation") == "complement":
@@ -824,7 +838,7 @@ def run_workload(args, ctx, light=False):
 
     # ---- N > 1: a second timed pass in the weak regime (--batch graphs PER GPU), the regime the kernels are sized for
     weak = None
-    if world > 1 and strong and not args.no_weak_pass and not light and args.shard_of == 1:
+    if args.full and world > 1 and strong and not args.no_weak_pass and not light and args.shard_of == 1:
         dbw, ydw, _, bw_local, _, nw_global, nw_denom, _ = make_batch(False, B)
         with torch.cuda.stream(stream):
             nw, ew = timed_region(stepper(eng, trainer, dbw, ydw, nw_denom), 50, min(2.0, args.min_seconds), max(args.warmup, 5))
@@ -1076,7 +1090,7 @@ def other_workloads(args, ctx):
 
 
 def summary(out, others, dropin, cpu):
-    """Every figure of the default run that is quoted beside the headline, as one flat object of numbers: ms per step of the shares of
+    """Every figure of a --full run that is quoted beside the headline, as one flat object of numbers: ms per step of the shares of
     the metric's batch (2 / 4 / 8 GPUs), configs[3] / [4] at their shares with the dominant kernel's roofline fraction and the CPU
     leg (graphs/s), the per-edge CSR gather step, both DQN loops (50 simulators as arrays; the reference's one-simulator shape) and the
     dict-API replay at the reference's configuration."""
@@ -1143,22 +1157,22 @@ def main():
             dist.init_process_group(backend, rank=rank, world_size=world)
     ctx = Ctx(world, rank, local, dist, force_dp)
 
-    # Order of a default run: CPU legs first, then every GPU pass, the contract's timed region (--steps steps) last but
-    # for its own fast-path / weak companions.
+    # Order of a --full run: CPU legs first, then every GPU pass, the contract's timed region (--steps steps) last but
+    # for its own fast-path / weak companions.  A plain run does the timed region alone.
     ragged = args.ragged is not None
     solo = rank == 0 and world == 1 and args.shard_of == 1
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not ragged:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline and not ragged:
         b_local = args.batch // (args.shard_of if args.scaling == "strong" else 1)
         cpu = cpu_baseline(args.nodes, args.feat, args.layers, args.share_weights, b_local, args.cpu_seconds, full=args.other_kernels)
     dropin = None
-    if solo and args.workload == "cfg2" and not args.no_dropin:
+    if solo and args.workload == "cfg2" and args.full and not args.no_dropin:
         try:
             dropin = dropin_boundary(local)
         except Exception as exc:
             dropin = {"error": "%s: %s" % (type(exc).__name__, exc)}
     others = None
-    if solo and args.workload == "cfg2" and not args.no_other_workloads:
+    if solo and args.workload == "cfg2" and args.full and not args.no_other_workloads:
         others = other_workloads(args, ctx)
     out = run_workload(args, ctx)
     if rank == 0:
@@ -1176,7 +1190,8 @@ def main():
             pe = others.get("per_edge_gather") or {}
             out["config"]["per_edge_gather"] = {k_: pe.get(k_) for k_ in ("value", "unit", "ms_per_step", "aggregation", "graph_layers", "error") if k_ in pe}
         # numbers only, LAST key of the line: survives a record that keeps a tail of stdout or filters keys
-        out["summary"] = summary(out, others, dropin, cpu)
+        if args.full:
+            out["summary"] = summary(out, others, dropin, cpu)
     if dist is not None:
         dist.destroy_process_group()
     if rank == 0:

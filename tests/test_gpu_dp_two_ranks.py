@@ -159,8 +159,8 @@ def test_bench_two_ranks_on_one_gpu(scaling, batch, global_batch, per_gpu):
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` with NO launcher around it: bench.py re-executes itself through
     torch.distributed.run with two ranks (both on the box's one GPU here, gloo collective), and the one line carries BOTH
-    regimes -- the strong-scaling value of the metric (global batch fixed) and a second timed pass at --batch graphs per GPU
-    (config.weak) -- plus the ranks the process group really had."""
+    regimes -- the strong-scaling value of the metric (global batch fixed) and, with --full, a second timed pass at --batch
+    graphs per GPU (config.weak) -- plus the ranks the process group really had."""
     import json
     import subprocess
     import sys
@@ -168,7 +168,7 @@ def test_bench_starts_its_own_ranks():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     env.update(V2X_BENCH_ONE_DEVICE="1", V2X_BENCH_BACKEND="gloo")
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "2", "--min-seconds", "0",
-           "--batch", "512", "--no-roofline"]
+           "--batch", "512", "--no-roofline", "--full"]
     out = subprocess.run(cmd, env=env, cwd=root, capture_output=True, text=True, timeout=900)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -366,6 +366,33 @@ def test_bench_runs_exactly_steps_and_dumps_the_same_outputs_twice(tmp_path):
     assert np.abs(arrays["grads"]).max() > 0 and np.all(arrays["adam_v"] >= 0)
 
 
+def test_plain_bench_run_times_the_same_steps_as_a_full_run(tmp_path):
+    """A plain `bench.py` run leaves out every leg besides the headline (no CPU baseline, roofline, fast path, drop-in leg,
+    other workloads or summary), yet its timed steps start from the same weights as those of a --full run: both dump the
+    same arrays after the last timed step."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "3"]
+    res = {}
+    for d, extra in (("plain", []), ("full", ["--full", "--no-cpu-baseline", "--no-dropin", "--no-other-workloads"])):
+        out = subprocess.run(base + extra + ["--dump-outputs", str(tmp_path / d)], cwd=root, capture_output=True, text=True,
+                             timeout=600)
+        assert out.returncode == 0, out.stderr[-2000:]
+        res[d] = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = res["plain"], res["full"]
+    assert plain["steps"] == 7 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    assert plain["roofline"] is None and plain["cpu_baseline"] is None and plain["fast_path"] is None
+    assert not {"kernels", "summary", "dropin_ref_config"} & set(plain) and "other_workloads" not in plain["config"]
+    assert set(plain["config"]["launch_probe_ms"]) == {"hipGraph replay", "eager"}
+    assert full["roofline"] is not None and full["kernels"] and full["fast_path"]["aggregation"] == "complement"
+    assert "summary" in full
+    for name in ("params", "grads", "adam_m", "adam_v"):
+        a, b = (np.load(str(tmp_path / d / (name + ".npy"))) for d in ("plain", "full"))
+        assert np.array_equal(a, b), name
+
+
 def test_ragged_large_batch_loss_is_split_reduced():
     """> 16k node rows with one Huber mean: the loss reduction is cut into ranges combined by the last workgroup.
     Checked against numpy on the engine's own q, twice (the arrival counter must re-arm itself)."""

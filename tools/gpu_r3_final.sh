@@ -14,11 +14,11 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INST_CYCLES_VMEM SQ_WAIT_INST_VMEM SQ_BUSY_CYCLES -d $O/st3 -o pmc -- $B > /dev/null 2> $O/st3.err
 python tools/stall_table.py $(ls $O/st1/*/*.db $O/st1/*.db | head -1) $(ls $O/st2/*/*.db $O/st2/*.db | head -1) $(ls $O/st3/*/*.db $O/st3/*.db | head -1) > $O/stalls.txt 2>&1
 # headline + kernel stats of the same command
-python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-700 $O/bench.json
+python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-700 $O/bench.json
 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python bench.py --no-cpu-baseline --no-roofline --no-edge-gather --min-seconds 0.5 > $O/prof_bench.json 2> $O/prof.err
 python tools/rocpd_summary.py $(ls $O/prof/*/*.db $O/prof/*.db 2>/dev/null | head -1) > $O/kernel_stats.txt 2>&1; head -9 $O/kernel_stats.txt
 # shares of the fixed global batch, other workloads
-Q="python bench.py --no-cpu-baseline"
+Q="python bench.py --full --no-cpu-baseline"
 for g in 2 4 8; do $Q --shard-of $g --no-edge-gather > $O/bench_b$((4096/g)).json 2>/dev/null; done
 $Q --share-weights > $O/bench_shared.json 2>/dev/null
 $Q --batch 65536 --steps 20 --warmup 3 --no-edge-gather > $O/bench_b65536.json 2>/dev/null
@@ -33,7 +33,7 @@ for wl in cfg4 cfg5; do
   for d in fetch write mfma; do python tools/rocpd_summary.py $(ls $O/${d}_$wl/*/*.db $O/${d}_$wl/*.db 2>/dev/null | head -1) > $O/${d}_$wl.txt 2>&1; done
   python tools/roofline_table2.py $O/bench_$wl.json $O/fetch_$wl.txt $O/write_$wl.txt $O/mfma_$wl.txt > $O/roofline_$wl.md 2>&1
 done
-python bench.py --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
+python bench.py --full --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
 python bench.py --workload cfg2loop --envs 50 > $O/bench_cfg2loop_envs50.json 2>/dev/null
 python tools/predict_latency.py 2>&1 | grep -v amdgpu.ids > $O/predict_latency.txt
 python tools/roofline_table.py $O/bench.json $O/hbm_traffic.json > $O/roofline.md 2>&1

@@ -23,11 +23,11 @@ for form in 0 1; do
   python tools/rocpd_summary.py $(db $O/lds$form) 2>&1 | grep -e "^kernel" -e k_gnn_ > $O/lds_form$form.txt
 done
 # headline + kernel stats of the same command
-python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo
+python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo
 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python bench.py --no-cpu-baseline --no-roofline --no-dropin --no-other-workloads --min-seconds 1 > $O/prof_bench.json 2> $O/prof.err
 python tools/rocpd_summary.py $(db $O/prof) > $O/kernel_stats.txt 2>&1; head -12 $O/kernel_stats.txt
 # shares of the fixed global batch, other workloads
-Q="python bench.py --no-cpu-baseline --no-dropin --no-other-workloads --min-seconds 2"
+Q="python bench.py --full --no-cpu-baseline --no-dropin --no-other-workloads --min-seconds 2"
 for g in 2 4 8; do $Q --shard-of $g > $O/bench_b$((4096/g)).json 2>/dev/null; done
 $Q --share-weights > $O/bench_shared.json 2>/dev/null
 $Q --batch 65536 --steps 20 --warmup 3 > $O/bench_b65536.json 2>/dev/null
@@ -47,7 +47,7 @@ V2X_RAGGED_PACKED=0 $Q --workload cfg5 --shard-of 8 > $O/bench_cfg5_intervalplan
 python tools/ragged_phases.py 2>&1 | grep -v amdgpu.ids > $O/ragged_phases.txt
 python tools/prof_rl_sections.py 2>&1 | grep -v amdgpu.ids | cut -c1-400 > $O/rl_sections.txt
 python tools/sim_threads.py 2>&1 | grep -v amdgpu.ids > $O/sim_threads.txt
-python bench.py --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
+python bench.py --full --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
 for i in 1 2 3; do python bench.py --workload cfg2loop --envs 50 > $O/bench_cfg2loop_envs50_run$i.json 2>/dev/null; done
 python tools/predict_latency.py 2>&1 | grep -v amdgpu.ids > $O/predict_latency.txt
 python tools/dropin_profile.py 2>&1 | grep -v amdgpu.ids > $O/dropin_profile.txt

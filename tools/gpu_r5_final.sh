@@ -17,11 +17,11 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VMEM SQ_ACTIVE_
 rocprofv3 --pmc SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_MFMA SQ_INST_CYCLES_VMEM SQ_WAIT_INST_VMEM SQ_BUSY_CYCLES -d $O/st3 -o pmc -- $B > /dev/null 2> $O/st3.err
 python tools/stall_table.py $(db $O/st1) $(db $O/st2) $(db $O/st3) > $O/stalls.txt 2>&1
 # headline + kernel stats of the same command
-python bench.py > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo
+python bench.py --full > $O/bench.json 2> $O/bench.err; cut -c1-600 $O/bench.json; echo
 rocprofv3 --kernel-trace --stats -d $O/prof -o stats -- python bench.py --no-cpu-baseline --no-roofline --no-dropin --no-other-workloads --min-seconds 1 > $O/prof_bench.json 2> $O/prof.err
 python tools/rocpd_summary.py $(db $O/prof) > $O/kernel_stats.txt 2>&1; head -12 $O/kernel_stats.txt
 # shares of the fixed global batch: split-tile kernels (the library's choice) against whole tiles, + rocprofv3 of the 512- and 1024-graph shares
-Q="python bench.py --no-cpu-baseline --no-dropin --no-other-workloads --min-seconds 2"
+Q="python bench.py --full --no-cpu-baseline --no-dropin --no-other-workloads --min-seconds 2"
 for g in 2 4 8; do
   $Q --shard-of $g > $O/bench_b$((4096/g)).json 2>/dev/null
   V2X_FUSED_SPLIT=0 $Q --shard-of $g > $O/bench_b$((4096/g))_wholetiles.json 2>/dev/null
@@ -58,7 +58,7 @@ python tools/prof_rl_sections.py 2>&1 | grep -v amdgpu.ids | cut -c1-400 > $O/rl
 V2X_SIM_LOOKAHEAD=0 V2X_RL_PACKED=0 python tools/prof_rl_sections.py 2>&1 | grep -v amdgpu.ids | cut -c1-400 > $O/rl_sections_arrays_no_lookahead.txt
 bash tools/rl_loop_kernels.sh 2>&1 | grep -v -e amdgpu.ids -e rocprofv3 | cut -c1-200 > $O/rl_loop_kernels.txt
 cat /sys/fs/cgroup/cpu.max > $O/cpu_quota.txt 2>/dev/null; nproc >> $O/cpu_quota.txt
-python bench.py --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
+python bench.py --full --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null
 for i in 1 2 3; do python bench.py --workload cfg2loop --envs 50 --episodes 5 > $O/bench_cfg2loop_envs50_run$i.json 2>/dev/null; done
 python bench.py --workload cfg2loop --envs 50 --episodes 200 > $O/bench_cfg2loop_envs50_4000steps.json 2>/dev/null
 V2X_RL_NATIVE_SAMPLER=0 python bench.py --workload cfg2loop --envs 50 --episodes 200 > $O/bench_cfg2loop_envs50_4000steps_numpy_sampler.json 2>/dev/null

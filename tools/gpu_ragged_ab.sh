@@ -1,7 +1,7 @@
 # ragged (configs[4] share) A/B on one box + its parity tests
 cd $GRAFT_REPO_ROOT
 run() {
-  env "$@" python bench.py --workload $WL --shard-of 8 --no-cpu-baseline --no-fast-path --no-dropin --no-other-workloads --min-seconds 1 2>/dev/null | python -c "
+  env "$@" python bench.py --full --workload $WL --shard-of 8 --no-cpu-baseline --no-fast-path --no-dropin --no-other-workloads --min-seconds 1 2>/dev/null | python -c "
 import sys,json
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('$WL $*', d['ms_per_step'], d['config']['kernel_path']['graph_layers'], {k:v['avg_us'] for k,v in d['kernels'].items()})"
 }
