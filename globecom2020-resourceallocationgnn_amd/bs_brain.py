@@ -41,7 +41,8 @@ class GnnQModel(object):
                  lr=1e-3, beta_1=0.5, beta_2=0.999, epsilon=1e-7, data_parallel=False, process_group=None, engine=None,
                  model_index=0, adjacency_cache=None):
         """data_parallel: every fit step shards the minibatch over the ranks of `process_group` (default group) and
-        all-reduces the gradient (v2xgnn.dp); all ranks must call fit with the SAME full minibatch.
+        all-reduces the gradient (v2xgnn.dp); all ranks must call fit with the SAME full minibatch.  "native": the same
+        with the whole data-parallel step, collectives included, as one library call (DataParallelTrainer(native=True)).
         engine: an object with GnnEngine's interface (the CPU tests inject one); default: the gfx950 engine,
         which raises without a GPU."""
         self.spec = spec
@@ -54,7 +55,8 @@ class GnnQModel(object):
             from .dp import DataParallelTrainer
             import os
             self.trainer = DataParallelTrainer(self.engine, process_group=process_group,
-                                               force=os.environ.get("V2X_FORCE_DP") == "1")
+                                               force=os.environ.get("V2X_FORCE_DP") == "1",
+                                               native=isinstance(data_parallel, str) and data_parallel == "native")
         self.validate_adjacency = validate_adjacency
         # which Adjacency_Matrix objects already passed the Kronecker check (shared by the two models of a BS: one
         # replay hands the same array to predict and to fit, BS_brain.py:603 -> :652, :716)
@@ -66,6 +68,14 @@ class GnnQModel(object):
         self.input_names.append('Adjacency_Matrix')
         self.output_names = ['D%d_Decide_Output' % k for k in range(1, N + 1)]       # :208
         self.engine.set_weights(_glorot_list(spec, np.random.default_rng(seed)))
+
+    def close(self):
+        """free the trainer's collective table (an RCCL communicator under data_parallel="native") and the engine"""
+        if self.trainer is not None:
+            self.trainer.close()
+        close = getattr(self.engine, "close", None)
+        if close is not None:
+            close()
 
     # ------------------------------------------------------------------ data plumbing
     def _named(self, x, names, what):
@@ -302,6 +312,11 @@ class BS(object):
         return GnnQModel(self._spec, device=self._device, seed=seed, use_graph=self._use_graph,
                          data_parallel=self._dp, process_group=self._group, engine=engine, model_index=index,
                          adjacency_cache=self._adj_cache)
+
+    def close(self):
+        """free both models (engines, and the RCCL communicator of a data_parallel="native" trainer)"""
+        self.model.close()
+        self.target_model.close()
 
     def train_dnn(self, data_train, labels, batch_size):
         epochs = 1

@@ -132,6 +132,9 @@ struct v2x_model {
   bool prof_no_fuse = false;
   std::vector<WideWgradPlan> wide_roles_buf;
   std::vector<WideWgradPlan>* wide_roles = nullptr;      // non-null: wide_wgrad collects instead of launching
+  // v2x_train_step_dp (dp_native.hpp): the stream the bucket collectives run on and its events, made on first use
+  hipStream_t dp_st = nullptr;
+  std::vector<hipEvent_t> dp_ev;
 };
 
 namespace {
@@ -370,6 +373,9 @@ int ensure_slabs(v2x_model* m, int nc) {
   m->slab = nullptr;
   HIPCHK(m, hipMalloc(reinterpret_cast<void**>(&m->slab), (size_t)nc * m->P * sizeof(float)));
   HIPCHK(m, hipMemset(m->slab, 0, (size_t)nc * m->P * sizeof(float)));
+  // (hipMemset runs on the null stream, which does not order against the caller's stream when that is non-blocking -- as
+  //  every stream of PyTorch's pool is: wait here, or the zeroing may land after this step's first launches)
+  HIPCHK(m, hipDeviceSynchronize());
   m->slab_cap = nc;
   return V2X_OK;
 }
@@ -1103,7 +1109,7 @@ int launch_wgrad_multi(v2x_model* m, hipStream_t st, const IdxMap& x, WgradMulti
     nc = std::max(nc, mu.w[i].n_chunks);
   }
   {                                     // phase stamps (V2X_FUSED_TS=1): of ONE role, V2X_WG_TS_ROLE (default: the first)
-    const int ts_role = env_int("V2X_WG_TS_ROLE", 0);
+    static const int ts_role = env_int("V2X_WG_TS_ROLE", 0);
     for (int i = 0; i < n_roles; ++i)
       if (i != ts_role) mu.w[i].ts = nullptr;
   }
@@ -1229,7 +1235,7 @@ bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x) {
   // tiles per workgroup = 4 x tiles per wave.  Measured (profiles/r06_dense0_role_shares.txt): 512 / 1024 / 2048 graphs of 20 links
   // (4 / 8 / 12 tiles per workgroup) 0.1201 -> 0.1131, 0.1512 -> 0.1463, 0.1929 -> 0.1880 ms per step; at 4096 (20-24 tiles) the chip
   // is full either way and the heavier weight-gradient launch costs more than the MLP launch saves (0.2554 -> 0.2658)
-  const int max_tiles = env_int("V2X_MLP_WG0_TILES", 12);
+  static const int max_tiles = env_int("V2X_MLP_WG0_TILES", 12);
   return mlp_wg_split(x.n_idx, x.grid_y).tiles_per_wg <= max_tiles;
 }
 
@@ -1957,7 +1963,8 @@ int run_backward(v2x_model* m, hipStream_t st, hipStream_t sw, const DevBatch& d
   else if (mlp_wg) CHK(launch_mlp_train_wg(m, st, a, !m->dense0_out_now));
   else if (mlp_fused_training(m)) CHK(launch_mlp_train(m, st, a));
   else CHK(launch_mlp(m, st, a, true));
-  const bool merged = !mlp_wg && !two && wgrad_all_fits(m) && env_int("V2X_WG_SPLIT", 0) == 0;
+  static const int wg_split = env_int("V2X_WG_SPLIT", 0);
+  const bool merged = !mlp_wg && !two && wgrad_all_fits(m) && wg_split == 0;
   CHK(fork());
   if (!merged && !mlp_wg) CHK(wgrad_mlp(m, sw, x, d.xe, m->h[L], m->a[L]));        // 4 Dense layers, one launch (side stream if two)
   // V2X_WG_PER_STAGE=1: every GNN stage's weight gradient goes to the side stream as soon as its dpre exists
@@ -1997,7 +2004,8 @@ int run_step(v2x_model* m, hipStream_t st, const DevBatch& d, bool bwd, const fl
   if (bwd) {
     // measured: with the current kernels the side-stream overlap of the Dense weight gradients no longer pays
     // (0.397 vs 0.390 ms/step), so one stream is the default; V2X_TWO_STREAMS=1 restores the fork/join
-    const bool two = !m->prof && m->side && getenv("V2X_TWO_STREAMS") != nullptr;
+    static const bool two_env = getenv("V2X_TWO_STREAMS") != nullptr;
+    const bool two = !m->prof && m->side && two_env;
     CHK(run_backward(m, st, two ? m->side : st, d, all, y_dev, n_global));
   }
   return V2X_OK;
@@ -2085,7 +2093,9 @@ GraphKey make_key(int kind, const DevBatch& d, const void* y, int n_global) {
 int max_slabs(const v2x_model* m, int n_idx, int n_slots) {
   int chunk, nc = 1;
   const int mr = m->L >= 1 ? merged_wg_rows(m, n_idx, n_slots) : 0;
-  for (int rows : {env_int("V2X_WG_CHUNK_GNN", 1024), env_int("V2X_WG_CHUNK_DENSE", 1024), env_int("V2X_WG_CHUNK_EMBED", 1024), env_int("V2X_WG_CHUNK_D123", 512), 768, 896, mr > 0 ? mr : 1024})
+  static const int c_gnn = env_int("V2X_WG_CHUNK_GNN", 1024), c_dense = env_int("V2X_WG_CHUNK_DENSE", 1024),
+                   c_embed = env_int("V2X_WG_CHUNK_EMBED", 1024), c_d123 = env_int("V2X_WG_CHUNK_D123", 512);
+  for (int rows : {c_gnn, c_dense, c_embed, c_d123, 768, 896, mr > 0 ? mr : 1024})
     if (rows > 0) nc = std::max(nc, role_chunks(n_idx, n_slots, 1000, 1000, &chunk, rows));     // (a switch set to 0 = its default)
   if (is_wide(m)) nc = std::max(nc, wide_splits(n_idx, 1, n_slots));     // the fewest tiles (one) split most
   else nc = std::max(nc, mlp_wg_split(n_idx, n_slots).n_slabs);         // k_mlp_train_wg: one slab per workgroup and slot
@@ -2122,7 +2132,8 @@ int presize_rows(v2x_model* m, int n_rows) {
 bool wide_adam_fusable(const v2x_model* m, const DevBatch& d) {
   static const int on = env_int("V2X_WIDE_ADAM", 1), wide_merge = env_int("V2X_WIDE_MERGE", 1);
   if (!on || !wide_merge || !is_wide(m) || m->bucketed || m->prof_no_fuse || !m->adam_scal || m->L + 2 > WWM_ROLES) return false;
-  if (getenv("V2X_TWO_STREAMS")) return false;
+  static const bool two_env = getenv("V2X_TWO_STREAMS") != nullptr;
+  if (two_env) return false;
   const IdxMap x = idx_map(m, d, Range{0, d.B});
   const int kt = 2 * ((m->F + 127) / 128);                    // [h | agg] K tiles ([x | e] folded or one more: more tiles = fewer splits)
   return wide_splits(x.n_idx, kt, x.grid_y) == 1;
@@ -2235,6 +2246,11 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
   m->ev.resize(2 * m->L + 6);
   for (auto& e : m->ev)
     if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail("event");
+  // The memsets above run on the null stream and may still be in flight when this returns; the caller's next call
+  // (v2x_set_weights: a copy into the parameters) goes to ITS stream, which a non-blocking stream -- every stream of PyTorch's
+  // pool -- does not order behind the null stream.  Without this wait the zeroing could land on top of the weights just set:
+  // seen as zeroed leading parameters after set_weights on a side stream, now and then, once a process had made and freed models.
+  if (hipDeviceSynchronize() != hipSuccess) return fail("synchronisation");
   *out = m;
   return V2X_OK;
 }
@@ -2251,6 +2267,8 @@ void v2x_destroy(v2x_model* m) {
   if (m->gate_bits) hipFree(m->gate_bits);
   if (m->nbmask) hipFree(m->nbmask);
   for (auto& e : m->ev) if (e) hipEventDestroy(e);
+  for (auto& e : m->dp_ev) if (e) hipEventDestroy(e);
+  if (m->dp_st) hipStreamDestroy(m->dp_st);
   if (m->side) hipStreamDestroy(m->side);
   if (m->cap) hipStreamDestroy(m->cap);
   for (float* p : ptrs) if (p) hipFree(p);
@@ -2546,9 +2564,11 @@ int v2x_forward_backward(v2x_model* m, const v2x_batch* b, const float* y, int y
 // One DQN replay step (Agent.replay, BS_brain.py:555-748) in a single call: target forward on s', online forward on s
 // (its activations are kept), y = q with the taken action's entry replaced by r + gamma * max q', then backward +
 // Adam on the online network WITHOUT a second forward of the graph layers (predict + fit would run them twice).
-int v2x_dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, const v2x_batch* s_next, const int32_t* action,
-                 const double* reward, double gamma, int32_t n_graphs_global, float* y_out, float* loss_out,
-                 int loss_on_device, void* stream) {
+// comm: the data-parallel form, v2x_dqn_step_dp (dp_native.hpp); NULL on one GPU
+static int dp_dqn_collectives(v2x_model* m, const v2x_comm* comm, bool want_loss, hipStream_t st);
+static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, const v2x_batch* s_next, const int32_t* action,
+                    const double* reward, double gamma, int32_t n_graphs_global, float* y_out, float* loss_out,
+                    int loss_on_device, void* stream, const v2x_comm* comm) {
   v2x_model* m = online;
   if (!online || !target || !action || !reward) FAIL(m, V2X_EINVAL, "dqn_step: null argument");
   if (online == target) FAIL(m, V2X_EINVAL, "dqn_step: online and target must be different models");
@@ -2602,9 +2622,23 @@ int v2x_dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, const
     online->dqn_tq = nullptr; online->dqn_y = nullptr;
     return rc;
   }));
-  CHK(launch_reduce_adam(online, st, 1, true, nullptr, loss_job(online, ds, n_graphs_global)));
+  if (!comm) {
+    CHK(launch_reduce_adam(online, st, 1, true, nullptr, loss_job(online, ds, n_graphs_global)));
+  } else {
+    // data parallelism: the slab sums and the losses, the collectives (eager, never captured), then Adam alone
+    CHK(launch_reduce_adam(online, st, 1, false, nullptr, loss_job(online, ds, n_graphs_global)));
+    CHK(dp_dqn_collectives(online, comm, loss_out != nullptr, st));
+    CHK(launch_reduce_adam(online, st, 0, true, nullptr));
+  }
   online->have_fwd = target->have_fwd = true;
   return emit_loss(online, loss_out, loss_on_device, st);
+}
+
+int v2x_dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, const v2x_batch* s_next, const int32_t* action,
+                 const double* reward, double gamma, int32_t n_graphs_global, float* y_out, float* loss_out,
+                 int loss_on_device, void* stream) {
+  return dqn_step(online, target, s, s_next, action, reward, gamma, n_graphs_global, y_out, loss_out, loss_on_device, stream,
+                  nullptr);
 }
 
 int v2x_apply_gradients(v2x_model* m, void* stream) {
@@ -2959,3 +2993,6 @@ int v2x_profile_read(v2x_model* m, char* names_out, int names_cap, double* ms_ou
 }
 
 }  // extern "C"
+
+// data parallelism driven by the library: the collective table, the RCCL table, v2x_train_step_dp, v2x_dqn_step_dp
+#include "dp_native.hpp"

@@ -9,7 +9,11 @@ differentiates its shard of the GLOBAL Huber mean (n_global = B), so the sum of 
 gradients is exactly the single-GPU gradient and no rescale is needed.  The target-network
 sync stays a local device-to-device copy.
 """
+import ctypes as C
+
 import numpy as np
+
+from . import lib as _lib
 
 
 class DataParallelTrainer(object):
@@ -17,7 +21,10 @@ class DataParallelTrainer(object):
     grad_tensor() -> flat torch tensor aliasing the gradient buffer, apply_gradients().
     `GnnEngine` is the GPU backend."""
 
-    def __init__(self, backend, process_group=None, force=False, overlap=None, shard_optimizer=None):
+    def __init__(self, backend, process_group=None, force=False, overlap=None, shard_optimizer=None, native=False, comm=None):
+        """native: every train_step is ONE library call (GnnEngine.train_step_dp) that runs the forward / backward, the
+        collectives of this trainer's form and Adam; the collectives go through `comm` (default, made on the first step: an
+        RcclComm on the nccl backend, a TorchComm on any other).  The same launches and collectives as the Python form."""
         import torch.distributed as dist
         self.dist = dist
         self.backend = backend
@@ -49,6 +56,29 @@ class DataParallelTrainer(object):
         self._has_reduce_scatter = True
         self._bucket_ranges = None
         self._param = None
+        self.native = bool(native)
+        self._comm = comm
+
+    @property
+    def form(self):
+        """the v2x_train_step_dp form this trainer's switches select"""
+        if self.shard_optimizer:
+            return _lib.V2X_DP_SHARDED
+        return _lib.V2X_DP_BUCKETS if self.overlap else _lib.V2X_DP_ALLREDUCE
+
+    def comm(self):
+        """the collective table of the native step (made on first use: every rank must call it at the same point)"""
+        if self._comm is None:
+            nccl = self.dist.is_initialized() and self.dist.get_backend(self.group) == "nccl"
+            self._comm = (RcclComm if nccl else TorchComm)(self.group, device=getattr(self.backend, "device", None))
+            self._own_comm = True
+        return self._comm
+
+    def close(self):
+        """free the collective table comm() made (an RcclComm holds an RCCL communicator); one handed in stays the caller's"""
+        if getattr(self, "_own_comm", False) and self._comm is not None:
+            self._comm.close()
+            self._comm, self._own_comm = None, False
 
     def shard(self, batch, y):
         """Contiguous shard of whole graphs for this rank (variable-size batches: balanced by edges + nodes,
@@ -107,6 +137,8 @@ class DataParallelTrainer(object):
             n_graphs_global = n_denominator
         if n_graphs_global is None:
             raise ValueError("train_step: the global Huber denominator (n_denominator) is required under data parallelism")
+        if self.native:
+            return self.backend.train_step_dp(local_batch, local_y, self.comm(), self.form, n_graphs_global, want_loss)
         reduce_now = self.world > 1 or self.force
         if reduce_now and self._overlapped(local_batch):
             return self._train_step_phased(local_batch, local_y, n_graphs_global, want_loss)
@@ -200,6 +232,8 @@ class DataParallelTrainer(object):
         if not self.shard_optimizer or self.world == 1:
             return m, v, it
         import torch
+        if self._grad is None and self.native:
+            self._grad = self.backend.grad_tensor()          # (the device the slices travel through)
         dev = self._grad.device if self._grad is not None else "cpu"
         out = []
         for arr in (m, v):
@@ -224,3 +258,102 @@ class DataParallelTrainer(object):
         t = torch.as_tensor(np.asarray(arr, np.float64), device=self._grad.device)
         self.dist.all_reduce(t, op=self.dist.ReduceOp.SUM, group=self.group)
         return t.cpu().numpy()
+
+
+# ---- collective tables of the native step (v2x_comm, include/v2xgnn.h) -------------------------------------------------------
+def _device_view(ptr, n, device):
+    """torch view (no copy) of n float32 at device address ptr"""
+    import torch
+
+    class _Holder(object):
+        pass
+    h = _Holder()
+    h.__cuda_array_interface__ = {"shape": (int(n),), "typestr": "<f4", "data": (int(ptr), False), "version": 2, "strides": None}
+    return torch.as_tensor(h, device="cuda:%d" % device)
+
+
+def _group_ranks(group):
+    import torch.distributed as dist
+    if not dist.is_initialized():
+        return 1, 0
+    return dist.get_world_size(group), dist.get_rank(group)
+
+
+class RcclComm(object):
+    """The library's RCCL table (v2x_comm_rccl_create) for the ranks of `group`: rank 0's unique id reaches the others over the
+    process group.  Creating it is collective over the group.  `comm` is the lib.Comm to hand to the library; close() frees
+    the communicator."""
+
+    def __init__(self, group=None, device=None):
+        import torch
+        import torch.distributed as dist
+        self._lib = _lib.load_library()
+        self.world, self.rank = _group_ranks(group)
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        uid = (C.c_uint8 * 128)()
+        if self.rank == 0:
+            _lib.check(self._lib, self._lib.v2x_comm_rccl_unique_id(uid))
+        if self.world > 1:
+            box = [bytes(uid)]
+            src = dist.get_global_rank(group, 0) if group is not None else 0
+            dist.broadcast_object_list(box, src=src, group=group)
+            C.memmove(uid, box[0], 128)
+        self.comm = _lib.Comm()
+        _lib.check(self._lib, self._lib.v2x_comm_rccl_create(uid, self.world, self.rank, self.device, C.byref(self.comm)))
+
+    def close(self):
+        if getattr(self, "comm", None) is not None and self.comm.ctx:
+            _lib.check(self._lib, self._lib.v2x_comm_rccl_destroy(C.byref(self.comm)))
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class TorchComm(object):
+    """A v2x_comm whose entries are ctypes callbacks into torch.distributed on `group`, for backends the library cannot drive
+    itself (gloo: the one-GPU two-rank tests).  Each entry runs its collective on the stream the library hands over and
+    blocks the host until it is done.  Reduce-scatter is the whole-bucket all-reduce (gloo has none; the rank's slice then
+    holds the sum, as DataParallelTrainer._reduce_scatter does).  An exception inside an entry returns -1 (V2X_ECOMM) and is
+    kept in `last_error`."""
+
+    def __init__(self, group=None, device=None):
+        import torch
+        self.group = group
+        self.world, self.rank = _group_ranks(group)
+        self.device = torch.cuda.current_device() if device is None else int(device)
+        self.last_error = None
+        self._fns = [_lib.COLLECTIVE(self._entry(f)) for f in (self._all_reduce, self._reduce_scatter, self._all_gather)]
+        self.comm = _lib.Comm(self.world, self.rank, None, *self._fns)
+
+    def _entry(self, body):
+        def call(buf, n, stream, ctx):
+            try:
+                if self.world == 1:
+                    return 0                         # the sum over one rank, the gather of one slice: nothing to do
+                import torch
+                st = torch.cuda.ExternalStream(stream, device=self.device) if stream else torch.cuda.default_stream(self.device)
+                with torch.cuda.stream(st):
+                    body(_device_view(buf, n, self.device), int(n))
+                st.synchronize()
+                return 0
+            except Exception as exc:                 # (nothing may propagate through the C frames)
+                self.last_error = exc
+                return -1
+        return call
+
+    def _all_reduce(self, t, n):
+        import torch.distributed as dist
+        dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.group)
+
+    _reduce_scatter = _all_reduce
+
+    def _all_gather(self, t, n):
+        import torch.distributed as dist
+        c = n // self.world
+        dist.all_gather_into_tensor(t, t[self.rank * c:(self.rank + 1) * c].clone(), group=self.group)
+
+    def close(self):
+        pass

@@ -68,6 +68,13 @@ def _batch_struct(b):
     return s
 
 
+def _comm_ref(comm):
+    """a v2x_comm for the C ABI: a lib.Comm, or an object that holds one in `.comm` (dp.RcclComm, dp.TorchComm); None stays NULL"""
+    if comm is None:
+        return None
+    return C.byref(getattr(comm, "comm", comm))
+
+
 class GnnEngine(object):
     """use_graph: forward / fit steps are captured once per (batch pointers, sizes) as a hipGraph and replayed.
     Capture needs a NON-default stream: calls made while torch's current stream is the default one run eagerly
@@ -233,6 +240,14 @@ class GnnEngine(object):
         last = int(self._lib.v2x_grad_bucket_count(self._h)) - 1
         return self._step(fn, batch, y, n_global, want_loss and phase == last)
 
+    def train_step_dp(self, batch, y, comm, form, n_global, want_loss=True):
+        """One data-parallel fit step in ONE call (v2x_train_step_dp): forward + backward on this rank's shard, the collectives
+        of `form` (lib.V2X_DP_ALLREDUCE / _BUCKETS / _SHARDED) through `comm` (a dp.RcclComm / dp.TorchComm or a lib.Comm), Keras
+        Adam.  n_global: the global batch (required).  Returns the per-output losses summed over the ranks."""
+        cref = _comm_ref(comm)
+        fn = lambda h, s, yp, yd, ng, lo, ld, st: self._lib.v2x_train_step_dp(h, s, yp, yd, ng, cref, int(form), lo, ld, st)
+        return self._step(fn, batch, y, n_global, want_loss)
+
     def param_tensor(self):
         """torch view (no copy) of the flat parameter buffer in HBM (the all-gather of a sharded optimizer step writes it).
         Taking it tells the library that the parameters may change behind its back (v2x_param_ptr)."""
@@ -274,6 +289,20 @@ class GnnEngine(object):
         self._check(self._lib.v2x_dqn_step(self._h, target._h, C.byref(sb), C.byref(sn), action.data_ptr(), reward.data_ptr(),
                                            float(gamma), int(n_global or 0), None if y_out is None else y_out.data_ptr(),
                                            None if loss is None else loss.data_ptr(), 1, self._stream()))
+        return loss
+
+    def dqn_step_dp(self, target, batch, batch_next, action, reward, gamma, comm, n_global, y_out=None, want_loss=True):
+        """dqn_step on this rank's share of a minibatch of n_global graphs with the gradient and the losses all-reduced through
+        `comm` before Adam (v2x_dqn_step_dp): still one call, the online graph layers run once."""
+        torch = _torch()
+        if not isinstance(batch, DeviceBatch) or not isinstance(batch_next, DeviceBatch):
+            raise ValueError("dqn_step_dp takes device-resident batches")
+        sb, sn = _batch_struct(batch), _batch_struct(batch_next)
+        loss = torch.empty(self.n_outputs, dtype=torch.float32, device=batch.device) if want_loss else None
+        self._check(self._lib.v2x_dqn_step_dp(self._h, target._h, C.byref(sb), C.byref(sn), action.data_ptr(), reward.data_ptr(),
+                                              float(gamma), int(n_global or 0), _comm_ref(comm),
+                                              None if y_out is None else y_out.data_ptr(),
+                                              None if loss is None else loss.data_ptr(), 1, self._stream()))
         return loss
 
     def validate(self, batch):

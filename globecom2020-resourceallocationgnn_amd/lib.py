@@ -10,6 +10,11 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _LIB = None
 
 V2X_OK = 0
+V2X_EINVAL = -1
+V2X_ECOMM = -5          # a collective of a v2x_comm table returned non-zero
+
+# forms of v2x_train_step_dp
+V2X_DP_ALLREDUCE, V2X_DP_BUCKETS, V2X_DP_SHARDED = 0, 1, 2
 
 
 class V2XError(RuntimeError):
@@ -18,6 +23,10 @@ class V2XError(RuntimeError):
 
 class V2XInvalidArgument(V2XError, ValueError):
     """V2X_EINVAL: a library error (V2XError) and the exception class Keras raises on bad inputs (ValueError)."""
+
+
+class V2XCommError(V2XError):
+    """V2X_ECOMM: a collective of the v2x_comm table failed (the text names it and its bucket)."""
 
 
 class Config(C.Structure):
@@ -51,6 +60,16 @@ class OptProblem(C.Structure):
     _fields_ = [("E", C.c_int32), ("n", C.c_int32), ("rb", C.c_int32), ("pad_", C.c_int32),
                 ("v2v_ff", C.c_void_p), ("v2i_ff", C.c_void_p), ("v2i_abs", C.c_void_p), ("dest", C.c_void_p)] + \
         [(k, C.c_double) for k in ("p_v2v", "p_v2i", "veh_gain", "bs_gain", "bs_nf", "veh_nf", "sig2", "w_v2v", "w_v2i")]
+
+
+# int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
+COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
+
+
+class Comm(C.Structure):
+    """v2x_comm of include/v2xgnn.h"""
+    _fields_ = [("world", C.c_int32), ("rank", C.c_int32), ("ctx", C.c_void_p), ("all_reduce_sum", COLLECTIVE),
+                ("reduce_scatter_sum", COLLECTIVE), ("all_gather", COLLECTIVE)]
 
 
 # every symbol include/v2xgnn.h declares: (name, restype, argtypes)
@@ -90,6 +109,12 @@ SYMBOLS = [
     ("v2x_q_stats", C.c_int, [_P, _I, _I, _I, _P, _P]),
     ("v2x_dqn_targets", C.c_int, [_P, _P, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("v2x_dqn_step", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_int32, _P, _P, C.c_int, _P]),
+    ("v2x_comm_rccl_unique_id", C.c_int, [_P]),
+    ("v2x_comm_rccl_create", C.c_int, [_P, _I, _I, _I, C.POINTER(Comm)]),
+    ("v2x_comm_rccl_destroy", C.c_int, [C.POINTER(Comm)]),
+    ("v2x_train_step_dp", C.c_int, [_P, C.POINTER(Batch), _P, C.c_int, _I, C.POINTER(Comm), C.c_int, _P, C.c_int, _P]),
+    ("v2x_dqn_step_dp", C.c_int, [_P, _P, C.POINTER(Batch), C.POINTER(Batch), _P, _P, C.c_double, C.c_int32, C.POINTER(Comm),
+                                  _P, _P, C.c_int, _P]),
     ("v2x_pack_feed", C.c_int, [C.POINTER(Feed), C.c_int, _P, _P, _P, _P, _P]),
     ("v2x_validate_batch", C.c_int, [_P, C.POINTER(Batch), _I, _P]),
     ("v2x_check_errors", C.c_int, [_P, _P]),
@@ -146,6 +171,8 @@ def check(lib, rc, handle=None):
     if rc != V2X_OK:
         msg = lib.v2x_last_error(handle)
         text = msg.decode() if msg else "unknown error"
-        if rc == -1:
-            raise V2XInvalidArgument(text)      # V2X_EINVAL
+        if rc == V2X_EINVAL:
+            raise V2XInvalidArgument(text)
+        if rc == V2X_ECOMM:
+            raise V2XCommError("v2xgnn error %d: %s" % (rc, text))
         raise V2XError("v2xgnn error %d: %s" % (rc, text))

@@ -643,6 +643,13 @@ class Agent(object):
             # single GPU: the whole step in one call, the online graph layers run once (v2x_dqn_step)
             y = rep.target_buffer(len(idx), self.num_CH)
             loss = model.engine.dqn_step(target.engine, sb, sb_next, action, reward, self.gamma, y_out=y)
+        elif getattr(trainer, 'native', False) and not trainer.shard_optimizer and hasattr(model.engine, 'dqn_step_dp'):
+            # data_parallel="native": still one call; the gradient and the losses are all-reduced inside it (v2x_dqn_step_dp).
+            # That is the one-all-reduce form, full-range Adam on every rank: a trainer with a SHARDED optimizer keeps Adam's
+            # moments current on its own slices only, so it takes the four calls below (its train_step stays sharded) -- mixing
+            # the two would let the replicas' moments part without an error
+            y = rep.target_buffer(len(idx), self.num_CH)
+            loss = model.engine.dqn_step_dp(target.engine, sb, sb_next, action, reward, self.gamma, trainer.comm(), B, y_out=y)
         else:
             q = model.engine.forward(sb)                              # online  [k*n, C]
             q_next = target.engine.forward(sb_next)                   # target  (adjacency reused, :583)

@@ -65,6 +65,7 @@ extern "C" {
 #define V2X_EHIP         -2   /* a HIP runtime call failed                */
 #define V2X_ENOMEM       -3
 #define V2X_ESTATE       -4   /* call order violated (e.g. backward before forward) */
+#define V2X_ECOMM        -5   /* a collective of a v2x_comm table returned non-zero   */
 
 #define V2X_XE_WIDTH     16   /* packed [x|e|pad] row width */
 
@@ -139,7 +140,8 @@ int  v2x_train_step(v2x_model* m, const v2x_batch* b, const float* y, int y_on_d
                     int32_t n_graphs_global, float* loss_out, int loss_on_device, void* stream);
 
 /* the same step split for data parallelism: (1) forward+backward leaves the local gradient
- * in v2x_grad_ptr(); the host all-reduces (sum) it over ranks; (2) apply the Adam update.  */
+ * in v2x_grad_ptr(); the host all-reduces (sum) it over ranks; (2) apply the Adam update.
+ * (v2x_train_step_dp below runs the whole data-parallel step, collectives included, in one call.)  */
 int  v2x_forward_backward(v2x_model* m, const v2x_batch* b, const float* y, int y_on_device,
                           int32_t n_graphs_global, float* loss_out, int loss_on_device, void* stream);
 int  v2x_apply_gradients(v2x_model* m, void* stream);
@@ -159,6 +161,54 @@ int64_t v2x_grad_bucket(const v2x_model* m, int bucket, int64_t* offset);
  * a rank that owns a 1 / G slice of every bucket after a reduce-scatter (the host all-gathers the parameters afterwards).
  * advance_iteration != 0 on the first call of a step (Adam's t), 0 on the others.                                       */
 int  v2x_apply_gradients_range(v2x_model* m, int64_t offset, int64_t count, int advance_iteration, void* stream);
+
+/* ---- data parallelism driven by the library ----------------------------------------------------------------------
+ * A collective table: the library calls it between the backward pass and Adam, on the caller's stream (the bucket collectives
+ * of forms V2X_DP_BUCKETS and V2X_DP_SHARDED on a stream the model owns, joined back into the caller's stream).  Every entry returns 0 on success; `stream` is a hipStream_t.  Ordering contract: a call
+ * sees all work enqueued on `stream` before it, and work enqueued on `stream` after it sees its result.  A table may also
+ * block the host until the collective is done.
+ *   all_reduce_sum      in place: buf[0..n) = sum over ranks
+ *   reduce_scatter_sum  in place over a bucket of n floats (n % world == 0): afterwards rank r's slice
+ *                       [r n / world, (r + 1) n / world) holds the sum; the rest of buf is unspecified (ncclReduceScatter)
+ *   all_gather          in place: rank r's slice of the n floats is its input (ncclAllGather)                             */
+typedef struct v2x_comm {
+  int32_t world, rank;
+  void* ctx;
+  int (*all_reduce_sum)(float* buf, int64_t n, void* stream, void* ctx);
+  int (*reduce_scatter_sum)(float* buf, int64_t n, void* stream, void* ctx);
+  int (*all_gather)(float* buf, int64_t n, void* stream, void* ctx);
+} v2x_comm;
+
+/* The RCCL table, built by the library.  RCCL is resolved at run time (dlopen "librccl.so.1" -- inside a PyTorch process
+ * that is torch's own copy -- then /opt/rocm/lib): libv2xgnn.so has no link-time dependency on it.  Without RCCL these
+ * return V2X_EINVAL with the text in v2x_last_error(NULL).  create: every rank passes rank 0's unique id; fills `out` (ctx =
+ * the communicator) for HIP device `device`.                                                                            */
+int  v2x_comm_rccl_unique_id(uint8_t out[128]);
+int  v2x_comm_rccl_create(const uint8_t id[128], int32_t world, int32_t rank, int32_t device, v2x_comm* out);
+int  v2x_comm_rccl_destroy(v2x_comm* c);
+
+#define V2X_DP_ALLREDUCE  0   /* forward + backward, ONE all-reduce of the flat gradient, Adam on every rank              */
+#define V2X_DP_BUCKETS    1   /* the v2x_forward_backward_phase phases; bucket k's all-reduce starts on a stream of the model
+                                 as soon as phase k is done and overlaps the later phases; Adam after all of them          */
+#define V2X_DP_SHARDED    2   /* per bucket: reduce-scatter, Adam on this rank's slice, all-gather of the parameters.  A bucket
+                                 of n floats is cut into `world` slices only when n % (4 world) == 0; otherwise it is
+                                 all-reduced and updated whole.  Adam's moments are then current on the owned slices only.  */
+
+/* One data-parallel fit step on this rank's shard `b` of a global batch of n_graphs_global graphs (node rows for
+ * variable_graphs models; > 0, no local default): forward + backward, the collectives of `form` through `comm`, Keras Adam.
+ * The same launches and collectives, in the same order, as v2xgnn.dp.DataParallelTrainer.train_step in that form; the
+ * collectives are never captured into a hipGraph (with use_graph the compute part is replayed, the rest goes out eagerly).
+ * loss_out: the per-output losses summed over the ranks.  Host batches run forms 1 and 2 without phases (as the Python
+ * trainer does).  A collective that fails: V2X_ECOMM, the text names it and its bucket; in forms 0 and 1, and for a failing
+ * reduction in form 2, Adam is not applied and the iteration count does not advance (a failing all-gather of form 2 comes
+ * after Adam on the owned slices).                                                                                       */
+int  v2x_train_step_dp(v2x_model* m, const v2x_batch* b, const float* y, int y_on_device, int32_t n_graphs_global,
+                       const v2x_comm* comm, int form, float* loss_out, int loss_on_device, void* stream);
+/* v2x_dqn_step under data parallelism: s / s_next / action / reward are this rank's share of a minibatch of n_graphs_global
+ * graphs; one all-reduce of the gradient and of the losses before Adam (form V2X_DP_ALLREDUCE only).                      */
+int  v2x_dqn_step_dp(v2x_model* online, v2x_model* target, const v2x_batch* s, const v2x_batch* s_next,
+                     const int32_t* action, const double* reward, double gamma, int32_t n_graphs_global,
+                     const v2x_comm* comm, float* y_out, float* loss_out, int loss_on_device, void* stream);
 
 /* ---- per-kernel entry points (parity tests; all pointers [dev]) ------------------------ */
 /* AggLayer.call forward: out[q] = sum_{p in N(q)} h[p]            (BS_brain.py:69-76)      */
