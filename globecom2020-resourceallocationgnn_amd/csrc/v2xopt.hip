@@ -11,6 +11,7 @@
 //                 the prefix links' interference is folded once per prefix into thread-private LDS slots
 //   k_opt_reduce  one workgroup per state folds the per-workgroup partials in a fixed order
 //   k_opt_rewards the reward of every index of a range (m = 0: every link is a prefix link)
+//   k_opt_bound_* the same optimum by branch and bound (v2x_opt_search_bound; described above its kernels)
 // Search and rewards call the same opt_prefix_init / opt_eval, and every sum is a left fold in ascending link order that
 // only skips links on other channels, so where the prefix ends does not change a single bit: rewards[best] == best.
 #include "../../include/v2xgnn.h"
@@ -291,6 +292,377 @@ __global__ __launch_bounds__(OPT_BLOCK) void k_opt_rewards(OptParams q, const do
   }
 }
 
+// ------------------------------------------------------------------------------------------------ branch and bound
+// The same optimum without enumerating C^N joint actions (v2x_opt_search_bound): a depth-first search over the links in
+// their natural order, link d branched at depth d, with an admissible upper bound on every completion of a prefix.
+//
+// Node state of a lane (its slots, in LDS):  I[l][c] = tx[l][c] + sum over ASSIGNED k != l on c of cross[l][k][c]
+// for every link l and channel c, and B[r] = sum over assigned k on r of bs[k][r].  Both are left folds over ascending k, as
+// in opt_prefix_init: descending appends the largest k, and backtracking recomputes the one column that changed from
+// scratch, so a slot's bits depend on the prefix alone, never on the path that led to it.  That makes the order of a node's
+// children (by own rate sig / (I + sig2), descending, lower channel first among equals) a function of the prefix too: a
+// lane needs no stack beyond the prefix digits, and a suspended search resumes from (root depth, depth, digits).
+//
+// Bound of a prefix of d links (every factor can only fall as more links are assigned, because interference only grows):
+//   ub = w_v2v * log2( prod_{l < d} (1 + sig[l][a_l] / (I[l][a_l] + sig2)) * prod_{l >= d} (1 + max_c sig[l][c] / (I[l][c] + sig2)) )
+//      + w_v2i * log2( prod_{r < nr} (1 + v2i[r] / (B[r] + sig2)) )
+// -- the sum of every rate's own bound, each sum of logarithms taken as ONE logarithm of a product (two log2, not
+// N * C + C, per node; a product that overflows gives ub = inf, which never prunes).
+//
+// Rounding margin.  u = 2^-53.  I is a sum of <= N positive terms (relative error <= N u), + sig2, the quotient and 1 + x
+// add 3 u: each factor is within (N + 3) u; a product of N of them within N (N + 4) u; so log2 of the product is off by at
+// most 1.4427 * N (N + 4) u <= 1.9e-13 absolutely (N = 32), per unit weight.  A leaf's sum of N logarithms carries the same
+// (N + 3) u per argument, hence the same absolute 1.9e-13 per unit weight, plus relative terms: log2's own rounding, the
+// N + C additions and the two weights, <= (N + C + 8) u <= 6.3e-15.  OPT_BOUND_EPS = 2^-40 = 9.1e-13 is used BOTH as the
+// absolute margin per unit weight (> 2 * 1.9e-13) and as the relative margin (> 140 times 6.3e-15).  A node is pruned only
+// when  ub * (1 + EPS) + EPS * (w_v2v + w_v2i) < incumbent,  strictly: every completion then scores strictly below the
+// incumbent as a leaf would score it, so neither a better action nor an equal one with a lower index is lost.
+//
+// Launches of one round, all on the caller's stream (the host reads two counters back per round, nothing else):
+//   k_opt_bound_search   lanes take work items (state, root depth, depth, prefix digits) through an integer counter and run
+//                        the depth-first search of each for at most `cap` nodes.  An unfinished item goes back into the
+//                        item's own slot of the output queue; while the queue has room its untried siblings along the
+//                        path are split off as items of their own first (that is the breadth-first seeding: round 0 runs
+//                        the root for N + 1 nodes, a greedy dive to the first leaf = the first incumbent).  Leaves are
+//                        scored with opt_prefix_init / opt_eval; the incumbent's bit pattern is shared per state with a
+//                        64-bit integer atomicMax; a lane whose best leaf equals the incumbent when its item ends appends
+//                        (state, index, bits) to the round's candidate list.
+//   k_opt_bound_fold_a/b per state: forget the index when the incumbent rose; per candidate that still equals the
+//                        incumbent: integer atomicMin on the index = opt_better's rule among equal rewards.
+//   k_opt_bound_compact  output queue (with holes: finished items, failed reservations) -> dense input queue of the next
+//                        round, one integer atomic per wave.
+// Every loop is bounded: a lane visits <= cap nodes per item and an item runs once per launch.
+
+constexpr int OPTB_BLOCK = 64;                    // one wave per workgroup: lanes diverge freely, nothing is shared
+constexpr int OPTB_QCAP = 1 << 18;                // work items of a queue
+constexpr int OPTB_CUS = 256;                     // search workgroups: as many per CU as their LDS allows, 3 at most
+constexpr size_t OPTB_LDS_CU = 160 * 1024;        // LDS of a CU; a workgroup may take all of it (15 x 16: 128 KiB of slots)
+constexpr int OPTB_CAP_SEED = 256;                // nodes per item and launch while the queue is short of items ...
+constexpr int OPTB_CAP_RUN = 4096;                // ... and once every lane has several
+constexpr int OPTB_ITEMS_PER_LANE = 4;            // split suspended items while the queue holds fewer than this per lane
+constexpr int OPTB_POLL = 16;                     // nodes between two reads of the shared incumbent
+constexpr double OPT_BOUND_EPS = 0x1p-40;         // see "Rounding margin" above
+constexpr unsigned long long OPTB_NO_INDEX = (unsigned long long)INT64_MAX;
+
+struct OptItem {            // 32 bytes; e < 0: a hole
+  uint64_t lo, hi;          // digits of links 0 .. d - 1
+  int32_t e;                // state
+  int16_t d0, d;            // the item's root depth (never backtracked above), depth of the node to visit next
+  int64_t pad_;
+};
+struct OptCand {
+  unsigned long long bits;  // reward bit pattern
+  int64_t idx;
+  int32_t e, pad_;
+};
+enum { OPTB_HEAD = 0, OPTB_TAIL = 1, OPTB_NCAND = 2, OPTB_OUT = 3, OPTB_NODES = 4, OPTB_CTRL = 8 };
+
+struct OptBoundArgs {
+  OptParams q;                      // p = n, m = 0: the leaf's opt_prefix_init / opt_eval
+  const double* tabs;
+  const OptItem* qin;
+  OptItem* qout;
+  int n_in, cap, allow_split;
+  unsigned long long* ctrl;         // OPTB_* counters
+  unsigned long long* inc;          // [E] incumbent reward bits
+  OptCand* cand;
+  double* leaf;                     // [n + C][lanes] scratch of opt_prefix_init
+};
+
+struct OptSlots {             // slot i of this lane: lane-strided, so a wave's lanes hit consecutive words
+  double* base;
+  __device__ __forceinline__ double& operator[](int i) const { return base[i * OPTB_BLOCK]; }
+};
+
+__device__ __forceinline__ void opt_set_digit(uint64_t& lo, uint64_t& hi, int l, int c) {
+  if (l < 16) lo = (lo & ~(15ull << (4 * l))) | ((uint64_t)c << (4 * l));
+  else hi = (hi & ~(15ull << (4 * (l - 16)))) | ((uint64_t)c << (4 * (l - 16)));
+}
+
+// tx[l][c] + sum over k < dlim, k != l, on channel c of cross[l][k][c], ascending k
+__device__ __forceinline__ double opt_row_fold(const OptParams& q, const double* __restrict__ tab, uint64_t lo, uint64_t hi,
+                                               int l, int c, int dlim) {
+  const int n = q.n, C = q.C;
+  const double* cross = tab + 3ll * n * C;
+  double acc = tab[(int64_t)n * C + l * C + c];
+  for (int k = 0; k < dlim; ++k)
+    if (k != l && opt_digit(lo, hi, k) == c) acc += cross[(l * n + k) * C + c];
+  return acc;
+}
+
+// the child after `cur` (cur < 0: the first) in the order: key descending, lower channel first among equal keys; -1: none
+template <class Key>
+__device__ __forceinline__ int opt_pick_child(Key key, int C, int cur) {
+  const double xc = cur >= 0 ? key(cur) : 0.0;
+  int best = -1;
+  double xb = 0.0;
+  for (int c = 0; c < C; ++c) {
+    const double x = key(c);
+    if (cur >= 0 && !(x < xc || (x == xc && c > cur))) continue;
+    if (best < 0 || x > xb) { best = c; xb = x; }
+  }
+  return best;
+}
+
+// LDS: [the state's table when TAB_LDS (one state, E = 1: every item reads the same table)] [n * C + C slots x 64 lanes].
+// Measured, ten 20-link states: median 317 ms per state with the table read from global memory, 251 ms from LDS; 147 ms
+// with the folds restructured (column-wise, only the links on the channel) and the quotients of the bound four in flight.
+template <bool TAB_LDS>
+__global__ __launch_bounds__(OPTB_BLOCK) void k_opt_bound_search(OptBoundArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double opt_lds[];
+  const OptParams q = a.q;
+  const int n = q.n, C = q.C, nr = q.nr;
+  const int64_t lanes = (int64_t)gridDim.x * OPTB_BLOCK, lane = (int64_t)blockIdx.x * OPTB_BLOCK + threadIdx.x;
+  const int64_t tab_pad = TAB_LDS ? ((q.tab + 1) & ~1ll) : 0;
+  if constexpr (TAB_LDS) {
+    for (int64_t i = threadIdx.x; i < q.tab; i += OPTB_BLOCK) opt_lds[i] = a.tabs[i];
+    __syncthreads();
+  }
+  OptSlots S;
+  S.base = opt_lds + tab_pad + threadIdx.x;
+  double* lf = a.leaf + lane;
+  unsigned long long visited = 0;
+  for (;;) {                                                   // <= n_in items in all lanes together
+    const unsigned long long it = atomicAdd(&a.ctrl[OPTB_HEAD], 1ull);
+    if (it >= (unsigned long long)a.n_in) break;
+    const OptItem item = a.qin[it];
+    const int e = item.e, d0 = item.d0;
+    int d = item.d;
+    uint64_t lo = item.lo, hi = item.hi;
+    const double* tab = TAB_LDS ? opt_lds : a.tabs + (int64_t)e * q.tab;
+    const double* sig = tab;
+    const double* tx = tab + (int64_t)n * C;
+    const double* bs = tab + 2ll * n * C;
+    const double* cross = tab + 3ll * n * C;
+    const double* v2i = cross + (int64_t)n * n * C;
+    // the folds of opt_row_fold for every (l, c) at once: per slot the same additions in the same (ascending k) order
+    for (int i = 0; i < n * C; ++i) S[i] = tx[i];
+    for (int k = 0; k < d; ++k) {
+      const int c = opt_digit(lo, hi, k);
+      for (int l = 0; l < n; ++l)
+        if (l != k) S[l * C + c] += cross[(l * n + k) * C + c];
+    }
+    for (int r = 0; r < C; ++r) {
+      double acc = 0.0;
+      if (r < nr)
+        for (int k = 0; k < d; ++k)
+          if (opt_digit(lo, hi, k) == r) acc += bs[k * C + r];
+      S[n * C + r] = acc;
+    }
+    double incumbent = __longlong_as_double((long long)__hip_atomic_load(&a.inc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    double lr = -1.0;                                          // best leaf of this run of the item
+    int64_t li = INT64_MAX;
+    int cnt = 0;
+    bool visit = true, finished = false;
+    // every iteration visits a node (<= cap of them) or steps one level back (<= n in a row)
+    for (;;) {
+      if (visit) {
+        if (cnt >= a.cap) break;                               // suspended: the node at depth d is still to visit
+        ++cnt;
+        if (d == n) {                                          // leaf: the exhaustive search's own arithmetic
+          opt_prefix_init(q, tab, lo, hi, lf, (int)lanes);
+          const double r = opt_eval(q, tab, lo, hi, 0, lf, (int)lanes);
+          if (r >= 0.0) {                                      // (not NaN)
+            int64_t idx = 0;
+            for (int l = 0; l < n; ++l) idx = idx * C + opt_digit(lo, hi, l);
+            const unsigned long long bits = (unsigned long long)__double_as_longlong(r);
+            const unsigned long long old = atomicMax(&a.inc[e], bits);
+            incumbent = __longlong_as_double((long long)(old > bits ? old : bits));
+            if (opt_better(r, idx, lr, li)) { lr = r; li = idx; }
+          }
+          visit = false;
+          continue;
+        }
+        if ((cnt & (OPTB_POLL - 1)) == 0)
+          incumbent = __longlong_as_double((long long)__hip_atomic_load(&a.inc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+        double pv = 1.0, pi = 1.0;
+        // independent quotients, four in flight: at one wave per SIMD nothing else hides the divide's latency
+#pragma unroll 4
+        for (int l = 0; l < d; ++l) {
+          const int c = opt_digit(lo, hi, l);
+          pv *= 1.0 + sig[l * C + c] / (S[l * C + c] + q.sig2);
+        }
+        for (int l = d; l < n; ++l) {
+          double x = 0.0;
+#pragma unroll 4
+          for (int c = 0; c < C; ++c) x = fmax(x, sig[l * C + c] / (S[l * C + c] + q.sig2));
+          pv *= 1.0 + x;
+        }
+#pragma unroll 4
+        for (int r = 0; r < nr; ++r) pi *= 1.0 + v2i[r] / (S[n * C + r] + q.sig2);
+        const double ub = q.w_v2v * log2(pv) + q.w_v2i * log2(pi);
+        if (ub * (1.0 + OPT_BOUND_EPS) + OPT_BOUND_EPS * (q.w_v2v + q.w_v2i) < incumbent) {
+          visit = false;
+          continue;
+        }
+        const int c = opt_pick_child([&](int cc) { return sig[d * C + cc] / (S[d * C + cc] + q.sig2); }, C, -1);
+        for (int l = 0; l < n; ++l)
+          if (l != d) S[l * C + c] += cross[(l * n + d) * C + c];
+        if (c < nr) S[n * C + c] += bs[d * C + c];
+        opt_set_digit(lo, hi, d, c);
+        ++d;
+      } else {
+        if (d == d0) { finished = true; break; }
+        const int k = d - 1, c = opt_digit(lo, hi, k);
+        d = k;
+        for (int l = 0; l < n; ++l) S[l * C + c] = tx[l * C + c];          // column c again from scratch (opt_row_fold's order)
+        for (int kk = 0; kk < d; ++kk)
+          if (opt_digit(lo, hi, kk) == c)
+            for (int l = 0; l < n; ++l)
+              if (l != kk) S[l * C + c] += cross[(l * n + kk) * C + c];
+        if (c < nr) {
+          double acc = 0.0;
+          for (int kk = 0; kk < d; ++kk)
+            if (opt_digit(lo, hi, kk) == c) acc += bs[kk * C + c];
+          S[n * C + c] = acc;
+        }
+        const int c2 = opt_pick_child([&](int cc) { return sig[k * C + cc] / (S[k * C + cc] + q.sig2); }, C, c);
+        if (c2 >= 0) {
+          for (int l = 0; l < n; ++l)
+            if (l != k) S[l * C + c2] += cross[(l * n + k) * C + c2];
+          if (c2 < nr) S[n * C + c2] += bs[k * C + c2];
+          opt_set_digit(lo, hi, k, c2);
+          d = k + 1;
+          visit = true;
+        }
+      }
+    }
+    visited += (unsigned long long)cnt;
+    if (lr >= 0.0) {
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(lr);
+      if (bits == __hip_atomic_load(&a.inc[e], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
+        const unsigned long long at = atomicAdd(&a.ctrl[OPTB_NCAND], 1ull);     // <= one per item: at < n_in <= OPTB_QCAP
+        OptCand cd;
+        cd.bits = bits;
+        cd.idx = li;
+        cd.e = e;
+        cd.pad_ = 0;
+        a.cand[at] = cd;
+      }
+    }
+    OptItem back;
+    back.lo = lo;
+    back.hi = hi;
+    back.e = finished ? -1 : e;
+    back.d0 = (int16_t)d0;
+    back.d = (int16_t)d;
+    back.pad_ = 0;
+    if (!finished && a.allow_split && d > d0) {
+      // the untried siblings along the path d0 .. d - 1 become items of their own, the node at depth d its own root.
+      // A sibling of link j is ordered by link j's keys at the prefix of j links: the same bits the search would see.
+      int need = 0;
+      for (int j = d0; j < d; ++j) {
+        const int cj = opt_digit(lo, hi, j);
+        const double xc = sig[j * C + cj] / (opt_row_fold(q, tab, lo, hi, j, cj, j) + q.sig2);
+        for (int c = 0; c < C; ++c) {
+          const double x = sig[j * C + c] / (opt_row_fold(q, tab, lo, hi, j, c, j) + q.sig2);
+          if (x < xc || (x == xc && c > cj)) ++need;
+        }
+      }
+      const unsigned long long at = a.n_in + atomicAdd(&a.ctrl[OPTB_TAIL], (unsigned long long)need);
+      if (at + need <= (unsigned long long)OPTB_QCAP) {
+        unsigned long long w = at;
+        for (int j = d0; j < d; ++j) {
+          const int cj = opt_digit(lo, hi, j);
+          const double xc = sig[j * C + cj] / (opt_row_fold(q, tab, lo, hi, j, cj, j) + q.sig2);
+          for (int c = 0; c < C; ++c) {
+            const double x = sig[j * C + c] / (opt_row_fold(q, tab, lo, hi, j, c, j) + q.sig2);
+            if (x < xc || (x == xc && c > cj)) {
+              OptItem sib;
+              sib.lo = j < 16 ? (lo & ((1ull << (4 * j)) - 1)) : lo;
+              sib.hi = j < 16 ? 0ull : (hi & ((1ull << (4 * (j - 16))) - 1));
+              opt_set_digit(sib.lo, sib.hi, j, c);
+              sib.e = e;
+              sib.d0 = sib.d = (int16_t)(j + 1);
+              sib.pad_ = 0;
+              a.qout[w++] = sib;
+            }
+          }
+        }
+        back.d0 = (int16_t)d;
+      } else {                                                 // no room: holes where the reservation lies inside the queue
+        OptItem hole;
+        hole.lo = hole.hi = 0;
+        hole.e = -1;
+        hole.d0 = hole.d = 0;
+        hole.pad_ = 0;
+        for (unsigned long long w = at; w < at + need && w < (unsigned long long)OPTB_QCAP; ++w) a.qout[w] = hole;
+      }
+    }
+    a.qout[it] = back;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) visited += __shfl_xor(visited, off, 64);
+  if (threadIdx.x == 0 && visited) atomicAdd(&a.ctrl[OPTB_NODES], visited);
+}
+
+// grid ceil(E / 256): a fresh search -- one root item per state, no incumbent
+__global__ __launch_bounds__(256) void k_opt_bound_init(int E, OptItem* q0, unsigned long long* inc, unsigned long long* best_idx,
+                                                        unsigned long long* idx_bits, unsigned long long* ctrl) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e < OPTB_CTRL) ctrl[e] = 0;
+  if (e >= E) return;
+  OptItem it;
+  it.lo = it.hi = 0;
+  it.e = e;
+  it.d0 = it.d = 0;
+  it.pad_ = 0;
+  q0[e] = it;
+  inc[e] = 0;                                  // +0.0: rewards are >= 0
+  best_idx[e] = OPTB_NO_INDEX;
+  idx_bits[e] = ~0ull;
+}
+
+// grid ceil(E / 256): the index kept so far belongs to a reward the incumbent has passed
+__global__ __launch_bounds__(256) void k_opt_bound_fold_a(int E, const unsigned long long* inc, unsigned long long* best_idx,
+                                                          unsigned long long* idx_bits) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  if (idx_bits[e] != inc[e]) {
+    idx_bits[e] = inc[e];
+    best_idx[e] = OPTB_NO_INDEX;
+  }
+}
+
+// grid-stride over the round's candidates: the lowest index among those equal to the incumbent
+__global__ __launch_bounds__(256) void k_opt_bound_fold_b(const unsigned long long* ctrl, const OptCand* cand,
+                                                          const unsigned long long* inc, unsigned long long* best_idx) {
+  const unsigned long long nc = ctrl[OPTB_NCAND];
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < nc; i += (unsigned long long)gridDim.x * 256) {
+    const OptCand cd = cand[i];
+    if (cd.bits == inc[cd.e]) atomicMin(&best_idx[cd.e], (unsigned long long)cd.idx);
+  }
+}
+
+// grid-stride, whole waves: src[0, min(n_in + tail, QCAP)) without its holes -> dst, count in ctrl[OPTB_OUT]
+__global__ __launch_bounds__(256) void k_opt_bound_compact(int n_in, unsigned long long* ctrl, const OptItem* src, OptItem* dst) {
+  const unsigned long long total = std::min<unsigned long long>((unsigned long long)n_in + ctrl[OPTB_TAIL], (unsigned long long)OPTB_QCAP);
+  const int ln = threadIdx.x & 63;
+  for (unsigned long long base = ((unsigned long long)blockIdx.x * 256 + threadIdx.x) - ln; base < total;
+       base += (unsigned long long)gridDim.x * 256) {
+    const unsigned long long i = base + ln;
+    OptItem it;
+    it.e = -1;
+    if (i < total) it = src[i];
+    const bool keep = i < total && it.e >= 0;
+    const unsigned long long mask = __ballot(keep);
+    unsigned long long at = 0;
+    if (ln == 0 && mask) at = atomicAdd(&ctrl[OPTB_OUT], (unsigned long long)__popcll(mask));
+    at = __shfl(at, 0, 64);
+    if (keep) dst[at + __popcll(mask & ((1ull << ln) - 1ull))] = it;
+  }
+}
+
+// grid ceil(E / 256)
+__global__ __launch_bounds__(256) void k_opt_bound_finish(int E, const unsigned long long* inc, const unsigned long long* best_idx,
+                                                          int64_t* best_index, double* best_reward) {
+  const int e = blockIdx.x * 256 + threadIdx.x;
+  if (e >= E) return;
+  best_index[e] = (int64_t)best_idx[e];
+  best_reward[e] = __longlong_as_double((long long)inc[e]);
+}
+
 // ---------------------------------------------------------------------------------------------------------------- host
 
 struct OptPlan {
@@ -434,6 +806,139 @@ int v2x_opt_rewards(const v2x_opt_problem* p, void* workspace, int64_t first, in
                      count, out);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_rewards: launch failed: %s", hipGetErrorString(err));
+  return V2X_OK;
+}
+
+}  // extern "C"
+
+// ---- branch and bound: workspace = tables | counters | per-state incumbent, index, index's reward | two queues | candidates
+//      | leaf scratch
+namespace {
+
+struct OptBoundPlan {
+  bool tab_lds;             // the table of the (one) state beside the slots in LDS
+  int wgs;                  // workgroups of a search launch at most
+  size_t lds_bytes;
+  int64_t off_ctrl, off_inc, off_idx, off_bits, off_qa, off_qb, off_cand, off_leaf, bytes;
+};
+
+int opt_bound_plan(const v2x_opt_problem* p, int64_t max_nodes, const char* who, OptPlan& pl, OptBoundPlan& bp) {
+  int rc = opt_plan(p, who, pl);
+  if (rc != V2X_OK) return rc;
+  if (pl.total < 0) OPT_FAIL(V2X_EINVAL, "%s: %d^%d joint actions exceed 2^62 (64-bit indices)", who, pl.q.C, pl.q.n);
+  if (max_nodes < 1) OPT_FAIL(V2X_EINVAL, "%s: max_nodes = %lld (>= 1)", who, (long long)max_nodes);
+  if (!(p->w_v2v >= 0.0) || !(p->w_v2i >= 0.0))
+    OPT_FAIL(V2X_EINVAL, "%s: weights %g / %g (the bound needs both >= 0)", who, p->w_v2v, p->w_v2i);
+  pl.q.p = pl.q.n;
+  pl.q.m = 0;
+  const int64_t slots = (int64_t)pl.q.n * pl.q.C + pl.q.C;
+  bp.lds_bytes = (size_t)slots * OPTB_BLOCK * sizeof(double);       // <= 128 KiB: rb^n <= 2^62 caps n * rb + rb at 256
+  const size_t with_tab = bp.lds_bytes + (size_t)((pl.q.tab + 1) & ~1ll) * sizeof(double);
+  bp.tab_lds = p->E == 1 && with_tab <= OPTB_LDS_CU - 1024;
+  if (bp.tab_lds) bp.lds_bytes = with_tab;
+  if (bp.lds_bytes > OPTB_LDS_CU - 1024)
+    OPT_FAIL(V2X_EINVAL, "%s: %zu bytes of LDS needed (n = %d, rb = %d)", who, bp.lds_bytes, pl.q.n, pl.q.C);
+  bp.wgs = OPTB_CUS * (int)std::min<size_t>(3, (OPTB_LDS_CU - 1024) / bp.lds_bytes);
+  const int64_t lanes = (int64_t)bp.wgs * OPTB_BLOCK;
+  auto al = [](int64_t v) { return (v + 255) & ~255ll; };
+  int64_t o = opt_tables_bytes(p, pl);
+  bp.off_ctrl = o;  o += al(OPTB_CTRL * 8);
+  bp.off_inc = o;   o += al((int64_t)p->E * 8);
+  bp.off_idx = o;   o += al((int64_t)p->E * 8);
+  bp.off_bits = o;  o += al((int64_t)p->E * 8);
+  bp.off_qa = o;    o += al((int64_t)OPTB_QCAP * (int64_t)sizeof(OptItem));
+  bp.off_qb = o;    o += al((int64_t)OPTB_QCAP * (int64_t)sizeof(OptItem));
+  bp.off_cand = o;  o += al((int64_t)OPTB_QCAP * (int64_t)sizeof(OptCand));
+  bp.off_leaf = o;  o += al((int64_t)(pl.q.n + pl.q.C) * lanes * 8);
+  bp.bytes = o;
+  return V2X_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t v2x_opt_bound_workspace_bytes(const v2x_opt_problem* p, int64_t max_nodes) {
+  OptPlan pl;
+  OptBoundPlan bp;
+  if (opt_bound_plan(p, max_nodes, "opt_bound_workspace_bytes", pl, bp) != V2X_OK) return V2X_EINVAL;
+  return bp.bytes;
+}
+
+int v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, int64_t* best_index, double* best_reward,
+                         int64_t* nodes_visited, void* stream) {
+  OptPlan pl;
+  OptBoundPlan bp;
+  int rc = opt_bound_plan(p, max_nodes, "opt_search_bound", pl, bp);
+  if (rc != V2X_OK) return rc;
+  if (!best_index || !best_reward) OPT_FAIL(V2X_EINVAL, "opt_search_bound: null output");
+  hipStream_t s = (hipStream_t)stream;
+  rc = opt_prep(p, pl, workspace, s, "opt_search_bound");
+  if (rc != V2X_OK) return rc;
+  char* ws = (char*)workspace;
+  unsigned long long* ctrl = (unsigned long long*)(ws + bp.off_ctrl);
+  unsigned long long* inc = (unsigned long long*)(ws + bp.off_inc);
+  unsigned long long* idx = (unsigned long long*)(ws + bp.off_idx);
+  unsigned long long* bits = (unsigned long long*)(ws + bp.off_bits);
+  OptItem* qa = (OptItem*)(ws + bp.off_qa);
+  OptItem* qb = (OptItem*)(ws + bp.off_qb);
+  const unsigned egrid = (unsigned)((p->E + 255) / 256);
+  hipError_t err;
+#define OPTB_LAUNCHED(what)                                                                                        \
+  if ((err = hipGetLastError()) != hipSuccess)                                                                     \
+  OPT_FAIL(V2X_EHIP, "opt_search_bound: %s failed: %s", what, hipGetErrorString(err))
+  hipLaunchKernelGGL(k_opt_bound_init, dim3(egrid), dim3(256), 0, s, p->E, qa, inc, idx, bits, ctrl);
+  OPTB_LAUNCHED("init launch");
+  OptBoundArgs a;
+  a.q = pl.q;
+  a.tabs = (const double*)workspace;
+  a.qin = qa;
+  a.qout = qb;
+  a.ctrl = ctrl;
+  a.inc = inc;
+  a.cand = (OptCand*)(ws + bp.off_cand);
+  a.leaf = (double*)(ws + bp.off_leaf);
+  if (bp.lds_bytes > 64 * 1024) {          // above the default dynamic-LDS size a kernel has to be told; the launch check decides
+    if (bp.tab_lds) (void)hipFuncSetAttribute((const void*)k_opt_bound_search<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.lds_bytes);
+    else (void)hipFuncSetAttribute((const void*)k_opt_bound_search<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.lds_bytes);
+    (void)hipGetLastError();
+  }
+  const int64_t short_of = (int64_t)bp.wgs * OPTB_BLOCK * OPTB_ITEMS_PER_LANE;
+  int64_t n_in = p->E, nodes = 0;
+  // one round per pass; every round visits at least one node per item, so the node budget also bounds the rounds
+  for (int64_t round = 0; n_in > 0 && nodes < max_nodes; ++round) {
+    const bool few = n_in < short_of;
+    a.n_in = (int)n_in;
+    a.cap = round == 0 ? pl.q.n + 1 : (few ? OPTB_CAP_SEED : OPTB_CAP_RUN);
+    a.allow_split = few ? 1 : 0;
+    if ((err = hipMemsetAsync(ctrl, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess)
+      OPT_FAIL(V2X_EHIP, "opt_search_bound: counter reset failed: %s", hipGetErrorString(err));
+    const unsigned wgs = (unsigned)std::min<int64_t>(bp.wgs, (n_in + OPTB_BLOCK - 1) / OPTB_BLOCK);
+    if (bp.tab_lds) hipLaunchKernelGGL(k_opt_bound_search<true>, dim3(wgs), dim3(OPTB_BLOCK), bp.lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_opt_bound_search<false>, dim3(wgs), dim3(OPTB_BLOCK), bp.lds_bytes, s, a);
+    OPTB_LAUNCHED("search launch");
+    hipLaunchKernelGGL(k_opt_bound_fold_a, dim3(egrid), dim3(256), 0, s, p->E, inc, idx, bits);
+    OPTB_LAUNCHED("fold launch");
+    hipLaunchKernelGGL(k_opt_bound_fold_b, dim3(64), dim3(256), 0, s, ctrl, a.cand, inc, idx);
+    OPTB_LAUNCHED("fold launch");
+    hipLaunchKernelGGL(k_opt_bound_compact, dim3(256), dim3(256), 0, s, a.n_in, ctrl, a.qout, qa);
+    OPTB_LAUNCHED("compact launch");
+    unsigned long long back[2];                                  // { items of the next round, nodes visited so far }
+    if ((err = hipMemcpyAsync(back, ctrl + OPTB_OUT, sizeof(back), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (err = hipStreamSynchronize(s)) != hipSuccess)
+      OPT_FAIL(V2X_EHIP, "opt_search_bound: round %lld failed: %s", (long long)round, hipGetErrorString(err));
+    n_in = (int64_t)back[0];
+    nodes = (int64_t)back[1];
+  }
+#undef OPTB_LAUNCHED
+  hipLaunchKernelGGL(k_opt_bound_finish, dim3(egrid), dim3(256), 0, s, p->E, inc, idx, best_index, best_reward);
+  if ((err = hipGetLastError()) != hipSuccess)
+    OPT_FAIL(V2X_EHIP, "opt_search_bound: finish launch failed: %s", hipGetErrorString(err));
+  if (nodes_visited) *nodes_visited = nodes;
+  if (n_in > 0)
+    OPT_FAIL(V2X_EBUDGET, "opt_search_bound: node budget spent at %d links x %d channels: %lld nodes visited (max_nodes = %lld), "
+             "%lld subtrees open; the result is the best leaf found, not proven optimal", pl.q.n, pl.q.C, (long long)nodes,
+             (long long)max_nodes, (long long)n_in);
   return V2X_OK;
 }
 

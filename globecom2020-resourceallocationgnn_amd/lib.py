@@ -12,6 +12,7 @@ _LIB = None
 V2X_OK = 0
 V2X_EINVAL = -1
 V2X_ECOMM = -5          # a collective of a v2x_comm table returned non-zero
+V2X_EBUDGET = -6        # v2x_opt_search_bound spent its node budget (the result is a lower bound)
 
 # forms of v2x_train_step_dp
 V2X_DP_ALLREDUCE, V2X_DP_BUCKETS, V2X_DP_SHARDED = 0, 1, 2
@@ -129,6 +130,8 @@ SYMBOLS = [
     ("v2x_opt_workspace_bytes", _L, [C.POINTER(OptProblem)]),
     ("v2x_opt_search", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P]),
     ("v2x_opt_rewards", C.c_int, [C.POINTER(OptProblem), _P, _L, _L, _P, _P]),
+    ("v2x_opt_bound_workspace_bytes", _L, [C.POINTER(OptProblem), _L]),
+    ("v2x_opt_search_bound", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, C.POINTER(_L), _P]),
 ]
 
 

@@ -4,4 +4,4 @@ from .environment import Environ, Vehicle                      # noqa: F401
 from .sim_config import RL_Config                              # noqa: F401
 from .agent import Agent, Memory                               # noqa: F401
 from .batched_env import BatchedEnviron                        # noqa: F401
-from .optimum import OptimalAllocation                          # noqa: F401
+from .optimum import OptimalAllocation, BoundBudgetExceeded     # noqa: F401

@@ -24,7 +24,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 
 
-OPT_BACKENDS = ('host', 'device')
+OPT_BACKENDS = ('host', 'device', 'bound')
 
 
 def _check_opt_backend(opt_backend):
@@ -797,33 +797,41 @@ class Agent(object):
         best = int(np.argmax(rewards))
         return best, float(rewards[best]), res[best]
 
-    def _brute_force_device(self, opt):
+    def _brute_force_device(self, opt, bound=False):
         """_brute_force on the GPU (rl/optimum.py): the kernel picks the index, the numpy reward of the decoded joint action
-        gives the recorded rates and the reward the `reward > 0` rule sees, as on the host path."""
-        index, _ = opt.search(self.env, self.v2v_weight, self.v2i_weight)
+        gives the recorded rates and the reward the `reward > 0` rule sees, as on the host path.  bound: by branch and
+        bound (search_bound) instead of the exhaustive search; the same index."""
+        search = opt.search_bound if bound else opt.search
+        index, _ = search(self.env, self.v2v_weight, self.v2i_weight)
         best = int(index[0])
         res = self.dump_act(opt.decode(best, self.num_D2D, self.num_CH).reshape(self.num_D2D, 1))
         return best, float(self.v2v_weight * np.sum(res[0]) + self.v2i_weight * np.sum(res[1])), res
 
     def _optimum_search(self, opt_backend):
         """-> a callable () -> (index, reward, rates) of the optimum of the CURRENT simulator state.  opt_backend 'host':
-        _brute_force over _joint_actions() (C^N <= 65536); 'device': the exhaustive search in HIP (C^N <= 2^36)."""
+        _brute_force over _joint_actions() (C^N <= 65536); 'device': the exhaustive search in HIP (C^N <= 2^36); 'bound':
+        branch and bound in HIP (the same optimum; up to 32 links, 20 x 4 included)."""
         _check_opt_backend(opt_backend)
         if opt_backend == 'host':
             joint = self._joint_actions()
             return lambda: self._brute_force(joint)
         from .optimum import OptimalAllocation
-        OptimalAllocation.check_size(self.num_D2D, self.num_CH)
+        bound = opt_backend == 'bound'
+        if bound:
+            OptimalAllocation.check_bound(self.num_D2D, self.num_CH, self.v2v_weight, self.v2i_weight)
+        else:
+            OptimalAllocation.check_size(self.num_D2D, self.num_CH)
         if self.num_Neighbor != 1:
-            raise ValueError("opt_backend='device' supports one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor)
+            raise ValueError("opt_backend=%r supports one receiver per link (num_Neighbor = 1), got %d"
+                             % (opt_backend, self.num_Neighbor))
         opt = OptimalAllocation()
-        return lambda: self._brute_force_device(opt)
+        return lambda: self._brute_force_device(opt, bound)
 
     def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host'):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
         :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
-        rl/optimum.py).  Same return tuple as the reference: 15 arrays with opt_flag, 10 without."""
+        rl/optimum.py, or up to 32 links with opt_backend='bound': the same optimum by branch and bound on the GPU).  Same return tuple as the reference: 15 arrays with opt_flag, 10 without."""
         _check_opt_backend(opt_backend)
         n, C = self.num_D2D, self.num_CH
         self.num_Episodes, self.num_Test_Step = num_episodes, num_test_step

@@ -30,8 +30,8 @@ def main(argv=None):
     ap.add_argument("--trials", type=int, default=10)             # :39
     ap.add_argument("--epsilon", type=float, default=0.0)         # :37
     ap.add_argument("--opt", action="store_true")
-    ap.add_argument("--opt-backend", choices=("host", "device"), default="host",
-                    help="where the optimum is searched: numpy on the host (C^N <= 65536) or the GPU (C^N <= 2^36)")
+    ap.add_argument("--opt-backend", choices=("host", "device", "bound"), default="host",
+                    help="where the optimum is searched: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4)")
     ap.add_argument("--seed", type=int, default=1)                # :22
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:

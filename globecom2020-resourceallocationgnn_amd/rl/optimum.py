@@ -10,17 +10,40 @@ among exactly equal rewards the lowest index wins, like np.argmax.
     opt = OptimalAllocation()
     index, reward = opt.search(env, agent.v2v_weight, agent.v2i_weight)      # env: Environ (E = 1) or BatchedEnviron
     actions = opt.decode(index, n, C)                                          # [E, N]
+
+`search` enumerates all C^N joint actions (C^N <= 2^36: 18 links x 4 channels).  `search_bound` finds the same pair by
+branch and bound (v2x_opt_search_bound: a depth-first search that prunes with an upper bound on every completion of a
+partial assignment), which reaches the 20 links x 4 channels the training loops run at, and beyond; its cost depends on
+the state, so it takes a node budget and raises BoundBudgetExceeded with the best allocation found when that is spent.
 """
 import ctypes as C
 
 import numpy as np
 
-from ..lib import OptProblem, check, load_library
+from ..lib import OptProblem, V2X_EBUDGET, check, load_library
 
 MAX_SEARCH = 1 << 36                 # joint actions per state the search accepts (v2x_opt_search)
 MAX_INDEX = 1 << 62                  # ... and the reward range (v2x_opt_rewards)
 HOST_S_PER_ACTION = 57e-6            # one numpy reward of the host path (Agent._brute_force)
 DEVICE_S_PER_ACTION = 2e-10          # search kernel time per joint action at 16 links on one MI355X (DESIGN.md 3.6): the estimate in errors
+
+# Node budget of one search_bound call.  A single CPU thread needed 2.1e5 .. 1.9e6 search-tree nodes for 20 links x 4
+# channels and 2.3e6 .. 9.6e7 for 24 x 4 (DESIGN.md 3.6); the parallel search visits more than that, because subtrees start
+# before the incumbent that would have pruned them is known: 4.8e4 .. 3.0e7 on ten seeded 20-link states, 1.7e6 .. 9.5e7 at
+# 24 links.  2^32 = 4.3e9 is three orders of magnitude above the worst 20-link state of the prototype, 140 times the worst
+# one measured on the GPU and 45 times the worst 24-link one; at the 2.7e7 nodes/s of the longest measured search it ends
+# after about three minutes: a safety stop, not a tuning knob.
+DEFAULT_MAX_NODES = 1 << 32
+
+
+class BoundBudgetExceeded(RuntimeError):
+    """search_bound spent max_nodes before the optimum was proven.  `index` / `reward` ([E] host arrays; torch tensors
+    from search_bound_device): the best joint action found so far in every state -- a lower bound on the optimum, with
+    rewards(first=index, count=1) == reward; index is 2^63 - 1 where no leaf was reached.  `nodes_visited`: nodes spent."""
+
+    def __init__(self, text, index, reward, nodes_visited):
+        RuntimeError.__init__(self, text)
+        self.index, self.reward, self.nodes_visited = index, reward, nodes_visited
 
 
 def decode(index, n, rb):
@@ -88,6 +111,7 @@ class OptimalAllocation(object):
         self.torch = None
         self._ws = None
         self._keep = None
+        self.nodes_visited = 0                            # of the last search_bound
 
     def _init_device(self):
         if self.torch is None:
@@ -110,17 +134,34 @@ class OptimalAllocation(object):
                              % (rb, n, float(total), limit.bit_length() - 1, _seconds(total * DEVICE_S_PER_ACTION),
                                 _seconds(total * HOST_S_PER_ACTION)))
 
-    def _setup(self, env, v2v_weight, v2i_weight, limit):
+    @staticmethod
+    def check_bound(n, rb, v2v_weight=0.0, v2i_weight=0.0, max_nodes=DEFAULT_MAX_NODES):
+        """The argument checks of search_bound (ValueError), before any device work: no cap on rb^n but the 64-bit index."""
+        OptimalAllocation.check_size(n, rb, MAX_INDEX)
+        if not (float(v2v_weight) >= 0.0 and float(v2i_weight) >= 0.0):
+            raise ValueError("the branch-and-bound search needs weights >= 0 (its bound assumes interference can only "
+                             "lower the reward), got %r / %r" % (v2v_weight, v2i_weight))
+        if int(max_nodes) != max_nodes or int(max_nodes) < 1:
+            raise ValueError("max_nodes must be an integer >= 1, got %r" % (max_nodes,))
+
+    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None):
+        """max_nodes not None: the problem of search_bound (its checks, its workspace)."""
         v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
         E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
-        self.check_size(n, rb, limit)
+        if max_nodes is None:
+            self.check_size(n, rb, limit)
+        else:
+            self.check_bound(n, rb, v2v_weight, v2i_weight, max_nodes)
         self._init_device()
         t = self.torch
         dev = [t.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (v2v, v2i, v2i_abs, dest)]
         prob = OptProblem(E=E, n=n, rb=rb, pad_=0, v2v_ff=dev[0].data_ptr(), v2i_ff=dev[1].data_ptr(),
                           v2i_abs=dev[2].data_ptr(), dest=dev[3].data_ptr(), w_v2v=float(v2v_weight),
                           w_v2i=float(v2i_weight), **const)
-        need = int(self._lib.v2x_opt_workspace_bytes(C.byref(prob)))
+        if max_nodes is None:
+            need = int(self._lib.v2x_opt_workspace_bytes(C.byref(prob)))
+        else:
+            need = int(self._lib.v2x_opt_bound_workspace_bytes(C.byref(prob), int(max_nodes)))
         if need < 0:
             check(self._lib, need)
         if self._ws is None or self._ws.numel() < need:
@@ -144,6 +185,34 @@ class OptimalAllocation(object):
     def search(self, env, v2v_weight, v2i_weight):
         """-> (index int64 [E], reward float64 [E]) host arrays: the optimum of every state of the simulator."""
         index, reward = self.search_device(env, v2v_weight, v2i_weight)
+        return index.cpu().numpy(), reward.cpu().numpy()
+
+    def search_bound_device(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES):
+        """search_bound() with the results left on the device: (index int64 [E], reward float64 [E]) torch tensors.
+        `nodes_visited` of the object holds the nodes of the last call."""
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX, max_nodes)
+        t = self.torch
+        index = t.empty(E, dtype=t.int64, device=self.device)
+        reward = t.empty(E, dtype=t.float64, device=self.device)
+        nodes = C.c_int64(0)
+        rc = self._lib.v2x_opt_search_bound(C.byref(prob), self._ws.data_ptr(), int(max_nodes), index.data_ptr(),
+                                            reward.data_ptr(), C.byref(nodes), self._stream())
+        self.nodes_visited = int(nodes.value)
+        if rc == V2X_EBUDGET:
+            msg = self._lib.v2x_last_error(None)
+            raise BoundBudgetExceeded(msg.decode() if msg else "node budget spent", index, reward, self.nodes_visited)
+        check(self._lib, rc)
+        return index, reward
+
+    def search_bound(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES):
+        """The pair search() returns -- the largest reward and, among exactly equal rewards, the lowest index, bit for bit
+        -- by branch and bound: 1..32 links, 2..16 channels, rb^n <= 2^62.  max_nodes: search-tree nodes the call may visit
+        over all states of `env`; BoundBudgetExceeded (carrying the best allocation found) when they are spent."""
+        try:
+            index, reward = self.search_bound_device(env, v2v_weight, v2i_weight, max_nodes)
+        except BoundBudgetExceeded as exc:
+            exc.index, exc.reward = exc.index.cpu().numpy(), exc.reward.cpu().numpy()
+            raise
         return index.cpu().numpy(), reward.cpu().numpy()
 
     def rewards_device(self, env, v2v_weight, v2i_weight, first=0, count=None):

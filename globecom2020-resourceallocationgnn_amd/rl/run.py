@@ -4,7 +4,7 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device]
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound]
 """
 import argparse
 import json
@@ -57,8 +57,8 @@ def main(argv=None):
     ap.add_argument("--test-episodes", type=int, default=10)
     ap.add_argument("--test-steps", type=int, default=50)
     ap.add_argument("--opt", action="store_true", help="also run the brute-force optimum (C^N joint actions)")
-    ap.add_argument("--opt-backend", choices=("host", "device"), default="host",
-                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU (C^N <= 2^36)")
+    ap.add_argument("--opt-backend", choices=("host", "device", "bound"), default="host",
+                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4)")
     ap.add_argument("--seed", type=int, default=11)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:

@@ -66,6 +66,7 @@ extern "C" {
 #define V2X_ENOMEM       -3
 #define V2X_ESTATE       -4   /* call order violated (e.g. backward before forward) */
 #define V2X_ECOMM        -5   /* a collective of a v2x_comm table returned non-zero   */
+#define V2X_EBUDGET      -6   /* v2x_opt_search_bound spent its node budget: the result is a lower bound, not proven */
 
 #define V2X_XE_WIDTH     16   /* packed [x|e|pad] row width */
 
@@ -344,6 +345,19 @@ int  v2x_opt_search(const v2x_opt_problem* p, void* workspace, int64_t* best_ind
 /* out[E][count]: the reward of every index in [first, first + count) (the reference's Curr_Feasible_Reward vector); the
  * same device arithmetic as the search, so out[best_index - first] == best_reward bit for bit */
 int  v2x_opt_rewards(const v2x_opt_problem* p, void* workspace, int64_t first, int64_t count, double* out, void* stream);
+/* The same optimum by branch and bound (a depth-first search with an admissible upper bound on every completion of a
+ * partial assignment; csrc/v2xopt.hip): no cap on rb^n beyond the 64-bit index (rb^n <= 2^62), so 20 links x 4 channels and
+ * more.  Bit for bit the pair v2x_opt_search defines: leaves are scored with the same arithmetic, and nothing is pruned
+ * that could equal the incumbent.  Both weights must be >= 0 (V2X_EINVAL).  max_nodes (>= 1): search-tree nodes the call
+ * may visit over all E states, checked between launches (a launch visits a bounded number); when it is spent the call
+ * returns V2X_EBUDGET with links, channels and nodes in v2x_last_error(NULL), and best_index / best_reward hold the best
+ * leaf found so far: a lower bound, not proven optimal.  nodes_visited: [host], may be NULL; varies from run to run, the
+ * result does not.  Unlike the calls above this one synchronises `stream` once per round of launches to read two counters
+ * back (not capturable); it allocates nothing.  v2x_opt_bound_workspace_bytes: its workspace (>= what v2x_opt_rewards
+ * needs for the same problem); < 0 on a bad problem or budget.                                                          */
+int64_t v2x_opt_bound_workspace_bytes(const v2x_opt_problem* p, int64_t max_nodes);
+int  v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, int64_t* best_index,
+                          double* best_reward, int64_t* nodes_visited, void* stream);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream

@@ -4,6 +4,12 @@ for (N, C) = (4, 4), (8, 4), (12, 4), (16, 4) at one state, 50 states at (8, 4),
 action) and at (8, 4) (extrapolated from the first 4096 joint actions).
 
     python tools/opt_search_timing.py [--out profiles/opt_search_timing.json] [--reps 20]
+
+With --bound: the branch-and-bound search (search_bound, v2x_opt_search_bound) at 12, 16, 20 and 24 links x 4 RBs, ten
+seeded states each (min / median / max of the wall and kernel time per state and of the nodes visited), beside the
+exhaustive search() at 12 and 16 links on the same states in the same run.
+
+    python tools/opt_search_timing.py --bound [--out profiles/opt_bound_timing.json] [--states 10]
 """
 import argparse
 import json
@@ -81,14 +87,94 @@ def host_row(n, first):
             "ms_per_state" + ("" if len(joint) == total else "_extrapolated"): round(dt / len(joint) * total * 1e3, 2)}
 
 
+def _mmm(v):
+    return {"min": float(np.min(v)), "median": float(np.median(v)), "max": float(np.max(v))}
+
+
+def bound_rows(opt, n, states, max_nodes):
+    """search_bound on `states` seeded states of n links x 4 RBs, one call per state: wall of the call (upload, launches,
+    the per-round counter read-backs, download) and the time between HIP events around v2x_opt_search_bound alone; the
+    exhaustive search on the same states at n <= 16 (3 states at 16: 0.8 s each)."""
+    import ctypes
+    import torch
+    from v2xgnn.rl.optimum import BoundBudgetExceeded, MAX_INDEX
+    w_v2v, w_v2i = 1.0, 0.1
+    wall, kern, nodes, spent, ex_wall, results = [], [], [], [], [], []
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    for seed in range(states):
+        env = _state(n, seed)
+        try:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            idx, rew = opt.search_bound(env, w_v2v, w_v2i, max_nodes)
+            wall.append((time.perf_counter() - t0) * 1e3)
+            spent.append(False)
+        except BoundBudgetExceeded as exc:
+            wall.append((time.perf_counter() - t0) * 1e3)
+            idx, rew = exc.index, exc.reward
+            spent.append(True)
+        nodes.append(opt.nodes_visited)
+        results.append((int(idx[0]), float(rew[0])))
+        prob, _, _, _ = opt._setup(env, w_v2v, w_v2i, MAX_INDEX, max_nodes)
+        ix = torch.empty(1, dtype=torch.int64, device=opt.device)
+        rw = torch.empty(1, dtype=torch.float64, device=opt.device)
+        cnt = ctypes.c_int64(0)
+        ev[0].record()
+        opt._lib.v2x_opt_search_bound(ctypes.byref(prob), opt._ws.data_ptr(), int(max_nodes), ix.data_ptr(), rw.data_ptr(),
+                                      ctypes.byref(cnt), opt._stream())
+        ev[1].record()
+        torch.cuda.synchronize()
+        kern.append(ev[0].elapsed_time(ev[1]))
+        if n <= 12 or (n <= 16 and seed < 3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ei, er = opt.search(env, w_v2v, w_v2i)
+            ex_wall.append((time.perf_counter() - t0) * 1e3)
+            assert int(ei[0]) == results[-1][0] and float(er[0]) == results[-1][1], (n, seed)
+        print(json.dumps({"n": n, "seed": seed, "wall_ms": round(wall[-1], 3), "kernel_ms": round(kern[-1], 3),
+                          "nodes": nodes[-1], "budget_spent": spent[-1], "index": results[-1][0],
+                          "reward": results[-1][1]}), flush=True)
+    row = {"case": "bound %d links" % n, "n": n, "rb": 4, "states": states, "joint_actions_per_state": 4 ** n,
+           "max_nodes": int(max_nodes), "wall_ms_per_state": _mmm(wall), "kernel_ms_per_state": _mmm(kern),
+           "nodes_visited": _mmm(nodes), "states_that_spent_the_budget": int(np.sum(spent)),
+           "nodes_per_s_kernel_median": float("%.4g" % (np.median(np.array(nodes) / (np.array(kern) * 1e-3))))}
+    if ex_wall:
+        row["exhaustive_wall_ms_per_state"] = _mmm(ex_wall)
+        row["exhaustive_states"] = len(ex_wall)
+    return row
+
+
+def main_bound(args):
+    import torch
+    from v2xgnn.rl import OptimalAllocation
+    from v2xgnn.rl.optimum import DEFAULT_MAX_NODES
+    opt = OptimalAllocation()
+    opt.search_bound(_state(8), 1.0, 0.1)                              # warm-up: code objects, workspace
+    rows = []
+    for n in args.links:
+        rows.append(bound_rows(opt, n, args.states, DEFAULT_MAX_NODES))
+        print(json.dumps(rows[-1]), flush=True)
+    out = {"device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--bound", action="store_true", help="measure the branch-and-bound search instead")
+    ap.add_argument("--states", type=int, default=10, help="--bound: seeded states per size")
+    ap.add_argument("--links", type=int, nargs="+", default=[12, 16, 20, 24], help="--bound: sizes")
     args = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("opt_search_timing.py measures the GPU search: no GPU here")
+    if args.bound:
+        return main_bound(args)
     from v2xgnn.rl import OptimalAllocation
     opt = OptimalAllocation()
     rows = []
