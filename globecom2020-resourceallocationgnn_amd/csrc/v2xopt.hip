@@ -12,6 +12,8 @@
 //   k_opt_reduce  one workgroup per state folds the per-workgroup partials in a fixed order
 //   k_opt_rewards the reward of every index of a range (m = 0: every link is a prefix link)
 //   k_opt_bound_* the same optimum by branch and bound (v2x_opt_search_bound; described above its kernels)
+//   k_opt_local_* a near-optimal allocation for up to 128 links by multi-start local search (v2x_opt_search_local; described
+//                 above its kernels), k_opt_rewards_actions: the reward of joint actions given as channel arrays
 // Search and rewards call the same opt_prefix_init / opt_eval, and every sum is a left fold in ascending link order that
 // only skips links on other channels, so where the prefix ends does not change a single bit: rewards[best] == best.
 #include "../../include/v2xgnn.h"
@@ -614,6 +616,37 @@ __global__ __launch_bounds__(256) void k_opt_bound_init(int E, OptItem* q0, unsi
   idx_bits[e] = ~0ull;
 }
 
+// grid-stride over the states (v2x_opt_search_bound_seeded): the caller's start action of state e, scored as a leaf with
+// the search's own arithmetic, becomes the incumbent, and its index the first candidate -- exactly the state a lane leaves
+// behind that found this leaf.  A start with a channel outside [0, C) or a reward that is not a number seeds nothing.
+// slots: [n + C][ld] scratch of opt_prefix_init, ld = threads of the launch.
+__global__ __launch_bounds__(256) void k_opt_bound_seed(OptParams q, const double* __restrict__ tabs, int E,
+                                                        const int32_t* __restrict__ start, unsigned long long* inc,
+                                                        unsigned long long* best_idx, unsigned long long* idx_bits, double* slots) {
+  const int ld = (int)(gridDim.x * 256), t = (int)(blockIdx.x * 256 + threadIdx.x);
+  for (int e = t; e < E; e += ld) {
+    uint64_t lo = 0, hi = 0;
+    int64_t idx = 0;
+    bool ok = true;
+    for (int l = 0; l < q.n; ++l) {
+      int c = start[(int64_t)e * q.n + l];
+      if (c < 0 || c >= q.C) { ok = false; c = 0; }
+      opt_set_digit(lo, hi, l, c);
+      idx = idx * q.C + c;
+    }
+    if (!ok) continue;
+    const double* tab = tabs + (int64_t)e * q.tab;
+    opt_prefix_init(q, tab, lo, hi, slots + t, ld);
+    const double r = opt_eval(q, tab, lo, hi, 0, slots + t, ld);
+    if (r >= 0.0) {                                            // (not NaN)
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(r);
+      inc[e] = bits;
+      best_idx[e] = (unsigned long long)idx;
+      idx_bits[e] = bits;
+    }
+  }
+}
+
 // grid ceil(E / 256): the index kept so far belongs to a reward the incumbent has passed
 __global__ __launch_bounds__(256) void k_opt_bound_fold_a(int E, const unsigned long long* inc, unsigned long long* best_idx,
                                                           unsigned long long* idx_bits) {
@@ -865,8 +898,13 @@ int64_t v2x_opt_bound_workspace_bytes(const v2x_opt_problem* p, int64_t max_node
   return bp.bytes;
 }
 
-int v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, int64_t* best_index, double* best_reward,
-                         int64_t* nodes_visited, void* stream) {
+}  // extern "C"
+
+namespace {
+
+// v2x_opt_search_bound (start_actions NULL: the launches it always made) and v2x_opt_search_bound_seeded
+int opt_search_bound_impl(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, const int32_t* start_actions,
+                          int64_t* best_index, double* best_reward, int64_t* nodes_visited, void* stream) {
   OptPlan pl;
   OptBoundPlan bp;
   int rc = opt_bound_plan(p, max_nodes, "opt_search_bound", pl, bp);
@@ -889,6 +927,13 @@ int v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_
   OPT_FAIL(V2X_EHIP, "opt_search_bound: %s failed: %s", what, hipGetErrorString(err))
   hipLaunchKernelGGL(k_opt_bound_init, dim3(egrid), dim3(256), 0, s, p->E, qa, inc, idx, bits, ctrl);
   OPTB_LAUNCHED("init launch");
+  if (start_actions) {
+    const int64_t lanes = (int64_t)bp.wgs * OPTB_BLOCK;          // the leaf scratch holds this many slot columns
+    const unsigned sgrid = (unsigned)std::min<int64_t>(egrid, lanes / 256);
+    hipLaunchKernelGGL(k_opt_bound_seed, dim3(sgrid), dim3(256), 0, s, pl.q, (const double*)workspace, p->E, start_actions, inc,
+                       idx, bits, (double*)(ws + bp.off_leaf));
+    OPTB_LAUNCHED("seed launch");
+  }
   OptBoundArgs a;
   a.q = pl.q;
   a.tabs = (const double*)workspace;
@@ -939,6 +984,492 @@ int v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_
     OPT_FAIL(V2X_EBUDGET, "opt_search_bound: node budget spent at %d links x %d channels: %lld nodes visited (max_nodes = %lld), "
              "%lld subtrees open; the result is the best leaf found, not proven optimal", pl.q.n, pl.q.C, (long long)nodes,
              (long long)max_nodes, (long long)n_in);
+  return V2X_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, int64_t* best_index, double* best_reward,
+                         int64_t* nodes_visited, void* stream) {
+  return opt_search_bound_impl(p, workspace, max_nodes, nullptr, best_index, best_reward, nodes_visited, stream);
+}
+
+int v2x_opt_search_bound_seeded(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, const int32_t* start_actions,
+                                int64_t* best_index, double* best_reward, int64_t* nodes_visited, void* stream) {
+  if (!start_actions) OPT_FAIL(V2X_EINVAL, "opt_search_bound_seeded: null start_actions");
+  return opt_search_bound_impl(p, workspace, max_nodes, start_actions, best_index, best_reward, nodes_visited, stream);
+}
+
+}  // extern "C"
+
+// -------------------------------------------------------------------------------------------------- local search
+// A near-optimal allocation where the exact searches cannot go (v2x_opt_search_local: 1..128 links): a multi-start
+// best-response local search, one wave per (state, restart), a lane per link (two above 64 links).  A joint action is an
+// array of channel numbers here, never an index.
+//
+//   start    restart 0: a[l] = l mod C; restart r: a[l] = splitmix64((seed << 32) ^ (r << 8) ^ l) mod C
+//   sweep    for l = 0 .. n - 1: the total reward of each of the C channels of link l with the other links fixed; move to the
+//            best one (lowest channel among equals) if it is strictly larger than the current total.  Sweeps repeat until
+//            one makes no move, max_sweeps at most.
+//   result   of a restart: its action, scored from scratch by optl_score -- the additions of opt_prefix_init / opt_eval with
+//            every link a prefix link, in their order, so the reward equals v2x_opt_rewards of the action's index bit for
+//            bit; of a state: the best restart by (larger reward, else lexicographically lower action): opt_better's rule.
+//
+// Wave state in LDS: I[c][l] = tx[l][c] + sum over the OTHER links k on c of cross[l][k][c] for every channel c (what link l
+// would suffer on c), B[r] = sum over the links on r of bs[k][r].  A visit of link k (k on channel o):
+//   1. column o is folded again over the links that remain -- never `big + small - big`: linear-domain terms span ten orders
+//      of magnitude.  The wave's ballot of "on channel o" gives the links to add; each is one coalesced load of the
+//      receiver-minor copy crossT[k][c][l] of the cross table (k_opt_local_transpose).
+//   2. every other link l holds two rates: without k, and with k on l's channel.  The total of candidate c is one wave sum of
+//      (l on c ? with : without), lane c adding link k's own rate on c and the V2I rates: C wave sums, 2 log2 per lane.
+//      A butterfly sum leaves the same bits in every lane, so the decision is wave-uniform.
+//   3. k is appended to the column of its new channel.
+constexpr int OPTL_MAX_N = 128, OPTL_MAX_RESTARTS = 65536;
+constexpr int OPTL_BLOCK = 64;                    // one wave
+constexpr int OPTL_BATCH = 8;                     // interferer columns in flight while a column is folded again
+constexpr int64_t OPTL_REWARDS_WGS = 1 << 20;     // workgroups of a v2x_opt_rewards_actions launch (grid-stride beyond)
+
+namespace {
+
+struct OptLocalArgs {
+  OptParams q;                 // p = n, m = 0
+  const double* tabs;          // [E][tab]
+  const double* crossT;        // [E][n][C][n]: cross[l][k][c] at [k][c][l]
+  int restarts, max_sweeps;
+  unsigned long long seed;
+  uint8_t* act;                // [E][R][n]   final action of every restart
+  double* rew;                 // [E][R]
+  uint8_t* conv;               // [E][R]      the last sweep made no move
+  int32_t* all_actions;        // [E][R][n], may be null
+  double* all_rewards;         // [E][R], may be null
+};
+
+__host__ __device__ inline unsigned long long optl_splitmix64(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
+__device__ __forceinline__ double optl_wave_sum(double x) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// doubles of dynamic LDS of a wave: I[C][n] | B[C] | rates[n + C] | action bytes
+inline size_t optl_search_lds(int n, int C) { return (size_t)((int64_t)C * n + C + n + C) * sizeof(double) + (size_t)((n + 7) & ~7); }
+inline size_t optl_score_lds(int n, int C) { return (size_t)(n + C) * sizeof(double) + (size_t)((n + 7) & ~7); }
+
+// grid (ceil(n * n * C / 256), E): crossT[k][c][l] = cross[l][k][c]
+__global__ __launch_bounds__(256) void k_opt_local_transpose(int n, int C, int64_t tab, const double* __restrict__ tabs,
+                                                             double* __restrict__ crossT) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x, total = (int64_t)n * n * C;
+  if (i >= total) return;
+  const int e = blockIdx.y;
+  const int l = (int)(i % n), c = (int)((i / n) % C), k = (int)(i / ((int64_t)n * C));
+  crossT[(int64_t)e * total + i] = tabs[(int64_t)e * tab + 3ll * n * C + ((int64_t)l * n + k) * C + c];
+}
+
+// The wave's reward of the joint action ab[0..n) (LDS bytes, every one in [0, C)), valid in lane 0: per link the left fold
+// of opt_prefix_init (ascending k, only the links on the same channel), per rate the expression of opt_eval, then the two
+// sums in link / RB order by one lane.  red: n + C doubles of LDS.
+template <int LPL>
+__device__ __forceinline__ double optl_score(const OptParams& q, const double* __restrict__ tab, const double* __restrict__ crossT,
+                                             const uint8_t* ab, double* red, int lane) {
+#pragma clang fp contract(off)
+  const int n = q.n, C = q.C;
+  const double* sig = tab;
+  const double* tx = tab + (int64_t)n * C;
+  const double* bs = tab + 2ll * n * C;
+  const double* v2i = tab + 3ll * n * C + (int64_t)n * n * C;
+#pragma unroll
+  for (int h = 0; h < LPL; ++h) {
+    const int l = lane + 64 * h;
+    if (l < n) {
+      const int c = ab[l];
+      double acc = tx[l * C + c];
+      for (int k = 0; k < n; ++k)
+        if (k != l && ab[k] == c) acc += crossT[((int64_t)k * C + c) * n + l];
+      red[l] = log2(1.0 + sig[l * C + c] / (acc + q.sig2));
+    }
+  }
+  if (lane < q.nr) {
+    double b = 0.0;
+    for (int k = 0; k < n; ++k)
+      if (ab[k] == lane) b += bs[k * C + lane];
+    red[n + lane] = log2(1.0 + v2i[lane] / (b + q.sig2));
+  }
+  __syncthreads();
+  double out = 0.0;
+  if (lane == 0) {
+    double v2v_sum = 0.0, v2i_sum = 0.0;
+    for (int l = 0; l < n; ++l) v2v_sum += red[l];
+    for (int r = 0; r < q.nr; ++r) v2i_sum += red[n + r];
+    out = q.w_v2v * v2v_sum + q.w_v2i * v2i_sum;
+  }
+  __syncthreads();
+  return out;
+}
+
+// grid (restarts, E): the restarts of a state are neighbours in dispatch order and share its tables in L2.
+template <int LPL>
+__global__ __launch_bounds__(OPTL_BLOCK) void k_opt_local_search(OptLocalArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double opt_lds[];
+  const OptParams q = a.q;
+  const int n = q.n, C = q.C, nr = q.nr;
+  const int lane = threadIdx.x, r = blockIdx.x, e = blockIdx.y;
+  const double* tab = a.tabs + (int64_t)e * q.tab;
+  const double* crossT = a.crossT + (int64_t)e * n * n * C;
+  const double* sig = tab;
+  const double* tx = tab + (int64_t)n * C;
+  const double* bs = tab + 2ll * n * C;
+  const double* v2i = tab + 3ll * n * C + (int64_t)n * n * C;
+  double* I = opt_lds;                       // [C][n]
+  double* B = I + C * n;                     // [C]
+  double* red = B + C;                       // [n + C]
+  uint8_t* ab = (uint8_t*)(red + n + C);     // [n]
+  int act[LPL];
+#pragma unroll
+  for (int h = 0; h < LPL; ++h) {
+    const int l = lane + 64 * h;
+    act[h] = -1;
+    if (l < n) {
+      act[h] = r == 0 ? l % C
+                      : (int)(optl_splitmix64((a.seed << 32) ^ ((unsigned long long)r << 8) ^ (unsigned long long)l) % (unsigned)C);
+      ab[l] = (uint8_t)act[h];
+    }
+  }
+  __syncthreads();
+#pragma unroll
+  for (int h = 0; h < LPL; ++h) {
+    const int l = lane + 64 * h;
+    if (l < n) {
+      for (int c = 0; c < C; ++c) I[c * n + l] = tx[l * C + c];
+      for (int j = 0; j < n; ++j) {
+        const int cj = ab[j];
+        if (j != l) I[cj * n + l] += crossT[((int64_t)j * C + cj) * n + l];
+      }
+    }
+  }
+  if (lane < C) {
+    double b = 0.0;
+    if (lane < nr)
+      for (int j = 0; j < n; ++j)
+        if (ab[j] == lane) b += bs[j * C + lane];
+    B[lane] = b;
+  }
+  __syncthreads();
+  int converged = 0;
+  for (int sweep = 0; sweep < a.max_sweeps; ++sweep) {
+    bool moved = false;
+    for (int k = 0; k < n; ++k) {
+      const int o = ab[k];
+      // 1. column o without link k, folded over the links that remain (ascending)
+      double acc[LPL];
+#pragma unroll
+      for (int h = 0; h < LPL; ++h) {
+        const int l = lane + 64 * h;
+        acc[h] = l < n ? tx[l * C + o] : 0.0;
+      }
+      double bo = 0.0;
+#pragma unroll
+      for (int g = 0; g < LPL; ++g) {
+        unsigned long long on = __ballot(act[g] == o);
+        if ((k >> 6) == g) on &= ~(1ull << (k & 63));
+        while (on) {                                           // <= 64 links, OPTL_BATCH per turn
+          // the loads of a batch are independent and go out together; the additions keep their ascending order
+          int jj[OPTL_BATCH];
+          double v[OPTL_BATCH][LPL], vb[OPTL_BATCH];
+#pragma unroll
+          for (int u = 0; u < OPTL_BATCH; ++u) {
+            jj[u] = on ? 64 * g + (int)__builtin_ctzll(on) : -1;
+            on &= on - 1;                                      // (0 stays 0)
+          }
+#pragma unroll
+          for (int u = 0; u < OPTL_BATCH; ++u) {
+            const double* col = crossT + ((int64_t)(jj[u] < 0 ? 0 : jj[u]) * C + o) * n;
+#pragma unroll
+            for (int h = 0; h < LPL; ++h) {
+              const int l = lane + 64 * h;
+              v[u][h] = (jj[u] >= 0 && l < n) ? col[l] : 0.0;
+            }
+            vb[u] = (jj[u] >= 0 && o < nr) ? bs[jj[u] * C + o] : 0.0;
+          }
+#pragma unroll
+          for (int u = 0; u < OPTL_BATCH; ++u) {
+            if (jj[u] >= 0) {
+#pragma unroll
+              for (int h = 0; h < LPL; ++h)
+                if (lane + 64 * h != jj[u]) acc[h] += v[u][h];
+              if (o < nr) bo += vb[u];
+            }
+          }
+        }
+      }
+#pragma unroll
+      for (int h = 0; h < LPL; ++h) {
+        const int l = lane + 64 * h;
+        if (l < n) I[o * n + l] = acc[h];
+      }
+      if (lane == 0) B[o] = bo;
+      __syncthreads();
+      // 2. both rates of every other link; lane c: link k's own rate on c and the V2I rate of RB c without / with k
+      double r0[LPL], r1[LPL];
+#pragma unroll
+      for (int h = 0; h < LPL; ++h) {
+        const int l = lane + 64 * h;
+        r0[h] = r1[h] = 0.0;
+        if (l < n && l != k) {
+          const int c = act[h];
+          const double x = I[c * n + l], s = sig[l * C + c];
+          r0[h] = log2(1.0 + s / (x + q.sig2));
+          r1[h] = log2(1.0 + s / ((x + crossT[((int64_t)k * C + c) * n + l]) + q.sig2));
+        }
+      }
+      double own = 0.0, v0 = 0.0, v1 = 0.0;
+      if (lane < C) {
+        own = log2(1.0 + sig[k * C + lane] / (I[lane * n + k] + q.sig2));
+        if (lane < nr) {
+          v0 = log2(1.0 + v2i[lane] / (B[lane] + q.sig2));
+          v1 = log2(1.0 + v2i[lane] / ((B[lane] + bs[k * C + lane]) + q.sig2));
+        }
+      }
+      int best = 0;
+      double best_t = 0.0, cur_t = 0.0;
+      for (int c = 0; c < C; ++c) {
+        double t = 0.0;
+#pragma unroll
+        for (int h = 0; h < LPL; ++h) t += (lane + 64 * h != k && act[h] == c) ? r1[h] : r0[h];
+        t *= q.w_v2v;
+        if (lane < C) t += lane == c ? q.w_v2v * own + q.w_v2i * v1 : q.w_v2i * v0;
+        t = optl_wave_sum(t);
+        if (c == o) cur_t = t;
+        if (c == 0 || t > best_t) { best = c; best_t = t; }
+      }
+      const int to = best_t > cur_t ? best : o;
+      // 3. link k joins the column of its channel
+      const double* colk = crossT + ((int64_t)k * C + to) * n;
+#pragma unroll
+      for (int h = 0; h < LPL; ++h) {
+        const int l = lane + 64 * h;
+        if (l < n && l != k) I[to * n + l] += colk[l];
+        if (l == k) { act[h] = to; ab[k] = (uint8_t)to; }
+      }
+      if (lane == 0 && to < nr) B[to] += bs[k * C + to];
+      moved |= to != o;
+      __syncthreads();
+    }
+    if (!moved) { converged = 1; break; }
+  }
+  const double reward = optl_score<LPL>(q, tab, crossT, ab, red, lane);
+  const int64_t at = (int64_t)e * a.restarts + r;
+#pragma unroll
+  for (int h = 0; h < LPL; ++h) {
+    const int l = lane + 64 * h;
+    if (l < n) {
+      a.act[at * n + l] = (uint8_t)act[h];
+      if (a.all_actions) a.all_actions[at * n + l] = act[h];
+    }
+  }
+  if (lane == 0) {
+    a.rew[at] = reward;
+    a.conv[at] = (uint8_t)converged;
+    if (a.all_rewards) a.all_rewards[at] = reward;
+  }
+}
+
+// restart i beats restart b of the same state: larger reward (a reward that is not a number counts as -inf), else the
+// lexicographically lower action, else the lower restart (the same action: only the reported restart depends on it)
+__device__ __forceinline__ bool optl_better(const double* rew, const uint8_t* act, int n, int i, int b) {
+  if (b < 0) return true;
+  const double ri = rew[i] == rew[i] ? rew[i] : -INFINITY, rb = rew[b] == rew[b] ? rew[b] : -INFINITY;
+  if (ri != rb) return ri > rb;
+  const uint8_t* ai = act + (int64_t)i * n;
+  const uint8_t* ab = act + (int64_t)b * n;
+  for (int l = 0; l < n; ++l)
+    if (ai[l] != ab[l]) return ai[l] < ab[l];
+  return i < b;
+}
+
+// grid E: the best restart of a state; the rule has a unique answer, so the order of the comparisons does not matter
+__global__ __launch_bounds__(256) void k_opt_local_best(int n, int restarts, const double* __restrict__ rew,
+                                                        const uint8_t* __restrict__ act, const uint8_t* __restrict__ conv,
+                                                        int32_t* best_actions, double* best_reward, int32_t* best_info) {
+  __shared__ int cand[256];
+  const int e = blockIdx.x;
+  rew += (int64_t)e * restarts;
+  act += (int64_t)e * restarts * n;
+  int b = -1;
+  for (int i = threadIdx.x; i < restarts; i += 256)
+    if (optl_better(rew, act, n, i, b)) b = i;
+  cand[threadIdx.x] = b;
+  __syncthreads();
+  for (int half = 128; half > 0; half >>= 1) {
+    if ((int)threadIdx.x < half) {
+      const int i = cand[threadIdx.x + half];
+      if (i >= 0 && optl_better(rew, act, n, i, cand[threadIdx.x])) cand[threadIdx.x] = i;
+    }
+    __syncthreads();
+  }
+  b = cand[0];                                                 // >= 0: restarts >= 1
+  for (int l = threadIdx.x; l < n; l += 256) best_actions[(int64_t)e * n + l] = act[(int64_t)b * n + l];
+  if (threadIdx.x == 0) {
+    best_reward[e] = rew[b];
+    if (best_info) {
+      best_info[2 * e] = b;
+      best_info[2 * e + 1] = conv[(int64_t)e * restarts + b];
+    }
+  }
+}
+
+// grid (chunks, E), one wave per joint action: out[e][j] = reward of actions[e][j][0..n); a channel outside [0, C): NaN
+template <int LPL>
+__global__ __launch_bounds__(OPTL_BLOCK) void k_opt_rewards_actions(OptParams q, const double* __restrict__ tabs,
+                                                                    const double* __restrict__ crossT_all,
+                                                                    const int32_t* __restrict__ actions, int64_t K, double* out) {
+  extern __shared__ double opt_lds[];
+  const int n = q.n, C = q.C, lane = threadIdx.x, e = blockIdx.y;
+  const double* tab = tabs + (int64_t)e * q.tab;
+  const double* crossT = crossT_all + (int64_t)e * n * n * C;
+  double* red = opt_lds;                     // [n + C]
+  uint8_t* ab = (uint8_t*)(red + n + C);     // [n]
+  for (int64_t j = blockIdx.x; j < K; j += gridDim.x) {
+    const int32_t* src = actions + ((int64_t)e * K + j) * n;
+    bool bad = false;
+#pragma unroll
+    for (int h = 0; h < LPL; ++h) {
+      const int l = lane + 64 * h;
+      if (l < n) {
+        const int c = src[l];
+        if (c < 0 || c >= C) bad = true;
+        else ab[l] = (uint8_t)c;
+      }
+    }
+    const bool any_bad = __ballot(bad) != 0ull;
+    __syncthreads();
+    double r = __builtin_nan("");
+    if (!any_bad) r = optl_score<LPL>(q, tab, crossT, ab, red, lane);
+    if (lane == 0) out[(int64_t)e * K + j] = r;
+    __syncthreads();
+  }
+}
+
+struct OptLocalPlan {
+  OptParams q;
+  int64_t off_crossT, off_rew, off_act, off_conv, bytes;
+};
+
+int opt_local_plan(const v2x_opt_problem* p, int restarts, const char* who, OptLocalPlan& lp) {
+  if (!p) OPT_FAIL(V2X_EINVAL, "%s: null problem", who);
+  if (p->E < 1 || p->E > 65535) OPT_FAIL(V2X_EINVAL, "%s: E = %d states (1..65535)", who, p->E);
+  if (p->n < 1 || p->n > OPTL_MAX_N) OPT_FAIL(V2X_EINVAL, "%s: n = %d links (1..%d)", who, p->n, OPTL_MAX_N);
+  if (p->rb < OPT_MIN_C || p->rb > OPT_MAX_C) OPT_FAIL(V2X_EINVAL, "%s: rb = %d channels (%d..%d)", who, p->rb, OPT_MIN_C, OPT_MAX_C);
+  if (restarts < 1 || restarts > OPTL_MAX_RESTARTS)
+    OPT_FAIL(V2X_EINVAL, "%s: restarts = %d (1..%d)", who, restarts, OPTL_MAX_RESTARTS);
+  OptParams& q = lp.q;
+  q.n = q.p = p->n;
+  q.m = 0;
+  q.C = p->rb;
+  q.nr = std::min(p->rb, p->n);
+  q.tab = opt_tab_doubles(q.n, q.C);
+  q.sig2 = p->sig2;
+  q.w_v2v = p->w_v2v;
+  q.w_v2i = p->w_v2i;
+  auto al = [](int64_t v) { return (v + 255) & ~255ll; };
+  const int64_t ER = (int64_t)p->E * restarts;
+  int64_t o = al((int64_t)p->E * q.tab * 8);
+  lp.off_crossT = o;  o += al((int64_t)p->E * q.n * q.n * q.C * 8);
+  lp.off_rew = o;     o += al(ER * 8);
+  lp.off_act = o;     o += al(ER * q.n);
+  lp.off_conv = o;    o += al(ER);
+  lp.bytes = o;
+  return V2X_OK;
+}
+
+// tables and their receiver-minor cross copy: two launches
+int opt_local_prep(const v2x_opt_problem* p, const OptLocalPlan& lp, void* workspace, hipStream_t s, const char* who) {
+  OptPlan pl;
+  pl.q = lp.q;
+  int rc = opt_prep(p, pl, workspace, s, who);
+  if (rc != V2X_OK) return rc;
+  const int64_t total = (int64_t)lp.q.n * lp.q.n * lp.q.C;
+  hipLaunchKernelGGL(k_opt_local_transpose, dim3((unsigned)((total + 255) / 256), (unsigned)p->E), dim3(256), 0, s, lp.q.n, lp.q.C,
+                     lp.q.tab, (const double*)workspace, (double*)((char*)workspace + lp.off_crossT));
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "%s: transpose launch failed: %s", who, hipGetErrorString(err));
+  return V2X_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t v2x_opt_local_workspace_bytes(const v2x_opt_problem* p, int32_t restarts) {
+  OptLocalPlan lp;
+  if (opt_local_plan(p, restarts, "opt_local_workspace_bytes", lp) != V2X_OK) return V2X_EINVAL;
+  return lp.bytes;
+}
+
+int v2x_opt_search_local(const v2x_opt_problem* p, void* workspace, int32_t restarts, uint64_t seed, int32_t max_sweeps,
+                         int32_t* best_actions, double* best_reward, int32_t* best_info, int32_t* all_actions,
+                         double* all_rewards, void* stream) {
+  OptLocalPlan lp;
+  int rc = opt_local_plan(p, restarts, "opt_search_local", lp);
+  if (rc != V2X_OK) return rc;
+  if (max_sweeps < 1) OPT_FAIL(V2X_EINVAL, "opt_search_local: max_sweeps = %d (>= 1)", max_sweeps);
+  if (!best_actions || !best_reward) OPT_FAIL(V2X_EINVAL, "opt_search_local: null output");
+  hipStream_t s = (hipStream_t)stream;
+  rc = opt_local_prep(p, lp, workspace, s, "opt_search_local");
+  if (rc != V2X_OK) return rc;
+  char* ws = (char*)workspace;
+  OptLocalArgs a;
+  a.q = lp.q;
+  a.tabs = (const double*)workspace;
+  a.crossT = (const double*)(ws + lp.off_crossT);
+  a.restarts = restarts;
+  a.max_sweeps = max_sweeps;
+  a.seed = seed;
+  a.act = (uint8_t*)(ws + lp.off_act);
+  a.rew = (double*)(ws + lp.off_rew);
+  a.conv = (uint8_t*)(ws + lp.off_conv);
+  a.all_actions = all_actions;
+  a.all_rewards = all_rewards;
+  const size_t lds = optl_search_lds(lp.q.n, lp.q.C);          // <= 17.5 KiB (128 x 16)
+  const dim3 grid((unsigned)restarts, (unsigned)p->E);
+  if (lp.q.n <= 64) hipLaunchKernelGGL(k_opt_local_search<1>, grid, dim3(OPTL_BLOCK), lds, s, a);
+  else hipLaunchKernelGGL(k_opt_local_search<2>, grid, dim3(OPTL_BLOCK), lds, s, a);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_search_local: search launch failed: %s", hipGetErrorString(err));
+  hipLaunchKernelGGL(k_opt_local_best, dim3((unsigned)p->E), dim3(256), 0, s, lp.q.n, restarts, a.rew, a.act, a.conv, best_actions,
+                     best_reward, best_info);
+  err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_search_local: reduce launch failed: %s", hipGetErrorString(err));
+  return V2X_OK;
+}
+
+int v2x_opt_rewards_actions(const v2x_opt_problem* p, void* workspace, const int32_t* actions, int64_t K, double* out, void* stream) {
+  OptLocalPlan lp;
+  int rc = opt_local_plan(p, 1, "opt_rewards_actions", lp);
+  if (rc != V2X_OK) return rc;
+  if (K < 1 || K > INT64_MAX / 8 / p->E / lp.q.n) OPT_FAIL(V2X_EINVAL, "opt_rewards_actions: K = %lld joint actions per state", (long long)K);
+  if (!actions || !out) OPT_FAIL(V2X_EINVAL, "opt_rewards_actions: null actions or output");
+  hipStream_t s = (hipStream_t)stream;
+  rc = opt_local_prep(p, lp, workspace, s, "opt_rewards_actions");
+  if (rc != V2X_OK) return rc;
+  const double* crossT = (const double*)((char*)workspace + lp.off_crossT);
+  const size_t lds = optl_score_lds(lp.q.n, lp.q.C);
+  const dim3 grid((unsigned)std::min<int64_t>(K, OPTL_REWARDS_WGS), (unsigned)p->E);
+  if (lp.q.n <= 64)
+    hipLaunchKernelGGL(k_opt_rewards_actions<1>, grid, dim3(OPTL_BLOCK), lds, s, lp.q, (const double*)workspace, crossT, actions, K, out);
+  else
+    hipLaunchKernelGGL(k_opt_rewards_actions<2>, grid, dim3(OPTL_BLOCK), lds, s, lp.q, (const double*)workspace, crossT, actions, K, out);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_rewards_actions: launch failed: %s", hipGetErrorString(err));
   return V2X_OK;
 }
 

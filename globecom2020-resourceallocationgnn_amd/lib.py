@@ -132,6 +132,10 @@ SYMBOLS = [
     ("v2x_opt_rewards", C.c_int, [C.POINTER(OptProblem), _P, _L, _L, _P, _P]),
     ("v2x_opt_bound_workspace_bytes", _L, [C.POINTER(OptProblem), _L]),
     ("v2x_opt_search_bound", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, C.POINTER(_L), _P]),
+    ("v2x_opt_search_bound_seeded", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, _P, C.POINTER(_L), _P]),
+    ("v2x_opt_local_workspace_bytes", _L, [C.POINTER(OptProblem), C.c_int32]),
+    ("v2x_opt_search_local", C.c_int, [C.POINTER(OptProblem), _P, C.c_int32, C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    ("v2x_opt_rewards_actions", C.c_int, [C.POINTER(OptProblem), _P, _P, _L, _P, _P]),
 ]
 
 

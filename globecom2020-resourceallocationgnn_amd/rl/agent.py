@@ -24,7 +24,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 
 
-OPT_BACKENDS = ('host', 'device', 'bound')
+OPT_BACKENDS = ('host', 'device', 'bound', 'local')
 
 
 def _check_opt_backend(opt_backend):
@@ -807,15 +807,35 @@ class Agent(object):
         res = self.dump_act(opt.decode(best, self.num_D2D, self.num_CH).reshape(self.num_D2D, 1))
         return best, float(self.v2v_weight * np.sum(res[0]) + self.v2i_weight * np.sum(res[1])), res
 
-    def _optimum_search(self, opt_backend):
+    def _local_search_device(self, opt, restarts):
+        """The `optimum` of opt_backend='local': the allocation the multi-start local search of rl/optimum.py finds -- a
+        LOWER BOUND on the optimum, not the optimum.  As in _brute_force_device the numpy reward of the returned actions
+        gives the recorded rates; the index is encode(actions) where C^N <= 2^62, else -1."""
+        from .optimum import MAX_INDEX, encode
+        actions, _ = opt.search_local(self.env, self.v2v_weight, self.v2i_weight, restarts=restarts)
+        best = int(encode(actions, self.num_CH)[0]) if self.num_CH ** self.num_D2D <= MAX_INDEX else -1
+        res = self.dump_act(actions[0].reshape(self.num_D2D, 1))
+        return best, float(self.v2v_weight * np.sum(res[0]) + self.v2i_weight * np.sum(res[1])), res
+
+    def _optimum_search(self, opt_backend, opt_restarts=None):
         """-> a callable () -> (index, reward, rates) of the optimum of the CURRENT simulator state.  opt_backend 'host':
         _brute_force over _joint_actions() (C^N <= 65536); 'device': the exhaustive search in HIP (C^N <= 2^36); 'bound':
-        branch and bound in HIP (the same optimum; up to 32 links, 20 x 4 included)."""
+        branch and bound in HIP (the same optimum; up to 32 links, 20 x 4 included); 'local': NOT the optimum but a lower
+        bound on it -- the best of opt_restarts best-response local searches in HIP, up to 128 links."""
         _check_opt_backend(opt_backend)
         if opt_backend == 'host':
             joint = self._joint_actions()
             return lambda: self._brute_force(joint)
         from .optimum import OptimalAllocation
+        if opt_backend == 'local':
+            from .optimum import DEFAULT_LOCAL_RESTARTS
+            restarts = DEFAULT_LOCAL_RESTARTS if opt_restarts is None else opt_restarts
+            OptimalAllocation.check_local(self.num_D2D, self.num_CH, restarts)
+            if self.num_Neighbor != 1:
+                raise ValueError("opt_backend=%r supports one receiver per link (num_Neighbor = 1), got %d"
+                                 % (opt_backend, self.num_Neighbor))
+            opt = OptimalAllocation()
+            return lambda: self._local_search_device(opt, restarts)
         bound = opt_backend == 'bound'
         if bound:
             OptimalAllocation.check_bound(self.num_D2D, self.num_CH, self.v2v_weight, self.v2i_weight)
@@ -827,11 +847,14 @@ class Agent(object):
         opt = OptimalAllocation()
         return lambda: self._brute_force_device(opt, bound)
 
-    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host'):
+    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
         :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
-        rl/optimum.py, or up to 32 links with opt_backend='bound': the same optimum by branch and bound on the GPU).  Same return tuple as the reference: 15 arrays with opt_flag, 10 without."""
+        rl/optimum.py, or up to 32 links with opt_backend='bound': the same optimum by branch and bound on the GPU).
+        opt_backend='local' (up to 128 links) records in the optimum's place the allocation of a multi-start local search
+        on the GPU with opt_restarts restarts: a lower bound on the optimum, not the optimum.  Same return tuple as the
+        reference: 15 arrays with opt_flag, 10 without."""
         _check_opt_backend(opt_backend)
         n, C = self.num_D2D, self.num_CH
         self.num_Episodes, self.num_Test_Step = num_episodes, num_test_step
@@ -850,7 +873,7 @@ class Agent(object):
 
         rl, ra, opt = book(), book(), book()
         if opt_flag:
-            optimum = self._optimum_search(opt_backend)
+            optimum = self._optimum_search(opt_backend, opt_restarts)
         for ep in range(num_episodes):
             self.env.new_random_game(self.num_D2D)
             for st in range(num_test_step):
@@ -872,14 +895,16 @@ class Agent(object):
         return os.path.join(root if root is not None else os.getcwd(), name)
 
     def evaluate_training_diff_trials(self, num_episodes, num_test_step, opt_flag, fixed_epsilon, num_evaluate_trials,
-                                      model_dir=None, num_train_steps=20, load=True, opt_backend='host'):
+                                      model_dir=None, num_train_steps=20, load=True, opt_backend='host',
+                                      opt_restarts=None):
         """Evaluation of the TRAINING PROCESS (BS_brain.py:1164-1451): for every saved checkpoint (one per 5 training
         episodes, :1218,:1228) and every trial, an episode under a FIXED epsilon-greedy policy (:1376-1397) next to the
         random-action baseline (:1330-1338) and -- per step of the first checkpoint -- the brute-force optimum (:1282-
         1328); with opt_flag also the optimum of every step (:1340-1374).  Trial t re-seeds the Python / numpy RNGs with
         t + 1 before every episode (:1262-1265).  Same return tuples as the reference: 9 arrays with opt_flag, 5 without.
         model_dir: checkpoint folder (default: checkpoint_dir()); load=False evaluates the weights already in the brain
-        for every checkpoint (tests with a recording brain).  opt_backend: where the optimum is searched, as in test_run."""
+        for every checkpoint (tests with a recording brain).  opt_backend / opt_restarts: where the optimum is searched, as in
+        test_run ('local': a lower bound on the optimum, not the optimum)."""
         import random
         _check_opt_backend(opt_backend)
         n, C, nn = self.num_D2D, self.num_CH, self.num_Neighbor
@@ -894,7 +919,7 @@ class Agent(object):
             opt_return, opt_reward = np.zeros((n_tr, n_ep)), np.zeros((n_tr, n_ep, n_st))
             opt_v2v, opt_v2i, opt_intf = np.zeros((n_tr, n_ep, n_st, n)), np.zeros((n_tr, n_ep, n_st, C)), np.zeros((n_tr, n_ep, n_st, C))
         ret, rew = np.zeros((n_tr, n_ep)), np.zeros((n_tr, n_ep, n_st))
-        optimum = self._optimum_search(opt_backend)
+        optimum = self._optimum_search(opt_backend, opt_restarts)
         for trial in range(n_tr):
             for ep in range(n_ep):
                 if load:

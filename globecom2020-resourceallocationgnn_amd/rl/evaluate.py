@@ -30,8 +30,10 @@ def main(argv=None):
     ap.add_argument("--trials", type=int, default=10)             # :39
     ap.add_argument("--epsilon", type=float, default=0.0)         # :37
     ap.add_argument("--opt", action="store_true")
-    ap.add_argument("--opt-backend", choices=("host", "device", "bound"), default="host",
-                    help="where the optimum is searched: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4)")
+    ap.add_argument("--opt-backend", choices=("host", "device", "bound", "local"), default="host",
+                    help="where the optimum is searched: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4);\n                         local: NOT the optimum but a lower bound on it, the best of --opt-restarts local searches on the GPU\n                         (up to 128 links, e.g. 100 x 4)")
+    ap.add_argument("--opt-restarts", type=int, default=None,
+                    help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
     ap.add_argument("--seed", type=int, default=1)                # :22
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
@@ -44,7 +46,7 @@ def main(argv=None):
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False)
     out = agent.evaluate_training_diff_trials(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials,
                                               model_dir=args.save_dir, num_train_steps=args.train_steps,
-                                              opt_backend=args.opt_backend)
+                                              opt_backend=args.opt_backend, opt_restarts=args.opt_restarts)
     ret, ra = (out[0], out[2]) if args.opt else (out[1], out[3])
     summary = {"links": args.links, "checkpoints": int(ret.shape[1]), "trials": args.trials,
                "mean_return_per_checkpoint": [round(float(v), 4) for v in ret.mean(axis=0)],

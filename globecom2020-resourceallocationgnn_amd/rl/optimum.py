@@ -15,6 +15,12 @@ among exactly equal rewards the lowest index wins, like np.argmax.
 branch and bound (v2x_opt_search_bound: a depth-first search that prunes with an upper bound on every completion of a
 partial assignment), which reaches the 20 links x 4 channels the training loops run at, and beyond; its cost depends on
 the state, so it takes a node budget and raises BoundBudgetExceeded with the best allocation found when that is spent.
+
+Beyond 32 links (the 100-link wide path, the 8-128 links of the ragged one) no exact search applies.  `search_local` is the
+baseline there: a multi-start best-response local search (v2x_opt_search_local, up to 128 links), which returns a LOWER
+BOUND on the optimum -- a 1-opt allocation, in practice the optimum itself at the sizes where that can be checked
+ -- as an array of channel numbers, not an index.  `rewards_of` scores given joint actions at any of those
+sizes, and `search_bound(..., incumbent='local')` starts the exact search from the local search's result.
 """
 import ctypes as C
 
@@ -34,6 +40,50 @@ DEVICE_S_PER_ACTION = 2e-10          # search kernel time per joint action at 16
 # one measured on the GPU and 45 times the worst 24-link one; at the 2.7e7 nodes/s of the longest measured search it ends
 # after about three minutes: a safety stop, not a tuning knob.
 DEFAULT_MAX_NODES = 1 << 32
+
+
+MAX_LOCAL_LINKS = 128               # v2x_opt_search_local / v2x_opt_rewards_actions
+MAX_LOCAL_RESTARTS = 65536
+# Restarts of one search_local call.  Measured on ten seeded states per size (profiles/opt_local_timing.json):
+# 128 restarts find the exact optimum in 10 / 8 / 9 / 10 of 10 states at 12 / 16 / 20 / 24 links, 1024 in 10 / 9 / 10 / 10; at 100
+# links 1024 gain 0.4 % over 128 at the median (4 % at most) for 12.5 against 10.3 ms per state -- 128 waves leave half of
+# an MI355X idle -- while 8192 cost 2.4 times more for another 0.3 %.
+DEFAULT_LOCAL_RESTARTS = 1024
+DEFAULT_MAX_SWEEPS = 64
+_MASK64 = (1 << 64) - 1
+
+
+def splitmix64(x):
+    x = (x + 0x9E3779B97F4A7C15) & _MASK64
+    x = ((x ^ (x >> 30)) * 0xBF58476D1CE4E5B9) & _MASK64
+    x = ((x ^ (x >> 27)) * 0x94D049BB133111EB) & _MASK64
+    return x ^ (x >> 31)
+
+
+def local_start(seed, r, n, rb):
+    """-> int64 [n]: the joint action restart r of search_local starts from (the rule of v2x_opt_search_local): l mod rb
+    for restart 0, else splitmix64((seed << 32) ^ (r << 8) ^ l) mod rb in unsigned 64-bit arithmetic.  It depends on
+    neither the state nor its position in a batch."""
+    seed, r = int(seed), int(r)
+    if r == 0:
+        return np.arange(n, dtype=np.int64) % rb
+    return np.array([splitmix64((((seed << 32) & _MASK64) ^ ((r << 8) & _MASK64) ^ l) & _MASK64) % rb for l in range(n)],
+                    np.int64)
+
+
+def encode(actions, rb):
+    """actions [..., n] -> int64 index [...]: the inverse of decode (link 0 most significant).  ValueError above
+    rb^n = 2^62, where no 64-bit index exists."""
+    a = np.asarray(actions)
+    n = a.shape[-1]
+    if int(rb) ** n > MAX_INDEX:
+        raise ValueError("%d^%d joint actions exceed 2^62: such an action has no 64-bit index" % (rb, n))
+    if a.size and (a.min() < 0 or a.max() >= rb):
+        raise ValueError("channel outside [0, %d)" % rb)
+    out = np.zeros(a.shape[:-1], np.int64)
+    for l in range(n):
+        out = out * int(rb) + a[..., l].astype(np.int64)
+    return out
 
 
 class BoundBudgetExceeded(RuntimeError):
@@ -112,6 +162,7 @@ class OptimalAllocation(object):
         self._ws = None
         self._keep = None
         self.nodes_visited = 0                            # of the last search_bound
+        self.local_info = None                            # of the last search_local: int32 [E, 2] (winning restart, converged)
 
     def _init_device(self):
         if self.torch is None:
@@ -144,11 +195,36 @@ class OptimalAllocation(object):
         if int(max_nodes) != max_nodes or int(max_nodes) < 1:
             raise ValueError("max_nodes must be an integer >= 1, got %r" % (max_nodes,))
 
-    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None):
-        """max_nodes not None: the problem of search_bound (its checks, its workspace)."""
+    @staticmethod
+    def check_local(n, rb, restarts=DEFAULT_LOCAL_RESTARTS, max_sweeps=DEFAULT_MAX_SWEEPS):
+        """The argument checks of search_local / rewards_of (ValueError), before any device work."""
+        if not 1 <= n <= MAX_LOCAL_LINKS or not 2 <= rb <= 16:
+            raise ValueError("the local search supports 1..%d links and 2..16 channels, got %d x %d" % (MAX_LOCAL_LINKS, n, rb))
+        if int(restarts) != restarts or not 1 <= int(restarts) <= MAX_LOCAL_RESTARTS:
+            raise ValueError("restarts must be an integer in 1..%d, got %r" % (MAX_LOCAL_RESTARTS, restarts))
+        if int(max_sweeps) != max_sweeps or int(max_sweeps) < 1:
+            raise ValueError("max_sweeps must be an integer >= 1, got %r" % (max_sweeps,))
+
+    @staticmethod
+    def _check_actions(actions, E, n, rb):
+        """host joint actions [E, K, n] or [E, n] -> (int32 [E, K, n], had K)"""
+        a = np.asarray(actions)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("joint actions must be integers, got dtype %s" % a.dtype)
+        if a.ndim not in (2, 3) or a.shape[0] != E or a.shape[-1] != n or a.size == 0:
+            raise ValueError("joint actions of shape [%d, K, %d] or [%d, %d] expected, got %s" % (E, n, E, n, list(a.shape)))
+        if a.min() < 0 or a.max() >= rb:
+            raise ValueError("channel outside [0, %d) in the joint actions" % rb)
+        return np.ascontiguousarray(a.reshape(E, -1, n), np.int32), a.ndim == 3
+
+    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None):
+        """max_nodes not None: the problem of search_bound (its checks, its workspace); local = (restarts, max_sweeps): of
+        search_local / rewards_of."""
         v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
         E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
-        if max_nodes is None:
+        if local is not None:
+            self.check_local(n, rb, *local)
+        elif max_nodes is None:
             self.check_size(n, rb, limit)
         else:
             self.check_bound(n, rb, v2v_weight, v2i_weight, max_nodes)
@@ -158,7 +234,9 @@ class OptimalAllocation(object):
         prob = OptProblem(E=E, n=n, rb=rb, pad_=0, v2v_ff=dev[0].data_ptr(), v2i_ff=dev[1].data_ptr(),
                           v2i_abs=dev[2].data_ptr(), dest=dev[3].data_ptr(), w_v2v=float(v2v_weight),
                           w_v2i=float(v2i_weight), **const)
-        if max_nodes is None:
+        if local is not None:
+            need = int(self._lib.v2x_opt_local_workspace_bytes(C.byref(prob), int(local[0])))
+        elif max_nodes is None:
             need = int(self._lib.v2x_opt_workspace_bytes(C.byref(prob)))
         else:
             need = int(self._lib.v2x_opt_bound_workspace_bytes(C.byref(prob), int(max_nodes)))
@@ -187,16 +265,39 @@ class OptimalAllocation(object):
         index, reward = self.search_device(env, v2v_weight, v2i_weight)
         return index.cpu().numpy(), reward.cpu().numpy()
 
-    def search_bound_device(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES):
+    def search_bound_device(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES, incumbent=None,
+                            restarts=DEFAULT_LOCAL_RESTARTS, seed=0):
         """search_bound() with the results left on the device: (index int64 [E], reward float64 [E]) torch tensors.
         `nodes_visited` of the object holds the nodes of the last call."""
+        start = None
+        if incumbent is not None:
+            n, rb = _sizes(env)
+            self.check_bound(n, rb, v2v_weight, v2i_weight, max_nodes)
+            if isinstance(incumbent, str):
+                if incumbent != 'local':
+                    raise ValueError("incumbent must be None, 'local' or an [E, n] array of channels, got %r" % (incumbent,))
+                self.check_local(n, rb, restarts)
+                start = self.search_local_device(env, v2v_weight, v2i_weight, restarts=restarts, seed=seed)[0]
+            else:
+                E = env.E if hasattr(env, 'E') else 1
+                start, had_k = self._check_actions(incumbent, E, n, rb)
+                if had_k:
+                    raise ValueError("incumbent: one joint action per state ([%d, %d]) expected, got %s"
+                                     % (E, n, list(np.shape(incumbent))))
         prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX, max_nodes)
         t = self.torch
+        if start is not None and not t.is_tensor(start):
+            start = t.from_numpy(start).to(self.device)
         index = t.empty(E, dtype=t.int64, device=self.device)
         reward = t.empty(E, dtype=t.float64, device=self.device)
         nodes = C.c_int64(0)
-        rc = self._lib.v2x_opt_search_bound(C.byref(prob), self._ws.data_ptr(), int(max_nodes), index.data_ptr(),
-                                            reward.data_ptr(), C.byref(nodes), self._stream())
+        if start is None:
+            rc = self._lib.v2x_opt_search_bound(C.byref(prob), self._ws.data_ptr(), int(max_nodes), index.data_ptr(),
+                                                reward.data_ptr(), C.byref(nodes), self._stream())
+        else:
+            start = start.contiguous()
+            rc = self._lib.v2x_opt_search_bound_seeded(C.byref(prob), self._ws.data_ptr(), int(max_nodes), start.data_ptr(),
+                                                       index.data_ptr(), reward.data_ptr(), C.byref(nodes), self._stream())
         self.nodes_visited = int(nodes.value)
         if rc == V2X_EBUDGET:
             msg = self._lib.v2x_last_error(None)
@@ -204,16 +305,86 @@ class OptimalAllocation(object):
         check(self._lib, rc)
         return index, reward
 
-    def search_bound(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES):
+    def search_bound(self, env, v2v_weight, v2i_weight, max_nodes=DEFAULT_MAX_NODES, incumbent=None,
+                     restarts=DEFAULT_LOCAL_RESTARTS, seed=0):
         """The pair search() returns -- the largest reward and, among exactly equal rewards, the lowest index, bit for bit
         -- by branch and bound: 1..32 links, 2..16 channels, rb^n <= 2^62.  max_nodes: search-tree nodes the call may visit
-        over all states of `env`; BoundBudgetExceeded (carrying the best allocation found) when they are spent."""
+        over all states of `env`; BoundBudgetExceeded (carrying the best allocation found) when they are spent.
+        incumbent: None (the default: the unseeded call, unchanged), 'local' (search_local with `restarts` / `seed` runs first and its
+        allocation is the first incumbent: v2x_opt_search_bound_seeded) or an [E, n] array of channels used as it is.  The
+        result is the same pair either way; only the nodes visited change."""
         try:
-            index, reward = self.search_bound_device(env, v2v_weight, v2i_weight, max_nodes)
+            index, reward = self.search_bound_device(env, v2v_weight, v2i_weight, max_nodes, incumbent, restarts, seed)
         except BoundBudgetExceeded as exc:
             exc.index, exc.reward = exc.index.cpu().numpy(), exc.reward.cpu().numpy()
             raise
         return index.cpu().numpy(), reward.cpu().numpy()
+
+    def search_local_device(self, env, v2v_weight, v2i_weight, restarts=DEFAULT_LOCAL_RESTARTS, seed=0,
+                            max_sweeps=DEFAULT_MAX_SWEEPS, all_restarts=False):
+        """search_local() with the results left on the device (torch tensors; actions int32, `local_info` a tensor too)."""
+        if int(seed) != seed or not 0 <= int(seed) < (1 << 32):
+            raise ValueError("seed must be an integer in [0, 2^32), got %r" % (seed,))
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX, local=(restarts, max_sweeps))
+        t = self.torch
+        R = int(restarts)
+        actions = t.empty((E, n), dtype=t.int32, device=self.device)
+        reward = t.empty(E, dtype=t.float64, device=self.device)
+        info = t.empty((E, 2), dtype=t.int32, device=self.device)
+        all_a = t.empty((E, R, n), dtype=t.int32, device=self.device) if all_restarts else None
+        all_r = t.empty((E, R), dtype=t.float64, device=self.device) if all_restarts else None
+        check(self._lib, self._lib.v2x_opt_search_local(
+            C.byref(prob), self._ws.data_ptr(), R, int(seed), int(max_sweeps), actions.data_ptr(), reward.data_ptr(),
+            info.data_ptr(), all_a.data_ptr() if all_restarts else None, all_r.data_ptr() if all_restarts else None,
+            self._stream()))
+        self.local_info = info
+        return (actions, reward, all_a, all_r) if all_restarts else (actions, reward)
+
+    def search_local(self, env, v2v_weight, v2i_weight, restarts=DEFAULT_LOCAL_RESTARTS, seed=0,
+                     max_sweeps=DEFAULT_MAX_SWEEPS, all_restarts=False):
+        """-> (actions int64 [E, n], reward float64 [E]): the best allocation a multi-start best-response local search
+        finds in every state -- a LOWER BOUND on the optimum, not the optimum; 1..128 links, 2..16 channels.  `restarts`
+        independent searches per state (restart r starts from local_start(seed, r, n, rb)), each sweeping the links in
+        order until no single link can improve the reward by changing its channel (max_sweeps sweeps at most); the best
+        restart wins, by (larger reward, else lexicographically lower action).  The reward is that of rewards_of(actions),
+        bit for bit.  all_restarts: also (all_actions int64 [E, R, n], all_rewards float64 [E, R]).  `local_info` of the
+        object: int32 [E, 2] -- the winning restart and whether its last sweep made no move."""
+        out = self.search_local_device(env, v2v_weight, v2i_weight, restarts, seed, max_sweeps, all_restarts)
+        self.local_info = self.local_info.cpu().numpy()
+        host = [o.cpu().numpy() for o in out]
+        host[0] = host[0].astype(np.int64)
+        if all_restarts:
+            host[2] = host[2].astype(np.int64)
+        return tuple(host)
+
+    def rewards_of_device(self, env, v2v_weight, v2i_weight, actions):
+        """rewards_of() with the result left on the device.  actions: a host array (checked) or an int32 torch tensor on
+        the device (a channel outside [0, rb) then gives NaN)."""
+        n, rb = _sizes(env)
+        self.check_local(n, rb)
+        E = env.E if hasattr(env, 'E') else 1
+        if hasattr(actions, 'data_ptr'):                                # a torch tensor
+            if actions.dim() not in (2, 3) or actions.shape[0] != E or actions.shape[-1] != n or actions.numel() == 0:
+                raise ValueError("joint actions of shape [%d, K, %d] or [%d, %d] expected, got %s"
+                                 % (E, n, E, n, list(actions.shape)))
+            had_k, host = actions.dim() == 3, None
+        else:
+            host, had_k = self._check_actions(actions, E, n, rb)
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX, local=(1, 1))
+        t = self.torch
+        dev = (t.from_numpy(host).to(self.device) if host is not None
+               else actions.to(device=self.device, dtype=t.int32).reshape(E, -1, n).contiguous())
+        K = dev.shape[1]
+        out = t.empty((E, K), dtype=t.float64, device=self.device)
+        check(self._lib, self._lib.v2x_opt_rewards_actions(C.byref(prob), self._ws.data_ptr(), dev.data_ptr(), K,
+                                                           out.data_ptr(), self._stream()))
+        self._keep = self._keep + [dev]
+        return out if had_k else out[:, 0]
+
+    def rewards_of(self, env, v2v_weight, v2i_weight, actions):
+        """The reward of given joint actions: actions [E, K, n] -> float64 [E, K], or [E, n] -> [E]; channel numbers, at
+        any size up to 128 links.  Up to 32 links bit for bit rewards(first=encode(action), count=1)."""
+        return self.rewards_of_device(env, v2v_weight, v2i_weight, actions).cpu().numpy()
 
     def rewards_device(self, env, v2v_weight, v2i_weight, first=0, count=None):
         """The reward of every joint action index in [first, first + count) of every state: float64 [E, count] torch
@@ -239,3 +410,7 @@ class OptimalAllocation(object):
     @staticmethod
     def decode(index, n, rb):
         return decode(index, n, rb)
+
+    @staticmethod
+    def encode(actions, rb):
+        return encode(actions, rb)

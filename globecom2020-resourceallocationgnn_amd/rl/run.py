@@ -4,7 +4,7 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound]
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local]
 """
 import argparse
 import json
@@ -33,10 +33,12 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
     return agent
 
 
-def run_test(cfg, agent, opt_backend='host'):
+def run_test(cfg, agent, opt_backend='host', opt_restarts=None):
     """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme.  opt_backend: where the
-    optimum is searched ('host': numpy over every joint action; 'device': the GPU search of rl/optimum.py)."""
-    out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend)
+    optimum is searched ('host': numpy over every joint action; 'device' / 'bound': the GPU searches of rl/optimum.py;
+    'local': its local search with opt_restarts restarts -- a lower bound on the optimum, not the optimum)."""
+    out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend,
+                         opt_restarts=opt_restarts)
     names = ['Expect_Return', 'Reward', 'Per_V2V_Rate', 'Per_V2I_Rate', 'Per_V2B_Interference']
     res = {}
     for prefix, chunk in zip(('', 'RA_', 'Opt_'), (out[0:5], out[5:10], out[10:15])):
@@ -57,8 +59,10 @@ def main(argv=None):
     ap.add_argument("--test-episodes", type=int, default=10)
     ap.add_argument("--test-steps", type=int, default=50)
     ap.add_argument("--opt", action="store_true", help="also run the brute-force optimum (C^N joint actions)")
-    ap.add_argument("--opt-backend", choices=("host", "device", "bound"), default="host",
-                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4)")
+    ap.add_argument("--opt-backend", choices=("host", "device", "bound", "local"), default="host",
+                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4);\n                         local: NOT the optimum but a lower bound on it, the best of --opt-restarts local searches on the GPU\n                         (up to 128 links, e.g. 100 x 4)")
+    ap.add_argument("--opt-restarts", type=int, default=None,
+                    help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
     ap.add_argument("--seed", type=int, default=11)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
@@ -73,7 +77,7 @@ def main(argv=None):
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = start_env(args.links)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed)
-    res = run_test(cfg, agent, opt_backend=args.opt_backend)
+    res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,
                "mean_reward_gnn": float(res['Reward'].mean()), "mean_reward_random": float(res['RA_Reward'].mean())}
     if args.opt:

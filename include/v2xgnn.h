@@ -359,6 +359,34 @@ int64_t v2x_opt_bound_workspace_bytes(const v2x_opt_problem* p, int64_t max_node
 int  v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, int64_t* best_index,
                           double* best_reward, int64_t* nodes_visited, void* stream);
 
+/* v2x_opt_search_bound with a start: the incumbent of state e begins as the reward of start_actions[e] ([dev] [E][n] channel
+ * numbers) scored as a leaf, and that action is entered as a candidate exactly like a leaf a lane found.  Same limits and
+ * the same (index, reward) bits as the unseeded call: a node is still pruned only strictly below the incumbent, so an equal
+ * reward at a lower index is still found; only nodes_visited changes.  A start with a channel outside [0, rb) seeds nothing.
+ * Workspace: v2x_opt_bound_workspace_bytes. */
+int  v2x_opt_search_bound_seeded(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, const int32_t* start_actions,
+                                 int64_t* best_index, double* best_reward, int64_t* nodes_visited, void* stream);
+/* A near-optimal allocation where the exact searches cannot go: multi-start best-response local search, one wave per
+ * (state, restart) -- a LOWER BOUND on the optimum, not the optimum.  1 <= n <= 128 links, 2 <= rb <= 16, E <= 65535; a joint
+ * action is an array of n channel numbers, never an index.  Restart 0 starts from a[l] = l mod rb, restart r from
+ * a[l] = splitmix64((seed << 32) ^ (r << 8) ^ l) mod rb; a sweep visits the links in order and moves each to the channel
+ * with the largest total reward if that is strictly larger than the current total (lowest channel among equals); sweeps
+ * repeat until one makes no move, max_sweeps (>= 1) at most.  A restart's reward is its final action scored from scratch
+ * with the arithmetic of v2x_opt_rewards; a state's result is the best restart by (larger reward, else lexicographically
+ * lower action), so it does not depend on the states around it or on the order of anything.  restarts: 1..65536.
+ * best_info[e] = { winning restart, 1 if its last sweep made no move }.  all_actions / all_rewards: every restart's result.
+ * Asynchronous on `stream`, four launches, no allocation, no synchronisation (capturable). */
+int64_t v2x_opt_local_workspace_bytes(const v2x_opt_problem* p, int32_t restarts);
+int  v2x_opt_search_local(const v2x_opt_problem* p, void* workspace, int32_t restarts, uint64_t seed, int32_t max_sweeps,
+                          int32_t* best_actions /*[E][n]*/, double* best_reward /*[E]*/,
+                          int32_t* best_info /*[E][2]; may be NULL*/, int32_t* all_actions /*[E][restarts][n]; may be NULL*/,
+                          double* all_rewards /*[E][restarts]; may be NULL*/, void* stream);
+/* out[E][K]: the reward of the joint actions actions[E][K][n] ([dev] channel numbers), 1 <= n <= 128; for n <= 32 bit for bit
+ * what v2x_opt_rewards returns for the action's index.  A channel outside [0, rb) gives that action the reward NaN.
+ * Workspace: v2x_opt_local_workspace_bytes(p, 1).  Asynchronous on `stream`, three launches (capturable). */
+int  v2x_opt_rewards_actions(const v2x_opt_problem* p, void* workspace, const int32_t* actions, int64_t K, double* out,
+                             void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

@@ -10,6 +10,13 @@ seeded states each (min / median / max of the wall and kernel time per state and
 exhaustive search() at 12 and 16 links on the same states in the same run.
 
     python tools/opt_search_timing.py --bound [--out profiles/opt_bound_timing.json] [--states 10]
+
+With --local: the multi-start local search (search_local, v2x_opt_search_local) on the same seeded states: wall and kernel
+time per state at 20 x 4, 100 x 4, 128 x 4 and 128 x 16 for 128 / 1024 / 8192 restarts and for 50 stacked 20-link states, sweeps per
+restart, the share of restarts that end at the winner; hits and worst gap against search_bound at 12 - 24 links; the reward at
+100 links against random actions and against 8 x the restarts; search_bound seeded with the local search against unseeded.
+
+    python tools/opt_search_timing.py --local [--out profiles/opt_local_timing.json] [--states 10]
 """
 import argparse
 import json
@@ -162,19 +169,161 @@ def main_bound(args):
     return 0
 
 
+def _state_rb(n, rb, seed):
+    env = _state(n, seed)
+    if rb != env.n_RB:
+        env.n_RB = rb
+        env.new_random_game(n)
+    return env
+
+
+RESTARTS = (128, 1024, 8192)
+
+
+def local_time_rows(opt, n, rb, envs, label):
+    """one call per state (or one call of a stacked simulator) and restart count: wall of search_local (upload, four
+    launches, download) and the time between HIP events around v2x_opt_search_local alone"""
+    import ctypes
+    import torch
+    from v2xgnn.rl.optimum import MAX_INDEX
+    w_v2v, w_v2i = 1.0, 0.1
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    rows = []
+    for R in RESTARTS:
+        wall, kern, share = [], [], []
+        for env in envs:
+            E = getattr(env, 'E', 1)
+            opt.search_local(env, w_v2v, w_v2i, restarts=R)            # workspace of this size
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            _, rew, _, all_r = opt.search_local(env, w_v2v, w_v2i, restarts=R, all_restarts=True)
+            wall.append((time.perf_counter() - t0) * 1e3 / E)
+            share.append(float(np.mean(all_r == rew[:, None])))
+            prob, _, _, _ = opt._setup(env, w_v2v, w_v2i, MAX_INDEX, local=(R, 64))
+            act = torch.empty((E, n), dtype=torch.int32, device=opt.device)
+            rw = torch.empty(E, dtype=torch.float64, device=opt.device)
+            ev[0].record()
+            rc = opt._lib.v2x_opt_search_local(ctypes.byref(prob), opt._ws.data_ptr(), R, 0, 64, act.data_ptr(), rw.data_ptr(),
+                                               None, None, None, opt._stream())
+            ev[1].record()
+            assert rc == 0
+            torch.cuda.synchronize()
+            kern.append(ev[0].elapsed_time(ev[1]) / E)
+        rows.append({"case": label, "n": n, "rb": rb, "restarts": R, "calls": len(envs), "states_per_call": getattr(envs[0], 'E', 1),
+                     "wall_ms_per_state": _mmm(wall), "kernel_ms_per_state": _mmm(kern),
+                     "share_of_restarts_at_the_winner": _mmm(share)})
+        print(json.dumps(rows[-1]), flush=True)
+    return rows
+
+
+def local_sweeps(opt, n, rb, env, R=128):
+    """sweeps a restart runs (the last one makes no move): 1 + the smallest max_sweeps whose result is the final one"""
+    final = opt.search_local(env, 1.0, 0.1, restarts=R, all_restarts=True)[2][0]
+    need = np.full(R, -1)
+    for k in range(1, 25):
+        got = opt.search_local(env, 1.0, 0.1, restarts=R, max_sweeps=k, all_restarts=True)[2][0]
+        same = np.all(got == final, axis=1)
+        need[(need < 0) & same] = k + 1
+        if np.all(need > 0):
+            break
+    return {"case": "sweeps", "n": n, "rb": rb, "restarts": R, "sweeps_per_restart": _mmm(need), "mean": float(need.mean())}
+
+
+def local_quality_row(opt, n, states):
+    """against the exact optimum (unseeded search_bound) and search_bound seeded with 128 restarts, on the seeded states"""
+    import torch
+    w_v2v, w_v2i = 1.0, 0.1
+    hits = {R: 0 for R in RESTARTS}
+    gaps = {R: [] for R in RESTARTS}
+    wall_plain, wall_seeded, wall_local, nodes_plain, nodes_seeded = [], [], [], [], []
+    for seed in range(states):
+        env = _state(n, seed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        idx, rew = opt.search_bound(env, w_v2v, w_v2i)
+        wall_plain.append((time.perf_counter() - t0) * 1e3)
+        nodes_plain.append(opt.nodes_visited)
+        t0 = time.perf_counter()
+        si, sr = opt.search_bound(env, w_v2v, w_v2i, incumbent='local', restarts=128)
+        wall_seeded.append((time.perf_counter() - t0) * 1e3)
+        nodes_seeded.append(opt.nodes_visited)
+        assert int(si[0]) == int(idx[0]) and float(sr[0]) == float(rew[0]), (n, seed)
+        for R in RESTARTS:
+            t0 = time.perf_counter()
+            a, r = opt.search_local(env, w_v2v, w_v2i, restarts=R)
+            if R == 128:
+                wall_local.append((time.perf_counter() - t0) * 1e3)
+            assert r[0] <= rew[0]
+            hits[R] += int(r[0] == rew[0] and int(opt.encode(a, 4)[0]) == int(idx[0]))
+            gaps[R].append(float((rew[0] - r[0]) / rew[0]))
+    return {"case": "quality %d links" % n, "n": n, "rb": 4, "states": states,
+            "exact_optimum_found": {str(R): hits[R] for R in RESTARTS},
+            "worst_relative_gap": {str(R): max(gaps[R]) for R in RESTARTS},
+            "wall_ms_search_local_128": _mmm(wall_local),
+            "wall_ms_bound_unseeded": _mmm(wall_plain), "wall_ms_bound_seeded_including_local_128": _mmm(wall_seeded),
+            "nodes_unseeded": _mmm(nodes_plain), "nodes_seeded": _mmm(nodes_seeded),
+            "per_state": {"wall_unseeded": [round(v, 2) for v in wall_plain], "wall_seeded": [round(v, 2) for v in wall_seeded],
+                          "nodes_unseeded": nodes_plain, "nodes_seeded": nodes_seeded}}
+
+
+def local_wide_row(opt, n, states):
+    """100 links: no exact optimum; the reward against 200 random joint actions and against 8 x the restarts"""
+    out = []
+    for seed in range(states):
+        env = _state(n, seed)
+        rng = np.random.default_rng(seed)
+        rnd = opt.rewards_of(env, 1.0, 0.1, rng.integers(0, env.n_RB, size=(1, 200, n)))[0]
+        row = {"seed": seed, "random_mean": float(rnd.mean()), "random_best": float(rnd.max())}
+        for R in (1, 16) + RESTARTS:
+            row["local_%d" % R] = float(opt.search_local(env, 1.0, 0.1, restarts=R)[1][0])
+        out.append(row)
+    gain = lambda a, b: _mmm([r["local_%d" % b] / r["local_%d" % a] - 1.0 for r in out])
+    return {"case": "reward at %d links" % n, "n": n, "rb": 4, "states": out, "gain_128_over_16": gain(16, 128),
+            "gain_1024_over_128": gain(128, 1024), "gain_8192_over_1024": gain(1024, 8192)}
+
+
+def main_local(args):
+    import torch
+    from v2xgnn.rl import OptimalAllocation
+    opt = OptimalAllocation()
+    opt.search_local(_state(8), 1.0, 0.1)                              # warm-up: code objects
+    opt.search_bound(_state(8), 1.0, 0.1, incumbent='local')
+    rows = []
+    for n, rb in ((20, 4), (100, 4), (128, 4), (128, 16)):
+        envs = [_state_rb(n, rb, seed) for seed in range(args.states)]
+        rows += local_time_rows(opt, n, rb, envs, "local %d x %d" % (n, rb))
+        rows.append(local_sweeps(opt, n, rb, envs[0]))
+        print(json.dumps(rows[-1]), flush=True)
+    rows += local_time_rows(opt, 20, 4, [_stack(20, 50)], "local 20 x 4, 50 stacked states")
+    for n in args.links:
+        rows.append(local_quality_row(opt, n, args.states))
+        print(json.dumps(rows[-1]), flush=True)
+    rows.append(local_wide_row(opt, 100, args.states))
+    print(json.dumps(rows[-1]), flush=True)
+    out = {"device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--bound", action="store_true", help="measure the branch-and-bound search instead")
-    ap.add_argument("--states", type=int, default=10, help="--bound: seeded states per size")
-    ap.add_argument("--links", type=int, nargs="+", default=[12, 16, 20, 24], help="--bound: sizes")
+    ap.add_argument("--local", action="store_true", help="measure the multi-start local search instead")
+    ap.add_argument("--states", type=int, default=10, help="--bound / --local: seeded states per size")
+    ap.add_argument("--links", type=int, nargs="+", default=[12, 16, 20, 24], help="--bound / --local: sizes against the exact optimum")
     args = ap.parse_args(argv)
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("opt_search_timing.py measures the GPU search: no GPU here")
     if args.bound:
         return main_bound(args)
+    if args.local:
+        return main_local(args)
     from v2xgnn.rl import OptimalAllocation
     opt = OptimalAllocation()
     rows = []
