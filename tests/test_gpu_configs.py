@@ -10,6 +10,7 @@ test_cfg4_share_vs_oracle); here are the size-independent properties of the path
 mean of the engine's own forward output, the gradient is additive over shards taken with the global denominator (what the
 data-parallel all-reduce relies on), hipGraph replay == eager.
 """
+import contextlib
 import os
 import random
 
@@ -37,46 +38,51 @@ def _weights(spec, rng):
 
 
 # ------------------------------------------------------------------------------------------------ v2x_dqn_step vs oracle
-def _oracle_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma):
+def _oracle_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma, nbr=None, nbr2=None):
     """Agent.replay (BS_brain.py:664-728) in float64: target forward on s', online forward on s, the target rule
-    (:684-692), one fit step.  -> (y, per-output losses, weights after the step)"""
+    (:684-692), one fit step.  -> (y, per-output losses, weights after the step)
+    nbr / nbr2 [B, N, F]: the Neighbor_Input of s / of s' (None: the reference's zeros)"""
     os_ = ospec(spec)
     B, N = x.shape[0], spec.n_nodes
     graph = oc.adj_to_csr(adj)
     online = oc.OracleModel(os_, oc.params_from_list(os_, w_online), dtype=np.float64)
     target = oc.OracleModel(os_, oc.params_from_list(os_, w_target), dtype=np.float64)
     flat = lambda a: a.reshape(B * N, -1).astype(np.float64)
-    q = online.predict(flat(x), flat(e), graph).reshape(B, N, -1)
-    qn = target.predict(flat(x2), flat(e2), graph).reshape(B, N, -1)               # same adjacency (:583)
+    n1, n2 = (None if n is None else flat(n) for n in (nbr, nbr2))
+    q = online.predict(flat(x), flat(e), graph, n1).reshape(B, N, -1)
+    qn = target.predict(flat(x2), flat(e2), graph, n2).reshape(B, N, -1)           # same adjacency (:583)
     y = q.copy()
     tgt = reward[:, None] + gamma * qn.max(axis=2)
     y[np.arange(B)[:, None], np.arange(N)[None, :], action] = tgt
-    _, g_ref, _ = online.loss_and_grads(flat(x), flat(e), graph, y.reshape(B * N, -1))
-    loss = online.train_step(flat(x), flat(e), graph, y.reshape(B * N, -1))
+    _, g_ref, _ = online.loss_and_grads(flat(x), flat(e), graph, y.reshape(B * N, -1), n1)
+    loss = online.train_step(flat(x), flat(e), graph, y.reshape(B * N, -1), n1)
     return y, loss, oc.params_to_list(online.params), oc.params_to_list(g_ref)
 
 
-def _run_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma):
+def _run_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma, nbr=None, nbr2=None, use_graph=False):
     import torch
-    online, target = GnnEngine(spec), GnnEngine(spec)
+    online, target = GnnEngine(spec, use_graph=use_graph), GnnEngine(spec, use_graph=use_graph)
     online.set_weights(w_online)
     target.set_weights(w_target)
-    sb = online.to_device(PackedBatch.from_dense(x, e, adj))
-    sn = online.to_device(PackedBatch.from_dense(x2, e2, adj))
+    sb = online.to_device(PackedBatch.from_dense(x, e, adj, nbr))
+    sn = online.to_device(PackedBatch.from_dense(x2, e2, adj, nbr2))
     B, N = x.shape[0], spec.n_nodes
     y = torch.empty((B * N, 4), dtype=torch.float32, device="cuda")
     a_dev = torch.from_numpy(np.ascontiguousarray(action, np.int32)).cuda()
     r_dev = torch.from_numpy(np.ascontiguousarray(reward, np.float64)).cuda()
-    loss = online.dqn_step(target, sb, sn, a_dev, r_dev, gamma, y_out=y)
+    with torch.cuda.stream(torch.cuda.Stream()) if use_graph else contextlib.nullcontext():    # (a capture needs a non-default stream)
+        loss = online.dqn_step(target, sb, sn, a_dev, r_dev, gamma, y_out=y)
+        if use_graph:
+            torch.cuda.synchronize()
     out = y.cpu().numpy().reshape(B, N, 4), loss.cpu().numpy(), online.get_weights()
     online.close()
     target.close()
     return out
 
 
-def _check_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma):
-    y, loss, w1 = _run_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma)
-    y_ref, loss_ref, w_ref, g_ref = _oracle_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma)
+def _check_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma, nbr=None, nbr2=None):
+    y, loss, w1 = _run_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma, nbr, nbr2)
+    y_ref, loss_ref, w_ref, g_ref = _oracle_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward, gamma, nbr, nbr2)
     assert_fwd_close(y, y_ref, "training targets of the fused replay step")
     assert_close(loss, loss_ref, 5e-3, 1e-6, "per-output Huber losses")
     moved = 0
@@ -90,6 +96,7 @@ def _check_dqn_step(spec, w_online, w_target, x, e, adj, x2, e2, action, reward,
         assert (err[~tight] <= 1.1e-3).all(), ("weights (ill-conditioned)", i, err[~tight].max())
         moved += int(np.any(a != c))
     assert moved > len(w1) // 2
+    return y, loss, w1
 
 
 def test_dqn_step_vs_oracle_on_the_reference_agents_replay_memory():

@@ -52,13 +52,15 @@ def _env(**kw):
                 os.environ[k] = v
 
 
-def _draw(N, F, L, shared, B, topo, seed, density=0.3):
-    """-> spec, fp32-exact params, x, e, packed batch, graph (node-row CSR of the oracle), rng"""
+def _draw(N, F, L, shared, B, topo, seed, density=0.3, with_nbr=False):
+    """-> spec, fp32-exact params, x, e, packed batch, graph (node-row CSR of the oracle), rng
+    with_nbr: the batch carries a Neighbor_Input ~ N(0, 0.5) (test_gpu_kernels._setup's draw); its node rows are pb.nbr"""
     rng = np.random.default_rng(seed)
     spec = GnnSpec(n_nodes=N, feat_dim=F, n_mp_layers=L, share_weights=shared)
     P = f32_params(spec, rng)
     x, e, adj = random_inputs(rng, B, N, ref_topology=topo, density=density)
-    pb = PackedBatch.from_dense(x, e, adj)
+    nbr = rng.normal(0, 0.5, size=(B, N, F)).astype(np.float32) if with_nbr else None
+    pb = PackedBatch.from_dense(x, e, adj, nbr)
     graph = ((np.arange(B + 1) * N).astype(np.int32), pb.row_ptr, pb.col_idx)
     return spec, P, x.reshape(B * N, -1), e.reshape(B * N, -1), pb, graph, rng
 
@@ -85,13 +87,14 @@ def _assert_informative(step, L, what):
 
 
 def _parity(spec, P, x, e, pb, graph, rng, eng, what, n_global=None):
-    """forward / loss / every gradient of one forward_backward against the oracle; -> names of the launches of that step"""
+    """forward / loss / every gradient of one forward_backward against the oracle (with the batch's Neighbor_Input, if it
+    carries one); -> names of the launches of that step"""
     L = spec.n_mp_layers
     q = eng.forward(pb)
     # targets around the kernels' own q as in test_gpu_shapes._check, the spread widened with |q|: deep stacks on dense
     # graphs reach |q| ~ 1e9, where q + N(0, 1.2) rounds back to q in fp32 and those rows would have no loss gradient
     y = (q + rng.normal(0, 1.2, size=q.shape) * np.maximum(1.0, 1e-3 * np.abs(q))).astype(np.float32)
-    step = oracle_step(spec, P, x, e, graph, y, q_at=q, n_denominator=n_global)
+    step = oracle_step(spec, P, x, e, graph, y, q_at=q, n_denominator=n_global, nbr=pb.nbr)
     live, ratio = _assert_informative(step, L, what)
     assert_fwd_close(q, step['q'], what + ": forward")
     eng.profile(True)

@@ -443,13 +443,16 @@ def test_two_phase_step_equals_single_call(N, F, B, use_graph, monkeypatch):
 
 def _ragged_batch(rng, sizes, kind):
     """kind: 'ref' = the reference topology (in-degree n - 2), 'mixed' = per graph one of: reference, half-dense random,
-    sparse random; a few rows of the larger graphs lose ALL their in-edges (isolated destinations)."""
+    sparse random; a few rows of the larger graphs lose ALL their in-edges (isolated destinations); a float = every edge
+    p -> q (p == q included) present with that probability."""
     offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
     R = int(offs[-1])
     row_ptr, cols, max_e = [0], [], 0
     for gi, n in enumerate(sizes):
         mode = 0 if kind == 'ref' else gi % 3
-        if mode == 0:
+        if isinstance(kind, float):
+            adj = rng.uniform(size=(n, n)) < kind
+        elif mode == 0:
             adj = ~np.eye(n, dtype=bool)
             if n > 1:
                 dest = rng.integers(0, n - 1, size=n)

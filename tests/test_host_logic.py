@@ -184,6 +184,37 @@ def test_batch_shard_partitions_graphs():
         pb.shard(0, 3)
 
 
+def test_batch_shard_cuts_the_neighbor_input_with_its_rows():
+    """PackedBatch.shard / slice_graphs on a batch that carries a Neighbor_Input: every shard's nbr is the row range of its
+    graphs (fixed-size and variable-size batches), and a batch without one stays without."""
+    rng = np.random.default_rng(8)
+    B, N, F = 8, 5, 16
+    x, e, adj = random_inputs(rng, B, N, ref_topology=False)
+    nbr = rng.normal(0, 0.5, size=(B, N, F)).astype(np.float32)
+    pb = PackedBatch.from_dense(x, e, adj, nbr)
+    assert pb.nbr.shape == (B * N, F) and np.array_equal(pb.nbr, nbr.reshape(B * N, F))
+    for r in range(4):
+        sh, (r0, r1) = pb.shard(r, 4, with_rows=True)
+        assert (r0, r1) == (2 * N * r, 2 * N * (r + 1))
+        assert sh.nbr.dtype == np.float32 and np.array_equal(sh.nbr, nbr[2 * r:2 * r + 2].reshape(2 * N, F))
+        assert np.array_equal(sh.xe, pb.xe[r0:r1])
+    assert PackedBatch.from_dense(x, e, adj).shard(1, 4).nbr is None
+    # variable-size graphs: the cuts fall on graph boundaries that are no multiple of anything
+    import bench
+    sizes, offs, row_ptr, col_idx, xr, er, _ = bench.synth_ragged(rng, 23, 2, 40)
+    nr = rng.normal(0, 0.5, size=(int(offs[-1]), F)).astype(np.float32)
+    rb = PackedBatch(len(sizes), 0, v2xgnn.pack_xe(xr, er), row_ptr, col_idx, nbr=nr, graph_off=offs)
+    for world in (2, 3, 5):
+        b = rb.shard_bounds(world)
+        parts = [rb.shard(r, world, with_rows=True) for r in range(world)]
+        for r, (sh, (r0, r1)) in enumerate(parts):
+            assert (r0, r1) == (offs[b[r]], offs[b[r + 1]]) and sh.n_rows == r1 - r0
+            assert np.array_equal(sh.nbr, nr[r0:r1]) and np.array_equal(sh.xe, rb.xe[r0:r1])
+        assert np.array_equal(np.concatenate([sh.nbr for sh, _ in parts]), nr)
+    sub, (r0, r1) = rb.slice_graphs(3, 4)
+    assert np.array_equal(sub.nbr, nr[offs[3]:offs[4]]) and sub.n_graphs == 1
+
+
 def test_keras_hdf5_weight_files_roundtrip(tmp_path):
     """h5weights.py writes / reads the layout of Keras `save_weights` through libhdf5 itself: layer_names /
     weight_names attributes, nested '<layer>/<layer>/<weight>:0' float32 datasets; order-based matching."""

@@ -124,7 +124,10 @@ def _relu_layer_inputs(os_, cache, t):
         i = t - L
         return 'dense', i, [('W', cache['z'][i])], cache['z'][i + 1]
     if t == 0:
-        return 'gnn', 0, [('W1', cache['x']), ('W2', cache['e'])], cache['h'][0]
+        ins = [('W1', cache['x']), ('W2', cache['e'])]
+        if cache.get('nbr') is not None:          # a non-zero Neighbor_Input: the embed stage's third term, nbr . W3
+            ins.append(('W3', cache['nbr']))
+        return 'gnn', 0, ins, cache['h'][0]
     return 'gnn', t, [('W1', np.concatenate([cache['h'][t - 1], cache['x']], axis=1)), ('W2', cache['e']),
                       ('W3', cache['a'][t - 1])], cache['h'][t]
 
@@ -196,13 +199,15 @@ def resolve_relu_gates(os_, P, cache, dq, got, ref, pre_gate, rtol=AMBIG_RTOLS[0
     return ref, n_cand, n_flip
 
 
-def oracle_step(spec, P, x, e, graph, y, q_at=None, n_denominator=None):
+def oracle_step(spec, P, x, e, graph, y, q_at=None, n_denominator=None, nbr=None):
     """Float64 oracle of one fit step's forward / Huber / backward on node-row inputs.  q_at: differentiate the loss at
     this q (the kernels' own fp32 output -- forward parity is asserted separately) instead of at the oracle's.
+    nbr: node rows [R, F] of a non-zero Neighbor_Input (None: the reference's zeros).
     -> dict(q, loss, grads (structure of the parameters), cache, dq, pre_gate)"""
     os_ = ospec(spec)
     M = oc.csr_to_matrix(*graph, dtype=np.float64)
-    q_ref, cache = oc.forward(os_, P, np.asarray(x, np.float64), np.asarray(e, np.float64), M)
+    q_ref, cache = oc.forward(os_, P, np.asarray(x, np.float64), np.asarray(e, np.float64), M,
+                              None if nbr is None else np.asarray(nbr, np.float64))
     q_use = q_ref if q_at is None else np.asarray(q_at, np.float64)
     if getattr(spec, 'variable_graphs', False):
         R, C = q_use.shape
@@ -257,3 +262,24 @@ def assert_grads_match_oracle(got_list, P, step, what="", max_flips=MAX_GATE_FLI
         assert n_flip <= max_flips, "%s: %d ReLU gates (of %d candidates) had to be taken the kernels' way -- more than " \
             "rounding at the gate explains" % (what, n_flip, n_cand)
     return ref, n_cand, n_flip
+
+
+def assert_weights_after_adam_step(got, ref, grads, step, what=""):
+    """Weights after fit step `step` (0-based) against the oracle's.  got / ref: Keras-shaped lists; grads: the oracle's
+    gradient of that step BEFORE its update (a Keras-shaped list), or the list of such lists of EVERY step the optimizer has
+    taken so far.  Adam divides by sqrt(v) + 1e-7: where |g| is at rounding-noise level the update direction is not
+    determined by fp32 arithmetic -- those entries are compared to within one full step (lr) per step taken, the others
+    tightly.  Adam's moments carry an indeterminate step forward, so with a history an entry is well-conditioned only if it
+    was at every step at which its ARRAY had a gradient.  A step at which the whole array's gradient is exactly zero (stage
+    0's W3 on a batch without a neighbour input) adds exactly nothing to the moments: it is fully determined and leaves the
+    class of every entry as it was -- an array that never had a gradient is held to the tight bound throughout."""
+    steps = grads if isinstance(grads[0], (list, tuple)) else [grads]
+    for i, (a, b) in enumerate(zip(got, ref)):
+        tight = np.ones(np.shape(b), bool)
+        for gl in steps:
+            g = np.asarray(gl[i])
+            if g.any():
+                tight &= np.abs(g) > 1e-4 * np.abs(g).max()
+        err = np.abs(np.asarray(a, np.float64) - b)
+        assert (err[tight] <= 2e-5 + 2e-4 * np.abs(b[tight])).all(), (what, "weights", i, step, err[tight].max())
+        assert (err[~tight] <= 1.1e-3 * (step + 1)).all(), (what, "weights(ill-cond)", i, step, err[~tight].max())
