@@ -10,6 +10,7 @@
 // step of the CPU restatement.  Here: one read of the adjacency (graphs split over a few threads), the Kronecker
 // structure checked while it streams by, CSR by destination and the [x | e | pad] rows written directly.
 #pragma once
+#include "knobs.hpp"
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -154,9 +155,9 @@ class WorkerPool {
   unsigned long gen_ = 0;
 };
 
-// threads for a scan of `bytes` bytes over n_graphs graphs: >= 1 MB each, at most 8 (V2X_PACK_THREADS overrides)
+// threads for a scan of `bytes` bytes over n_graphs graphs: >= 1 MB each, at most 8 (V2X_PACK_THREADS overrides: knobs.hpp)
 inline int n_pack_threads(int n_graphs, size_t bytes) {
-  static const int env = getenv("V2X_PACK_THREADS") ? atoi(getenv("V2X_PACK_THREADS")) : 0;
+  const int env = v2x::process_knobs().pack_threads;
   int t;
   if (env > 0) t = env;
   else {

@@ -902,154 +902,9 @@ __global__ __launch_bounds__(256, 2) void k_mlp_bwd(MlpArgs a) {
   V2X_TILE_LOOP(inA, inB, load_in, compute)
 }
 
-// Training form: forward + Huber + reverse chain of the decision MLP in ONE pass over the rows (the hidden
-// activations never leave the registers between the two directions; z1..z3 and the pre-activation gradients are
-// still written once for k_wgrad).  Saves a launch and the read-back of q, z1, z2, z3 per fit step.
+// one tile's inputs of the training form of the decision MLP (k_mlp_train_wg, kernels_mlpwg.hpp)
 template <int F>
 struct MlpTrainIn { f32x4 z0[2 * (F / 16) + 1]; f32x4 y; int64_t row; };
-
-template <int F>
-__global__ __launch_bounds__(256, 2) void k_mlp_train(MlpArgs a) {
-  using L = MlpLds<F>;
-  constexpr int FB = F / 16, KB1 = 2 * FB + 1;
-  extern __shared__ __attribute__((aligned(16))) float smem[];
-  const int slot = blockIdx.y;
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  const int j = lane & 15, kg = lane >> 4;
-  const int n_tiles = (a.n_idx + 15) >> 4;
-  const int per = (n_tiles + gridDim.x - 1) / gridDim.x;
-  const int t_end = min((int)(blockIdx.x + 1) * per, n_tiles);
-  const int cq = 4 * kg < a.C ? 4 * kg : 0;
-
-  auto load_in = [&](int t, MlpTrainIn<F>& in) {
-    const int idx = min(t * 16 + j, a.n_idx - 1);
-    const int64_t row = (int64_t)(a.idx_base + idx) * a.row_stride + slot * a.base_mul;
-    in.row = row;
-#pragma unroll
-    for (int b = 0; b < FB; ++b) in.z0[b] = ld4(a.h + row * F + b * 16 + 4 * kg);
-    in.z0[FB] = ld4(a.xe + row * XE + 4 * kg);
-#pragma unroll
-    for (int b = 0; b < FB; ++b) in.z0[FB + 1 + b] = ld4(a.agg + row * F + b * 16 + 4 * kg);
-    in.y = ld4(a.y + row * a.C + cq);
-  };
-  auto compute = [&](int t, const MlpTrainIn<F>& in) {
-    const bool valid = t * 16 + j < a.n_idx;
-    const int64_t row = in.row;
-    const int64_t srow = (int64_t)slot * a.srow_stride + a.idx_base + min(t * 16 + j, a.n_idx - 1);
-    // ================= forward
-    f32x4 z1[1][5];
-#pragma unroll
-    for (int nt = 0; nt < 5; ++nt) z1[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < KB1; ++kb) {
-      f32x4 blk[1] = {in.z0[kb]};
-      mfma_cols<1, 5>(smem + L::W1, LD1, kb, j, kg, blk, z1);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 5; ++nt) {
-      z1[0][nt] = relu4(z1[0][nt] + ld4(smem + L::B1 + nt * 16 + 4 * kg));
-      if (valid) st4(a.z1 + row * H1 + nt * 16 + 4 * kg, z1[0][nt]);
-    }
-    f32x4 z2[1][3];
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) z2[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 5; ++kb) {
-      f32x4 blk[1] = {z1[0][kb]};
-      mfma_cols<1, 3>(smem + L::W2, LD2, kb, j, kg, blk, z2);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
-      z2[0][nt] = relu4(z2[0][nt] + ld4(smem + L::B2 + nt * 16 + 4 * kg));
-      if (valid && nt * 16 + 4 * kg < H2) st4(a.z2 + srow * H2 + nt * 16 + 4 * kg, z2[0][nt]);
-    }
-    f32x4 z3[1][2];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) z3[0][nt] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 3; ++kb) {
-      f32x4 blk[1] = {z2[0][kb]};
-      mfma_cols<1, 2>(smem + L::W3, LD3, kb, j, kg, blk, z3);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      z3[0][nt] = relu4(z3[0][nt] + ld4(smem + L::B3 + nt * 16 + 4 * kg));
-      if (valid && nt * 16 + 4 * kg < H3) st4(a.z3 + srow * H3 + nt * 16 + 4 * kg, z3[0][nt]);
-    }
-    f32x4 qa[1][1];
-    qa[0][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) {
-      f32x4 blk[1] = {z3[0][kb]};
-      mfma_cols<1, 1>(smem + L::W4, LD4, kb, j, kg, blk, qa);
-    }
-    const f32x4 qv = qa[0][0] + ld4(smem + L::B4 + 4 * kg);
-    if (valid && 4 * kg < a.C) st4(a.q + row * a.C + 4 * kg, qv);
-    // ================= Huber (delta = 1) and the reverse chain
-    f32x4 g4 = (f32x4){0.f, 0.f, 0.f, 0.f};
-    if (4 * kg < a.C) {
-      float ls = 0.f;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const float err = qv[c] - in.y[c];
-        const float ab = fabsf(err), quad = fminf(ab, 1.f);
-        ls += 0.5f * quad * quad + (ab - quad);
-        g4[c] = fminf(fmaxf(err, -1.f), 1.f) * a.inv_denom;
-      }
-      if (valid) {
-        st4(a.dq + srow * a.C + 4 * kg, g4);
-        a.rowloss[srow] = ls;
-      }
-    }
-    const auto lin = [](int nt) { return nt * 16; };
-    f32x4 d3[2][1];
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) d3[nt][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    mfma_rows_multi<2>(smem + L::W4, LD4, lin, 0, j, kg, g4, d3);
-#pragma unroll
-    for (int nt = 0; nt < 2; ++nt) {
-      const bool in_range = nt * 16 + 4 * kg < H3;
-      d3[nt][0] = in_range ? gate4(d3[nt][0], z3[0][nt]) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (valid && in_range) st4(a.dz3 + srow * H3 + nt * 16 + 4 * kg, d3[nt][0]);
-    }
-    f32x4 d2[3][1];
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) d2[nt][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 2; ++kb) mfma_rows_multi<3>(smem + L::W3, LD3, lin, kb, j, kg, d3[kb][0], d2);
-#pragma unroll
-    for (int nt = 0; nt < 3; ++nt) {
-      const bool in_range = nt * 16 + 4 * kg < H2;
-      d2[nt][0] = in_range ? gate4(d2[nt][0], z2[0][nt]) : (f32x4){0.f, 0.f, 0.f, 0.f};
-      if (valid && in_range) st4(a.dz2 + srow * H2 + nt * 16 + 4 * kg, d2[nt][0]);
-    }
-    f32x4 d1[5][1];
-#pragma unroll
-    for (int nt = 0; nt < 5; ++nt) d1[nt][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 3; ++kb) mfma_rows_multi<5>(smem + L::W2, LD2, lin, kb, j, kg, d2[kb][0], d1);
-#pragma unroll
-    for (int nt = 0; nt < 5; ++nt) {
-      d1[nt][0] = gate4(d1[nt][0], z1[0][nt]);
-      if (valid) st4(a.dz1 + row * H1 + nt * 16 + 4 * kg, d1[nt][0]);
-    }
-    const auto skip_xe = [](int nt) { return nt < FB ? nt * 16 : F + XE + (nt - FB) * 16; };
-    f32x4 o[2 * FB][1];
-#pragma unroll
-    for (int nt = 0; nt < 2 * FB; ++nt) o[nt][0] = (f32x4){0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int kb = 0; kb < 5; ++kb) mfma_rows_multi<2 * FB>(smem + L::W1, LD1, skip_xe, kb, j, kg, d1[kb][0], o);
-#pragma unroll
-    for (int nt = 0; nt < 2 * FB; ++nt)
-      if (valid) st4(a.gha + row * (2 * F) + nt * 16 + 4 * kg, o[nt][0]);
-  };
-
-  MlpTrainIn<F> inA, inB;
-  V2X_TILE_PROLOGUE(blockIdx.x * per + wv, t_end, inA, load_in)
-  mlp_fill_lds<F>(smem, a, slot, true, threadIdx.x);
-  __syncthreads();
-  V2X_TILE_LOOP(inA, inB, load_in, compute)
-}
 
 // =====================================================================================
 // k_wgrad : dW[k][n] = sum_rows in[row][k] * dpre[row][n],  db[n] = sum_rows dpre[row][n]
@@ -1081,10 +936,6 @@ struct WgradArgs {
   // a role that covers only PART of the layer's K rows (Dense-0 cut in two, WG_KIND_DENSE0A / B): padded K row of its first
   // segment; the bias gradient is written by the role with bias_too set
   int k_off, no_bias;
-  // k_wgrad MODE 4: the next `chain` roles of the launch have no workgroups of their own -- this role's workgroup runs them after
-  // its own body, for the same (chunk, slot): the light Dense 1..3 roles behind the Dense-0 halves, whose workgroups are the
-  // lightest of the grid (25 + 8 and 20 + 15 accumulator tiles against a graph layer's 36 + its share of the embed layer)
-  int chain, pad_;
 };
 
 constexpr int WG_TR = 16;        // rows per MFMA block (chunk sizes are multiples of it)
@@ -1501,9 +1352,8 @@ enum { WG_KIND_GNN = 0, WG_KIND_EMBED = 1, WG_KIND_DENSE0 = 2, WG_KIND_DENSE1 = 
        // _F: h_L / a_L fragment-major
        WG_KIND_DENSE0A = 10, WG_KIND_DENSE0A_F = 11, WG_KIND_DENSE0B = 12, WG_KIND_DENSE0B_F = 13 };
 
-// MODE 0: the GNN stages, 1: the Dense layers, 2: both families in one launch (roles ordered heaviest first),
-// 3: the GNN stages + Dense-0 in two halves (small batches: kernels_mlpwg.hpp WG0 = false leaves dz1 for it),
-// 4: 3 + Dense 1..3 (smaller batches still: kernels_mlpstream.hpp)
+// MODE 0: the GNN stages, 1: the Dense layers (Dense 1..3 of a wide model: the only launch site is k_wgrad<64, 1>),
+// 3: the GNN stages + Dense-0 in two halves (small batches: kernels_mlpwg.hpp WG0 = false leaves dz1 for it)
 template <int F, int MODE>
 __global__ __launch_bounds__(256, 1) void k_wgrad(WgradMulti mu) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -1538,7 +1388,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad(WgradMulti mu) {
     if (a.kind == WG_KIND_EMBED) { wgrad_body<XE, F, 0, F, 3>(a, smem, bx_, slot_); return; }
     if (a.kind == WG_KIND_EMBED_NONBR) { wgrad_body<XE, F, 0, F, 3, true>(a, smem, bx_, slot_); return; }
   }
-  if constexpr (MODE == 3 || MODE == 4) {
+  if constexpr (MODE == 3) {
     // (a half's block is 100 / 80 MFMAs, 1.2-1.4 us: with one block of loads in flight -- DEPTH 2 -- a wave waits 3.6 us per
     //  block for memory, measured at the 512- / 1024-graph shares; three in flight next to 100 accumulators still fit)
     if (a.kind == WG_KIND_DENSE0A) wgrad_body<F, XE, 0, H1, V2X_WG_DEPTH_D0>(a, smem, bx_, slot_);
@@ -1548,19 +1398,7 @@ __global__ __launch_bounds__(256, 1) void k_wgrad(WgradMulti mu) {
       else if (a.kind == WG_KIND_DENSE0B_F) wgrad_body<F, 0, 0, H1, V2X_WG_DEPTH_D0, false, 0, true>(a, smem, bx_, slot_);
     }
   }
-  if constexpr (MODE == 4) {              // + Dense 1..3 (kernels_mlpstream.hpp leaves their operands in memory), chained behind the halves
-    const int n_chain = a.chain;          // (workgroup-uniform)
-    for (int c = 1; c <= n_chain; ++c) {
-      __syncthreads();                    // (the previous body's accumulator exchange is done with the LDS)
-      CWords cw = kw + (role + c) * NW;
-#pragma unroll
-      for (int i = 0; i < NW; ++i) dstw[i] = cw[i];
-      if (a.kind == WG_KIND_DENSE1) wgrad_body<H1, 0, 0, H2P>(a, smem, bx_, slot_);
-      else if (a.kind == WG_KIND_DENSE2) wgrad_body<H2P, 0, 0, H3P>(a, smem, bx_, slot_);
-      else if (a.kind == WG_KIND_DENSE3) wgrad_body<H3P, 0, 0, CP>(a, smem, bx_, slot_);
-    }
-  }
-  if constexpr (MODE == 1 || MODE == 2) {
+  if constexpr (MODE == 1) {
     if (a.kind == WG_KIND_DENSE0) wgrad_body<F, XE, F, H1>(a, smem, bx_, slot_);
     else if (a.kind == WG_KIND_DENSE1) wgrad_body<H1, 0, 0, H2P>(a, smem, bx_, slot_);
     else if (a.kind == WG_KIND_DENSE2) wgrad_body<H2P, 0, 0, H3P>(a, smem, bx_, slot_);

@@ -1,6 +1,6 @@
 // k_mlp_train_wg: the decision MLP of a fit step with its four weight gradients in the SAME pass over the rows.
 //
-// Replaces, for narrow features, k_mlp_train + the four Dense roles of k_wgrad (TF autodiff of the K.dot's of
+// Replaced, for narrow features, the earlier k_mlp_train launch + four Dense roles of k_wgrad (TF autodiff of the K.dot's of
 // BS_brain.py:176-179 under keras' fit, :231-239).  In that split the hidden activations z1..z3 and the pre-activation
 // gradients dz1..dz3, dq existed in HBM only to reach the weight-gradient launch (1.1 KB written and read back per node
 // row, 2.4x the algorithmic bytes of the MLP) and Dense-0's inputs h | x | agg were streamed twice.  Here a wave keeps

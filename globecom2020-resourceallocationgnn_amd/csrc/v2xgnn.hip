@@ -7,11 +7,11 @@
 #include "kernels_fused.hpp"
 #include "kernels_fused_split.hpp"
 #include "kernels_mlpwg.hpp"
-#include "kernels_mlpstream.hpp"
 #include "kernels_small.hpp"
 #include "kernels_ragged.hpp"
 #include "kernels_ragged_small.hpp"
 #include "host_pack.hpp"
+#include "knobs.hpp"
 
 #include <hip/hip_runtime.h>
 #include <algorithm>
@@ -73,9 +73,7 @@ struct v2x_model {
   bool frag_live = false;                // h_L, a_L (and then gha) of the last training forward are fragment-major (frag_layout)
   unsigned short* gate_bits = nullptr;   // ReLU' gates of the fused forward for the fused backward: [L][gate_stride]
   int64_t gate_stride = 0;               // ushorts per stage: N x ceil(B / 16) x 64 <= 4 R + 64 N
-  hipStream_t side = nullptr;   // weight-gradient kernels run here, forked/joined around the data chain
   hipStream_t cap = nullptr;    // hipGraphs are recorded on this stream and launched on the caller's (run_maybe_graph)
-  std::vector<hipEvent_t> ev;   // fork / per-stage / join events of the side stream
   float* loss_dev = nullptr;
   float* loss_part = nullptr;  // 64 partial sums + the arrival counter of the split loss reduction
   float* zero_buf = nullptr;   // 4 KiB of zeros
@@ -85,22 +83,16 @@ struct v2x_model {
   DevBuf adj_mask;              // adjacency bit masks of the current batch (dense-graph aggregation)
   DevBuf plan_buf;              // work plan of the ragged fused forward (kernels_ragged.hpp): first graph of every workgroup
   int plan_len = 0;             // entries of the last plan (workgroups + 1)
-  long long* ts_buf = nullptr;                  // V2X_FUSED_TS=1: phase time stamps of the fused forward (measurement)
+  Knobs knobs;                                  // the environment switches, read once at v2x_create (knobs.hpp)
+  long long* ts_buf = nullptr;                  // Knobs::fused_ts: phase time stamps of the fused forward (measurement)
   bool raw_params = false;                      // v2x_param_ptr was called: re-pack before every fused forward
   bool pk_stale = false;                        // the fragment-major copy must be rebuilt before the next fused forward
-  bool compl_sums = true;                       // V2X_FUSED_COMPL (read at create): dense graphs aggregate through the complement
-  bool ragged_fused = true, ragged_fused_bwd = true;   // V2X_RAGGED_FUSED / V2X_RAGGED_FUSED_BWD (read at create): kernels_ragged.hpp
-  bool ragged_small_env = false; // V2X_RAGGED_SMALL (read at create): the small-tile ragged kernels (kernels_ragged_small.hpp)
-  bool ragged_packed = true;    // V2X_RAGGED_PACKED: tiles packed by k_ragged_plan (0: the row-interval plan of k_adj_masks)
-  bool ragged_plan_fold = true; // V2X_RAGGED_PLAN_FOLD: the packed plan as a workgroup of the mask launch when its tables are small
-  bool small_predict = true;                    // V2X_SMALL_PREDICT (read at create): few-graph forwards in one launch (kernels_small.hpp)
-  unsigned long long* small_h = nullptr;        // its exchange buffer [L + 1][SMALL_ROWS][F] tagged words
+  unsigned long long* small_h = nullptr;        // exchange buffer of the few-graph predict (kernels_small.hpp) [L + 1][SMALL_ROWS][F] tagged words
   unsigned long long* small_sync = nullptr;     // and per-graph departure counters [SMALL_ROWS] (64-bit)
   char* pin_h = nullptr; char* pin_d = nullptr;  // pinned, device-mapped window for host-resident few-graph predicts: the
                                                 // kernel reads the batch and writes q THROUGH it (no copy launches)
   float *pk_fwd = nullptr, *pk_bwd = nullptr;   // fragment-major copies of the GNN weights (kernels_fused.hpp)
   // split-tile fused kernels (kernels_fused_split.hpp): K workgroups per 16-graph tile at the shares of the global batch
-  int split_env = -1;                           // V2X_FUSED_SPLIT (read at create): -1 auto, 0 / 1 off, K forced
   unsigned long long* xchg_buf = nullptr;       // [2 L slabs][xchg_cap_tiles][N][F / 16][64][4] tagged words
   unsigned long long* xchg_sync = nullptr;      // [xchg_cap_tiles] departures
   int xchg_cap_tiles = 0;
@@ -120,8 +112,6 @@ struct v2x_model {
   std::map<GraphKey, GraphEntry> graphs;
   bool capturing = false;
   // wide path, single-GPU training: the layers' weight gradients are collected and launched as ONE grid (wide_wgrad_flush)
-  float* mlp_img = nullptr;                     // padded images of the Dense layers per slot in global memory (kernels_mlpstream.hpp)
-  bool mlp_stream_now = false;                  // inside a backward pass whose MLP is k_mlp_stream: ALL Dense weight gradients are roles of k_wgrad
   bool dense0_out_now = false;                  // inside a backward pass whose MLP launch leaves Dense-0's weight gradient to k_wgrad
   // inside a DQN replay step whose MLP launch forms the targets itself (MlpArgs::tq): replaced entries, actions, where y goes
   const float* dqn_tq = nullptr; float* dqn_y = nullptr;
@@ -158,6 +148,9 @@ namespace {
     int _r = (x);              \
     if (_r != V2X_OK) return _r; \
   } while (0)
+
+// the switches of a call: the model's, or the process-wide copy for the entry points that may come without a model
+const Knobs& knobs_of(const v2x_model* m) { return m ? m->knobs : process_knobs(); }
 
 // Captured graphs bake in the addresses of the workspace buffers: whenever one of them is re-allocated every cached
 // graph is dropped (it would replay into freed memory and its outputs would no longer be where the caller reads them).
@@ -240,14 +233,9 @@ void set_attrs_f() {
   allow_big_lds((const void*)k_gemm_rows<F, true, true, false>);
   allow_big_lds((const void*)k_gemm_rows<F, true, false, true>);
   allow_big_lds((const void*)k_mlp_fwd<F>);
-  allow_big_lds((const void*)k_mlp_bwd<F>);
-  allow_big_lds((const void*)k_mlp_train<F>);
   allow_big_lds((const void*)k_mlp_train_wg<F>);
   allow_big_lds((const void*)k_mlp_train_wg<F, true>);
   allow_big_lds((const void*)k_wgrad<F, 0>);
-  allow_big_lds((const void*)k_wgrad<F, 1>);
-  allow_big_lds((const void*)k_wgrad<F, 2>);
-  if (F == 64) { allow_big_lds((const void*)k_wgrad<64, 4>); allow_big_lds((const void*)k_mlp_image<64>); }
 }
 
 template <int F>
@@ -270,7 +258,7 @@ void set_attrs_fused() {
   }
 }
 
-void set_attrs(int F) {
+void set_attrs(int F, const Knobs& kn) {
   if (F == 16) set_attrs_fused<16>();
   if (F == 32) set_attrs_fused<32>();
   if (F == 64) set_attrs_fused<64>();
@@ -282,7 +270,7 @@ void set_attrs(int F) {
   if (F == 32) set_attrs_f<32>();
   if (F == 64) set_attrs_f<64>();
   if (F >= 128) {                     // wide path: tail MLP kernels + the narrow weight-gradient kernel for Dense 1..3
-    if (getenv("V2X_DEBUG_OCC")) {
+    if (kn.debug_occ) {
       int n1 = 0, n2 = 0, n3 = 0, n4 = 0;
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&n1, k_wide_gemm<false, 4>, 256, 0);
       hipOccupancyMaxActiveBlocksPerMultiprocessor(&n2, k_wide_gemm<true, 4>, 256, 0);
@@ -340,12 +328,11 @@ int ensure_rows(v2x_model* m, int64_t R) {
 // one partial-sum slab each.  A workgroup walks its chunk sequentially (4 waves, 16-row blocks round-robin), so
 // the launch is as long as its longest workgroup: the chunk count of every role fused into a launch is chosen
 // proportional to the role's MFMA work (KT*NT tiles) so that the whole launch is about ONE balanced round of
-// the chip (V2X_WG_ROUNDS rounds), instead of the same chunking for a 45-tile and a 2-tile layer.
+// the chip (Knobs::wg_rounds rounds), instead of the same chunking for a 45-tile and a 2-tile layer.
 int n_cus();
-int role_chunks(int n_idx, int n_slots, int work, int total_work, int* chunk_out, int dflt_rows = 768) {
-  static const int rounds = getenv("V2X_WG_ROUNDS") ? atoi(getenv("V2X_WG_ROUNDS")) : 0;
-  static const int env_rows = getenv("V2X_WG_CHUNK") ? atoi(getenv("V2X_WG_CHUNK")) : 0;
-  const int rows = env_rows > 0 ? env_rows : dflt_rows;
+int role_chunks(const Knobs& kn, int n_idx, int n_slots, int work, int total_work, int* chunk_out, int dflt_rows = 768) {
+  const int rounds = kn.wg_rounds;
+  const int rows = kn.wg_chunk > 0 ? kn.wg_chunk : dflt_rows;
   int nc;
   if (rounds > 0) {                                             // work-proportional workgroup counts
     long target = ((long)n_cus() * rounds * work + total_work / 2) / total_work;
@@ -462,7 +449,7 @@ int validate_host_batch(v2x_model* m, const v2x_batch* b, int n_nodes) {
   const int32_t *go = b->graph_off, *rp = b->row_ptr, *ci = b->col_idx;
   if (rp[0] != 0 || rp[R] != b->n_edges) FAIL(m, V2X_EINVAL, "batch: row_ptr[0] != 0 or row_ptr[n_rows] != n_edges");
   if (go && (go[0] != 0 || go[B] != R)) FAIL(m, V2X_EINVAL, "batch: graph_off[0] != 0 or graph_off[n_graphs] != n_rows");
-  static const bool trusted = getenv("V2X_TRUSTED_BATCHES") != nullptr;
+  const bool trusted = knobs_of(m).trusted_batches;
   for (int g = 0; g < B; ++g) {
     const int64_t r0 = go ? go[g] : (int64_t)g * n_nodes, r1 = go ? go[g + 1] : r0 + n_nodes;
     const int64_t n = r1 - r0;
@@ -530,10 +517,6 @@ int resolve_batch(v2x_model* m, const v2x_batch* b, DevBatch* d, hipStream_t st)
 }
 
 // ------------------------------------------------------------------------------------ launchers
-int env_int(const char* name, int dflt) {
-  const char* v = getenv(name);
-  return v ? atoi(v) : dflt;
-}
 
 // A launch covers graphs [g0, g0+ng) of the batch.  Every activation / gradient buffer is indexed by the
 // ABSOLUTE node row, so disjoint ranges (micro-batches) can be in flight concurrently on different streams.
@@ -565,8 +548,8 @@ int n_cus() {
 
 // Large dense graphs (e.g. 100 links, in-degree 98): the contraction runs on the MFMA pipe against adjacency
 // bit masks (k_agg_dense) instead of one LDS gather per edge.
-bool use_dense_agg(const DevBatch& d, int F) {
-  static const int dense_min_nodes = env_int("V2X_AGG_DENSE_MIN_NODES", 32);
+bool use_dense_agg(const Knobs& kn, const DevBatch& d, int F) {
+  const int dense_min_nodes = kn.agg_dense_min_nodes;
   const size_t rows_cap = (d.max_nodes + 15) / 16 * 16, mw = (d.max_nodes + 31) / 32;
   return F >= 64 && d.max_nodes >= dense_min_nodes && (int64_t)d.max_edges * 4 >= (int64_t)d.max_nodes * d.max_nodes &&
          rows_cap * AD_LDT * 4 + rows_cap * mw * 4 + 4 * 64 * 4 <= 160 * 1024;
@@ -603,7 +586,8 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
     return true;
   }();
   (void)attrs_once;
-  if (use_dense_agg(d, F)) {
+  const Knobs& kn = knobs_of(m);
+  if (use_dense_agg(kn, d, F)) {
     AggDenseArgs q = agg_dense_args(d, r, N, F);
     q.src = src; q.src_stride = src_stride; q.add = add; q.add_stride = add_stride; q.mask = mask; q.out = out;
     q.err = flag_dev_of(m);
@@ -644,7 +628,7 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
   int gpw = 1;
   // few graphs per workgroup => many workers per graph => short per-worker row loops (the kernel is a
   // latency chain: stage -> barrier -> LDS gathers -> store); keep >= 8 workers per graph when F allows
-  static const int wpg_min = env_int("V2X_AGG_WORKERS_PER_GRAPH", 8);
+  const int wpg_min = kn.agg_workers_per_graph;
   while (gpw * 2 <= nworkers && nworkers / (gpw * 2) >= wpg_min && (size_t)(gpw * 2) * per_graph <= 48 * 1024 && gpw * 2 <= r.ng) gpw *= 2;
   a.gpw = gpw;
   a.rows_cap = gpw * d.max_nodes;
@@ -654,7 +638,7 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
   if (lds > 160 * 1024) FAIL(m, V2X_EINVAL, "agg: graph tile (%zu B) exceeds the 160 KiB LDS", lds);
   const dim3 grid((r.ng + gpw - 1) / gpw);
   // small tiles (the 20-link graphs of the headline configuration): everything fetched before the first wait
-  static const bool small_off = getenv("V2X_AGG_NO_SMALL") != nullptr;
+  const bool small_off = kn.agg_no_small;
   const int wpg = nworkers / gpw;
   const bool small = !small_off && d.ci != nullptr && (a.rows_cap << sh) <= 1024 && a.rows_cap + 1 <= 256 && a.edges_cap <= 1024 &&
                      (d.max_nodes + wpg - 1) / wpg <= 4;
@@ -704,7 +688,7 @@ int launch_wide_gemm(v2x_model* m, hipStream_t st, WideGemmArgs& a, int grid_z, 
   // Tiling (kernels_wide.hpp, WideTiling): 128-row tiles; when the launch is more than one round of the chip's resident
   // workgroups (five per CU) and its last round would be less than three quarters full, the row blocks of that last round run
   // as two 64-row tiles each, dispatched last (V2X_WIDE_TAIL=0: whole tiles only)
-  static const int tail = env_int("V2X_WIDE_TAIL", 1);
+  const int tail = m->knobs.wide_tail;
   WideTiling t;
   t.ny = (a.n_out + 16 * nt - 1) / (16 * nt);
   t.mbs = (a.n_idx + WD_TM - 1) / WD_TM;
@@ -780,7 +764,7 @@ int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x
   // costing a whole 128-wide K tile of its own.  Only worth it when the launch is balanced over many workgroups per CU
   // (the merged launch): on its own a stage is 500 workgroups on 256 CUs and as long as its fullest CU either way
   // (measured: 298 us unfolded, 333 us folded -- 400 workgroups, the same two per CU, one of them 12.5 % longer)
-  static const int fold = env_int("V2X_WIDE_FOLD", 1);
+  const int fold = m->knobs.wide_fold;
   for (int i = 0; i < n_seg; ++i) {
     if (fold && m->wide_merge_now && KW == 128 && n_seg > 1 && segs[i].width == XE && !a.xseg.ptr) { a.xseg = segs[i]; a.xseg_kpad = seg_kpad[i]; continue; }
     a.seg[ns] = segs[i]; a.seg_kpad[ns] = seg_kpad[i]; kt += (segs[i].width + KW - 1) / KW;
@@ -871,8 +855,7 @@ int launch_gemm_t(v2x_model* m, hipStream_t st, GemmArgs& a, int grid_y, const c
   constexpr int KB = DGRAD ? FB : ((HAS0 ? FB : 0) + 1 + (HAS2 ? FB : 0));
   constexpr int KP = DGRAD ? (2 * F + XE) : KB * 16;
   const size_t lds = (size_t)(KP * (F + 4) + F) * 4;
-  static const int wgs_per_cu = env_int("V2X_GEMM_WGS_PER_CU", 2);
-  const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, wgs_per_cu);
+  const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, m->knobs.gemm_wgs_per_cu);
   auto k = k_gemm_rows<F, HAS0, HAS2, DGRAD>;
   LAUNCH(m, name, k, dim3(gx, grid_y), lds, st, a);
   return V2X_OK;
@@ -946,47 +929,18 @@ void mlp_args(v2x_model* m, MlpArgs& a, const IdxMap& x, const float* xe, const 
 }
 
 template <int F>
-int launch_mlp_f(v2x_model* m, hipStream_t st, MlpArgs& a, int grid_y, bool bwd) {
+int launch_mlp_fwd_f(v2x_model* m, hipStream_t st, MlpArgs& a, int grid_y) {
   const size_t lds = (size_t)MlpLds<F>::TOTAL * 4;
-  static const int wgs_per_cu = env_int("V2X_MLP_WGS_PER_CU", 2);
-  const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, wgs_per_cu);
-  if (!bwd) { auto k = k_mlp_fwd<F>; LAUNCH(m, "k_mlp_fwd", k, dim3(gx, grid_y), lds, st, a); }
-  else { auto k = k_mlp_bwd<F>; LAUNCH(m, "k_mlp_bwd", k, dim3(gx, grid_y), lds, st, a); }
+  const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, m->knobs.mlp_wgs_per_cu);
+  auto k = k_mlp_fwd<F>;
+  LAUNCH(m, "k_mlp_fwd", k, dim3(gx, grid_y), lds, st, a);
   return V2X_OK;
 }
 
-// forward + Huber + backward of the decision MLP in one launch (narrow features only)
-template <int F>
-int launch_mlp_train_f(v2x_model* m, hipStream_t st, MlpArgs& a, int grid_y) {
-  const size_t lds = (size_t)MlpLds<F>::TOTAL * 4;
-  static const int wgs_per_cu = env_int("V2X_MLP_WGS_PER_CU", 2);
-  const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, wgs_per_cu);
-  auto k = k_mlp_train<F>;
-  LAUNCH(m, "k_mlp_train", k, dim3(gx, grid_y), lds, st, a);
-  return V2X_OK;
-}
-
-bool mlp_fused_training(const v2x_model* m) {
-  static const bool off = getenv("V2X_MLP_SPLIT") != nullptr;
-  return !off && m->F <= 64;
-}
-
-int launch_mlp_train(v2x_model* m, hipStream_t st, MlpArgs& a) {
-  const int gy = m->S == 1 ? 1 : m->N;
-  switch (m->F) {
-    case 16: return launch_mlp_train_f<16>(m, st, a, gy);
-    case 32: return launch_mlp_train_f<32>(m, st, a, gy);
-    case 64: return launch_mlp_train_f<64>(m, st, a, gy);
-  }
-  FAIL(m, V2X_EINVAL, "unsupported feat_dim %d", m->F);
-}
-
-// ... and with the four Dense weight gradients in the same pass (kernels_mlpwg.hpp): one workgroup per CU, each
-// writes one partial-sum slab of the Dense layers
-bool mlp_wg_path(const v2x_model* m) {
-  static const bool off = env_int("V2X_MLP_WG", 1) == 0;
-  return !off && mlp_fused_training(m);
-}
+// Training of a narrow model (F <= 64): forward + Huber + backward of the decision MLP and the four Dense weight gradients in
+// ONE launch (k_mlp_train_wg, kernels_mlpwg.hpp): one workgroup per CU, each writes one partial-sum slab of the Dense layers.
+// A wide model runs k_mlp_fwd<0> / k_mlp_bwd<0> around its wide GEMMs (launch_mlp) and wgrad_mlp.
+bool mlp_wg_path(const v2x_model* m) { return !is_wide(m); }
 
 // work split of k_mlp_train_wg (MlpWgArgs): one workgroup per CU, equal shares of the slot-major tile list
 struct MlpWgSplit { int tiles_per_slot, slot_span, tiles_per_wg, n_wgs, n_slabs; };
@@ -1054,15 +1008,18 @@ int launch_mlp(v2x_model* m, hipStream_t st, MlpArgs& a, bool bwd) {
     if (!bwd) {
       WideSeg s[3] = {WideSeg{a.h, F, F}, WideSeg{a.xe, XE, XE}, WideSeg{a.agg, F, F}};
       CHK(wide_fwd(m, st, m->dense[0], x, s, 3, m->z1, H1, 1, "k_dense0_fwd"));
-      return launch_mlp_f<0>(m, st, a, gy, false);
+      return launch_mlp_fwd_f<0>(m, st, a, gy);
     }
-    CHK(launch_mlp_f<0>(m, st, a, gy, true));
+    const int gx = persistent_wgs_per_slot(a.n_idx, gy, m->knobs.mlp_wgs_per_cu);
+    auto k = k_mlp_bwd<0>;
+    LAUNCH(m, "k_mlp_bwd", k, dim3(gx, gy), (size_t)MlpLds<0>::TOTAL * 4, st, a);
     return wide_dgrad(m, st, m->dense[0], x, m->dz1, H1, m->Dn, m->gha, "k_dense0_dgrad");
   }
+  if (bwd) FAIL(m, V2X_ESTATE, "mlp: the backward of a narrow model is part of k_mlp_train_wg");
   switch (m->F) {
-    case 16: return launch_mlp_f<16>(m, st, a, gy, bwd);
-    case 32: return launch_mlp_f<32>(m, st, a, gy, bwd);
-    case 64: return launch_mlp_f<64>(m, st, a, gy, bwd);
+    case 16: return launch_mlp_fwd_f<16>(m, st, a, gy);
+    case 32: return launch_mlp_fwd_f<32>(m, st, a, gy);
+    case 64: return launch_mlp_fwd_f<64>(m, st, a, gy);
   }
   FAIL(m, V2X_EINVAL, "unsupported feat_dim %d", m->F);
 }
@@ -1078,12 +1035,12 @@ int wgrad_role(v2x_model* m, LayerDesc& ld, int kind, const IdxMap& x, int total
   // 1024 / 768 for the GNN / Dense families (102 us, the optimum when the two families were separate launches)
   // (the graph layers on their own -- the Dense gradients come out of k_mlp_train_wg -- : 896, i.e. 5 x 832 rows per
   //  slot at batch 4096: 46.8 us against 53.1 at 1024, 48.7 at 768, 49.4 at 704, 57.2 at 640)
-  static const int rows_gnn = env_int("V2X_WG_CHUNK_GNN", 0), rows_dense = env_int("V2X_WG_CHUNK_DENSE", 1024);
-  int rows_g = rows_gnn > 0 ? rows_gnn : (mlp_wg_path(m) ? 896 : 1024);
-  static const int rows_embed = env_int("V2X_WG_CHUNK_EMBED", 0);       // the (light) embed role on its own chunking
+  const Knobs& kn = m->knobs;
+  const int rows_dense = kn.wg_chunk_dense, rows_embed = kn.wg_chunk_embed;       // (the light embed role may have its own chunking)
+  int rows_g = kn.wg_chunk_gnn > 0 ? kn.wg_chunk_gnn : (is_wide(m) ? 1024 : 896);
   if (rows_embed > 0 && (kind == WG_KIND_EMBED || kind == WG_KIND_EMBED_NONBR)) rows_g = rows_embed;
   if (rows_override > 0) rows_g = rows_override;
-  const int nc = role_chunks(x.n_idx, x.grid_y, layer_work(ld), total_work, &chunk, (gnn_kind || rows_override > 0) ? rows_g : rows_dense);
+  const int nc = role_chunks(kn, x.n_idx, x.grid_y, layer_work(ld), total_work, &chunk, (gnn_kind || rows_override > 0) ? rows_g : rows_dense);
   if (nc > m->slab_cap) FAIL(m, V2X_ESTATE, "wgrad: slabs not pre-sized (%d > %d)", nc, m->slab_cap);
   ld.n_slabs = nc;                       // remembered for the slab reduction
   memset(&a, 0, sizeof(a));
@@ -1108,53 +1065,41 @@ int launch_wgrad_multi(v2x_model* m, hipStream_t st, const IdxMap& x, WgradMulti
     maxt = std::max(maxt, (mu.w[i].kp / 16) * (mu.w[i].np / 16) + (mu.w[i].kind >= WG_KIND_GNN_E1 ? 4 : 0));
     nc = std::max(nc, mu.w[i].n_chunks);
   }
-  {                                     // phase stamps (V2X_FUSED_TS=1): of ONE role, V2X_WG_TS_ROLE (default: the first)
-    static const int ts_role = env_int("V2X_WG_TS_ROLE", 0);
-    for (int i = 0; i < n_roles; ++i)
-      if (i != ts_role) mu.w[i].ts = nullptr;
-  }
+  for (int i = 0; i < n_roles; ++i)     // phase stamps (Knobs::fused_ts): of ONE role, Knobs::wg_ts_role (default: the first)
+    if (i != m->knobs.wg_ts_role) mu.w[i].ts = nullptr;
   const size_t lds = (size_t)(2 * maxt * 64 * 4 + 4 * 9 * 16) * 4;      // accumulator exchange (two sets) + bias (per wave)
   dim3 grid(nc, x.grid_y, n_roles);
   {                                     // unequal chunk counts: a packed 1-D grid of the real workgroups (kernels.hpp WgradMulti)
     bool uneven = false;
-    for (int i = 0; i < n_roles; ++i) uneven = uneven || mu.w[i].n_chunks != nc || mu.w[i].chain > 0;
+    for (int i = 0; i < n_roles; ++i) uneven = uneven || mu.w[i].n_chunks != nc;
     mu.packed = uneven ? 1 : 0;
-    int at = 0, follow = 0;                 // (the `chain` roles behind a role are run by ITS workgroups: none of their own)
+    int at = 0;
     for (int i = 0; i <= WG_MAX_ROLES; ++i) {
       mu.wg_begin[i] = at;
-      if (i < n_roles) {
-        if (follow > 0) --follow;
-        else { at += mu.w[i].n_chunks * x.grid_y; follow = mu.w[i].chain; }
-      }
+      if (i < n_roles) at += mu.w[i].n_chunks * x.grid_y;
     }
     if (uneven) grid = dim3(at, 1, 1);
   }
-  bool dense = false, gnn = false;
-  bool halves = false;
+  // a narrow model's launch holds graph-layer roles (+ the Dense-0 halves); a wide model's only Dense 1..3
+  bool dense = false, halves = false;
   for (int i = 0; i < n_roles; ++i) {
-    if (mu.w[i].kind >= WG_KIND_DENSE0A) { halves = true; continue; }
-    ((mu.w[i].kind >= WG_KIND_DENSE0 && mu.w[i].kind <= WG_KIND_DENSE3) ? dense : gnn) = true;
+    if (mu.w[i].kind >= WG_KIND_DENSE0A) halves = true;
+    else if (mu.w[i].kind >= WG_KIND_DENSE0 && mu.w[i].kind <= WG_KIND_DENSE3) dense = true;
   }
 #define V2X_WG_CASE(FF)                                                              \
-  if (m->F == FF) {                                                                  \
-    if (halves && dense) {                                                           \
-      if constexpr (FF == 64) { auto k = k_wgrad<64, 4>; LAUNCH(m, name, k, grid, lds, st, mu); }  \
-      else FAIL(m, V2X_ESTATE, "wgrad: Dense roles next to the Dense-0 halves need feat_dim 64");  \
-    }                                                                                \
-    else if (halves) { auto k = k_wgrad<FF, 3>; LAUNCH(m, name, k, grid, lds, st, mu); }    \
-    else if (dense && gnn) { auto k = k_wgrad<FF, 2>; LAUNCH(m, name, k, grid, lds, st, mu); }  \
-    else if (dense) { auto k = k_wgrad<FF, 1>; LAUNCH(m, name, k, grid, lds, st, mu); }  \
+  if (m->F == FF && !dense) {                                                        \
+    if (halves) { auto k = k_wgrad<FF, 3>; LAUNCH(m, name, k, grid, lds, st, mu); }    \
     else { auto k = k_wgrad<FF, 0>; LAUNCH(m, name, k, grid, lds, st, mu); }           \
     return V2X_OK;                                                                   \
   }
   V2X_WG_CASE(16) V2X_WG_CASE(32) V2X_WG_CASE(64)
 #undef V2X_WG_CASE
-  if (is_wide(m) && dense) {            // Dense 1..3 only (their operand widths do not depend on F)
+  if (is_wide(m) && dense && !halves) { // (the operand widths of Dense 1..3 do not depend on F)
     auto k = k_wgrad<64, 1>;
     LAUNCH(m, name, k, grid, lds, st, mu);
     return V2X_OK;
   }
-  FAIL(m, V2X_EINVAL, "wgrad: %d output tiles unsupported", maxt);
+  FAIL(m, V2X_EINVAL, "wgrad: no kernel for these roles at feat_dim %d", m->F);
 }
 
 int wgrad_gnn_role(v2x_model* m, int stage, const IdxMap& x, int total_work, const float* xe, const float* h_prev,
@@ -1199,10 +1144,9 @@ int wide_wgrad_gnn(v2x_model* m, hipStream_t st, int stage, const IdxMap& x, con
 // workgroups walking 8 blocks per wave: 33.8 / 34.1 us per launch against 19.2 / 20.6 us with 128- / 192-row chunks.)
 // extra_roles: roles of about a graph layer's weight that ride in the same grid (Dense-0 at small batches, dense0_rides)
 int merged_wg_rows(const v2x_model* m, int n_idx, int n_slots, int extra_roles = 0) {
-  static const int rows_env = env_int("V2X_WG_CHUNK_MERGED", 0);
-  if (rows_env > 0) return rows_env;
+  if (m->knobs.wg_chunk_merged > 0) return m->knobs.wg_chunk_merged;
   const int nc_fit = n_cus() / std::max(1, (m->L + extra_roles) * n_slots);
-  static const int min_rows = env_int("V2X_WG_MERGED_MIN_ROWS", 64);
+  const int min_rows = m->knobs.wg_merged_min_rows;
   if (nc_fit >= 1 && n_idx / nc_fit >= min_rows) return ((n_idx + nc_fit - 1) / nc_fit + 63) / 64 * 64;
   return 0;
 }
@@ -1219,24 +1163,23 @@ int wgrad_gnn(v2x_model* m, hipStream_t st, int stage, const IdxMap& x, const fl
 
 // The embed layer's gradient rides on the graph layers' roles (wgrad_gnn_all)
 bool embed_rides(const v2x_model* m, const DevBatch& d) {
-  static const int merge_env = env_int("V2X_WG_EMBED_MERGE", 1);
+  const int merge_env = m->knobs.wg_embed_merge;
   const int NTf = m->F / 16;
   return merge_env && !is_wide(m) && !d.nbr && m->L >= 1 && m->L <= NTf && NTf % m->L == 0 && m->L + 3 <= WG_MAX_ROLES;
 }
 // Small batches (the shares of the metric's global batch on 4 / 8 GPUs): k_mlp_train_wg is ONE wave's latency chain there (<= 2
 // tiles per wave) and the graph layers' weight-gradient launch leaves a third of the chip idle: Dense-0's weight gradient -- 180
 // of a tile's 796 MFMAs, 45 of the 68 accumulator tiles the MLP launch exchanges and writes at its end -- moves over as a role
-// of that launch (kernels_mlpwg.hpp WG0 = false, kernels.hpp WG_KIND_DENSE0_FRAG).  V2X_MLP_WG0=1: never, =0: whenever possible.
+// of that launch (kernels_mlpwg.hpp WG0 = false, kernels.hpp WG_KIND_DENSE0_FRAG).  Knobs::mlp_wg0 = 1: never, 0: whenever possible.
 bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x) {
-  const int env = env_int("V2X_MLP_WG0", -1);                     // (read per call: the tests switch it inside one process)
+  const int env = m->knobs.mlp_wg0;
   if (env == 1 || m->F != 64 || m->cfg.variable_graphs || !embed_rides(m, d)) return false;
   if (x.n_idx % 16 || x.idx_base % 16) return false;             // whole 16-row groups (the fragment-major reader)
   if (env == 0) return true;
   // tiles per workgroup = 4 x tiles per wave.  Measured (profiles/r06_dense0_role_shares.txt): 512 / 1024 / 2048 graphs of 20 links
   // (4 / 8 / 12 tiles per workgroup) 0.1201 -> 0.1131, 0.1512 -> 0.1463, 0.1929 -> 0.1880 ms per step; at 4096 (20-24 tiles) the chip
   // is full either way and the heavier weight-gradient launch costs more than the MLP launch saves (0.2554 -> 0.2658)
-  static const int max_tiles = env_int("V2X_MLP_WG0_TILES", 12);
-  return mlp_wg_split(x.n_idx, x.grid_y).tiles_per_wg <= max_tiles;
+  return mlp_wg_split(x.n_idx, x.grid_y).tiles_per_wg <= m->knobs.mlp_wg0_tiles;
 }
 
 // all GNN stages (needs dpre[0..L]): one launch when the embed rides on the stage roles (embed_rides), else
@@ -1280,34 +1223,19 @@ int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch&
       const int F = m->F, L = m->L;
       const int groups = m->frag_live ? d.B / FZ_TG : 0;
       int chunk_g;
-      const int nc_g = role_chunks(x.n_idx, x.grid_y, 1, 1, &chunk_g, rows > 0 ? rows : 896);
+      const int nc_g = role_chunks(m->knobs, x.n_idx, x.grid_y, 1, 1, &chunk_g, rows > 0 ? rows : 896);
       const int rows_d = (((x.n_idx + std::max(1, nc_g / 2) - 1) / std::max(1, nc_g / 2)) + 63) / 64 * 64;
       WgSeg sa[2] = {WgSeg{m->h[L], F, F, 0, 0}, WgSeg{d.xe, XE, XE, F, 0}};
       CHK(wgrad_role(m, m->dense[0], groups ? WG_KIND_DENSE0A_F : WG_KIND_DENSE0A, x, total, sa, 2, m->dz1, H1, mu.w[n], rows_d));
       mu.w[n].frag_groups = groups; mu.w[n].kp = F + XE;
-      const int first_half = n++;
-      // (k_mlp_stream: Dense 1..3 from the rows it left -- z1..z3, dz2, dz3, dq -- as roles WITHOUT workgroups of their own, run by
-      //  the halves' workgroups behind their own bodies, WgradArgs::chain: as roles of their own in 512-row chunks they made the
-      //  launch 35 us instead of 21.6 at the 512-graph share)
-      if (m->mlp_stream_now) {
-        WgSeg s2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
-        CHK(wgrad_role(m, m->dense[2], WG_KIND_DENSE2, x, total, s2, 1, m->dz3, H3, mu.w[n++], rows_d));
-        WgSeg s3[1] = {WgSeg{m->z3, H3, H3, 0, 1}};
-        CHK(wgrad_role(m, m->dense[3], WG_KIND_DENSE3, x, total, s3, 1, m->dq, m->C, mu.w[n++], rows_d));
-        mu.w[first_half].chain = 2;
-      }
+      ++n;
       WgSeg sb[1] = {WgSeg{m->a[L], F, F, 0, 0}};
       CHK(wgrad_role(m, m->dense[0], groups ? WG_KIND_DENSE0B_F : WG_KIND_DENSE0B, x, total, sb, 1, m->dz1, H1, mu.w[n], rows_d));
       mu.w[n].frag_groups = groups; mu.w[n].kp = F; mu.w[n].k_off = F + XE; mu.w[n].no_bias = 1;
-      const int second_half = n++;
-      if (m->mlp_stream_now) {
-        WgSeg s1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
-        CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, s1, 1, m->dz2, H2, mu.w[n++], rows_d));
-        mu.w[second_half].chain = 1;
-      }
+      ++n;
     }
     m->gnn[0].n_slabs = m->gnn[1].n_slabs;                     // every stage role writes its columns of every embed slab
-    return launch_wgrad_multi(m, st, x, mu, n, m->mlp_stream_now ? "k_wgrad_gnn_d0123" : (d0 ? "k_wgrad_gnn_d0" : "k_wgrad_gnn"));
+    return launch_wgrad_multi(m, st, x, mu, n, d0 ? "k_wgrad_gnn_d0" : "k_wgrad_gnn");
   }
   if (m->dense0_out_now) FAIL(m, V2X_ESTATE, "wgrad: Dense-0 was left to a launch that cannot take it");
   int n = 0, s_first = m->L;
@@ -1321,60 +1249,25 @@ int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch&
   return V2X_OK;
 }
 
-// the 4 Dense layers in one launch
+// the Dense layers of a wide model: Dense-0 as a wide weight gradient (or a role of the merged launch), Dense 1..3 in one k_wgrad
+// launch.  (A narrow model's Dense gradients come out of k_mlp_train_wg, Dense-0's at small batches out of wgrad_gnn_all.)
 int wgrad_mlp(v2x_model* m, hipStream_t st, const IdxMap& x, const float* xe, const float* h, const float* agg) {
+  if (!is_wide(m)) FAIL(m, V2X_ESTATE, "wgrad_mlp: a narrow model's Dense gradients are part of k_mlp_train_wg");
   const int F = m->F;
   int total = 0;
   for (int i = 0; i < 4; ++i) total += layer_work(m->dense[i]);
   WgradMulti mu;
   memset(&mu, 0, sizeof(mu));
-  if (is_wide(m)) {
-    WideSeg w0[3] = {WideSeg{h, F, F}, WideSeg{xe, XE, XE}, WideSeg{agg, F, F}};
-    const int kp[3] = {0, F, F + XE};
-    if (!m->wide_merge_now) CHK(wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0"));   // else: a role of the merged launch
-    WgSeg t1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
-    CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, t1, 1, m->dz2, H2, mu.w[0]));
-    WgSeg t2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
-    CHK(wgrad_role(m, m->dense[2], WG_KIND_DENSE2, x, total, t2, 1, m->dz3, H3, mu.w[1]));
-    WgSeg t3[1] = {WgSeg{m->z3, H3, H3, 0, 1}};
-    CHK(wgrad_role(m, m->dense[3], WG_KIND_DENSE3, x, total, t3, 1, m->dq, m->C, mu.w[2]));
-    return launch_wgrad_multi(m, st, x, mu, 3, "k_wgrad_dense");
-  }
-  WgSeg s0[3] = {WgSeg{h, F, F, 0, 0}, WgSeg{xe, XE, XE, F, 0}, WgSeg{agg, F, F, F + XE, 0}};
-  CHK(wgrad_role(m, m->dense[0], WG_KIND_DENSE0, x, total, s0, 3, m->dz1, H1, mu.w[0]));
-  WgSeg s1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
-  CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, s1, 1, m->dz2, H2, mu.w[1]));
-  WgSeg s2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
-  CHK(wgrad_role(m, m->dense[2], WG_KIND_DENSE2, x, total, s2, 1, m->dz3, H3, mu.w[2]));
-  WgSeg s3[1] = {WgSeg{m->z3, H3, H3, 0, 1}};
-  CHK(wgrad_role(m, m->dense[3], WG_KIND_DENSE3, x, total, s3, 1, m->dq, m->C, mu.w[3]));
-  return launch_wgrad_multi(m, st, x, mu, 4, "k_wgrad_dense");
-}
-
-// every layer's weight gradient in ONE launch (single-stream backward): roles heaviest first, because workgroups
-// are dispatched in blockIdx.z order and the launch is as long as its last-finishing workgroup
-bool wgrad_all_fits(const v2x_model* m) { return !is_wide(m) && m->L + 1 + 4 <= WG_MAX_ROLES; }
-
-int wgrad_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch& d) {
-  const int F = m->F, L = m->L;
-  int total = 0;
-  for (int i = 0; i < 4; ++i) total += layer_work(m->dense[i]);
-  for (int s = 0; s <= L; ++s) total += layer_work(m->gnn[s]);
-  WgradMulti mu;
-  memset(&mu, 0, sizeof(mu));
-  int n = 0;
-  WgSeg s0[3] = {WgSeg{m->h[L], F, F, 0, 0}, WgSeg{d.xe, XE, XE, F, 0}, WgSeg{m->a[L], F, F, F + XE, 0}};
-  CHK(wgrad_role(m, m->dense[0], WG_KIND_DENSE0, x, total, s0, 3, m->dz1, H1, mu.w[n++]));
-  for (int s = L; s >= 1; --s)
-    CHK(wgrad_gnn_role(m, s, x, total, d.xe, m->h[s - 1], m->a[s - 1], m->dpre[s], mu.w[n++]));
-  CHK(wgrad_gnn_role(m, 0, x, total, d.xe, nullptr, d.nbr, m->dpre[0], mu.w[n++]));
-  WgSeg s1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
-  CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, s1, 1, m->dz2, H2, mu.w[n++]));
-  WgSeg s2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
-  CHK(wgrad_role(m, m->dense[2], WG_KIND_DENSE2, x, total, s2, 1, m->dz3, H3, mu.w[n++]));
-  WgSeg s3[1] = {WgSeg{m->z3, H3, H3, 0, 1}};
-  CHK(wgrad_role(m, m->dense[3], WG_KIND_DENSE3, x, total, s3, 1, m->dq, m->C, mu.w[n++]));
-  return launch_wgrad_multi(m, st, x, mu, n, "k_wgrad_all");
+  WideSeg w0[3] = {WideSeg{h, F, F}, WideSeg{xe, XE, XE}, WideSeg{agg, F, F}};
+  const int kp[3] = {0, F, F + XE};
+  if (!m->wide_merge_now) CHK(wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0"));   // else: a role of the merged launch
+  WgSeg t1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
+  CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, t1, 1, m->dz2, H2, mu.w[0]));
+  WgSeg t2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
+  CHK(wgrad_role(m, m->dense[2], WG_KIND_DENSE2, x, total, t2, 1, m->dz3, H3, mu.w[1]));
+  WgSeg t3[1] = {WgSeg{m->z3, H3, H3, 0, 1}};
+  CHK(wgrad_role(m, m->dense[3], WG_KIND_DENSE3, x, total, t3, 1, m->dq, m->C, mu.w[2]));
+  return launch_wgrad_multi(m, st, x, mu, 3, "k_wgrad_dense");
 }
 
 struct LossJob { int n_out, n_idx, stride; float scale; int64_t slot_stride; };   // n_out == 0: no loss role;
@@ -1476,7 +1369,7 @@ bool fused_path(const v2x_model* m, const DevBatch& d) {
 }
 // Aggregations through the complement (kernels_fused.hpp, compl_sums): dense graphs whose extra LDS fits
 bool fused_compl(const v2x_model* m, const DevBatch& d) {
-  if (!m->compl_sums || m->N < 4) return false;
+  if (!m->knobs.fused_compl || m->N < 4) return false;
   if (2 * (int64_t)d.E <= (int64_t)d.B * m->N * (m->N - 1)) return false;      // average in-degree <= (N - 1) / 2
   return fused_lds(m, d, true, true) <= 160 * 1024;
 }
@@ -1495,11 +1388,12 @@ int launch_check(v2x_model* m, const char* kname) {
 // tile admits no second one), and a member should keep at least four slots (below that the hand-overs cost more than the
 // node updates they spread).  Edge form only.
 int fused_split(const v2x_model* m, const DevBatch& d) {
-  if (m->split_env == 0 || m->split_env == 1 || !fused_path(m, d) || m->L < 1 || m->L > 3) return 1;
+  const int split_env = m->knobs.fused_split;                        // -1 auto, 0 / 1 off, K forced
+  if (split_env == 0 || split_env == 1 || !fused_path(m, d) || m->L < 1 || m->L > 3) return 1;
   if (fused_lds(m, d, true) + (size_t)m->N * m->F * 4 > 160 * 1024) return 1;      // + the embed biases of all slots (forward)
   const int tiles = (d.B + FZ_TG - 1) / FZ_TG;
   auto fits = [&](int k) { return (m->N + k - 1) / k <= FZ_WAVES && tiles * k <= n_cus(); };      // one slot per wave, all co-resident
-  if (m->split_env > 1) return (2 * m->split_env <= m->N && fits(m->split_env)) ? m->split_env : 1;
+  if (split_env > 1) return (2 * split_env <= m->N && fits(split_env)) ? split_env : 1;
   for (int k : {5, 4, 3, 2})
     if (4 * k <= m->N && fits(k)) return k;
   return 1;
@@ -1580,20 +1474,18 @@ int launch_pack(v2x_model* m, hipStream_t st) {
 
 // Fragment-major hand-off between the fused graph-layer kernels and k_mlp_train_wg (MlpArgs::frag_groups): whole batch in
 // whole 16-graph groups, per-node weights (a tile of the MLP kernel is then a group of one node), at least one graph layer.
-bool mlp_wg_path(const v2x_model* m);
 bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x);
 bool frag_layout(const v2x_model* m, const DevBatch& d, Range r) {
-  static const int on = env_int("V2X_FRAG_HANDOFF", 1), per_stage = env_int("V2X_WG_PER_STAGE", 0);
-  // (V2X_FRAG_WITH_DENSE0_ROLE=0: row-major hand-over where Dense-0's weight gradient is a role of k_wgrad -- measured slower: the
+  // (Knobs::frag_with_dense0_role = 0: row-major hand-over where Dense-0's weight gradient is a role of k_wgrad -- measured slower: the
   //  fragment-major reader of that role costs nothing next to what the MLP launch and the fused kernels gain from 1 KiB accesses,
   //  0.1131 against 0.1157 ms at the 512-graph share)
-  static const int frag_d0 = env_int("V2X_FRAG_WITH_DENSE0_ROLE", 1);
-  return on && !per_stage && fused_path(m, d) && r.g0 == 0 && r.ng == d.B && mlp_wg_path(m) && m->S == m->N && m->L >= 1 &&
+  const int on = m->knobs.frag_handoff, frag_d0 = m->knobs.frag_with_dense0_role;
+  return on && fused_path(m, d) && r.g0 == 0 && r.ng == d.B && mlp_wg_path(m) && m->S == m->N && m->L >= 1 &&
          d.B % FZ_TG == 0 && (frag_d0 || !dense0_rides(m, d, idx_map(m, d, r)));
 }
 
 int launch_fused_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, bool frag_out = false) {
-  static const int split_fwd = env_int("V2X_FUSED_SPLIT_FWD", 1);      // (debugging: one direction on whole tiles)
+  const int split_fwd = m->knobs.fused_split_fwd;                      // (debugging: one direction on whole tiles)
   // The copy follows the parameters by itself: Adam writes both (k_reduce_adam / pack_scatter), set / copy_weights
   // re-pack eagerly.  Only a caller that took the raw parameter pointer (v2x_param_ptr) forces a re-pack per forward.
   if (m->pk_stale) { CHK(launch_pack(m, st)); m->pk_stale = m->raw_params; }
@@ -1650,7 +1542,7 @@ int launch_fused_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, bool frag_
 }
 
 int launch_fused_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
-  static const int split_bwd = env_int("V2X_FUSED_SPLIT_BWD", 1);      // (debugging: one direction on whole tiles)
+  const int split_bwd = m->knobs.fused_split_bwd;                      // (debugging: one direction on whole tiles)
   FusedBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.row_ptr = d.rp; a.col_idx = d.ci; a.pk = m->pk_bwd; a.gha = m->gha;
@@ -1708,7 +1600,7 @@ int launch_fused_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
 // ------------------------------------------------------------------------------------ few-graph predict, one launch
 constexpr int SMALL_ROWS = 256;             // node rows (= workgroups) of one launch: all co-resident on any gfx950 part
 bool small_path(const v2x_model* m, const DevBatch& d) {
-  if (!m->small_predict || !m->small_h || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->L > FZ_MAXL) return false;
+  if (!m->knobs.small_predict || !m->small_h || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->L > FZ_MAXL) return false;
   if (m->N > 32) return false;                 // the kernel keeps a node's in-neighbours in a 32-entry LDS list
   return d.max_nodes == m->N && d.R <= std::min(SMALL_ROWS, n_cus());
 }
@@ -1740,16 +1632,16 @@ int launch_small_forward(v2x_model* m, hipStream_t st, const DevBatch& d, float*
 bool ragged_fused_path(const v2x_model* m, const DevBatch& d) {
   // (any density: a row's aggregation walks its mask's one bits or -- rows with more edges than non-edges in graphs of >= 16
   //  nodes -- the zero bits; the masks are built for this path whether or not the dense MFMA aggregation wants them)
-  return m->ragged_fused && m->cfg.variable_graphs && m->S == 1 && d.goff && !d.nbr && m->F <= 64 && m->L <= FZ_MAXL && d.max_nodes <= 128 &&
+  return m->knobs.ragged_fused && m->cfg.variable_graphs && m->S == 1 && d.goff && !d.nbr && m->F <= 64 && m->L <= FZ_MAXL && d.max_nodes <= 128 &&
          d.max_nodes <= RG_CAP / 2;
 }
-bool need_adj_masks(const v2x_model* m, const DevBatch& d) { return use_dense_agg(d, m->F) || ragged_fused_path(m, d); }
+bool need_adj_masks(const v2x_model* m, const DevBatch& d) { return use_dense_agg(m->knobs, d, m->F) || ragged_fused_path(m, d); }
 // Small tiles (kernels_ragged_small.hpp: 160-row tiles, 4-wave workgroups, weights as fragments from L2, three workgroups per
 // CU): built and measured in round 5 -- forward 123 us against 101, backward 161 against 103 at configs[4]'s share, + 19 us for
-// the plan as a launch of its own (profiles/r05_ragged_small_ab.txt) -- so OFF unless V2X_RAGGED_SMALL=1 (read at create too:
+// the plan as a launch of its own (profiles/r05_ragged_small_ab.txt) -- so OFF unless Knobs::ragged_small (read at create:
 // the fragment-major copy of a ragged model's weights is only kept then)
 bool ragged_small(const v2x_model* m, const DevBatch& d) {
-  return m->ragged_small_env && m->pk_fwd && m->pk_bwd && d.max_nodes <= 128 && m->L >= 1;
+  return m->knobs.ragged_small && m->pk_fwd && m->pk_bwd && d.max_nodes <= 128 && m->L >= 1;
 }
 int ragged_cap(const v2x_model* m, const DevBatch& d) { return ragged_small(m, d) ? RGS_CAP : RG_CAP; }
 int ragged_capp(const v2x_model* m, const DevBatch& d) { return ragged_cap(m, d) - d.max_nodes + 1; }
@@ -1757,7 +1649,7 @@ int ragged_wgs(const v2x_model* m, const DevBatch& d) { return (d.R + ragged_cap
 
 // k_ragged_plan's tables in LDS; past that (tens of thousands of graphs in one batch) the interval plan of k_adj_masks
 int ragged_plan_words(const v2x_model* m, const DevBatch& d) { return 3 * (d.B + 1) + ragged_wgs(m, d) + 1; }
-bool ragged_packed_plan(const v2x_model* m, const DevBatch& d) { return m->ragged_packed && ragged_plan_words(m, d) <= RG_PLAN_LDS_WORDS; }
+bool ragged_packed_plan(const v2x_model* m, const DevBatch& d) { return m->knobs.ragged_packed && ragged_plan_words(m, d) <= RG_PLAN_LDS_WORDS; }
 
 template <int F>
 int launch_ragged_fwd_f(v2x_model* m, hipStream_t st, const RaggedFwdArgs& a, int n_wgs) {
@@ -1844,28 +1736,6 @@ int launch_ragged_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
   FAIL(m, V2X_EINVAL, "ragged backward: unsupported feat_dim %d", m->F);
 }
 
-// OPT-IN (V2X_MLP_STREAM=1; measured slower, profiles/r06_mlp_stream_ab.txt): the decision MLP as one wave per (slot, tile) with its
-// weights streamed from L2 (kernels_mlpstream.hpp), ALL four Dense weight gradients as roles of the graph layers' launch -- wherever
-// Dense-0's weight gradient may ride (dense0_rides).  At the 512- / 1024- / 2048-graph shares the MLP launch itself goes 23.6 -> 19.1,
-// 35.3 -> 33.0, 48.2 -> 50.9 us (every wave of a slot streams the same 135 KB in the same order: 4.5-6.9 TB/s over the chip, 1.6-1.9x
-// the MFMA time even at 2.5 waves per SIMD), the Dense 1..3 roles chained behind the Dense-0 halves add 10-27 us to the
-// weight-gradient launch (three more operand pipelines and accumulator exchanges per workgroup) and the image 13.6 us per step
-// (it could ride on k_reduce_adam's scatter): 0.1284 / 0.1696 / 0.2274 ms per step against 0.1128 / 0.1445 / 0.1870.
-bool mlp_stream_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x) {
-  if (env_int("V2X_MLP_STREAM", 0) != 1) return false;             // (read per call: the tests switch it inside one process)
-  if (!m->mlp_img || m->dqn_tq || m->S != m->N || m->L + 5 > WG_MAX_ROLES) return false;
-  return env_int("V2X_MLP_WG0", -1) != 1 && dense0_rides(m, d, x);
-}
-
-int launch_mlp_stream(v2x_model* m, hipStream_t st, const MlpArgs& a, int n_slots) {
-  // the images follow the parameters: rebuilt from the flat buffer in front of every use (1.5 MB, one workgroup per slot)
-  { auto k = k_mlp_image<64>; LAUNCH_T(m, "k_mlp_image", k, dim3(n_slots), 256, (size_t)MlpLds<64>::TOTAL * 4, st, a, m->mlp_img); }
-  const int T = (a.n_idx + 15) / 16, units = T * n_slots;
-  if (a.frag_groups > 0) { auto k = k_mlp_stream<64, true>; LAUNCH_T(m, "k_mlp_stream", k, dim3(units), 64, 0, st, a, (const float*)m->mlp_img, T, units); }
-  else { auto k = k_mlp_stream<64, false>; LAUNCH_T(m, "k_mlp_stream", k, dim3(units), 64, 0, st, a, (const float*)m->mlp_img, T, units); }
-  return V2X_OK;
-}
-
 int run_forward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, bool with_mlp = true) {
   const int F = m->F, L = m->L;
   const IdxMap x = idx_map(m, d, r);
@@ -1884,7 +1754,7 @@ int run_forward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, bool w
       if (ragged && !packed) { q.plan = (int32_t*)m->plan_buf.p; q.plan_capp = ragged_capp(m, d); q.plan_n = ragged_wgs(m, d); }
       // the packed plan by workgroup 0 of the mask launch while its offsets + 16-bit tables leave the mask workgroups their
       // eight per CU (<= 19 KB of LDS: ~2,200 graphs); a launch of its own (k_ragged_plan, 32-bit tables) beyond
-      const bool folded = packed && m->ragged_plan_fold && d.B < 65000 && plan16_bytes(d.B, ragged_wgs(m, d)) <= 19 * 1024;
+      const bool folded = packed && m->knobs.ragged_plan_fold && d.B < 65000 && plan16_bytes(d.B, ragged_wgs(m, d)) <= 19 * 1024;
       if (folded) { q.plan = (int32_t*)m->plan_buf.p; q.plan_cap = ragged_cap(m, d); q.plan_n = ragged_wgs(m, d); }
       // (the plan reads the offsets, the masks the CSR: independent -- but as a forked branch of the captured step the two
       //  cost MORE than one after the other: 0.466 against 0.455 ms per configs[4] step, the graph's cross-branch
@@ -1909,7 +1779,7 @@ int run_forward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, bool w
     }
   }
 mlp:
-  if (!with_mlp) return V2X_OK;          // training: the MLP runs fused with its backward (k_mlp_train)
+  if (!with_mlp) return V2X_OK;          // training: the MLP runs fused with its backward (k_mlp_train_wg)
   MlpArgs a;
   mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
   CHK(launch_mlp(m, st, a, false));
@@ -1922,31 +1792,19 @@ float loss_denominator(const v2x_model* m, int n_global) {
   return (float)((double)n_global * m->C);
 }
 
-// backward kernel chain of one range.  sw != st: the weight-gradient kernels go to the side stream `sw`,
-// forked after the kernel producing their dpre (they only consume saved activations + dpre_s, and nothing
-// consumes them before the slab reduction); the caller joins sw back.
-int run_backward(v2x_model* m, hipStream_t st, hipStream_t sw, const DevBatch& d, Range r, const float* y_dev,
-                 int n_global) {
+// backward kernel chain of one range, after run_forward(with_mlp = wide): the decision MLP (a narrow model: forward + Huber +
+// backward + the Dense weight gradients in one launch), the graph layers' data chain, their weight gradients
+int run_backward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, const float* y_dev, int n_global) {
   const int F = m->F, L = m->L;
   const IdxMap x = idx_map(m, d, r);
-  const bool two = sw != st;
-  int evi = 0;
-  auto fork = [&]() -> int {      // side stream waits for everything issued on st so far
-    if (!two) return V2X_OK;
-    hipEvent_t e = m->ev[evi++];
-    HIPCHK(m, hipEventRecord(e, st));
-    HIPCHK(m, hipStreamWaitEvent(sw, e, 0));
-    return V2X_OK;
-  };
   MlpArgs a;
   mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
   a.y = y_dev;
   a.inv_denom = 1.0f / loss_denominator(m, n_global);
-  const bool mlp_wg = mlp_wg_path(m);      // the Dense weight gradients come out of the MLP launch itself
+  const bool mlp_wg = mlp_wg_path(m);      // narrow: the Dense weight gradients come out of the MLP launch itself
   // wide path: every layer's weight gradient in ONE launch after the data chain -- unless somebody wants a layer's gradient
   // as soon as it is final (per-layer all-reduce buckets of data parallelism: m->bucketed)
-  static const int wide_merge = env_int("V2X_WIDE_MERGE", 1);
-  m->wide_merge_now = is_wide(m) && wide_merge && !two && !m->bucketed && m->L + 2 <= WWM_ROLES;
+  m->wide_merge_now = is_wide(m) && m->knobs.wide_merge && !m->bucketed && m->L + 2 <= WWM_ROLES;
   struct MergeGuard { v2x_model* m; ~MergeGuard() { m->wide_merge_now = false; } } merge_guard{m};
   if (m->frag_live && !frag_layout(m, d, r)) FAIL(m, V2X_ESTATE, "backward: the saved forward is fragment-major, this backward cannot read it");
   a.frag_groups = m->frag_live ? d.B / FZ_TG : 0;
@@ -1954,60 +1812,35 @@ int run_backward(v2x_model* m, hipStream_t st, hipStream_t sw, const DevBatch& d
     if (!mlp_wg) FAIL(m, V2X_ESTATE, "backward: in-kernel DQN targets need the k_mlp_train_wg path");
     a.tq = m->dqn_tq; a.y = m->dqn_tq; a.q = m->dqn_y;
   }
-  // (the weight-gradient launch below must be the merged one of wgrad_gnn_all: one stream, no per-stage split)
-  m->dense0_out_now = mlp_wg && !two && r.g0 == 0 && r.ng == d.B && dense0_rides(m, d, x);
+  m->dense0_out_now = mlp_wg && r.g0 == 0 && r.ng == d.B && dense0_rides(m, d, x);
   struct D0Guard { v2x_model* m; ~D0Guard() { m->dense0_out_now = false; } } d0_guard{m};
-  m->mlp_stream_now = m->dense0_out_now && mlp_stream_rides(m, d, x);
-  struct MsGuard { v2x_model* m; ~MsGuard() { m->mlp_stream_now = false; } } ms_guard{m};
-  if (m->mlp_stream_now) CHK(launch_mlp_stream(m, st, a, x.grid_y));
-  else if (mlp_wg) CHK(launch_mlp_train_wg(m, st, a, !m->dense0_out_now));
-  else if (mlp_fused_training(m)) CHK(launch_mlp_train(m, st, a));
-  else CHK(launch_mlp(m, st, a, true));
-  static const int wg_split = env_int("V2X_WG_SPLIT", 0);
-  const bool merged = !mlp_wg && !two && wgrad_all_fits(m) && wg_split == 0;
-  CHK(fork());
-  if (!merged && !mlp_wg) CHK(wgrad_mlp(m, sw, x, d.xe, m->h[L], m->a[L]));        // 4 Dense layers, one launch (side stream if two)
-  // V2X_WG_PER_STAGE=1: every GNN stage's weight gradient goes to the side stream as soon as its dpre exists
-  // (overlaps the remaining agg/dgrad chain) instead of one fused launch after the chain
-  static const bool per_stage = env_int("V2X_WG_PER_STAGE", 0) != 0;
-  const bool split = two && per_stage && !is_wide(m);
-  const bool fused = fused_path(m, d) && r.g0 == 0 && r.ng == d.B && !split;
-  const bool ragged_bwd = m->ragged_fused_bwd;
+  if (mlp_wg) CHK(launch_mlp_train_wg(m, st, a, !m->dense0_out_now));
+  else {
+    CHK(launch_mlp(m, st, a, true));
+    CHK(wgrad_mlp(m, st, x, d.xe, m->h[L], m->a[L]));        // Dense-0 (unless merged below) + Dense 1..3
+  }
+  const bool fused = fused_path(m, d) && r.g0 == 0 && r.ng == d.B;
+  const bool ragged_bwd = m->knobs.ragged_fused_bwd;
   if (fused) {
     CHK(launch_fused_bwd(m, st, d));       // L+1 transposed aggregations + L data gradients: one launch
-  } else if (ragged_bwd && !split && ragged_fused_path(m, d) && r.g0 == 0 && r.ng == d.B) {
+  } else if (ragged_bwd && ragged_fused_path(m, d) && r.g0 == 0 && r.ng == d.B) {
     CHK(launch_ragged_bwd(m, st, d));      // the same for ragged graphs (masks and plan from this step's forward)
   } else {
     for (int s = L; s >= 1; --s) {
       // dpre_s = (dh_direct + Agg^T(dagg)) * relu'(h_s)
       CHK(launch_agg(m, st, d, r, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, s < L ? m->h[s] : nullptr, m->dpre[s], 1));
-      if (split) { CHK(fork()); CHK(wgrad_gnn(m, sw, s, x, d.xe, m->h[s - 1], m->a[s - 1], m->dpre[s])); }
       CHK(launch_dgrad(m, st, s, x, m->dpre[s], m->gha));
     }
     CHK(launch_agg(m, st, d, r, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, m->h[0], m->dpre[0], 1));
   }
-  if (split) { CHK(fork()); CHK(wgrad_gnn(m, sw, 0, x, d.xe, nullptr, d.nbr, m->dpre[0])); }
-  else if (merged) CHK(wgrad_all(m, st, x, d));             // every layer, one launch
-  else CHK(wgrad_gnn_all(m, st, x, d));                     // all L+1 GNN stages, one launch
-  if (two) {                      // join: st waits for the side stream
-    hipEvent_t e = m->ev[evi++];
-    HIPCHK(m, hipEventRecord(e, sw));
-    HIPCHK(m, hipStreamWaitEvent(st, e, 0));
-  }
-  return V2X_OK;
+  return wgrad_gnn_all(m, st, x, d);       // all L + 1 graph layers (+ what rides on them): one launch up to L = 7
 }
 
-// forward (+ backward) of the whole batch; everything is joined back into `st`
+// forward (+ backward) of the whole batch
 int run_step(v2x_model* m, hipStream_t st, const DevBatch& d, bool bwd, const float* y_dev, int n_global) {
   const Range all{0, d.B};
-  CHK(run_forward(m, st, d, all, !(bwd && mlp_fused_training(m))));
-  if (bwd) {
-    // measured: with the current kernels the side-stream overlap of the Dense weight gradients no longer pays
-    // (0.397 vs 0.390 ms/step), so one stream is the default; V2X_TWO_STREAMS=1 restores the fork/join
-    static const bool two_env = getenv("V2X_TWO_STREAMS") != nullptr;
-    const bool two = !m->prof && m->side && two_env;
-    CHK(run_backward(m, st, two ? m->side : st, d, all, y_dev, n_global));
-  }
+  CHK(run_forward(m, st, d, all, !(bwd && mlp_wg_path(m))));
+  if (bwd) CHK(run_backward(m, st, d, all, y_dev, n_global));
   return V2X_OK;
 }
 
@@ -2093,10 +1926,9 @@ GraphKey make_key(int kind, const DevBatch& d, const void* y, int n_global) {
 int max_slabs(const v2x_model* m, int n_idx, int n_slots) {
   int chunk, nc = 1;
   const int mr = m->L >= 1 ? merged_wg_rows(m, n_idx, n_slots) : 0;
-  static const int c_gnn = env_int("V2X_WG_CHUNK_GNN", 1024), c_dense = env_int("V2X_WG_CHUNK_DENSE", 1024),
-                   c_embed = env_int("V2X_WG_CHUNK_EMBED", 1024), c_d123 = env_int("V2X_WG_CHUNK_D123", 512);
-  for (int rows : {c_gnn, c_dense, c_embed, c_d123, 768, 896, mr > 0 ? mr : 1024})
-    if (rows > 0) nc = std::max(nc, role_chunks(n_idx, n_slots, 1000, 1000, &chunk, rows));     // (a switch set to 0 = its default)
+  const Knobs& kn = m->knobs;
+  for (int rows : {kn.wg_chunk_gnn, kn.wg_chunk_dense, kn.wg_chunk_embed, kn.wg_chunk_d123, 768, 896, 1024, mr})
+    if (rows > 0) nc = std::max(nc, role_chunks(kn, n_idx, n_slots, 1000, 1000, &chunk, rows));  // (a switch at 0 = a default, listed here)
   if (is_wide(m)) nc = std::max(nc, wide_splits(n_idx, 1, n_slots));     // the fewest tiles (one) split most
   else nc = std::max(nc, mlp_wg_split(n_idx, n_slots).n_slabs);         // k_mlp_train_wg: one slab per workgroup and slot
   return nc + 1;
@@ -2130,10 +1962,7 @@ int presize_rows(v2x_model* m, int n_rows) {
 // Adam in the weight-gradient epilogues (single-GPU fit step of a wide model): needs the merged launch and ONE row split
 // for every layer it covers (gnn[1..L], dense[0]) -- true as soon as K tiles x slots fill the chip (per-node weights)
 bool wide_adam_fusable(const v2x_model* m, const DevBatch& d) {
-  static const int on = env_int("V2X_WIDE_ADAM", 1), wide_merge = env_int("V2X_WIDE_MERGE", 1);
-  if (!on || !wide_merge || !is_wide(m) || m->bucketed || m->prof_no_fuse || !m->adam_scal || m->L + 2 > WWM_ROLES) return false;
-  static const bool two_env = getenv("V2X_TWO_STREAMS") != nullptr;
-  if (two_env) return false;
+  if (!m->knobs.wide_adam || !m->knobs.wide_merge || !is_wide(m) || m->bucketed || m->prof_no_fuse || !m->adam_scal || m->L + 2 > WWM_ROLES) return false;
   const IdxMap x = idx_map(m, d, Range{0, d.B});
   const int kt = 2 * ((m->F + 127) / 128);                    // [h | agg] K tiles ([x | e] folded or one more: more tiles = fewer splits)
   return wide_splits(x.n_idx, kt, x.grid_y) == 1;
@@ -2179,8 +2008,9 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
   m->N = cfg->n_nodes; m->C = cfg->n_channels; m->F = cfg->feat_dim; m->L = cfg->n_mp_layers;
   m->S = cfg->share_weights ? 1 : cfg->n_nodes;
   m->Dn = 2 * m->C + 1; m->De = m->C;               // BS_brain.py:101-102 with node_info=3, edge_info=1
+  m->knobs = read_knobs();        // every environment switch, fixed for the life of the model (knobs.hpp)
   build_layout(m);
-  set_attrs(m->F);
+  set_attrs(m->F, m->knobs);
   m->h.assign(m->L + 1, nullptr);
   m->a.assign(m->L + 1, nullptr);
   m->dpre.assign(m->L + 1, nullptr);
@@ -2194,17 +2024,8 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
       dev_alloc(m, &m->vel, m->P) || dev_alloc(m, &m->loss_dev, (size_t)m->N + 1) || dev_alloc(m, &m->zero_buf, 1024) ||
       dev_alloc(m, &m->loss_part, 128) || dev_alloc(m, &m->adam_scal, 16))
     return fail("allocation");
-  // V2X_FUSED=0 (read when the model is created) keeps the layer-by-layer kernels: A/B measurements and the test that
-  // the two paths agree bitwise
-  m->compl_sums = env_int("V2X_FUSED_COMPL", 1) != 0;
-  m->small_predict = env_int("V2X_SMALL_PREDICT", 1) != 0;
-  m->split_env = env_int("V2X_FUSED_SPLIT", -1);
-  m->ragged_fused = env_int("V2X_RAGGED_FUSED", 1) != 0;
-  m->ragged_fused_bwd = env_int("V2X_RAGGED_FUSED_BWD", 1) != 0;
-  m->ragged_packed = env_int("V2X_RAGGED_PACKED", 1) != 0;
-  m->ragged_small_env = env_int("V2X_RAGGED_SMALL", 0) != 0;
-  m->ragged_plan_fold = env_int("V2X_RAGGED_PLAN_FOLD", 1) != 0;
-  if (m->small_predict && !m->cfg.variable_graphs && m->F <= 64 && m->L <= FZ_MAXL) {
+  const Knobs& kn = m->knobs;
+  if (kn.small_predict && !m->cfg.variable_graphs && m->F <= 64 && m->L <= FZ_MAXL) {
     const size_t hb = (size_t)(m->L + 1) * SMALL_ROWS * m->F * sizeof(unsigned long long), sb = (size_t)2 * SMALL_ROWS * sizeof(unsigned);
     void *ph = nullptr, *ps = nullptr;
     if (hipMalloc(&ph, hb) != hipSuccess || hipMalloc(&ps, sb) != hipSuccess) return fail("allocation");
@@ -2212,7 +2033,7 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
     if (hipMemset(ph, 0, hb)) return fail("memset");             // tag 0 = never written
     m->small_sync = static_cast<unsigned long long*>(ps);
     void *hh = nullptr, *hdv = nullptr;
-    if (env_int("V2X_SMALL_PINNED", 1) != 0 && hipHostMalloc(&hh, PIN_BYTES, hipHostMallocMapped) == hipSuccess &&
+    if (kn.small_pinned && hipHostMalloc(&hh, PIN_BYTES, hipHostMallocMapped) == hipSuccess &&
         hipHostGetDevicePointer(&hdv, hh, 0) == hipSuccess) {
       m->pin_h = static_cast<char*>(hh); m->pin_d = static_cast<char*>(hdv);
     } else {
@@ -2221,16 +2042,16 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
     }
     if (hipMemset(m->small_sync, 0, (size_t)2 * SMALL_ROWS * sizeof(unsigned))) return fail("memset");
   }
+  // Knobs::fused = 0 keeps the layer-by-layer kernels: A/B measurements and the test that the two paths agree bitwise
   // (ragged models with shared weights stream the same copy in their small-tile kernels, kernels_ragged_small.hpp)
-  if (env_int("V2X_FUSED", 1) != 0 && (!m->cfg.variable_graphs || (m->S == 1 && m->ragged_small_env)) && m->F <= 64 && m->L <= FZ_MAXL) {
+  if (kn.fused && (!m->cfg.variable_graphs || (m->S == 1 && kn.ragged_small)) && m->F <= 64 && m->L <= FZ_MAXL) {
     const int FB = m->F / 16, KB = 2 * FB + 1;
     const size_t fwd0 = (size_t)FB * 256 + m->F, fwd = (size_t)KB * FB * 256 + m->F, bwd = (size_t)FB * 2 * FB * 256;
     if (dev_alloc(m, &m->pk_fwd, (size_t)m->S * fwd0 + (size_t)m->L * m->S * fwd) || dev_alloc(m, &m->pk_bwd, (size_t)m->L * m->S * bwd))
       return fail("allocation");
     m->pk_stale = true;             // first forward packs whatever the parameters are by then
-    if (m->F == 64 && !m->cfg.variable_graphs && dev_alloc(m, &m->mlp_img, (size_t)m->S * mlp_image_floats<64>())) return fail("allocation");
   }
-  if ((m->pk_fwd || m->cfg.variable_graphs) && env_int("V2X_FUSED_TS", 0)) {
+  if ((m->pk_fwd || m->cfg.variable_graphs) && kn.fused_ts) {
     if (dev_alloc(m, &m->ts_buf, 4 * 8 * 64)) return fail("allocation");
     hipMemset(m->ts_buf, 0, 4 * 8 * 64 * 8);
   }
@@ -2241,11 +2062,7 @@ int v2x_create(const v2x_config* cfg, v2x_model** out) {
     if (alloc_flag(&f) != V2X_OK) return fail("pinned flag word");
     m->flag_host = f.host; m->flag_dev = f.dev;
   }
-  if (hipStreamCreateWithFlags(&m->side, hipStreamNonBlocking) != hipSuccess) return fail("side stream");
   if (hipStreamCreateWithFlags(&m->cap, hipStreamNonBlocking) != hipSuccess) return fail("capture stream");
-  m->ev.resize(2 * m->L + 6);
-  for (auto& e : m->ev)
-    if (hipEventCreateWithFlags(&e, hipEventDisableTiming) != hipSuccess) return fail("event");
   // The memsets above run on the null stream and may still be in flight when this returns; the caller's next call
   // (v2x_set_weights: a copy into the parameters) goes to ITS stream, which a non-blocking stream -- every stream of PyTorch's
   // pool -- does not order behind the null stream.  Without this wait the zeroing could land on top of the weights just set:
@@ -2262,14 +2079,12 @@ void v2x_destroy(v2x_model* m) {
   for (auto& kv : m->graphs) hipGraphExecDestroy(kv.second.exec);
   for (auto& r : m->prof_recs) { hipEventDestroy(r.ev0); hipEventDestroy(r.ev1); }
   float* ptrs[] = {m->params, m->grads, m->mom, m->vel, m->z1, m->z2, m->z3, m->q, m->dq, m->dz1, m->dz2, m->dz3,
-                   m->gha, m->rowloss, m->loss_dev, m->slab, m->zero_buf, m->loss_part, m->pk_fwd, m->pk_bwd, m->adam_scal, m->mlp_img};
+                   m->gha, m->rowloss, m->loss_dev, m->slab, m->zero_buf, m->loss_part, m->pk_fwd, m->pk_bwd, m->adam_scal};
   for (float* p : m->dpre) if (p) hipFree(p);
   if (m->gate_bits) hipFree(m->gate_bits);
   if (m->nbmask) hipFree(m->nbmask);
-  for (auto& e : m->ev) if (e) hipEventDestroy(e);
   for (auto& e : m->dp_ev) if (e) hipEventDestroy(e);
   if (m->dp_st) hipStreamDestroy(m->dp_st);
-  if (m->side) hipStreamDestroy(m->side);
   if (m->cap) hipStreamDestroy(m->cap);
   for (float* p : ptrs) if (p) hipFree(p);
   for (float* p : m->h) if (p) hipFree(p);
@@ -2489,19 +2304,13 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
   }
   if (phase == 0) {
     CHK(run_maybe_graph(m, st, make_key(5, d, yd, n_global), [&]() -> int {
-      CHK(run_forward(m, st, d, all, !mlp_fused_training(m)));
+      CHK(run_forward(m, st, d, all, false));            // narrow: the MLP runs inside its training launch
       MlpArgs a;
       mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
       a.y = yd;
       a.inv_denom = 1.0f / loss_denominator(m, n_global);
       a.frag_groups = m->frag_live ? d.B / FZ_TG : 0;
-      if (mlp_wg_path(m)) {
-        CHK(launch_mlp_train_wg(m, st, a));
-      } else {
-        if (mlp_fused_training(m)) CHK(launch_mlp_train(m, st, a));
-        else CHK(launch_mlp(m, st, a, true));
-        CHK(wgrad_mlp(m, st, x, d.xe, m->h[L], m->a[L]));
-      }
+      CHK(launch_mlp_train_wg(m, st, a));
       return launch_reduce_adam(m, st, 1, false, nullptr, LossJob{0, 0, 0, 0.f, 0}, 0);
     }));
     m->have_fwd = true;
@@ -2599,10 +2408,9 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   // Narrow models (k_mlp_train_wg): the online network's decision MLP runs ONCE, inside the training launch, which forms the
   // targets from its own forward output (MlpArgs::tq) -- as Keras' fit re-computes the prediction it was handed as target, so
   // that the untouched entries carry exactly zero error (BS_brain.py:664-692, :728); the separate MLP forward of the online
-  // network, and the target kernel's pass over q, are gone (38 us of a 520-us step at 20 links, batch 4096).  V2X_DQN_FUSED_TARGETS=0:
-  // the three-launch form (forward, k_dqn_targets, training launch on y).
-  static const int fuse_env = env_int("V2X_DQN_FUSED_TARGETS", 1);
-  const bool fuse_targets = fuse_env && mlp_wg_path(online) && !is_wide(online) && online->C == 4;
+  // network, and the target kernel's pass over q, are gone (38 us of a 520-us step at 20 links, batch 4096).
+  // Knobs::dqn_fused_targets = 0: the three-launch form (forward, k_dqn_targets, training launch on y).
+  const bool fuse_targets = online->knobs.dqn_fused_targets && mlp_wg_path(online) && online->C == 4;
   CHK(run_maybe_graph(online, st, key, [&]() -> int {
     target->capturing = online->capturing;
     int rc = run_forward(target, st, dn, all, true);
@@ -2612,13 +2420,13 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
       CHK(run_forward(online, st, ds, all, true));
       hipLaunchKernelGGL(k_dqn_targets, dim3((ds.R + 255) / 256), dim3(256), 0, st, online->q, target->q, action, reward, gamma,
                          ds.R, online->N, online->C, y);
-      return run_backward(online, st, st, ds, all, y, n_graphs_global);
+      return run_backward(online, st, ds, all, y, n_graphs_global);
     }
     CHK(run_forward(online, st, ds, all, false));                          // graph layers only
     float* tq = online->dq;                                                // (a workspace this path does not use otherwise: [R][4])
     hipLaunchKernelGGL(k_dqn_tq, dim3((ds.R + 255) / 256), dim3(256), 0, st, target->q, action, reward, gamma, ds.R, online->N, online->C, tq);
     online->dqn_tq = tq; online->dqn_y = y;
-    rc = run_backward(online, st, st, ds, all, y, n_graphs_global);
+    rc = run_backward(online, st, ds, all, y, n_graphs_global);
     online->dqn_tq = nullptr; online->dqn_y = nullptr;
     return rc;
   }));
@@ -2725,12 +2533,8 @@ int v2x_mlp_huber_bwd(v2x_model* m, int32_t n_rows, int32_t n_global, const floa
   if (mlp_wg_path(m)) {
     CHK(launch_mlp_train_wg(m, st, a));
   } else {
-    if (mlp_fused_training(m)) {
-      CHK(launch_mlp_train(m, st, a));
-    } else {
-      CHK(launch_mlp(m, st, a, false));
-      CHK(launch_mlp(m, st, a, true));
-    }
+    CHK(launch_mlp(m, st, a, false));
+    CHK(launch_mlp(m, st, a, true));
     CHK(wgrad_mlp(m, st, x, xe, h, agg));
   }
   if (grad_out) CHK(launch_reduce_adam(m, st, 1, false, grad_out));
@@ -2928,7 +2732,7 @@ int v2x_path_info(v2x_model* m, const v2x_batch* b, char* out, int cap) {
   // walks the graph's rows in LDS once and adds each to the slots whose set holds it (sparse lanes walk their set bits only);
   // "edge-gather": the per-edge CSR gather / segment sum of k_agg (layer-wise path, any N)
   const char* agg = fused ? (split <= 1 && fused_compl(m, d) ? "complement" : "edge-bitset-walk")
-                          : (use_dense_agg(d, m->F) ? "dense(complement-or-mfma-per-graph)" : "edge-gather");
+                          : (use_dense_agg(m->knobs, d, m->F) ? "dense(complement-or-mfma-per-graph)" : "edge-gather");
   char gl[48];
   if (fused && split > 1) snprintf(gl, sizeof(gl), "fused(split%d)", split);
   else snprintf(gl, sizeof(gl), "%s", fused ? "fused" : (ragged_fused_path(m, d) ? "fused(ragged)" : "layerwise"));
@@ -2936,7 +2740,7 @@ int v2x_path_info(v2x_model* m, const v2x_batch* b, char* out, int cap) {
   // the graph layers' weight-gradient launch (dense0_rides)
   const bool d0 = mlp_wg_path(m) && !m->cfg.variable_graphs && dense0_rides(m, d, idx_map(m, d, Range{0, d.B}));
   snprintf(out, cap, "graph_layers=%s aggregation=%s mlp=%s handoff=%s dense0_dw=%s", gl, agg,
-           (d0 && mlp_stream_rides(m, d, idx_map(m, d, Range{0, d.B}))) ? "stream" : (mlp_wg_path(m) ? "train_wg" : (mlp_fused_training(m) ? "train" : "fwd+bwd")),
+           mlp_wg_path(m) ? "train_wg" : "fwd+bwd",
            frag_layout(m, d, Range{0, d.B}) ? "fragment-major" : "row-major",
            d0 ? "k_wgrad" : (mlp_wg_path(m) ? "k_mlp_train_wg" : (is_wide(m) ? "k_wide_wgrad" : "k_wgrad")));
   return V2X_OK;

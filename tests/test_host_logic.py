@@ -588,3 +588,26 @@ def test_weight_layout_at_depth(L, shared):
     assert len({ln for ln, _ in table}) == len(table)
     names = [w for _, ws_ in table for w in ws_]
     assert len(set(names)) == len(names)
+
+
+def test_library_switches_live_in_one_place_and_match_the_design_table():
+    """Every environment switch of libv2xgnn is read in csrc/knobs.hpp and nowhere else, its names are the library table of
+    DESIGN.md section 9, and the switches of the retired launch forms are gone from the sources."""
+    import glob
+    csrc = os.path.join(ROOT, 'globecom2020-resourceallocationgnn_amd', 'csrc')
+    files = sorted(f for ext in ('*.hip', '*.hpp', '*.c') for f in glob.glob(os.path.join(csrc, ext)))
+    text = {os.path.basename(f): open(f).read() for f in files}
+    assert 'knobs.hpp' in text and 'v2xgnn.hip' in text
+    # (a) one reader of the environment
+    assert [n for n, t in text.items() if 'getenv' in t] == ['knobs.hpp']
+    # (b) the header and the document list the same switches
+    in_header = set(re.findall(r'"(V2X_[A-Z0-9_]+)"', text['knobs.hpp']))
+    design = open(os.path.join(ROOT, 'DESIGN.md')).read()
+    table = design[design.index('### 9.1 Library switches'):design.index('### 9.2 ')]
+    in_design = set(re.findall(r'^\| `(V2X_[A-Z0-9_]+)` \|', table, re.M))
+    assert len(in_header) >= 30 and in_header == in_design, (sorted(in_header - in_design), sorted(in_design - in_header))
+    # (c) whole names: V2X_MLP_WG0 and V2X_MLP_WGS_PER_CU are not V2X_MLP_WG
+    retired = ('V2X_MLP_STREAM', 'V2X_MLP_WG', 'V2X_MLP_SPLIT', 'V2X_TWO_STREAMS', 'V2X_WG_SPLIT', 'V2X_WG_PER_STAGE')
+    for name, t in text.items():
+        found = [r for r in retired if re.search(r'(?<![A-Za-z0-9_])' + r + r'(?![A-Za-z0-9_])', t)]
+        assert not found, (name, found)

@@ -6,8 +6,6 @@ $B --workload cfg4 > $O/bench_cfg4.json 2>/dev/null
 $B --workload cfg5 > $O/bench_cfg5.json 2>/dev/null
 $B --batch 65536 --steps 20 --warmup 3 > $O/bench_b65536.json 2>/dev/null
 $B --scaling strong > $O/bench_strong.json 2>/dev/null
-V2X_FUSED=0 V2X_MLP_WG=0 $B > $O/bench_layerwise.json 2>/dev/null
-V2X_MLP_WG=0 $B > $O/bench_mlp_split.json 2>/dev/null
 V2X_FUSED_COMPL=0 $B > $O/bench_edge_gather.json 2>/dev/null
 python bench.py --full --workload cfg0 > $O/bench_cfg0_episode.json 2>/dev/null
 python bench.py --full --workload cfg0 --envs 10 > $O/bench_cfg0_episode_envs10.json 2>/dev/null

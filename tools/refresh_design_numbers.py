@@ -1,4 +1,4 @@
-"""Rewrite the round-6 figures of DESIGN.md section 3.2b / 4 / 5 from the files under profiles/ (after tools/copy_r6_profiles.sh)."""
+"""Rewrite the round-6 figures of DESIGN.md section 3.2b / 4 / 5 from the files under profiles/."""
 import json
 import re
 
