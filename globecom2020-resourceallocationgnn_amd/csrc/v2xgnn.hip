@@ -22,6 +22,7 @@
 #include <map>
 #include <mutex>
 #include <string>
+#include <type_traits>
 #include <vector>
 
 using namespace v2x;
@@ -70,7 +71,7 @@ struct v2x_model {
   float *dq = nullptr, *dz1 = nullptr, *dz2 = nullptr, *dz3 = nullptr, *gha = nullptr, *rowloss = nullptr;
   std::vector<float*> dpre;     // one pre-activation gradient per GNN stage (read concurrently by k_wgrad)
   unsigned* nbmask = nullptr;            // [cap_rows] non-neighbour masks: fused forward -> fused backward (complement form)
-  bool frag_live = false;                // h_L, a_L (and then gha) of the last training forward are fragment-major (frag_layout)
+  bool frag_live = false;                // h_L, a_L (and then gha) of the last training forward are fragment-major (BatchPlan::frag_ok)
   unsigned short* gate_bits = nullptr;   // ReLU' gates of the fused forward for the fused backward: [L][gate_stride]
   int64_t gate_stride = 0;               // ushorts per stage: N x ceil(B / 16) x 64 <= 4 R + 64 N
   hipStream_t cap = nullptr;    // hipGraphs are recorded on this stream and launched on the caller's (run_maybe_graph)
@@ -111,17 +112,8 @@ struct v2x_model {
   int64_t ws_gen = 0;           // bumped whenever a workspace buffer is re-allocated (keys of graphs that bake in ANOTHER model's workspace)
   std::map<GraphKey, GraphEntry> graphs;
   bool capturing = false;
-  // wide path, single-GPU training: the layers' weight gradients are collected and launched as ONE grid (wide_wgrad_flush)
-  bool dense0_out_now = false;                  // inside a backward pass whose MLP launch leaves Dense-0's weight gradient to k_wgrad
-  // inside a DQN replay step whose MLP launch forms the targets itself (MlpArgs::tq): replaced entries, actions, where y goes
-  const float* dqn_tq = nullptr; float* dqn_y = nullptr;
-  bool wide_merge_now = false;                  // inside a backward pass that merges
-  bool bucketed = false;                        // data parallelism wants each layer's gradient as soon as it is final
-  bool fuse_adam_now = false;                   // ... and applies Adam in the weight-gradient epilogues (WideWgradArgs::adam)
-  float* adam_scal = nullptr;                   // {lr_t, beta1, beta2, eps} of the current step, in device memory
+  float* adam_scal = nullptr;                   // {lr_t, beta1, beta2, eps} of the current step, in device memory (WideWgradArgs::adam)
   bool prof_no_fuse = false;
-  std::vector<WideWgradPlan> wide_roles_buf;
-  std::vector<WideWgradPlan>* wide_roles = nullptr;      // non-null: wide_wgrad collects instead of launching
   // v2x_train_step_dp (dp_native.hpp): the stream the bucket collectives run on and its events, made on first use
   hipStream_t dp_st = nullptr;
   std::vector<hipEvent_t> dp_ev;
@@ -185,7 +177,7 @@ int prof_id(v2x_model* m, const char* name) {
 }
 
 // launch wrapper: optional HIP-event bracket per kernel for in-situ timing
-#define LAUNCH(m, kname, kern, grid, lds, stream, args)                                  \
+#define LAUNCH(m, kname, kern, grid, threads, lds, stream, ...)                          \
   do {                                                                                  \
     ProfRec _r;                                                                         \
     const bool _p = (m) && (m)->prof && !(m)->capturing;                                \
@@ -194,11 +186,20 @@ int prof_id(v2x_model* m, const char* name) {
       hipEventCreate(&_r.ev0); hipEventCreate(&_r.ev1);                                     \
       hipEventRecord(_r.ev0, stream);                                                     \
     }                                                                                   \
-    hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, args);                       \
+    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, __VA_ARGS__);            \
     if (_p) { hipEventRecord(_r.ev1, stream); (m)->prof_recs.push_back(_r); }             \
     hipError_t _e = hipGetLastError();                                                  \
     if (_e != hipSuccess) FAIL(m, V2X_EHIP, "launch %s failed: %s", kname, hipGetErrorString(_e)); \
   } while (0)
+
+// A run-time value as a template argument: f(std::integral_constant<int, V>{}) for the V among Vs that equals v, and what it
+// returns (V2X_OK or a launch error); V2X_EINVAL when no V does -- the caller names the unsupported shape
+template <int... Vs, typename Fn>
+int with_const(int v, Fn&& f) {
+  int rc = V2X_EINVAL;
+  (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+  return rc;
+}
 
 // ------------------------------------------------------------------------------------ layout
 void build_layout(v2x_model* m) {
@@ -288,14 +289,6 @@ void set_attrs(int F, const Knobs& kn) {
 }
 
 inline bool is_wide(const v2x_model* m) { return m->F >= 128; }
-
-struct RowMapH { int n_idx, row_stride, base_mul, grid_y; };
-RowMapH row_map(const v2x_model* m, int n_rows) {
-  RowMapH r;
-  if (m->S == 1) { r.n_idx = n_rows; r.row_stride = 1; r.base_mul = 0; r.grid_y = 1; }
-  else { r.n_idx = n_rows / m->N; r.row_stride = m->N; r.base_mul = 1; r.grid_y = m->N; }
-  return r;
-}
 
 int ensure_rows(v2x_model* m, int64_t R) {
   if (R <= m->cap_rows) return V2X_OK;
@@ -518,22 +511,49 @@ int resolve_batch(v2x_model* m, const v2x_batch* b, DevBatch* d, hipStream_t st)
 
 // ------------------------------------------------------------------------------------ launchers
 
-// A launch covers graphs [g0, g0+ng) of the batch.  Every activation / gradient buffer is indexed by the
-// ABSOLUTE node row, so disjoint ranges (micro-batches) can be in flight concurrently on different streams.
-struct Range { int g0, ng; };
-
+// Every launch covers the whole batch: the kernels' g_base / idx_base arguments are 0, their g_end is B.
 struct IdxMap { int idx_base, n_idx, row_stride, base_mul, grid_y; };
-IdxMap idx_map(const v2x_model* m, const DevBatch& d, Range r) {
+IdxMap idx_map(const v2x_model* m, const DevBatch& d) {
   IdxMap x;
+  x.idx_base = 0;
   if (m->S == 1) {            // shared weights: the GEMM row index is the node row
     x.row_stride = 1; x.base_mul = 0; x.grid_y = 1;
-    if (m->cfg.variable_graphs) { x.idx_base = 0; x.n_idx = d.R; }   // ragged batches are never split
-    else { x.idx_base = r.g0 * m->N; x.n_idx = r.ng * m->N; }
+    x.n_idx = m->cfg.variable_graphs ? d.R : d.B * m->N;
   } else {                    // per-node weights: slot k owns rows b*N + k, index = graph b
-    x.idx_base = r.g0; x.n_idx = r.ng; x.row_stride = m->N; x.base_mul = 1; x.grid_y = m->N;
+    x.n_idx = d.B; x.row_stride = m->N; x.base_mul = 1; x.grid_y = m->N;
   }
   return x;
 }
+
+// How one batch runs: every path decision of the dispatcher, made ONCE per C-ABI call by plan_batch (below, with the predicates
+// and their measurements) and handed down by const reference.  A pure function of the model's shape and switches, what the
+// model allocated at create (pk_fwd, pk_bwd, small_h, adam_scal; prof_no_fuse, which nothing sets), the batch's sizes, whether
+// graph_off / nbr_init are given, and the chip's CU count: never cached, cheap to recompute, so the launches
+// outside a replayed hipGraph agree with the ones inside it.
+enum class GraphLayers { Layerwise, Fused, Ragged };
+enum class RaggedPlan { Interval, Packed, Folded };     // by k_adj_masks per row interval; k_ragged_plan; k_ragged_plan's tables by workgroup 0 of k_adj_masks
+struct BatchPlan {
+  IdxMap x;                              // GEMM row index of the whole batch
+  GraphLayers form = GraphLayers::Layerwise;
+  bool mlp_wg = false;                   // the decision MLP trains in one launch (k_mlp_train_wg): narrow features
+  bool small_predict = false;            // a forward alone is the one-launch few-graph predict
+  // fused graph layers
+  int tiles = 0, split = 1;              // 16-graph tiles; K workgroups per tile (1: whole tiles)
+  bool split_fwd = false, split_bwd = false;   // K > 1 and the direction's debugging switch leaves it on
+  bool compl_sums = false;               // aggregation through the complement (whole tiles only: already combined with K <= 1)
+  size_t fused_lds_fwd = 0, fused_lds_bwd = 0;
+  // ragged fused graph layers
+  bool ragged_small = false, ragged_bwd = false;       // small-tile kernels; the backward is fused too
+  int cap = 0, capp = 0, wgs = 0, plan_words = 0;
+  RaggedPlan plan_form = RaggedPlan::Interval;
+  // layer-wise aggregation
+  bool dense_agg = false, need_adj_masks = false;
+  // weight gradients and the hand-off to the MLP launch
+  bool embed_rides = false, dense0_rides = false;      // on the graph layers' k_wgrad roles
+  bool frag_ok = false;                  // h_L / a_L / gha may travel fragment-major between the fused kernels and k_mlp_train_wg
+  bool wide_merge = false;               // wide model: every layer's weight gradient in ONE launch (unless the call is bucketed)
+  bool wide_adam_fusable = false;        // ... whose epilogues may apply Adam
+};
 
 int n_cus() {
   static int n = 0;
@@ -555,11 +575,11 @@ bool use_dense_agg(const Knobs& kn, const DevBatch& d, int F) {
          rows_cap * AD_LDT * 4 + rows_cap * mw * 4 + 4 * 64 * 4 <= 160 * 1024;
 }
 
-AggDenseArgs agg_dense_args(const DevBatch& d, Range r, int N, int F) {
+AggDenseArgs agg_dense_args(const DevBatch& d, int N, int F) {
   AggDenseArgs q;
   memset(&q, 0, sizeof(q));
   q.graph_off = d.goff; q.row_ptr = d.rp; q.col_idx = d.ci;
-  q.g_base = r.g0; q.n_graphs = r.ng; q.n_nodes = N; q.F = F; q.n_fg = F / 64;
+  q.g_base = 0; q.n_graphs = d.B; q.n_nodes = N; q.F = F; q.n_fg = F / 64;
   q.rows_cap = (d.max_nodes + 15) / 16 * 16;
   q.mask_words = (d.max_nodes + 31) / 32;
   return q;
@@ -571,11 +591,12 @@ int build_adj_masks(v2x_model* m, hipStream_t st, const AggDenseArgs& q) {
   size_t lds = (size_t)2 * q.rows_cap * q.mask_words * 4 + (size_t)(q.rows_cap + 1) * 4;   // by source + by destination + row_ptr slice
   int grid = q.n_graphs;
   if (q.plan_cap > 0) lds = std::max(lds, plan16_bytes(q.n_graphs, q.plan_n));                   // workgroup 0 makes the plan first
-  LAUNCH(m, "k_adj_masks", k_adj_masks, dim3(grid), lds, st, q);
+  LAUNCH(m, "k_adj_masks", k_adj_masks, dim3(grid), 256, lds, st, q);
   return V2X_OK;
 }
 
-int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, int F, const float* src, int src_stride,
+// dense_agg: BatchPlan::dense_agg of a model's batch; use_dense_agg for the entry points that come without a model
+int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, bool dense_agg, int N, int F, const float* src, int src_stride,
                const float* add, int add_stride, const float* mask, float* out, int transpose) {
   if (F < 16 || F > 256 || (F & (F - 1))) FAIL(m, V2X_EINVAL, "agg: feat_dim must be a power of two in [16,256]");
   static const bool attrs_once = [] {        // the per-kernel entry points can get here without any model
@@ -587,8 +608,8 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
   }();
   (void)attrs_once;
   const Knobs& kn = knobs_of(m);
-  if (use_dense_agg(kn, d, F)) {
-    AggDenseArgs q = agg_dense_args(d, r, N, F);
+  if (dense_agg) {
+    AggDenseArgs q = agg_dense_args(d, N, F);
     q.src = src; q.src_stride = src_stride; q.add = add; q.add_stride = add_stride; q.mask = mask; q.out = out;
     q.err = flag_dev_of(m);
     if (m) {
@@ -608,15 +629,15 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
       CHK(build_adj_masks(m, st, q));
     }
     const size_t lds = (size_t)q.rows_cap * AD_LDT * 4 + (size_t)q.rows_cap * q.mask_words * 4 + 4 * 64 * 4;   // + partial column sums
-    const dim3 grid((r.ng + 7) / 8 * 8 * q.n_fg);
-    if (transpose) { auto k = k_agg_dense<true>; LAUNCH(m, "k_agg_bwd", k, grid, lds, st, q); }
-    else { auto k = k_agg_dense<false>; LAUNCH(m, "k_agg_fwd", k, grid, lds, st, q); }
+    const dim3 grid((d.B + 7) / 8 * 8 * q.n_fg);
+    if (transpose) { auto k = k_agg_dense<true>; LAUNCH(m, "k_agg_bwd", k, grid, 256, lds, st, q); }
+    else { auto k = k_agg_dense<false>; LAUNCH(m, "k_agg_fwd", k, grid, 256, lds, st, q); }
     return V2X_OK;
   }
   AggArgs a;
   a.src = src; a.src_stride = src_stride; a.add = add; a.add_stride = add_stride; a.mask = mask; a.out = out;
   a.graph_off = d.goff; a.row_ptr = d.rp; a.col_idx = d.ci;
-  a.g_base = r.g0; a.g_end = r.g0 + r.ng; a.n_nodes = N; a.F = F;
+  a.g_base = 0; a.g_end = d.B; a.n_nodes = N; a.F = F;
   int sh = 0; while ((4 << sh) < F) ++sh;
   a.lpr_shift = sh;
   a.mask_words = (d.max_nodes + 31) / 32;
@@ -629,21 +650,21 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
   // few graphs per workgroup => many workers per graph => short per-worker row loops (the kernel is a
   // latency chain: stage -> barrier -> LDS gathers -> store); keep >= 8 workers per graph when F allows
   const int wpg_min = kn.agg_workers_per_graph;
-  while (gpw * 2 <= nworkers && nworkers / (gpw * 2) >= wpg_min && (size_t)(gpw * 2) * per_graph <= 48 * 1024 && gpw * 2 <= r.ng) gpw *= 2;
+  while (gpw * 2 <= nworkers && nworkers / (gpw * 2) >= wpg_min && (size_t)(gpw * 2) * per_graph <= 48 * 1024 && gpw * 2 <= d.B) gpw *= 2;
   a.gpw = gpw;
   a.rows_cap = gpw * d.max_nodes;
   a.edges_cap = gpw * d.max_edges;
   const size_t lds = (size_t)a.rows_cap * F * 4 + (size_t)(a.rows_cap + 1) * 4 + (size_t)(gpw + 1) * 4 +
                      (size_t)a.edges_cap * 4 + (transpose ? (size_t)a.rows_cap * a.mask_words * 4 : 0);
   if (lds > 160 * 1024) FAIL(m, V2X_EINVAL, "agg: graph tile (%zu B) exceeds the 160 KiB LDS", lds);
-  const dim3 grid((r.ng + gpw - 1) / gpw);
+  const dim3 grid((d.B + gpw - 1) / gpw);
   // small tiles (the 20-link graphs of the headline configuration): everything fetched before the first wait
   const bool small_off = kn.agg_no_small;
   const int wpg = nworkers / gpw;
   const bool small = !small_off && d.ci != nullptr && (a.rows_cap << sh) <= 1024 && a.rows_cap + 1 <= 256 && a.edges_cap <= 1024 &&
                      (d.max_nodes + wpg - 1) / wpg <= 4;
   if (small) {
-#define V2X_AGG_SMALL(T, A, M, NAME) { auto k = k_agg_small<T, A, M>; LAUNCH(m, NAME, k, grid, lds, st, a); return V2X_OK; }
+#define V2X_AGG_SMALL(T, A, M, NAME) { auto k = k_agg_small<T, A, M>; LAUNCH(m, NAME, k, grid, 256, lds, st, a); return V2X_OK; }
     if (!transpose) {
       if (!add && !mask) V2X_AGG_SMALL(false, false, false, "k_agg_fwd")
     } else {
@@ -653,8 +674,8 @@ int launch_agg(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, int N, 
     }
 #undef V2X_AGG_SMALL
   }
-  if (transpose) { auto k = k_agg<true>; LAUNCH(m, "k_agg_bwd", k, grid, lds, st, a); }
-  else { auto k = k_agg<false>; LAUNCH(m, "k_agg_fwd", k, grid, lds, st, a); }
+  if (transpose) { auto k = k_agg<true>; LAUNCH(m, "k_agg_bwd", k, grid, 256, lds, st, a); }
+  else { auto k = k_agg<false>; LAUNCH(m, "k_agg_fwd", k, grid, 256, lds, st, a); }
   return V2X_OK;
 }
 
@@ -682,7 +703,6 @@ void set_idx(WideGemmArgs& a, const IdxMap& x) {
 // Dense-0's 80 columns are one 5-tile strip instead of a 64 + 16 split (154 -> 110 us).
 int wide_nt(int n_out) { return n_out <= 80 ? 5 : 4; }
 
-int launch_check(v2x_model* m, const char* kname);
 int launch_wide_gemm(v2x_model* m, hipStream_t st, WideGemmArgs& a, int grid_z, bool trans, const char* name) {
   const int nt = wide_nt(a.n_out);
   // Tiling (kernels_wide.hpp, WideTiling): 128-row tiles; when the launch is more than one round of the chip's resident
@@ -700,11 +720,7 @@ int launch_wide_gemm(v2x_model* m, hipStream_t st, WideGemmArgs& a, int grid_z, 
   // slots, three workgroups per CU instead of five): every row block as two half tiles (V2X_WIDE_TAIL=2 only: measured)
   if (tail == 2 && T < C && 2 * T > C) t.n_full_rb = 0;
   const dim3 grid(t.n_full_rb * t.ny + 2 * (t.n_rb - t.n_full_rb) * t.ny);
-#define V2X_WIDE_GEMM(T_, NTV) { auto k = k_wide_gemm<T_, NTV>; ProfRec _r; const bool _p = m->prof && !m->capturing;                      \
-    if (_p) { _r.id = prof_id(m, name); hipEventCreate(&_r.ev0); hipEventCreate(&_r.ev1); hipEventRecord(_r.ev0, st); }                     \
-    hipLaunchKernelGGL(k, grid, dim3(256), 0, st, a, t);                                                                                     \
-    if (_p) { hipEventRecord(_r.ev1, st); m->prof_recs.push_back(_r); }                                                                      \
-    return launch_check(m, name); }
+#define V2X_WIDE_GEMM(T_, NTV) { auto k = k_wide_gemm<T_, NTV>; LAUNCH(m, name, k, grid, 256, 0, st, a, t); return V2X_OK; }
   if (!trans) {
     if (nt == 5) V2X_WIDE_GEMM(false, 5)
     V2X_WIDE_GEMM(false, 4)
@@ -750,8 +766,9 @@ int wide_splits(int n_idx, int n_tiles, int n_slots) {
 }
 
 // arguments + tiling of one layer's wide weight gradient (and the memsets of an absent input segment's weight rows)
+// merged: a role of the merged launch (wide_wgrad_flush); adam: its epilogue applies Adam (WideWgradArgs::adam)
 int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x, const WideSeg* segs, const int* seg_kpad,
-                    int n_seg, const float* dpre, int d_stride, int zero_row0, int zero_rows, WideWgradPlan* out) {
+                    int n_seg, const float* dpre, int d_stride, int zero_row0, int zero_rows, bool merged, bool adam, WideWgradPlan* out) {
   WideWgradArgs& a = out->a;
   memset(&a, 0, sizeof(a));
   int k_width = 0;
@@ -766,7 +783,7 @@ int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x
   // (measured: 298 us unfolded, 333 us folded -- 400 workgroups, the same two per CU, one of them 12.5 % longer)
   const int fold = m->knobs.wide_fold;
   for (int i = 0; i < n_seg; ++i) {
-    if (fold && m->wide_merge_now && KW == 128 && n_seg > 1 && segs[i].width == XE && !a.xseg.ptr) { a.xseg = segs[i]; a.xseg_kpad = seg_kpad[i]; continue; }
+    if (fold && merged && KW == 128 && n_seg > 1 && segs[i].width == XE && !a.xseg.ptr) { a.xseg = segs[i]; a.xseg_kpad = seg_kpad[i]; continue; }
     a.seg[ns] = segs[i]; a.seg_kpad[ns] = seg_kpad[i]; kt += (segs[i].width + KW - 1) / KW;
     ++ns;
   }
@@ -785,7 +802,7 @@ int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x
     a.slab = m->grads;
     ld.n_slabs = 0;
   }
-  if (m->fuse_adam_now && &ld != &m->gnn[0]) {         // (the embed layer keeps k_reduce_adam: its absent-input rows have no tile)
+  if (adam && &ld != &m->gnn[0]) {         // (the embed layer keeps k_reduce_adam: its absent-input rows have no tile)
     if (sp != 1 || zero_rows > 0) FAIL(m, V2X_ESTATE, "wide wgrad: Adam cannot ride on a split weight gradient");
     a.adam = 1; a.param = m->params; a.mom = m->mom; a.vel = m->vel; a.adam_scal = m->adam_scal;
   }
@@ -801,28 +818,30 @@ int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x
   return V2X_OK;
 }
 
+// The roles of a backward pass that launches every wide weight gradient as ONE grid (wide_wgrad_flush); null = each on its own
+struct WideRoles { std::vector<WideWgradPlan> v; bool adam = false; };     // adam: the epilogues apply Adam (single-GPU fit step)
+
 int wide_wgrad(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x, const WideSeg* segs, const int* seg_kpad,
-               int n_seg, const float* dpre, int d_stride, const char* name, int zero_row0 = 0, int zero_rows = 0) {
+               int n_seg, const float* dpre, int d_stride, const char* name, WideRoles* roles, int zero_row0 = 0, int zero_rows = 0) {
   WideWgradPlan p;
-  CHK(wide_wgrad_plan(m, st, ld, x, segs, seg_kpad, n_seg, dpre, d_stride, zero_row0, zero_rows, &p));
-  if (m->wide_roles) {      // collected for the merged launch (wide_wgrad_flush)
-    if ((int)m->wide_roles->size() >= WWM_ROLES) FAIL(m, V2X_ESTATE, "wide wgrad: too many roles for one launch");
-    m->wide_roles->push_back(p);
+  CHK(wide_wgrad_plan(m, st, ld, x, segs, seg_kpad, n_seg, dpre, d_stride, zero_row0, zero_rows, roles != nullptr, roles && roles->adam, &p));
+  if (roles) {              // collected for the merged launch (wide_wgrad_flush)
+    if ((int)roles->v.size() >= WWM_ROLES) FAIL(m, V2X_ESTATE, "wide wgrad: too many roles for one launch");
+    roles->v.push_back(p);
     return V2X_OK;
   }
   const WideWgradArgs& a = p.a;
   const dim3 grid(p.kt, p.nt, x.grid_y * p.sp);
-  if (p.ntw == 4) { auto k = k_wide_wgrad<64, 4>; LAUNCH(m, name, k, grid, 0, st, a); }
-  else if (p.ntw == 5) { auto k = k_wide_wgrad<128, 5>; LAUNCH(m, name, k, grid, 0, st, a); }
-  else if (p.ntw == 8) { auto k = k_wide_wgrad<128, 8>; LAUNCH(m, name, k, grid, 0, st, a); }
-  else { auto k = k_wide_wgrad<128, 16>; LAUNCH(m, name, k, grid, 0, st, a); }
+  if (p.ntw == 4) { auto k = k_wide_wgrad<64, 4>; LAUNCH(m, name, k, grid, 256, 0, st, a); }
+  else if (p.ntw == 5) { auto k = k_wide_wgrad<128, 5>; LAUNCH(m, name, k, grid, 256, 0, st, a); }
+  else if (p.ntw == 8) { auto k = k_wide_wgrad<128, 8>; LAUNCH(m, name, k, grid, 256, 0, st, a); }
+  else { auto k = k_wide_wgrad<128, 16>; LAUNCH(m, name, k, grid, 256, 0, st, a); }
   return V2X_OK;
 }
 
 // launch the collected roles as one grid, heaviest workgroups first (they are dispatched in block order and the launch is
 // as long as its last-finishing workgroup)
-int wide_wgrad_flush(v2x_model* m, hipStream_t st, const IdxMap& x) {
-  std::vector<WideWgradPlan>& roles = *m->wide_roles;
+int wide_wgrad_flush(v2x_model* m, hipStream_t st, const IdxMap& x, std::vector<WideWgradPlan>& roles) {
   if (roles.empty()) return V2X_OK;
   std::stable_sort(roles.begin(), roles.end(), [](const WideWgradPlan& p, const WideWgradPlan& q) {
     auto w = [](const WideWgradPlan& r) { return (r.ntw == 4 ? 64 : 128) * 16 * r.ntw; };     // MFMA work of one workgroup
@@ -840,8 +859,7 @@ int wide_wgrad_flush(v2x_model* m, hipStream_t st, const IdxMap& x) {
   }
   for (int i = n; i <= WWM_ROLES; ++i) mu.start[i] = total;
   mu.n_roles = n;
-  roles.clear();
-  LAUNCH(m, "k_wgrad_wide_all", k_wide_wgrad_multi, dim3(total), 0, st, mu);
+  LAUNCH(m, "k_wgrad_wide_all", k_wide_wgrad_multi, dim3(total), 256, 0, st, mu);
   return V2X_OK;
 }
 
@@ -857,7 +875,7 @@ int launch_gemm_t(v2x_model* m, hipStream_t st, GemmArgs& a, int grid_y, const c
   const size_t lds = (size_t)(KP * (F + 4) + F) * 4;
   const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, m->knobs.gemm_wgs_per_cu);
   auto k = k_gemm_rows<F, HAS0, HAS2, DGRAD>;
-  LAUNCH(m, name, k, dim3(gx, grid_y), lds, st, a);
+  LAUNCH(m, name, k, dim3(gx, grid_y), 256, lds, st, a);
   return V2X_OK;
 }
 
@@ -933,7 +951,7 @@ int launch_mlp_fwd_f(v2x_model* m, hipStream_t st, MlpArgs& a, int grid_y) {
   const size_t lds = (size_t)MlpLds<F>::TOTAL * 4;
   const int gx = persistent_wgs_per_slot(a.n_idx, grid_y, m->knobs.mlp_wgs_per_cu);
   auto k = k_mlp_fwd<F>;
-  LAUNCH(m, "k_mlp_fwd", k, dim3(gx, grid_y), lds, st, a);
+  LAUNCH(m, "k_mlp_fwd", k, dim3(gx, grid_y), 256, lds, st, a);
   return V2X_OK;
 }
 
@@ -977,14 +995,14 @@ int launch_mlp_train_wg_f(v2x_model* m, hipStream_t st, const MlpArgs& a, int n_
   }
   if constexpr (F == 64) {
     if (!wg0) {             // Dense-0's weight gradient is a role of the graph layers' launch (dense0_rides): dz1 rows instead
-      if (a.frag_groups > 0) { auto k = k_mlp_train_wg<F, true, false>; LAUNCH(m, "k_mlp_train_wg123", k, dim3(sp.n_wgs), lds, st, t); }
-      else { auto k = k_mlp_train_wg<F, false, false>; LAUNCH(m, "k_mlp_train_wg123", k, dim3(sp.n_wgs), lds, st, t); }
+      if (a.frag_groups > 0) { auto k = k_mlp_train_wg<F, true, false>; LAUNCH(m, "k_mlp_train_wg123", k, dim3(sp.n_wgs), 256, lds, st, t); }
+      else { auto k = k_mlp_train_wg<F, false, false>; LAUNCH(m, "k_mlp_train_wg123", k, dim3(sp.n_wgs), 256, lds, st, t); }
       return V2X_OK;
     }
   }
   if (!wg0) FAIL(m, V2X_ESTATE, "mlp_train_wg: Dense-0 outside the launch needs feat_dim 64");
-  if (a.frag_groups > 0) { auto k = k_mlp_train_wg<F, true>; LAUNCH(m, "k_mlp_train_wg", k, dim3(sp.n_wgs), lds, st, t); }
-  else { auto k = k_mlp_train_wg<F>; LAUNCH(m, "k_mlp_train_wg", k, dim3(sp.n_wgs), lds, st, t); }
+  if (a.frag_groups > 0) { auto k = k_mlp_train_wg<F, true>; LAUNCH(m, "k_mlp_train_wg", k, dim3(sp.n_wgs), 256, lds, st, t); }
+  else { auto k = k_mlp_train_wg<F>; LAUNCH(m, "k_mlp_train_wg", k, dim3(sp.n_wgs), 256, lds, st, t); }
   return V2X_OK;
 }
 
@@ -1012,7 +1030,7 @@ int launch_mlp(v2x_model* m, hipStream_t st, MlpArgs& a, bool bwd) {
     }
     const int gx = persistent_wgs_per_slot(a.n_idx, gy, m->knobs.mlp_wgs_per_cu);
     auto k = k_mlp_bwd<0>;
-    LAUNCH(m, "k_mlp_bwd", k, dim3(gx, gy), (size_t)MlpLds<0>::TOTAL * 4, st, a);
+    LAUNCH(m, "k_mlp_bwd", k, dim3(gx, gy), 256, (size_t)MlpLds<0>::TOTAL * 4, st, a);
     return wide_dgrad(m, st, m->dense[0], x, m->dz1, H1, m->Dn, m->gha, "k_dense0_dgrad");
   }
   if (bwd) FAIL(m, V2X_ESTATE, "mlp: the backward of a narrow model is part of k_mlp_train_wg");
@@ -1088,15 +1106,15 @@ int launch_wgrad_multi(v2x_model* m, hipStream_t st, const IdxMap& x, WgradMulti
   }
 #define V2X_WG_CASE(FF)                                                              \
   if (m->F == FF && !dense) {                                                        \
-    if (halves) { auto k = k_wgrad<FF, 3>; LAUNCH(m, name, k, grid, lds, st, mu); }    \
-    else { auto k = k_wgrad<FF, 0>; LAUNCH(m, name, k, grid, lds, st, mu); }           \
+    if (halves) { auto k = k_wgrad<FF, 3>; LAUNCH(m, name, k, grid, 256, lds, st, mu); }    \
+    else { auto k = k_wgrad<FF, 0>; LAUNCH(m, name, k, grid, 256, lds, st, mu); }           \
     return V2X_OK;                                                                   \
   }
   V2X_WG_CASE(16) V2X_WG_CASE(32) V2X_WG_CASE(64)
 #undef V2X_WG_CASE
   if (is_wide(m) && dense && !halves) { // (the operand widths of Dense 1..3 do not depend on F)
     auto k = k_wgrad<64, 1>;
-    LAUNCH(m, name, k, grid, lds, st, mu);
+    LAUNCH(m, name, k, grid, 256, lds, st, mu);
     return V2X_OK;
   }
   FAIL(m, V2X_EINVAL, "wgrad: no kernel for these roles at feat_dim %d", m->F);
@@ -1121,7 +1139,7 @@ int wgrad_gnn_role(v2x_model* m, int stage, const IdxMap& x, int total_work, con
 }
 
 int wide_wgrad_gnn(v2x_model* m, hipStream_t st, int stage, const IdxMap& x, const float* xe, const float* h_prev,
-                   const float* agg_prev, const float* dpre) {
+                   const float* agg_prev, const float* dpre, WideRoles* roles = nullptr) {
   const int F = m->F;
   WideSeg s[3];
   int kp[3], n = 0;
@@ -1133,9 +1151,9 @@ int wide_wgrad_gnn(v2x_model* m, hipStream_t st, int stage, const IdxMap& x, con
     s[n] = WideSeg{xe, XE, XE}; kp[n++] = 0;
     if (agg_prev) { s[n] = WideSeg{agg_prev, F, F}; kp[n++] = XE; }
     // neighbour-init absent (the reference always feeds zeros): its F weight rows (real rows Dn+De ..) are memset
-    else return wide_wgrad(m, st, m->gnn[0], x, s, kp, n, dpre, F, "k_wgrad_embed", m->Dn + m->De, F);
+    else return wide_wgrad(m, st, m->gnn[0], x, s, kp, n, dpre, F, "k_wgrad_embed", roles, m->Dn + m->De, F);
   }
-  return wide_wgrad(m, st, m->gnn[stage], x, s, kp, n, dpre, F, stage ? "k_wgrad_gnn" : "k_wgrad_embed");
+  return wide_wgrad(m, st, m->gnn[stage], x, s, kp, n, dpre, F, stage ? "k_wgrad_gnn" : "k_wgrad_embed", roles);
 }
 
 // rows per workgroup of the graph layers' roles when the embed gradient rides on them: one workgroup per CU if that
@@ -1161,45 +1179,40 @@ int wgrad_gnn(v2x_model* m, hipStream_t st, int stage, const IdxMap& x, const fl
   return launch_wgrad_multi(m, st, x, mu, 1, stage ? "k_wgrad_gnn" : "k_wgrad_embed");
 }
 
-// The embed layer's gradient rides on the graph layers' roles (wgrad_gnn_all)
-bool embed_rides(const v2x_model* m, const DevBatch& d) {
-  const int merge_env = m->knobs.wg_embed_merge;
-  const int NTf = m->F / 16;
-  return merge_env && !is_wide(m) && !d.nbr && m->L >= 1 && m->L <= NTf && NTf % m->L == 0 && m->L + 3 <= WG_MAX_ROLES;
-}
-// Small batches (the shares of the metric's global batch on 4 / 8 GPUs): k_mlp_train_wg is ONE wave's latency chain there (<= 2
-// tiles per wave) and the graph layers' weight-gradient launch leaves a third of the chip idle: Dense-0's weight gradient -- 180
-// of a tile's 796 MFMAs, 45 of the 68 accumulator tiles the MLP launch exchanges and writes at its end -- moves over as a role
-// of that launch (kernels_mlpwg.hpp WG0 = false, kernels.hpp WG_KIND_DENSE0_FRAG).  Knobs::mlp_wg0 = 1: never, 0: whenever possible.
-bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x) {
-  const int env = m->knobs.mlp_wg0;
-  if (env == 1 || m->F != 64 || m->cfg.variable_graphs || !embed_rides(m, d)) return false;
-  if (x.n_idx % 16 || x.idx_base % 16) return false;             // whole 16-row groups (the fragment-major reader)
-  if (env == 0) return true;
-  // tiles per workgroup = 4 x tiles per wave.  Measured (profiles/r06_dense0_role_shares.txt): 512 / 1024 / 2048 graphs of 20 links
-  // (4 / 8 / 12 tiles per workgroup) 0.1201 -> 0.1131, 0.1512 -> 0.1463, 0.1929 -> 0.1880 ms per step; at 4096 (20-24 tiles) the chip
-  // is full either way and the heavier weight-gradient launch costs more than the MLP launch saves (0.2554 -> 0.2658)
-  return mlp_wg_split(x.n_idx, x.grid_y).tiles_per_wg <= m->knobs.mlp_wg0_tiles;
-}
+// What one backward pass was asked for by its C-ABI call: arguments handed down, nothing here outlives the call
+struct BwdCall {
+  bool bucketed = false;               // data parallelism wants each layer's gradient as soon as it is final: no merged wide launch
+  bool fuse_adam = false;              // the merged wide launch applies Adam in its epilogues (BatchPlan::wide_adam_fusable)
+  const float* tq = nullptr;           // a DQN replay step whose MLP launch forms the targets itself (MlpArgs::tq): replaced entries, actions
+  float* y_out = nullptr;              // ... and where y goes
+  bool phased = false;                 // one half of v2x_forward_backward_phase, not run_backward: see dense0_out and ragged_fused_bwd
+};
+// wide path: every layer's weight gradient in ONE launch after the data chain -- unless somebody wants a layer's gradient
+// as soon as it is final (per-layer all-reduce buckets of data parallelism)
+bool wide_merged(const BatchPlan& p, const BwdCall& c) { return p.wide_merge && !c.bucketed; }
+// The MLP launch leaves dz1 instead of Dense-0's weight gradient, which is then a role of wgrad_gnn_all: backward_mlp and
+// wgrad_gnn_all both ask here, so the two cannot disagree.
+// (phased: the phases always keep it in the MLP launch, although phase 0's forward consults dense0_rides for the hand-off layout)
+bool dense0_out(const BatchPlan& p, const BwdCall& c) { return p.dense0_rides && !c.phased; }
+// A ragged batch takes its one-launch backward.  (phased: phase 1 runs a ragged batch's data chain layer by layer)
+bool ragged_fused_bwd(const BatchPlan& p, const BwdCall& c) { return p.ragged_bwd && !c.phased; }
 
 // all GNN stages (needs dpre[0..L]): one launch when the embed rides on the stage roles (embed_rides), else
 // ceil((L+1)/WG_MAX_ROLES) launches of at most WG_MAX_ROLES stage roles -- one up to L = 7, two at L = 8
-int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch& d) {
+int wgrad_gnn_all(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, const BwdCall& c) {
+  const IdxMap& x = p.x;
   if (is_wide(m)) {
-    if (m->wide_merge_now) m->wide_roles = &m->wide_roles_buf;          // collect: L + 1 graph layers (+ Dense-0), one grid
-    int rc = V2X_OK;
-    for (int s = m->L; s >= 0 && rc == V2X_OK; --s)
-      rc = wide_wgrad_gnn(m, st, s, x, d.xe, s ? m->h[s - 1] : nullptr, s ? m->a[s - 1] : d.nbr, m->dpre[s]);
-    if (m->wide_merge_now && rc == V2X_OK) {
-      const int F = m->F, L = m->L;
-      WideSeg w0[3] = {WideSeg{m->h[L], F, F}, WideSeg{d.xe, XE, XE}, WideSeg{m->a[L], F, F}};
-      const int kp[3] = {0, F, F + XE};
-      rc = wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0");
-      if (rc == V2X_OK) rc = wide_wgrad_flush(m, st, x);
-    }
-    m->wide_roles = nullptr;
-    m->wide_roles_buf.clear();
-    return rc;
+    WideRoles merged;                                                   // collect: L + 1 graph layers (+ Dense-0), one grid
+    merged.adam = c.fuse_adam;
+    WideRoles* roles = wide_merged(p, c) ? &merged : nullptr;
+    for (int s = m->L; s >= 0; --s)
+      CHK(wide_wgrad_gnn(m, st, s, x, d.xe, s ? m->h[s - 1] : nullptr, s ? m->a[s - 1] : d.nbr, m->dpre[s], roles));
+    if (!roles) return V2X_OK;
+    const int F = m->F, L = m->L;
+    WideSeg w0[3] = {WideSeg{m->h[L], F, F}, WideSeg{d.xe, XE, XE}, WideSeg{m->a[L], F, F}};
+    const int kp[3] = {0, F, F + XE};
+    CHK(wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0", roles));
+    return wide_wgrad_flush(m, st, x, merged.v);
   }
   WgradMulti mu;
   // The embed layer's gradient (16 MFMAs per block, load-bound) rides on the graph layers' roles when its F / 16 output
@@ -1207,9 +1220,9 @@ int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch&
   // n_cus / (L * slots) chunks per slot (batch 4096 x 20 slots x 2 stages: 6 chunks = 240 workgroups x 11 blocks per wave
   // instead of 5 chunks = 200 x 13 with 100 embed workgroups queueing behind them).
   const int NTf = m->F / 16;
-  if (embed_rides(m, d)) {
+  if (p.embed_rides) {
     const int en = NTf / m->L;
-    const bool d0 = m->dense0_out_now;                           // + Dense-0 (k_mlp_train_wg left dz1 instead of dW0)
+    const bool d0 = dense0_out(p, c);                            // + Dense-0 (k_mlp_train_wg left dz1 instead of dW0)
     const int rows = merged_wg_rows(m, x.n_idx, x.grid_y, d0 ? 1 : 0);
     memset(&mu, 0, sizeof(mu));
     int total = 0, n = 0;
@@ -1237,7 +1250,7 @@ int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch&
     m->gnn[0].n_slabs = m->gnn[1].n_slabs;                     // every stage role writes its columns of every embed slab
     return launch_wgrad_multi(m, st, x, mu, n, d0 ? "k_wgrad_gnn_d0" : "k_wgrad_gnn");
   }
-  if (m->dense0_out_now) FAIL(m, V2X_ESTATE, "wgrad: Dense-0 was left to a launch that cannot take it");
+  if (dense0_out(p, c)) FAIL(m, V2X_ESTATE, "wgrad: Dense-0 was left to a launch that cannot take it");
   int n = 0, s_first = m->L;
   for (int s = m->L; s >= 0; --s) {
     if (n == 0) { memset(&mu, 0, sizeof(mu)); s_first = s; }
@@ -1251,7 +1264,7 @@ int wgrad_gnn_all(v2x_model* m, hipStream_t st, const IdxMap& x, const DevBatch&
 
 // the Dense layers of a wide model: Dense-0 as a wide weight gradient (or a role of the merged launch), Dense 1..3 in one k_wgrad
 // launch.  (A narrow model's Dense gradients come out of k_mlp_train_wg, Dense-0's at small batches out of wgrad_gnn_all.)
-int wgrad_mlp(v2x_model* m, hipStream_t st, const IdxMap& x, const float* xe, const float* h, const float* agg) {
+int wgrad_mlp(v2x_model* m, hipStream_t st, const IdxMap& x, const float* xe, const float* h, const float* agg, bool dense0_merged = false) {
   if (!is_wide(m)) FAIL(m, V2X_ESTATE, "wgrad_mlp: a narrow model's Dense gradients are part of k_mlp_train_wg");
   const int F = m->F;
   int total = 0;
@@ -1260,7 +1273,7 @@ int wgrad_mlp(v2x_model* m, hipStream_t st, const IdxMap& x, const float* xe, co
   memset(&mu, 0, sizeof(mu));
   WideSeg w0[3] = {WideSeg{h, F, F}, WideSeg{xe, XE, XE}, WideSeg{agg, F, F}};
   const int kp[3] = {0, F, F + XE};
-  if (!m->wide_merge_now) CHK(wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0"));   // else: a role of the merged launch
+  if (!dense0_merged) CHK(wide_wgrad(m, st, m->dense[0], x, w0, kp, 3, m->dz1, H1, "k_wgrad_dense0", nullptr));   // else: a role of the merged launch
   WgSeg t1[1] = {WgSeg{m->z1, H1, H1, 0, 0}};
   CHK(wgrad_role(m, m->dense[1], WG_KIND_DENSE1, x, total, t1, 1, m->dz2, H2, mu.w[0]));
   WgSeg t2[1] = {WgSeg{m->z2, H2, H2, 0, 1}};
@@ -1341,7 +1354,7 @@ int launch_reduce_adam(v2x_model* m, hipStream_t st, int n_slabs, bool do_adam, 
   a.loss_split = (lj.n_out == 1 && lj.n_idx > 16384) ? 64 : 1;
   a.loss_part = m->loss_part; a.loss_cnt = reinterpret_cast<unsigned*>(m->loss_part + 64);
   LAUNCH(m, do_adam ? (n_slabs > 0 ? "k_reduce_adam" : "k_adam") : "k_grad_reduce", k_reduce_adam,
-         dim3(blocks + lj.n_out * a.loss_split), 0, st, a);
+         dim3(blocks + lj.n_out * a.loss_split), 256, 0, st, a);
   return V2X_OK;
 }
 
@@ -1350,28 +1363,6 @@ LossJob loss_job(const v2x_model* m, const DevBatch& d, int n_global) {
   if (m->cfg.variable_graphs) return LossJob{1, d.R, 1, inv, 0};
   if (m->S == 1) return LossJob{m->N, d.B, m->N, inv, 1};          // shared weights: rowloss in node-row order
   return LossJob{m->N, d.B, 1, inv, srow_stride(m)};                // per-node weights: slot-major
-}
-
-// ------------------------------------------------------------------------------------ fused graph layers
-// (kernels_fused.hpp) fixed-size graphs of <= 32 nodes, narrow features, no neighbour-init input, tile fits the LDS
-int fused_rowf(int F) { return 4 * ((F / 16) | 1); }
-size_t fused_lds(const v2x_model* m, const DevBatch& d, bool bwd, bool compl_sums = false) {
-  const size_t rows = (size_t)FZ_TG * m->N;
-  size_t b = 4 * rows * fused_rowf(m->F) * 4 + (rows + 1) * 4 + (size_t)FZ_TG * d.max_edges;
-  b += rows * 4;                                       // bit masks: backward always, forward with compl_sums
-  if (compl_sums) b += (size_t)(FZ_SUMS_ROWS + FZ_TOT_ROWS) * fused_rowf(m->F) * 4;
-  return (b + 15) / 16 * 16 + 64;                      // + the turn flags of the backward (FzCtxB::sFlag)
-}
-bool fused_path(const v2x_model* m, const DevBatch& d) {
-  if (!m->pk_fwd || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->N > 32 || m->L > FZ_MAXL) return false;
-  if (d.max_nodes != m->N) return false;
-  return fused_lds(m, d, true) <= 160 * 1024;
-}
-// Aggregations through the complement (kernels_fused.hpp, compl_sums): dense graphs whose extra LDS fits
-bool fused_compl(const v2x_model* m, const DevBatch& d) {
-  if (!m->knobs.fused_compl || m->N < 4) return false;
-  if (2 * (int64_t)d.E <= (int64_t)d.B * m->N * (m->N - 1)) return false;      // average in-degree <= (N - 1) / 2
-  return fused_lds(m, d, true, true) <= 160 * 1024;
 }
 
 __global__ void k_set4(float* dst, float a, float b, float c, float d) {
@@ -1383,21 +1374,6 @@ int launch_check(v2x_model* m, const char* kname) {
   return V2X_OK;
 }
 
-// Split tiles (kernels_fused_split.hpp): K workgroups per 16-graph tile when whole-tile workgroups would leave most of the
-// chip idle (the shares of the metric's global batch).  All K x tiles workgroups must be co-resident (one per CU: their LDS
-// tile admits no second one), and a member should keep at least four slots (below that the hand-overs cost more than the
-// node updates they spread).  Edge form only.
-int fused_split(const v2x_model* m, const DevBatch& d) {
-  const int split_env = m->knobs.fused_split;                        // -1 auto, 0 / 1 off, K forced
-  if (split_env == 0 || split_env == 1 || !fused_path(m, d) || m->L < 1 || m->L > 3) return 1;
-  if (fused_lds(m, d, true) + (size_t)m->N * m->F * 4 > 160 * 1024) return 1;      // + the embed biases of all slots (forward)
-  const int tiles = (d.B + FZ_TG - 1) / FZ_TG;
-  auto fits = [&](int k) { return (m->N + k - 1) / k <= FZ_WAVES && tiles * k <= n_cus(); };      // one slot per wave, all co-resident
-  if (split_env > 1) return (2 * split_env <= m->N && fits(split_env)) ? split_env : 1;
-  for (int k : {5, 4, 3, 2})
-    if (4 * k <= m->N && fits(k)) return k;
-  return 1;
-}
 // The launch counters of a (re)allocated or re-armed exchange start at a value no counter of this process has had: tags must
 // never repeat at an address, also not across buffers (a freed buffer's address is handed out again) or across a re-arm.
 unsigned long long g_xchg_epoch_next = 1;
@@ -1448,44 +1424,210 @@ int launch_pack(v2x_model* m, hipStream_t st) {
   p.params = m->params; p.pk_fwd = m->pk_fwd; p.pk_bwd = m->pk_bwd; p.S = m->S;
   for (int s = 0; s <= m->L; ++s) { p.layer_off[s] = m->gnn[s].off; p.slot_stride[s] = m->gnn[s].slot_stride; p.pad[s] = m->gnn[s].pad; }
   const dim3 grid(4, m->S, m->L + 1);
-  switch (m->F) {
-    case 16: { auto k = k_pack_weights<16>; LAUNCH(m, "k_pack_weights", k, grid, 0, st, p); break; }
-    case 32: { auto k = k_pack_weights<32>; LAUNCH(m, "k_pack_weights", k, grid, 0, st, p); break; }
-    case 64: { auto k = k_pack_weights<64>; LAUNCH(m, "k_pack_weights", k, grid, 0, st, p); break; }
-    default: FAIL(m, V2X_EINVAL, "pack: unsupported feat_dim %d", m->F);
-  }
-  return V2X_OK;
+  const int rc = with_const<16, 32, 64>(m->F, [&](auto Fc) -> int {
+    LAUNCH(m, "k_pack_weights", k_pack_weights<decltype(Fc)::value>, grid, 256, 0, st, p);
+    return V2X_OK;
+  });
+  if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "pack: unsupported feat_dim %d", m->F);
+  return rc;
 }
 
-#define LAUNCH_T(m, kname, kern, grid, threads, lds, stream, ...)                         \
-  do {                                                                                  \
-    ProfRec _r;                                                                         \
-    const bool _p = (m) && (m)->prof && !(m)->capturing;                                \
-    if (_p) {                                                                           \
-      _r.id = prof_id(m, kname);                                                          \
-      hipEventCreate(&_r.ev0); hipEventCreate(&_r.ev1);                                     \
-      hipEventRecord(_r.ev0, stream);                                                     \
-    }                                                                                   \
-    hipLaunchKernelGGL(kern, grid, dim3(threads), lds, stream, __VA_ARGS__);            \
-    if (_p) { hipEventRecord(_r.ev1, stream); (m)->prof_recs.push_back(_r); }             \
-    hipError_t _e = hipGetLastError();                                                  \
-    if (_e != hipSuccess) FAIL(m, V2X_EHIP, "launch %s failed: %s", kname, hipGetErrorString(_e)); \
-  } while (0)
+// ------------------------------------------------------------------------------------ the plan of a batch
+// plan_batch decides every path of a batch once; the predicates below are its helpers and nothing else calls them.
 
+// ---- fused graph layers
+// (kernels_fused.hpp) fixed-size graphs of <= 32 nodes, narrow features, no neighbour-init input, tile fits the LDS
+int fused_rowf(int F) { return 4 * ((F / 16) | 1); }
+size_t fused_lds(const v2x_model* m, const DevBatch& d, bool bwd, bool compl_sums = false) {
+  const size_t rows = (size_t)FZ_TG * m->N;
+  size_t b = 4 * rows * fused_rowf(m->F) * 4 + (rows + 1) * 4 + (size_t)FZ_TG * d.max_edges;
+  b += rows * 4;                                       // bit masks: backward always, forward with compl_sums
+  if (compl_sums) b += (size_t)(FZ_SUMS_ROWS + FZ_TOT_ROWS) * fused_rowf(m->F) * 4;
+  return (b + 15) / 16 * 16 + 64;                      // + the turn flags of the backward (FzCtxB::sFlag)
+}
+bool fused_path(const v2x_model* m, const DevBatch& d) {
+  if (!m->pk_fwd || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->N > 32 || m->L > FZ_MAXL) return false;
+  if (d.max_nodes != m->N) return false;
+  return fused_lds(m, d, true) <= 160 * 1024;
+}
+// Aggregations through the complement (kernels_fused.hpp, compl_sums): dense graphs whose extra LDS fits
+bool fused_compl(const v2x_model* m, const DevBatch& d) {
+  if (!m->knobs.fused_compl || m->N < 4) return false;
+  if (2 * (int64_t)d.E <= (int64_t)d.B * m->N * (m->N - 1)) return false;      // average in-degree <= (N - 1) / 2
+  return fused_lds(m, d, true, true) <= 160 * 1024;
+}
+// Split tiles (kernels_fused_split.hpp): K workgroups per 16-graph tile when whole-tile workgroups would leave most of the
+// chip idle (the shares of the metric's global batch).  All K x tiles workgroups must be co-resident (one per CU: their LDS
+// tile admits no second one), and a member should keep at least four slots (below that the hand-overs cost more than the
+// node updates they spread).  Edge form only.  (Of a batch on the fused path.)
+int fused_split(const v2x_model* m, const DevBatch& d) {
+  const int split_env = m->knobs.fused_split;                        // -1 auto, 0 / 1 off, K forced
+  if (split_env == 0 || split_env == 1 || m->L < 1 || m->L > 3) return 1;
+  if (fused_lds(m, d, true) + (size_t)m->N * m->F * 4 > 160 * 1024) return 1;      // + the embed biases of all slots (forward)
+  const int tiles = (d.B + FZ_TG - 1) / FZ_TG;
+  auto fits = [&](int k) { return (m->N + k - 1) / k <= FZ_WAVES && tiles * k <= n_cus(); };      // one slot per wave, all co-resident
+  if (split_env > 1) return (2 * split_env <= m->N && fits(split_env)) ? split_env : 1;
+  for (int k : {5, 4, 3, 2})
+    if (4 * k <= m->N && fits(k)) return k;
+  return 1;
+}
+
+// ---- few-graph predict, one launch (kernels_small.hpp)
+constexpr int SMALL_ROWS = 256;             // node rows (= workgroups) of one launch: all co-resident on any gfx950 part
+bool small_path(const v2x_model* m, const DevBatch& d) {
+  if (!m->knobs.small_predict || !m->small_h || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->L > FZ_MAXL) return false;
+  if (m->N > 32) return false;                 // the kernel keeps a node's in-neighbours in a 32-entry LDS list
+  return d.max_nodes == m->N && d.R <= std::min(SMALL_ROWS, n_cus());
+}
+
+// ---- ragged fused graph layers
+// (kernels_ragged.hpp) variable-size graphs of <= 128 nodes, shared weights, narrow features, dense enough for the bit masks
+bool ragged_fused_path(const v2x_model* m, const DevBatch& d) {
+  // (any density: a row's aggregation walks its mask's one bits or -- rows with more edges than non-edges in graphs of >= 16
+  //  nodes -- the zero bits; the masks are built for this path whether or not the dense MFMA aggregation wants them)
+  return m->knobs.ragged_fused && m->cfg.variable_graphs && m->S == 1 && d.goff && !d.nbr && m->F <= 64 && m->L <= FZ_MAXL && d.max_nodes <= 128 &&
+         d.max_nodes <= RG_CAP / 2;
+}
+// Small tiles (kernels_ragged_small.hpp: 160-row tiles, 4-wave workgroups, weights as fragments from L2, three workgroups per
+// CU): built and measured in round 5 -- forward 123 us against 101, backward 161 against 103 at configs[4]'s share, + 19 us for
+// the plan as a launch of its own (profiles/r05_ragged_small_ab.txt) -- so OFF unless Knobs::ragged_small (read at create:
+// the fragment-major copy of a ragged model's weights is only kept then)
+bool ragged_small(const v2x_model* m, const DevBatch& d) {
+  return m->knobs.ragged_small && m->pk_fwd && m->pk_bwd && d.max_nodes <= 128 && m->L >= 1;
+}
+
+// ---- weight gradients that ride on the graph layers' launch, and the hand-off to the MLP launch
+// The embed layer's gradient rides on the graph layers' roles (wgrad_gnn_all)
+bool embed_rides(const v2x_model* m, const DevBatch& d) {
+  const int merge_env = m->knobs.wg_embed_merge;
+  const int NTf = m->F / 16;
+  return merge_env && !is_wide(m) && !d.nbr && m->L >= 1 && m->L <= NTf && NTf % m->L == 0 && m->L + 3 <= WG_MAX_ROLES;
+}
+// Small batches (the shares of the metric's global batch on 4 / 8 GPUs): k_mlp_train_wg is ONE wave's latency chain there (<= 2
+// tiles per wave) and the graph layers' weight-gradient launch leaves a third of the chip idle: Dense-0's weight gradient -- 180
+// of a tile's 796 MFMAs, 45 of the 68 accumulator tiles the MLP launch exchanges and writes at its end -- moves over as a role
+// of that launch (kernels_mlpwg.hpp WG0 = false, kernels.hpp WG_KIND_DENSE0_FRAG).  Knobs::mlp_wg0 = 1: never, 0: whenever possible.
+bool dense0_rides(const v2x_model* m, const BatchPlan& p) {
+  const int env = m->knobs.mlp_wg0;
+  if (env == 1 || !p.mlp_wg || m->F != 64 || m->cfg.variable_graphs || !p.embed_rides) return false;
+  if (p.x.n_idx % 16) return false;                              // whole 16-row groups (the fragment-major reader)
+  if (env == 0) return true;
+  // tiles per workgroup = 4 x tiles per wave.  Measured (profiles/r06_dense0_role_shares.txt): 512 / 1024 / 2048 graphs of 20 links
+  // (4 / 8 / 12 tiles per workgroup) 0.1201 -> 0.1131, 0.1512 -> 0.1463, 0.1929 -> 0.1880 ms per step; at 4096 (20-24 tiles) the chip
+  // is full either way and the heavier weight-gradient launch costs more than the MLP launch saves (0.2554 -> 0.2658)
+  return mlp_wg_split(p.x.n_idx, p.x.grid_y).tiles_per_wg <= m->knobs.mlp_wg0_tiles;
+}
 // Fragment-major hand-off between the fused graph-layer kernels and k_mlp_train_wg (MlpArgs::frag_groups): whole batch in
 // whole 16-graph groups, per-node weights (a tile of the MLP kernel is then a group of one node), at least one graph layer.
-bool dense0_rides(const v2x_model* m, const DevBatch& d, const IdxMap& x);
-bool frag_layout(const v2x_model* m, const DevBatch& d, Range r) {
+bool frag_layout(const v2x_model* m, const DevBatch& d, const BatchPlan& p) {
   // (Knobs::frag_with_dense0_role = 0: row-major hand-over where Dense-0's weight gradient is a role of k_wgrad -- measured slower: the
   //  fragment-major reader of that role costs nothing next to what the MLP launch and the fused kernels gain from 1 KiB accesses,
   //  0.1131 against 0.1157 ms at the 512-graph share)
   const int on = m->knobs.frag_handoff, frag_d0 = m->knobs.frag_with_dense0_role;
-  return on && fused_path(m, d) && r.g0 == 0 && r.ng == d.B && mlp_wg_path(m) && m->S == m->N && m->L >= 1 &&
-         d.B % FZ_TG == 0 && (frag_d0 || !dense0_rides(m, d, idx_map(m, d, r)));
+  return on && p.form == GraphLayers::Fused && p.mlp_wg && m->S == m->N && m->L >= 1 && d.B % FZ_TG == 0 && (frag_d0 || !p.dense0_rides);
 }
 
-int launch_fused_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, bool frag_out = false) {
-  const int split_fwd = m->knobs.fused_split_fwd;                      // (debugging: one direction on whole tiles)
+BatchPlan plan_batch(const v2x_model* m, const DevBatch& d) {
+  const Knobs& kn = m->knobs;
+  BatchPlan p;
+  p.x = idx_map(m, d);
+  p.mlp_wg = mlp_wg_path(m);
+  p.small_predict = small_path(m, d);
+  p.form = fused_path(m, d) ? GraphLayers::Fused : (ragged_fused_path(m, d) ? GraphLayers::Ragged : GraphLayers::Layerwise);
+  p.tiles = (d.B + FZ_TG - 1) / FZ_TG;
+  if (p.form == GraphLayers::Fused) {
+    p.split = fused_split(m, d);
+    p.split_fwd = p.split > 1 && kn.fused_split_fwd;      // (debugging: one direction on whole tiles)
+    p.split_bwd = p.split > 1 && kn.fused_split_bwd;
+    // (a batch the split-tile kernels are picked for runs the edge form in BOTH directions, also when a debugging switch keeps one
+    //  of them on whole tiles: the two kernels hand the rows' IN-neighbour sets over, the complement form would read them as
+    //  non-neighbour sets)
+    p.compl_sums = p.split <= 1 && fused_compl(m, d);
+    p.fused_lds_fwd = p.split_fwd ? fused_lds(m, d, false, false) + (size_t)m->N * m->F * 4 : fused_lds(m, d, false, p.compl_sums);
+    p.fused_lds_bwd = fused_lds(m, d, true, p.compl_sums);
+  }
+  if (p.form == GraphLayers::Ragged) {
+    p.ragged_small = ragged_small(m, d);
+    p.ragged_bwd = kn.ragged_fused_bwd;
+    p.cap = p.ragged_small ? RGS_CAP : RG_CAP;
+    p.capp = p.cap - d.max_nodes + 1;
+    p.wgs = (d.R + p.capp - 1) / p.capp;
+    // k_ragged_plan's tables in LDS; past that (tens of thousands of graphs in one batch) the interval plan of k_adj_masks
+    p.plan_words = 3 * (d.B + 1) + p.wgs + 1;
+    const bool packed = kn.ragged_packed && p.plan_words <= RG_PLAN_LDS_WORDS;
+    // the packed plan by workgroup 0 of the mask launch while its offsets + 16-bit tables leave the mask workgroups their
+    // eight per CU (<= 19 KB of LDS: ~2,200 graphs); a launch of its own (k_ragged_plan, 32-bit tables) beyond
+    const bool folded = packed && kn.ragged_plan_fold && d.B < 65000 && plan16_bytes(d.B, p.wgs) <= 19 * 1024;
+    p.plan_form = folded ? RaggedPlan::Folded : (packed ? RaggedPlan::Packed : RaggedPlan::Interval);
+  }
+  p.dense_agg = use_dense_agg(kn, d, m->F);
+  p.need_adj_masks = p.dense_agg || p.form == GraphLayers::Ragged;
+  p.embed_rides = embed_rides(m, d);
+  p.dense0_rides = dense0_rides(m, p);
+  p.frag_ok = frag_layout(m, d, p);
+  p.wide_merge = is_wide(m) && kn.wide_merge && m->L + 2 <= WWM_ROLES;
+  // Adam in the weight-gradient epilogues (single-GPU fit step of a wide model): needs the merged launch and ONE row split
+  // for every layer it covers (gnn[1..L], dense[0]) -- true as soon as K tiles x slots fill the chip (per-node weights)
+  const int kt = 2 * ((m->F + 127) / 128);                    // [h | agg] K tiles ([x | e] folded or one more: more tiles = fewer splits)
+  p.wide_adam_fusable = kn.wide_adam && p.wide_merge && !m->prof_no_fuse && m->adam_scal && wide_splits(p.x.n_idx, kt, p.x.grid_y) == 1;
+  return p;
+}
+
+// ------------------------------------------------------------------------------------ fused graph layers: the launches
+struct FusedFwd { using Args = FusedFwdArgs; static constexpr bool bwd = false; static constexpr const char* name = "k_gnn_fwd_fused"; };
+struct FusedBwd { using Args = FusedBwdArgs; static constexpr bool bwd = true; static constexpr const char* name = "k_gnn_bwd_fused"; };
+
+// whole tiles: (F, slots per wave, time stamps, complement form)
+template <typename D, int F, int SPW, bool TS, bool COMPL>
+int launch_fused_tiles_k(v2x_model* m, hipStream_t st, dim3 grid, size_t lds, const typename D::Args& a) {
+  if constexpr (D::bwd) LAUNCH(m, D::name, (k_gnn_bwd_fused<F, SPW, TS, COMPL>), grid, FZ_THREADS, lds, st, a);
+  else LAUNCH(m, D::name, (k_gnn_fwd_fused<F, SPW, TS, COMPL>), grid, FZ_THREADS, lds, st, a);
+  return V2X_OK;
+}
+// split tiles: (F, L, time stamps); recorded by the profiler under the whole-tile kernel's name
+template <typename D, int F, int L, bool TS>
+int launch_fused_split_k(v2x_model* m, hipStream_t st, dim3 grid, size_t lds, const typename D::Args& a, const FzXchg& xg) {
+  if constexpr (D::bwd) LAUNCH(m, D::name, (k_gnn_bwd_split<F, L, TS>), grid, FZ_THREADS, lds, st, a, xg);
+  else LAUNCH(m, D::name, (k_gnn_fwd_split<F, L, TS>), grid, FZ_THREADS, lds, st, a, xg);
+  return V2X_OK;
+}
+
+// one direction of the fused graph layers, `a` filled in but for ts and compl_sums
+template <typename D>
+int launch_fused(v2x_model* m, hipStream_t st, const BatchPlan& p, typename D::Args& a) {
+  const size_t lds = D::bwd ? p.fused_lds_bwd : p.fused_lds_fwd;
+  if (D::bwd ? p.split_bwd : p.split_fwd) {                             // the shares of the global batch: K workgroups per tile
+    CHK(ensure_xchg(m, p.tiles));
+    const FzXchg xg = xchg_args(m, p.split);
+    a.ts = m->ts_buf;
+    const dim3 grid((p.tiles + 7) / 8 * 8 * p.split);
+    const int rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return with_const<1, 2, 3>(m->L, [&](auto Lc) {
+      constexpr int F = decltype(Fc)::value, L = decltype(Lc)::value;
+      if constexpr (F == 64 && L == 2) {                                // (the time-stamp form exists for this shape only)
+        if (m->ts_buf) return launch_fused_split_k<D, 64, 2, true>(m, st, grid, lds, a, xg);
+      }
+      return launch_fused_split_k<D, F, L, false>(m, st, grid, lds, a, xg);
+    }); });
+    if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "split fused %s: unsupported shape", D::bwd ? "backward" : "forward");
+    return rc;
+  }
+  a.compl_sums = p.compl_sums ? 1 : 0;
+  const dim3 grid(p.tiles);
+  const int rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return with_const<1, 2, 3, 4>((m->N + FZ_WAVES - 1) / FZ_WAVES, [&](auto Sc) {
+    constexpr int F = decltype(Fc)::value, SPW = decltype(Sc)::value;
+    if constexpr (F == 64 && SPW == 3) {                                // (the time-stamp forms exist for this shape only)
+      if (m->ts_buf) {
+        a.ts = m->ts_buf;
+        return p.compl_sums ? launch_fused_tiles_k<D, 64, 3, true, true>(m, st, grid, lds, a) : launch_fused_tiles_k<D, 64, 3, true, false>(m, st, grid, lds, a);
+      }
+    }
+    return p.compl_sums ? launch_fused_tiles_k<D, F, SPW, false, true>(m, st, grid, lds, a) : launch_fused_tiles_k<D, F, SPW, false, false>(m, st, grid, lds, a);
+  }); });
+  if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "fused %s: unsupported shape", D::bwd ? "backward" : "forward");
+  return rc;
+}
+
+int launch_fused_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, bool frag_out) {
   // The copy follows the parameters by itself: Adam writes both (k_reduce_adam / pack_scatter), set / copy_weights
   // re-pack eagerly.  Only a caller that took the raw parameter pointer (v2x_param_ptr) forces a re-pack per forward.
   if (m->pk_stale) { CHK(launch_pack(m, st)); m->pk_stale = m->raw_params; }
@@ -1496,53 +1638,10 @@ int launch_fused_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, bool frag_
   a.n_graphs = d.B; a.N = m->N; a.L = m->L; a.S = m->S; a.edges_cap = FZ_TG * d.max_edges; a.n_edges = d.E; a.err = m->flag_dev;
   a.frag_out = frag_out ? 1 : 0;
   a.nbmask = m->nbmask;
-  const int tiles = (d.B + FZ_TG - 1) / FZ_TG;
-  if (const int K = fused_split(m, d); K > 1 && split_fwd) {            // the shares of the global batch: K workgroups per tile
-    CHK(ensure_xchg(m, tiles));
-    const FzXchg xg = xchg_args(m, K);
-    a.ts = m->ts_buf;
-    const dim3 grid((tiles + 7) / 8 * 8 * K);
-    const size_t lds = fused_lds(m, d, false, false) + (size_t)m->N * m->F * 4;
-    ProfRec r;
-    const bool pr = m->prof && !m->capturing;
-    if (pr) { r.id = prof_id(m, "k_gnn_fwd_fused"); hipEventCreate(&r.ev0); hipEventCreate(&r.ev1); hipEventRecord(r.ev0, st); }
-    int rc = V2X_EINVAL;
-    do {
-      if (m->ts_buf && m->F == 64 && m->L == 2) { hipLaunchKernelGGL((k_gnn_fwd_split<64, 2, true>), grid, dim3(FZ_THREADS), lds, st, a, xg); rc = launch_check(m, "k_gnn_fwd_split"); break; }
-#define V2X_FZ_FWDS(FF, LL) if (m->F == FF && m->L == LL) { hipLaunchKernelGGL((k_gnn_fwd_split<FF, LL>), grid, dim3(FZ_THREADS), lds, st, a, xg); rc = launch_check(m, "k_gnn_fwd_split"); break; }
-      V2X_FZ_FWDS(16, 1) V2X_FZ_FWDS(16, 2) V2X_FZ_FWDS(16, 3) V2X_FZ_FWDS(32, 1) V2X_FZ_FWDS(32, 2) V2X_FZ_FWDS(32, 3) V2X_FZ_FWDS(64, 1) V2X_FZ_FWDS(64, 2) V2X_FZ_FWDS(64, 3)
-#undef V2X_FZ_FWDS
-    } while (0);
-    if (pr) { hipEventRecord(r.ev1, st); m->prof_recs.push_back(r); }
-    if (rc == V2X_EINVAL && m->err.empty()) FAIL(m, V2X_EINVAL, "split fused forward: unsupported shape");
-    return rc;
-  }
-  const dim3 grid(tiles);
-  // (a batch the split-tile kernels are picked for runs the edge form in BOTH directions, also when a debugging switch keeps one
-  //  of them on whole tiles: the two kernels hand the rows' IN-neighbour sets over, the complement form would read them as
-  //  non-neighbour sets)
-  a.compl_sums = (fused_split(m, d) <= 1 && fused_compl(m, d)) ? 1 : 0;
-  const size_t lds = fused_lds(m, d, false, a.compl_sums != 0);
-  const int spw = (m->N + FZ_WAVES - 1) / FZ_WAVES;
-#define V2X_FZ_FWD(FF, SP)                                                                                            \
-  if (m->F == FF && spw == SP) {                                                                                      \
-    if (FF == 64 && SP == 3 && m->ts_buf) {                                                                          \
-      a.ts = m->ts_buf;                                                                                               \
-      if (a.compl_sums) { auto k = k_gnn_fwd_fused<64, 3, true, true>; LAUNCH_T(m, "k_gnn_fwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-      else { auto k = k_gnn_fwd_fused<64, 3, true>; LAUNCH_T(m, "k_gnn_fwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-    } else if (a.compl_sums) { auto k = k_gnn_fwd_fused<FF, SP, false, true>; LAUNCH_T(m, "k_gnn_fwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-    else { auto k = k_gnn_fwd_fused<FF, SP>; LAUNCH_T(m, "k_gnn_fwd_fused", k, grid, FZ_THREADS, lds, st, a); }        \
-    return V2X_OK;                                                                                                    \
-  }
-  V2X_FZ_FWD(16, 1) V2X_FZ_FWD(16, 2) V2X_FZ_FWD(16, 3) V2X_FZ_FWD(16, 4)
-  V2X_FZ_FWD(32, 1) V2X_FZ_FWD(32, 2) V2X_FZ_FWD(32, 3) V2X_FZ_FWD(32, 4)
-  V2X_FZ_FWD(64, 1) V2X_FZ_FWD(64, 2) V2X_FZ_FWD(64, 3) V2X_FZ_FWD(64, 4)
-#undef V2X_FZ_FWD
-  FAIL(m, V2X_EINVAL, "fused forward: unsupported shape");
+  return launch_fused<FusedFwd>(m, st, p, a);
 }
 
-int launch_fused_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
-  const int split_bwd = m->knobs.fused_split_bwd;                      // (debugging: one direction on whole tiles)
+int launch_fused_bwd(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p) {
   FusedBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.row_ptr = d.rp; a.col_idx = d.ci; a.pk = m->pk_bwd; a.gha = m->gha;
@@ -1551,60 +1650,11 @@ int launch_fused_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
   a.n_graphs = d.B; a.N = m->N; a.L = m->L; a.S = m->S; a.edges_cap = FZ_TG * d.max_edges; a.n_edges = d.E; a.err = m->flag_dev;
   a.frag_gha = m->frag_live ? 1 : 0;
   a.nbmask = m->nbmask;
-  const int tiles = (d.B + FZ_TG - 1) / FZ_TG;
-  if (const int K = fused_split(m, d); K > 1 && split_bwd) {
-    CHK(ensure_xchg(m, tiles));
-    const FzXchg xg = xchg_args(m, K);
-    a.ts = m->ts_buf;
-    const dim3 grid((tiles + 7) / 8 * 8 * K);
-    const size_t lds = fused_lds(m, d, true, false);
-    ProfRec r;
-    const bool pr = m->prof && !m->capturing;
-    if (pr) { r.id = prof_id(m, "k_gnn_bwd_fused"); hipEventCreate(&r.ev0); hipEventCreate(&r.ev1); hipEventRecord(r.ev0, st); }
-    int rc = V2X_EINVAL;
-    do {
-      if (m->ts_buf && m->F == 64 && m->L == 2) { hipLaunchKernelGGL((k_gnn_bwd_split<64, 2, true>), grid, dim3(FZ_THREADS), lds, st, a, xg); rc = launch_check(m, "k_gnn_bwd_split"); break; }
-#define V2X_FZ_BWDS(FF, LL) if (m->F == FF && m->L == LL) { hipLaunchKernelGGL((k_gnn_bwd_split<FF, LL>), grid, dim3(FZ_THREADS), lds, st, a, xg); rc = launch_check(m, "k_gnn_bwd_split"); break; }
-      V2X_FZ_BWDS(16, 1) V2X_FZ_BWDS(16, 2) V2X_FZ_BWDS(16, 3) V2X_FZ_BWDS(32, 1) V2X_FZ_BWDS(32, 2) V2X_FZ_BWDS(32, 3) V2X_FZ_BWDS(64, 1) V2X_FZ_BWDS(64, 2) V2X_FZ_BWDS(64, 3)
-#undef V2X_FZ_BWDS
-    } while (0);
-    if (pr) { hipEventRecord(r.ev1, st); m->prof_recs.push_back(r); }
-    if (rc == V2X_EINVAL && m->err.empty()) FAIL(m, V2X_EINVAL, "split fused backward: unsupported shape");
-    return rc;
-  }
-  const dim3 grid(tiles);
-  // (a batch the split-tile kernels are picked for runs the edge form in BOTH directions, also when a debugging switch keeps one
-  //  of them on whole tiles: the two kernels hand the rows' IN-neighbour sets over, the complement form would read them as
-  //  non-neighbour sets)
-  a.compl_sums = (fused_split(m, d) <= 1 && fused_compl(m, d)) ? 1 : 0;
-  const size_t lds = fused_lds(m, d, true, a.compl_sums != 0);
-  const int spw = (m->N + FZ_WAVES - 1) / FZ_WAVES;
-#define V2X_FZ_BWD(FF, SP)                                                                                            \
-  if (m->F == FF && spw == SP) {                                                                                      \
-    if (FF == 64 && SP == 3 && m->ts_buf) {                                                                          \
-      a.ts = m->ts_buf;                                                                                               \
-      if (a.compl_sums) { auto k = k_gnn_bwd_fused<64, 3, true, true>; LAUNCH_T(m, "k_gnn_bwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-      else { auto k = k_gnn_bwd_fused<64, 3, true>; LAUNCH_T(m, "k_gnn_bwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-    } else if (a.compl_sums) { auto k = k_gnn_bwd_fused<FF, SP, false, true>; LAUNCH_T(m, "k_gnn_bwd_fused", k, grid, FZ_THREADS, lds, st, a); } \
-    else { auto k = k_gnn_bwd_fused<FF, SP>; LAUNCH_T(m, "k_gnn_bwd_fused", k, grid, FZ_THREADS, lds, st, a); }        \
-    return V2X_OK;                                                                                                    \
-  }
-  V2X_FZ_BWD(16, 1) V2X_FZ_BWD(16, 2) V2X_FZ_BWD(16, 3) V2X_FZ_BWD(16, 4)
-  V2X_FZ_BWD(32, 1) V2X_FZ_BWD(32, 2) V2X_FZ_BWD(32, 3) V2X_FZ_BWD(32, 4)
-  V2X_FZ_BWD(64, 1) V2X_FZ_BWD(64, 2) V2X_FZ_BWD(64, 3) V2X_FZ_BWD(64, 4)
-#undef V2X_FZ_BWD
-  FAIL(m, V2X_EINVAL, "fused backward: unsupported shape");
+  return launch_fused<FusedBwd>(m, st, p, a);
 }
 
 // ------------------------------------------------------------------------------------ passes
 // ------------------------------------------------------------------------------------ few-graph predict, one launch
-constexpr int SMALL_ROWS = 256;             // node rows (= workgroups) of one launch: all co-resident on any gfx950 part
-bool small_path(const v2x_model* m, const DevBatch& d) {
-  if (!m->knobs.small_predict || !m->small_h || m->cfg.variable_graphs || d.goff || d.nbr || m->F > 64 || m->L > FZ_MAXL) return false;
-  if (m->N > 32) return false;                 // the kernel keeps a node's in-neighbours in a 32-entry LDS list
-  return d.max_nodes == m->N && d.R <= std::min(SMALL_ROWS, n_cus());
-}
-
 constexpr size_t PIN_XE = 0, PIN_RP = 16384, PIN_CI = 20480, PIN_Q = 53248, PIN_BYTES = 65536;   // SMALL_ROWS rows, <= 31 in-edges each
 
 int launch_small_forward(v2x_model* m, hipStream_t st, const DevBatch& d, float* q_dst = nullptr) {
@@ -1616,47 +1666,20 @@ int launch_small_forward(v2x_model* m, hipStream_t st, const DevBatch& d, float*
   a.hbuf = m->small_h; a.sync = m->small_sync; a.err = m->flag_dev; a.q = q_dst ? q_dst : m->q;
   a.N = m->N; a.L = m->L; a.S = m->S; a.C = m->C; a.Dn = m->Dn; a.De = m->De; a.n_rows = d.R; a.slab_rows = SMALL_ROWS;
   const dim3 grid(m->N, d.B);
-#define V2X_SMALL(FF)                                                                                   \
-  if (m->F == FF) {                                                                                     \
-    auto k = k_predict_small<FF>;                                                                       \
-    LAUNCH_T(m, "k_predict_small", k, grid, SM_BLOCK, 0, st, a);                                        \
-    return V2X_OK;                                                                                      \
-  }
-  V2X_SMALL(16) V2X_SMALL(32) V2X_SMALL(64)
-#undef V2X_SMALL
-  FAIL(m, V2X_EINVAL, "small forward: unsupported feat_dim %d", m->F);
+  const int rc = with_const<16, 32, 64>(m->F, [&](auto Fc) -> int {
+    LAUNCH(m, "k_predict_small", k_predict_small<decltype(Fc)::value>, grid, SM_BLOCK, 0, st, a);
+    return V2X_OK;
+  });
+  if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "small forward: unsupported feat_dim %d", m->F);
+  return rc;
 }
-
-// ------------------------------------------------------------------------------------ ragged fused forward
-// (kernels_ragged.hpp) variable-size graphs of <= 128 nodes, shared weights, narrow features, dense enough for the bit masks
-bool ragged_fused_path(const v2x_model* m, const DevBatch& d) {
-  // (any density: a row's aggregation walks its mask's one bits or -- rows with more edges than non-edges in graphs of >= 16
-  //  nodes -- the zero bits; the masks are built for this path whether or not the dense MFMA aggregation wants them)
-  return m->knobs.ragged_fused && m->cfg.variable_graphs && m->S == 1 && d.goff && !d.nbr && m->F <= 64 && m->L <= FZ_MAXL && d.max_nodes <= 128 &&
-         d.max_nodes <= RG_CAP / 2;
-}
-bool need_adj_masks(const v2x_model* m, const DevBatch& d) { return use_dense_agg(m->knobs, d, m->F) || ragged_fused_path(m, d); }
-// Small tiles (kernels_ragged_small.hpp: 160-row tiles, 4-wave workgroups, weights as fragments from L2, three workgroups per
-// CU): built and measured in round 5 -- forward 123 us against 101, backward 161 against 103 at configs[4]'s share, + 19 us for
-// the plan as a launch of its own (profiles/r05_ragged_small_ab.txt) -- so OFF unless Knobs::ragged_small (read at create:
-// the fragment-major copy of a ragged model's weights is only kept then)
-bool ragged_small(const v2x_model* m, const DevBatch& d) {
-  return m->knobs.ragged_small && m->pk_fwd && m->pk_bwd && d.max_nodes <= 128 && m->L >= 1;
-}
-int ragged_cap(const v2x_model* m, const DevBatch& d) { return ragged_small(m, d) ? RGS_CAP : RG_CAP; }
-int ragged_capp(const v2x_model* m, const DevBatch& d) { return ragged_cap(m, d) - d.max_nodes + 1; }
-int ragged_wgs(const v2x_model* m, const DevBatch& d) { return (d.R + ragged_capp(m, d) - 1) / ragged_capp(m, d); }
-
-// k_ragged_plan's tables in LDS; past that (tens of thousands of graphs in one batch) the interval plan of k_adj_masks
-int ragged_plan_words(const v2x_model* m, const DevBatch& d) { return 3 * (d.B + 1) + ragged_wgs(m, d) + 1; }
-bool ragged_packed_plan(const v2x_model* m, const DevBatch& d) { return m->knobs.ragged_packed && ragged_plan_words(m, d) <= RG_PLAN_LDS_WORDS; }
 
 template <int F>
 int launch_ragged_fwd_f(v2x_model* m, hipStream_t st, const RaggedFwdArgs& a, int n_wgs) {
   auto k = k_gnn_fwd_ragged<F>;
   static const bool once = [] { allow_big_lds((const void*)k_gnn_fwd_ragged<F>); return true; }();
   (void)once;
-  LAUNCH_T(m, "k_gnn_fwd_ragged", k, dim3(n_wgs), RG_THREADS, (size_t)RaggedLds<F>::TOTAL * 4, st, a);
+  LAUNCH(m, "k_gnn_fwd_ragged", k, dim3(n_wgs), RG_THREADS, (size_t)RaggedLds<F>::TOTAL * 4, st, a);
   return V2X_OK;
 }
 
@@ -1664,15 +1687,15 @@ template <int F, bool BWD, typename Args>
 int launch_ragged_small_f(v2x_model* m, hipStream_t st, const Args& a, int n_wgs) {
   if constexpr (BWD) {
     auto k = k_gnn_bwd_ragged_s<F>;
-    LAUNCH_T(m, "k_gnn_bwd_ragged", k, dim3(n_wgs), RGS_THREADS, (size_t)RaggedSmallBwdLds<F>::TOTAL * 4, st, a);
+    LAUNCH(m, "k_gnn_bwd_ragged", k, dim3(n_wgs), RGS_THREADS, (size_t)RaggedSmallBwdLds<F>::TOTAL * 4, st, a);
   } else {
     auto k = k_gnn_fwd_ragged_s<F>;
-    LAUNCH_T(m, "k_gnn_fwd_ragged", k, dim3(n_wgs), RGS_THREADS, (size_t)RaggedSmallLds<F>::TOTAL * 4, st, a);
+    LAUNCH(m, "k_gnn_fwd_ragged", k, dim3(n_wgs), RGS_THREADS, (size_t)RaggedSmallLds<F>::TOTAL * 4, st, a);
   }
   return V2X_OK;
 }
 
-int launch_ragged_fwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
+int launch_ragged_fwd(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p) {
   RaggedFwdArgs a;
   memset(&a, 0, sizeof(a));
   a.xe = d.xe; a.graph_off = d.goff; a.row_ptr = d.rp;
@@ -1680,24 +1703,19 @@ int launch_ragged_fwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
   a.adjT = (const unsigned*)m->adj_mask.p + (size_t)d.R * a.mask_words;
   a.plan = (const int32_t*)m->plan_buf.p;
   for (int s = 0; s <= m->L; ++s) { a.W[s] = m->params + m->gnn[s].off; a.h[s] = m->h[s]; a.a[s] = m->a[s]; }
-  a.n_graphs = d.B; a.n_rows = d.R; a.L = m->L; a.capp = ragged_capp(m, d); a.xr = m->Dn + m->De; a.err = m->flag_dev;
+  a.n_graphs = d.B; a.n_rows = d.R; a.L = m->L; a.capp = p.capp; a.xr = m->Dn + m->De; a.err = m->flag_dev;
   a.ts = m->ts_buf;
-  const int n_wgs = ragged_wgs(m, d);
-  if (ragged_small(m, d)) {                             // 160-row tiles, weights as fragments from L2 (kernels_ragged_small.hpp)
+  const int n_wgs = p.wgs;
+  int rc;
+  if (p.ragged_small) {                                 // 160-row tiles, weights as fragments from L2 (kernels_ragged_small.hpp)
     if (m->pk_stale) { CHK(launch_pack(m, st)); m->pk_stale = m->raw_params; }
     RaggedSmallFwdArgs sa{a, m->pk_fwd};
-    switch (m->F) {
-      case 16: return launch_ragged_small_f<16, false>(m, st, sa, n_wgs);
-      case 32: return launch_ragged_small_f<32, false>(m, st, sa, n_wgs);
-      case 64: return launch_ragged_small_f<64, false>(m, st, sa, n_wgs);
-    }
+    rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return launch_ragged_small_f<decltype(Fc)::value, false>(m, st, sa, n_wgs); });
+  } else {
+    rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return launch_ragged_fwd_f<decltype(Fc)::value>(m, st, a, n_wgs); });
   }
-  switch (m->F) {
-    case 16: return launch_ragged_fwd_f<16>(m, st, a, n_wgs);
-    case 32: return launch_ragged_fwd_f<32>(m, st, a, n_wgs);
-    case 64: return launch_ragged_fwd_f<64>(m, st, a, n_wgs);
-  }
-  FAIL(m, V2X_EINVAL, "ragged forward: unsupported feat_dim %d", m->F);
+  if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "ragged forward: unsupported feat_dim %d", m->F);
+  return rc;
 }
 
 template <int F>
@@ -1705,12 +1723,12 @@ int launch_ragged_bwd_f(v2x_model* m, hipStream_t st, const RaggedBwdArgs& a, in
   auto k = k_gnn_bwd_ragged<F>;
   static const bool once = [] { allow_big_lds((const void*)k_gnn_bwd_ragged<F>); return true; }();
   (void)once;
-  LAUNCH_T(m, "k_gnn_bwd_ragged", k, dim3(n_wgs), RG_THREADS, (size_t)RaggedBwdLds<F>::TOTAL * 4, st, a);
+  LAUNCH(m, "k_gnn_bwd_ragged", k, dim3(n_wgs), RG_THREADS, (size_t)RaggedBwdLds<F>::TOTAL * 4, st, a);
   return V2X_OK;
 }
 
 // L + 1 transposed aggregations + L data gradients of ragged graphs in one launch (masks and plan: the forward's)
-int launch_ragged_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
+int launch_ragged_bwd(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p) {
   RaggedBwdArgs a;
   memset(&a, 0, sizeof(a));
   a.gha = m->gha; a.graph_off = d.goff;
@@ -1718,72 +1736,61 @@ int launch_ragged_bwd(v2x_model* m, hipStream_t st, const DevBatch& d) {
   a.adj = (const unsigned*)m->adj_mask.p;
   a.plan = (const int32_t*)m->plan_buf.p;
   for (int s = 0; s <= m->L; ++s) { a.W[s] = m->params + m->gnn[s].off; a.h[s] = m->h[s]; a.dpre[s] = m->dpre[s]; }
-  a.n_graphs = d.B; a.n_rows = d.R; a.L = m->L; a.capp = ragged_capp(m, d); a.xr = m->Dn + m->De; a.err = m->flag_dev;
-  const int n_wgs = ragged_wgs(m, d);
-  if (ragged_small(m, d)) {
+  a.n_graphs = d.B; a.n_rows = d.R; a.L = m->L; a.capp = p.capp; a.xr = m->Dn + m->De; a.err = m->flag_dev;
+  const int n_wgs = p.wgs;
+  int rc;
+  if (p.ragged_small) {
     RaggedSmallBwdArgs sa{a, m->pk_bwd};
-    switch (m->F) {
-      case 16: return launch_ragged_small_f<16, true>(m, st, sa, n_wgs);
-      case 32: return launch_ragged_small_f<32, true>(m, st, sa, n_wgs);
-      case 64: return launch_ragged_small_f<64, true>(m, st, sa, n_wgs);
-    }
+    rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return launch_ragged_small_f<decltype(Fc)::value, true>(m, st, sa, n_wgs); });
+  } else {
+    rc = with_const<16, 32, 64>(m->F, [&](auto Fc) { return launch_ragged_bwd_f<decltype(Fc)::value>(m, st, a, n_wgs); });
   }
-  switch (m->F) {
-    case 16: return launch_ragged_bwd_f<16>(m, st, a, n_wgs);
-    case 32: return launch_ragged_bwd_f<32>(m, st, a, n_wgs);
-    case 64: return launch_ragged_bwd_f<64>(m, st, a, n_wgs);
-  }
-  FAIL(m, V2X_EINVAL, "ragged backward: unsupported feat_dim %d", m->F);
+  if (rc == V2X_EINVAL) FAIL(m, V2X_EINVAL, "ragged backward: unsupported feat_dim %d", m->F);
+  return rc;
 }
 
-int run_forward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, bool with_mlp = true) {
+int run_forward(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, bool with_mlp = true) {
   const int F = m->F, L = m->L;
-  const IdxMap x = idx_map(m, d, r);
-  m->frag_live = !with_mlp && frag_layout(m, d, r);
-  const bool ragged = ragged_fused_path(m, d) && r.g0 == 0 && r.ng == d.B;
-  if (fused_path(m, d) && r.g0 == 0 && r.ng == d.B) {
-    CHK(launch_fused_fwd(m, st, d, m->frag_live));       // embed + L stages + L+1 aggregations: one launch
+  const IdxMap& x = p.x;
+  const bool ragged = p.form == GraphLayers::Ragged;
+  m->frag_live = !with_mlp && p.frag_ok;
+  if (p.form == GraphLayers::Fused) {
+    CHK(launch_fused_fwd(m, st, d, p, m->frag_live));    // embed + L stages + L+1 aggregations: one launch
   } else {
-    if (need_adj_masks(m, d)) {
-      AggDenseArgs q = agg_dense_args(d, r, m->N, F);
+    if (p.need_adj_masks) {
+      AggDenseArgs q = agg_dense_args(d, m->N, F);
       q.adj = (unsigned*)m->adj_mask.p;
       q.adjT = q.adj + (size_t)d.R * q.mask_words;
       q.err = m->flag_dev;
-      const bool packed = ragged && ragged_packed_plan(m, d);
-      if (ragged) m->plan_len = ragged_wgs(m, d) + 1;
-      if (ragged && !packed) { q.plan = (int32_t*)m->plan_buf.p; q.plan_capp = ragged_capp(m, d); q.plan_n = ragged_wgs(m, d); }
-      // the packed plan by workgroup 0 of the mask launch while its offsets + 16-bit tables leave the mask workgroups their
-      // eight per CU (<= 19 KB of LDS: ~2,200 graphs); a launch of its own (k_ragged_plan, 32-bit tables) beyond
-      const bool folded = packed && m->knobs.ragged_plan_fold && d.B < 65000 && plan16_bytes(d.B, ragged_wgs(m, d)) <= 19 * 1024;
-      if (folded) { q.plan = (int32_t*)m->plan_buf.p; q.plan_cap = ragged_cap(m, d); q.plan_n = ragged_wgs(m, d); }
+      if (ragged) m->plan_len = p.wgs + 1;
+      if (ragged && p.plan_form == RaggedPlan::Interval) { q.plan = (int32_t*)m->plan_buf.p; q.plan_capp = p.capp; q.plan_n = p.wgs; }
+      if (ragged && p.plan_form == RaggedPlan::Folded) { q.plan = (int32_t*)m->plan_buf.p; q.plan_cap = p.cap; q.plan_n = p.wgs; }
       // (the plan reads the offsets, the masks the CSR: independent -- but as a forked branch of the captured step the two
       //  cost MORE than one after the other: 0.466 against 0.455 ms per configs[4] step, the graph's cross-branch
       //  dependencies outweigh the 5 us the plan takes)
-      if (packed && !folded) {
+      if (ragged && p.plan_form == RaggedPlan::Packed) {
         static const bool once = [] { allow_big_lds((const void*)k_ragged_plan); return true; }();
         (void)once;
-        RaggedPlanArgs pa{d.goff, (int32_t*)m->plan_buf.p, d.B, ragged_wgs(m, d), ragged_cap(m, d)};
-        LAUNCH_T(m, "k_ragged_plan", k_ragged_plan, dim3(1), RG_PLAN_THREADS, (size_t)ragged_plan_words(m, d) * 4, st, pa);
+        RaggedPlanArgs pa{d.goff, (int32_t*)m->plan_buf.p, d.B, p.wgs, p.cap};
+        LAUNCH(m, "k_ragged_plan", k_ragged_plan, dim3(1), RG_PLAN_THREADS, (size_t)p.plan_words * 4, st, pa);
       }
       CHK(build_adj_masks(m, st, q));
     }
     if (ragged) {                                        // embed + L stages + L + 1 aggregations of ragged graphs: one launch
-      CHK(launch_ragged_fwd(m, st, d));
-      goto mlp;
-    }
-    CHK(launch_node_fwd(m, st, 0, x, d.xe, nullptr, d.nbr, m->h[0]));
-    CHK(launch_agg(m, st, d, r, m->N, F, m->h[0], F, nullptr, 0, nullptr, m->a[0], 0));
-    for (int s = 1; s <= L; ++s) {
-      CHK(launch_node_fwd(m, st, s, x, d.xe, m->h[s - 1], m->a[s - 1], m->h[s]));
-      CHK(launch_agg(m, st, d, r, m->N, F, m->h[s], F, nullptr, 0, nullptr, m->a[s], 0));
+      CHK(launch_ragged_fwd(m, st, d, p));
+    } else {
+      CHK(launch_node_fwd(m, st, 0, x, d.xe, nullptr, d.nbr, m->h[0]));
+      CHK(launch_agg(m, st, d, p.dense_agg, m->N, F, m->h[0], F, nullptr, 0, nullptr, m->a[0], 0));
+      for (int s = 1; s <= L; ++s) {
+        CHK(launch_node_fwd(m, st, s, x, d.xe, m->h[s - 1], m->a[s - 1], m->h[s]));
+        CHK(launch_agg(m, st, d, p.dense_agg, m->N, F, m->h[s], F, nullptr, 0, nullptr, m->a[s], 0));
+      }
     }
   }
-mlp:
   if (!with_mlp) return V2X_OK;          // training: the MLP runs fused with its backward (k_mlp_train_wg)
   MlpArgs a;
   mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
-  CHK(launch_mlp(m, st, a, false));
-  return V2X_OK;
+  return launch_mlp(m, st, a, false);
 }
 
 float loss_denominator(const v2x_model* m, int n_global) {
@@ -1792,56 +1799,52 @@ float loss_denominator(const v2x_model* m, int n_global) {
   return (float)((double)n_global * m->C);
 }
 
-// backward kernel chain of one range, after run_forward(with_mlp = wide): the decision MLP (a narrow model: forward + Huber +
-// backward + the Dense weight gradients in one launch), the graph layers' data chain, their weight gradients
-int run_backward(v2x_model* m, hipStream_t st, const DevBatch& d, Range r, const float* y_dev, int n_global) {
-  const int F = m->F, L = m->L;
-  const IdxMap x = idx_map(m, d, r);
+// The decision MLP of a backward pass, after run_forward(with_mlp = wide).  A narrow model: forward + Huber + backward + the Dense
+// weight gradients in one launch.  A wide model: k_mlp_bwd, Dense-0's data gradient, Dense 1..3 (+ Dense-0 unless merged below).
+int backward_mlp(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, const BwdCall& c, const float* y_dev, int n_global) {
+  const int L = m->L;
   MlpArgs a;
-  mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
+  mlp_args(m, a, p.x, d.xe, m->h[L], m->a[L]);
   a.y = y_dev;
   a.inv_denom = 1.0f / loss_denominator(m, n_global);
-  const bool mlp_wg = mlp_wg_path(m);      // narrow: the Dense weight gradients come out of the MLP launch itself
-  // wide path: every layer's weight gradient in ONE launch after the data chain -- unless somebody wants a layer's gradient
-  // as soon as it is final (per-layer all-reduce buckets of data parallelism: m->bucketed)
-  m->wide_merge_now = is_wide(m) && m->knobs.wide_merge && !m->bucketed && m->L + 2 <= WWM_ROLES;
-  struct MergeGuard { v2x_model* m; ~MergeGuard() { m->wide_merge_now = false; } } merge_guard{m};
-  if (m->frag_live && !frag_layout(m, d, r)) FAIL(m, V2X_ESTATE, "backward: the saved forward is fragment-major, this backward cannot read it");
+  if (m->frag_live && !p.frag_ok) FAIL(m, V2X_ESTATE, "backward: the saved forward is fragment-major, this backward cannot read it");
   a.frag_groups = m->frag_live ? d.B / FZ_TG : 0;
-  if (m->dqn_tq) {
-    if (!mlp_wg) FAIL(m, V2X_ESTATE, "backward: in-kernel DQN targets need the k_mlp_train_wg path");
-    a.tq = m->dqn_tq; a.y = m->dqn_tq; a.q = m->dqn_y;
+  if (c.tq) {
+    if (!p.mlp_wg) FAIL(m, V2X_ESTATE, "backward: in-kernel DQN targets need the k_mlp_train_wg path");
+    a.tq = c.tq; a.y = c.tq; a.q = c.y_out;
   }
-  m->dense0_out_now = mlp_wg && r.g0 == 0 && r.ng == d.B && dense0_rides(m, d, x);
-  struct D0Guard { v2x_model* m; ~D0Guard() { m->dense0_out_now = false; } } d0_guard{m};
-  if (mlp_wg) CHK(launch_mlp_train_wg(m, st, a, !m->dense0_out_now));
-  else {
-    CHK(launch_mlp(m, st, a, true));
-    CHK(wgrad_mlp(m, st, x, d.xe, m->h[L], m->a[L]));        // Dense-0 (unless merged below) + Dense 1..3
-  }
-  const bool fused = fused_path(m, d) && r.g0 == 0 && r.ng == d.B;
-  const bool ragged_bwd = m->knobs.ragged_fused_bwd;
-  if (fused) {
-    CHK(launch_fused_bwd(m, st, d));       // L+1 transposed aggregations + L data gradients: one launch
-  } else if (ragged_bwd && ragged_fused_path(m, d) && r.g0 == 0 && r.ng == d.B) {
-    CHK(launch_ragged_bwd(m, st, d));      // the same for ragged graphs (masks and plan from this step's forward)
+  if (p.mlp_wg) return launch_mlp_train_wg(m, st, a, !dense0_out(p, c));      // the Dense weight gradients come out of the MLP launch itself
+  CHK(launch_mlp(m, st, a, true));
+  return wgrad_mlp(m, st, p.x, d.xe, m->h[L], m->a[L], wide_merged(p, c));
+}
+
+// The graph layers of a backward pass: their data chain, then all L + 1 weight gradients (+ what rides on them): one launch up to L = 7.
+int backward_graph_layers(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, const BwdCall& c) {
+  const int F = m->F, L = m->L;
+  if (p.form == GraphLayers::Fused) {
+    CHK(launch_fused_bwd(m, st, d, p));    // L+1 transposed aggregations + L data gradients: one launch
+  } else if (ragged_fused_bwd(p, c)) {
+    CHK(launch_ragged_bwd(m, st, d, p));   // the same for ragged graphs (masks and plan from this step's forward)
   } else {
     for (int s = L; s >= 1; --s) {
       // dpre_s = (dh_direct + Agg^T(dagg)) * relu'(h_s)
-      CHK(launch_agg(m, st, d, r, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, s < L ? m->h[s] : nullptr, m->dpre[s], 1));
-      CHK(launch_dgrad(m, st, s, x, m->dpre[s], m->gha));
+      CHK(launch_agg(m, st, d, p.dense_agg, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, s < L ? m->h[s] : nullptr, m->dpre[s], 1));
+      CHK(launch_dgrad(m, st, s, p.x, m->dpre[s], m->gha));
     }
-    CHK(launch_agg(m, st, d, r, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, m->h[0], m->dpre[0], 1));
+    CHK(launch_agg(m, st, d, p.dense_agg, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, m->h[0], m->dpre[0], 1));
   }
-  return wgrad_gnn_all(m, st, x, d);       // all L + 1 graph layers (+ what rides on them): one launch up to L = 7
+  return wgrad_gnn_all(m, st, d, p, c);
 }
 
-// forward (+ backward) of the whole batch
-int run_step(v2x_model* m, hipStream_t st, const DevBatch& d, bool bwd, const float* y_dev, int n_global) {
-  const Range all{0, d.B};
-  CHK(run_forward(m, st, d, all, !(bwd && mlp_wg_path(m))));
-  if (bwd) CHK(run_backward(m, st, d, all, y_dev, n_global));
-  return V2X_OK;
+int run_backward(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, const BwdCall& c, const float* y_dev, int n_global) {
+  CHK(backward_mlp(m, st, d, p, c, y_dev, n_global));
+  return backward_graph_layers(m, st, d, p, c);
+}
+
+// forward + backward of the whole batch
+int run_step(v2x_model* m, hipStream_t st, const DevBatch& d, const BatchPlan& p, const BwdCall& c, const float* y_dev, int n_global) {
+  CHK(run_forward(m, st, d, p, !p.mlp_wg));
+  return run_backward(m, st, d, p, c, y_dev, n_global);
 }
 
 int resolve_y(v2x_model* m, const float* y, int y_on_device, int R, hipStream_t st, const float** out) {
@@ -1934,22 +1937,21 @@ int max_slabs(const v2x_model* m, int n_idx, int n_slots) {
   return nc + 1;
 }
 
-int presize(v2x_model* m, const DevBatch& d) {
+int presize(v2x_model* m, const DevBatch& d, const BatchPlan& p) {
   CHK(ensure_rows(m, d.R));
-  if (need_adj_masks(m, d)) CHK(ensure(m, m->adj_mask, (size_t)2 * d.R * ((d.max_nodes + 31) / 32) * 4));
-  if (ragged_fused_path(m, d)) CHK(ensure(m, m->plan_buf, (size_t)(ragged_wgs(m, d) + 2) * 4));
-  if (fused_split(m, d) > 1) CHK(ensure_xchg(m, (d.B + FZ_TG - 1) / FZ_TG));
-  const IdxMap x = idx_map(m, d, Range{0, d.B});
-  CHK(ensure_slabs(m, max_slabs(m, x.n_idx, x.grid_y)));
+  if (p.need_adj_masks) CHK(ensure(m, m->adj_mask, (size_t)2 * d.R * ((d.max_nodes + 31) / 32) * 4));
+  if (p.form == GraphLayers::Ragged) CHK(ensure(m, m->plan_buf, (size_t)(p.wgs + 2) * 4));
+  if (p.split > 1) CHK(ensure_xchg(m, p.tiles));
+  CHK(ensure_slabs(m, max_slabs(m, p.x.n_idx, p.x.grid_y)));
   return V2X_OK;
 }
 
-// helpers for the per-kernel entry points: the whole batch as one range
+// helpers for the per-kernel entry points, which take rows and no batch
 IdxMap idx_map_rows(const v2x_model* m, int n_rows) {
   DevBatch d;
   memset(&d, 0, sizeof(d));
   d.R = n_rows; d.B = m->cfg.variable_graphs ? 1 : n_rows / m->N;
-  return idx_map(m, d, Range{0, d.B});
+  return idx_map(m, d);
 }
 
 int presize_rows(v2x_model* m, int n_rows) {
@@ -1957,15 +1959,6 @@ int presize_rows(v2x_model* m, int n_rows) {
   const IdxMap x = idx_map_rows(m, n_rows);
   CHK(ensure_slabs(m, max_slabs(m, x.n_idx, x.grid_y)));
   return V2X_OK;
-}
-
-// Adam in the weight-gradient epilogues (single-GPU fit step of a wide model): needs the merged launch and ONE row split
-// for every layer it covers (gnn[1..L], dense[0]) -- true as soon as K tiles x slots fill the chip (per-node weights)
-bool wide_adam_fusable(const v2x_model* m, const DevBatch& d) {
-  if (!m->knobs.wide_adam || !m->knobs.wide_merge || !is_wide(m) || m->bucketed || m->prof_no_fuse || !m->adam_scal || m->L + 2 > WWM_ROLES) return false;
-  const IdxMap x = idx_map(m, d, Range{0, d.B});
-  const int kt = 2 * ((m->F + 127) / 128);                    // [h | agg] K tiles ([x | e] folded or one more: more tiles = fewer splits)
-  return wide_splits(x.n_idx, kt, x.grid_y) == 1;
 }
 
 }  // namespace
@@ -2178,7 +2171,7 @@ int v2x_forward(v2x_model* m, const v2x_batch* b, float* q_out, int q_on_device,
     memset(&hd, 0, sizeof(hd));
     hd.B = b->n_graphs; hd.R = b->n_rows; hd.E = b->n_edges; hd.max_nodes = b->max_nodes; hd.max_edges = b->max_edges;
     hd.goff = b->graph_off; hd.nbr = b->nbr_init;
-    if (hd.B > 0 && !m->cfg.variable_graphs && hd.R == hd.B * m->N && small_path(m, hd)) {
+    if (hd.B > 0 && !m->cfg.variable_graphs && hd.R == hd.B * m->N && plan_batch(m, hd).small_predict) {
       CHK(validate_host_batch(m, b, m->N));
       memcpy(m->pin_h + PIN_XE, b->xe, (size_t)hd.R * XE * sizeof(float));
       memcpy(m->pin_h + PIN_RP, b->row_ptr, (size_t)(hd.R + 1) * 4);
@@ -2197,11 +2190,12 @@ int v2x_forward(v2x_model* m, const v2x_batch* b, float* q_out, int q_on_device,
   }
   DevBatch d;
   CHK(resolve_batch(m, b, &d, st));
-  CHK(presize(m, d));
+  const BatchPlan p = plan_batch(m, d);
+  CHK(presize(m, d, p));
   // a few graphs (the rollout predict): the whole network in one launch, nothing saved for a backward pass
-  const bool small = small_path(m, d);
+  const bool small = p.small_predict;
   if (small) CHK(run_maybe_graph(m, st, make_key(7, d, nullptr, 0), [&]() { return launch_small_forward(m, st, d); }));
-  else CHK(run_maybe_graph(m, st, make_key(1, d, nullptr, 0), [&]() { return run_step(m, st, d, false, nullptr, 0); }));
+  else CHK(run_maybe_graph(m, st, make_key(1, d, nullptr, 0), [&]() { return run_forward(m, st, d, p); }));
   m->have_fwd = !small;
   const size_t qb = (size_t)d.R * m->C * sizeof(float);
   if (q_on_device) {
@@ -2224,25 +2218,25 @@ static int fwd_bwd(v2x_model* m, const v2x_batch* b, const float* y, int y_on_de
   if (n_global <= 0) n_global = m->cfg.variable_graphs ? d.R : d.B;
   const float* yd;
   CHK(resolve_y(m, y, y_on_device, d.R, st, &yd));
-  CHK(presize(m, d));
+  const BatchPlan p = plan_batch(m, d);
+  CHK(presize(m, d, p));
   if (with_adam) {
     // lr_t depends on the iteration count, so the Adam node stays outside the replayed graph.  Wide path: Adam rides on the
     // weight-gradient launch for the layers that launch writes in place; this step's lr_t reaches the (replayed) kernels
     // through device memory, written by a one-thread launch whose ARGUMENTS carry the values (copied when the launch is
     // enqueued: no asynchronous read of host stack memory, no host / stream synchronisation -- ADVICE r04)
-    const bool fuse = wide_adam_fusable(m, d);
+    const bool fuse = p.wide_adam_fusable;
     if (fuse) {
       hipLaunchKernelGGL(k_set4, dim3(1), dim3(64), 0, st, m->adam_scal, adam_lr_t(m, m->iterations + 1), m->cfg.beta1, m->cfg.beta2, m->cfg.eps);
       CHK(launch_check(m, "k_set4"));
     }
-    m->fuse_adam_now = fuse;
-    const int rc = run_maybe_graph(m, st, make_key(fuse ? 9 : 2, d, yd, n_global), [&]() { return run_step(m, st, d, true, yd, n_global); });
-    m->fuse_adam_now = false;
-    CHK(rc);
+    BwdCall c;
+    c.fuse_adam = fuse;
+    CHK(run_maybe_graph(m, st, make_key(fuse ? 9 : 2, d, yd, n_global), [&]() { return run_step(m, st, d, p, c, yd, n_global); }));
     CHK(launch_reduce_adam(m, st, 1, true, nullptr, loss_job(m, d, n_global), -1, fuse));
   } else {
     CHK(run_maybe_graph(m, st, make_key(3, d, yd, n_global), [&]() {
-      CHK(run_step(m, st, d, true, yd, n_global));
+      CHK(run_step(m, st, d, p, BwdCall{}, yd, n_global));
       return launch_reduce_adam(m, st, 1, false, nullptr, loss_job(m, d, n_global));
     }));
   }
@@ -2265,52 +2259,43 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
   if (n_global <= 0) n_global = m->cfg.variable_graphs ? d.R : d.B;
   const float* yd;
   CHK(resolve_y(m, y, y_on_device, d.R, st, &yd));
-  CHK(presize(m, d));
-  const Range all{0, d.B};
-  const IdxMap x = idx_map(m, d, all);
+  const BatchPlan p = plan_batch(m, d);
+  CHK(presize(m, d, p));
+  const IdxMap& x = p.x;
   const int F = m->F, L = m->L;
   if (is_wide(m)) {
     // one weight-gradient launch per layer: phase 0 = forward, decision MLP backward, the Dense layers' gradients; phase k =
     // the data gradient handed down by stage s + 1 (not before: the all-reduce of the bucket a phase completes starts when the
     // phase's LAST launch is done), the transposed aggregation and the weight gradient of stage s = L + 1 - k
     if (phase > 0 && !m->have_fwd) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase %d before phase 0", phase);
-    m->bucketed = true;
-    const int rc = run_maybe_graph(m, st, make_key(20 + phase, d, yd, n_global), [&]() -> int {
+    BwdCall c;
+    c.bucketed = c.phased = true;
+    CHK(run_maybe_graph(m, st, make_key(20 + phase, d, yd, n_global), [&]() -> int {
       int64_t rb, re;
       phase_bucket_range(m, phase, &rb, &re);
       if (phase == 0) {
-        CHK(run_forward(m, st, d, all, true));
-        MlpArgs a;
-        mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
-        a.y = yd;
-        a.inv_denom = 1.0f / loss_denominator(m, n_global);
-        CHK(launch_mlp(m, st, a, true));
-        CHK(wgrad_mlp(m, st, x, d.xe, m->h[L], m->a[L]));
+        CHK(run_forward(m, st, d, p, true));
+        CHK(backward_mlp(m, st, d, p, c, yd, n_global));
         return launch_reduce_adam(m, st, 1, false, nullptr, LossJob{0, 0, 0, 0.f, 0}, -1, false, rb, re);
       }
       const int s = L + 1 - phase;
       if (s < L) CHK(launch_dgrad(m, st, s + 1, x, m->dpre[s + 1], m->gha));
-      CHK(launch_agg(m, st, d, all, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, (s < L) ? m->h[s] : nullptr, m->dpre[s], 1));
+      CHK(launch_agg(m, st, d, p.dense_agg, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, (s < L) ? m->h[s] : nullptr, m->dpre[s], 1));
       CHK(wide_wgrad_gnn(m, st, s, x, d.xe, s ? m->h[s - 1] : nullptr, s ? m->a[s - 1] : d.nbr, m->dpre[s]));
       const bool last = s == 0;
       if (m->gnn[s].n_slabs > 0 || last)
         return launch_reduce_adam(m, st, 1, false, nullptr, last ? loss_job(m, d, n_global) : LossJob{0, 0, 0, 0.f, 0}, -1, false, rb, re);
       return V2X_OK;
-    });
-    m->bucketed = false;
-    CHK(rc);
+    }));
     if (phase == 0) m->have_fwd = true;
     return phase == n_phase_buckets(m) - 1 ? emit_loss(m, loss_out, loss_on_device, st) : V2X_OK;
   }
+  BwdCall c;
+  c.phased = true;           // Dense-0's weight gradient stays in the MLP launch, a ragged data chain runs layer by layer (run_backward follows the plan)
   if (phase == 0) {
     CHK(run_maybe_graph(m, st, make_key(5, d, yd, n_global), [&]() -> int {
-      CHK(run_forward(m, st, d, all, false));            // narrow: the MLP runs inside its training launch
-      MlpArgs a;
-      mlp_args(m, a, x, d.xe, m->h[L], m->a[L]);
-      a.y = yd;
-      a.inv_denom = 1.0f / loss_denominator(m, n_global);
-      a.frag_groups = m->frag_live ? d.B / FZ_TG : 0;
-      CHK(launch_mlp_train_wg(m, st, a));
+      CHK(run_forward(m, st, d, p, false));              // narrow: the MLP runs inside its training launch
+      CHK(backward_mlp(m, st, d, p, c, yd, n_global));
       return launch_reduce_adam(m, st, 1, false, nullptr, LossJob{0, 0, 0, 0.f, 0}, 0);
     }));
     m->have_fwd = true;
@@ -2318,16 +2303,7 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
   }
   if (!m->have_fwd) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase 1 before phase 0");
   CHK(run_maybe_graph(m, st, make_key(6, d, yd, n_global), [&]() -> int {
-    if (fused_path(m, d)) {
-      CHK(launch_fused_bwd(m, st, d));
-    } else {
-      for (int s = L; s >= 1; --s) {
-        CHK(launch_agg(m, st, d, all, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, s < L ? m->h[s] : nullptr, m->dpre[s], 1));
-        CHK(launch_dgrad(m, st, s, x, m->dpre[s], m->gha));
-      }
-      CHK(launch_agg(m, st, d, all, m->N, F, m->gha + F, 2 * F, m->gha, 2 * F, m->h[0], m->dpre[0], 1));
-    }
-    CHK(wgrad_gnn_all(m, st, x, d));
+    CHK(backward_graph_layers(m, st, d, p, c));
     return launch_reduce_adam(m, st, 1, false, nullptr, loss_job(m, d, n_global), 1);
   }));
   return emit_loss(m, loss_out, loss_on_device, st);
@@ -2392,11 +2368,11 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   if (int rc = resolve_batch(target, s_next, &dn, st)) { online->err = target->err; return rc; }
   if (dn.R != ds.R) FAIL(m, V2X_EINVAL, "dqn_step: s and s' have different sizes");
   if (n_graphs_global <= 0) n_graphs_global = ds.B;
-  CHK(presize(online, ds));
-  if (int rc = presize(target, dn)) { online->err = target->err; return rc; }
+  const BatchPlan po = plan_batch(online, ds), pt = plan_batch(target, dn);
+  CHK(presize(online, ds, po));
+  if (int rc = presize(target, dn, pt)) { online->err = target->err; return rc; }
   CHK(ensure(online, online->st_y, (size_t)ds.R * online->C * sizeof(float)));
   float* y = y_out ? y_out : (float*)online->st_y.p;
-  const Range all{0, ds.B};
   // Everything up to the slab reduction is one replayable hipGraph (the Adam launch stays outside: lr_t changes per
   // step).  The key holds every pointer the launches bake in -- both batches, action / reward / target buffers and the
   // TARGET model's workspace, whose re-allocation must not leave a stale graph in the online model's cache.
@@ -2410,25 +2386,24 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   // that the untouched entries carry exactly zero error (BS_brain.py:664-692, :728); the separate MLP forward of the online
   // network, and the target kernel's pass over q, are gone (38 us of a 520-us step at 20 links, batch 4096).
   // Knobs::dqn_fused_targets = 0: the three-launch form (forward, k_dqn_targets, training launch on y).
-  const bool fuse_targets = online->knobs.dqn_fused_targets && mlp_wg_path(online) && online->C == 4;
+  const bool fuse_targets = online->knobs.dqn_fused_targets && po.mlp_wg && online->C == 4;
   CHK(run_maybe_graph(online, st, key, [&]() -> int {
     target->capturing = online->capturing;
-    int rc = run_forward(target, st, dn, all, true);
+    int rc = run_forward(target, st, dn, pt, true);
     target->capturing = false;
     if (rc) { online->err = target->err; return rc; }
     if (!fuse_targets) {
-      CHK(run_forward(online, st, ds, all, true));
+      CHK(run_forward(online, st, ds, po, true));
       hipLaunchKernelGGL(k_dqn_targets, dim3((ds.R + 255) / 256), dim3(256), 0, st, online->q, target->q, action, reward, gamma,
                          ds.R, online->N, online->C, y);
-      return run_backward(online, st, ds, all, y, n_graphs_global);
+      return run_backward(online, st, ds, po, BwdCall{}, y, n_graphs_global);
     }
-    CHK(run_forward(online, st, ds, all, false));                          // graph layers only
+    CHK(run_forward(online, st, ds, po, false));                           // graph layers only
     float* tq = online->dq;                                                // (a workspace this path does not use otherwise: [R][4])
     hipLaunchKernelGGL(k_dqn_tq, dim3((ds.R + 255) / 256), dim3(256), 0, st, target->q, action, reward, gamma, ds.R, online->N, online->C, tq);
-    online->dqn_tq = tq; online->dqn_y = y;
-    rc = run_backward(online, st, ds, all, y, n_graphs_global);
-    online->dqn_tq = nullptr; online->dqn_y = nullptr;
-    return rc;
+    BwdCall c;
+    c.tq = tq; c.y_out = y;
+    return run_backward(online, st, ds, po, c, y, n_graphs_global);
   }));
   if (!comm) {
     CHK(launch_reduce_adam(online, st, 1, true, nullptr, loss_job(online, ds, n_graphs_global)));
@@ -2468,13 +2443,13 @@ static int batch_dev_only(const v2x_batch* b, DevBatch* d) {
 int v2x_agg_fwd(const v2x_batch* b, int32_t n_nodes, int32_t feat_dim, const float* h, float* out, void* stream) {
   DevBatch d;
   CHK(batch_dev_only(b, &d));
-  return launch_agg(nullptr, (hipStream_t)stream, d, Range{0, d.B}, n_nodes, feat_dim, h, feat_dim, nullptr, 0, nullptr, out, 0);
+  return launch_agg(nullptr, (hipStream_t)stream, d, use_dense_agg(process_knobs(), d, feat_dim), n_nodes, feat_dim, h, feat_dim, nullptr, 0, nullptr, out, 0);
 }
 
 int v2x_agg_bwd(const v2x_batch* b, int32_t n_nodes, int32_t feat_dim, const float* g, float* out, void* stream) {
   DevBatch d;
   CHK(batch_dev_only(b, &d));
-  return launch_agg(nullptr, (hipStream_t)stream, d, Range{0, d.B}, n_nodes, feat_dim, g, feat_dim, nullptr, 0, nullptr, out, 1);
+  return launch_agg(nullptr, (hipStream_t)stream, d, use_dense_agg(process_knobs(), d, feat_dim), n_nodes, feat_dim, g, feat_dim, nullptr, 0, nullptr, out, 1);
 }
 
 int v2x_node_update_fwd(v2x_model* m, int32_t stage, int32_t n_rows, const float* xe, const float* h_prev,
@@ -2726,23 +2701,21 @@ int v2x_path_info(v2x_model* m, const v2x_batch* b, char* out, int cap) {
   memset(&d, 0, sizeof(d));
   d.B = b->n_graphs; d.R = b->n_rows; d.E = b->n_edges; d.max_nodes = b->max_nodes; d.max_edges = b->max_edges;
   d.goff = b->graph_off; d.nbr = b->nbr_init;
-  const bool fused = fused_path(m, d);
-  const int split = fused_split(m, d);
+  const BatchPlan p = plan_batch(m, d);
+  const bool fused = p.form == GraphLayers::Fused;
   // "edge-bitset-walk": what the fused kernels do with the edge index (N <= 32) -- every CSR row becomes a 32-bit set, a wave
   // walks the graph's rows in LDS once and adds each to the slots whose set holds it (sparse lanes walk their set bits only);
   // "edge-gather": the per-edge CSR gather / segment sum of k_agg (layer-wise path, any N)
-  const char* agg = fused ? (split <= 1 && fused_compl(m, d) ? "complement" : "edge-bitset-walk")
-                          : (use_dense_agg(m->knobs, d, m->F) ? "dense(complement-or-mfma-per-graph)" : "edge-gather");
+  const char* agg = fused ? (p.compl_sums ? "complement" : "edge-bitset-walk")
+                          : (p.dense_agg ? "dense(complement-or-mfma-per-graph)" : "edge-gather");
   char gl[48];
-  if (fused && split > 1) snprintf(gl, sizeof(gl), "fused(split%d)", split);
-  else snprintf(gl, sizeof(gl), "%s", fused ? "fused" : (ragged_fused_path(m, d) ? "fused(ragged)" : "layerwise"));
+  if (p.split > 1) snprintf(gl, sizeof(gl), "fused(split%d)", p.split);
+  else snprintf(gl, sizeof(gl), "%s", fused ? "fused" : (p.form == GraphLayers::Ragged ? "fused(ragged)" : "layerwise"));
   // dense0_dw: which launch takes Dense-0's weight gradient in a fit step -- the MLP launch itself, or (small batches) a role of
-  // the graph layers' weight-gradient launch (dense0_rides)
-  const bool d0 = mlp_wg_path(m) && !m->cfg.variable_graphs && dense0_rides(m, d, idx_map(m, d, Range{0, d.B}));
+  // the graph layers' weight-gradient launch (BatchPlan::dense0_rides)
   snprintf(out, cap, "graph_layers=%s aggregation=%s mlp=%s handoff=%s dense0_dw=%s", gl, agg,
-           mlp_wg_path(m) ? "train_wg" : "fwd+bwd",
-           frag_layout(m, d, Range{0, d.B}) ? "fragment-major" : "row-major",
-           d0 ? "k_wgrad" : (mlp_wg_path(m) ? "k_mlp_train_wg" : (is_wide(m) ? "k_wide_wgrad" : "k_wgrad")));
+           p.mlp_wg ? "train_wg" : "fwd+bwd", p.frag_ok ? "fragment-major" : "row-major",
+           p.dense0_rides ? "k_wgrad" : (p.mlp_wg ? "k_mlp_train_wg" : "k_wide_wgrad"));
   return V2X_OK;
 }
 
