@@ -11,6 +11,8 @@
 //                 the prefix links' interference is folded once per prefix into thread-private LDS slots
 //   k_opt_reduce  one workgroup per state folds the per-workgroup partials in a fixed order
 //   k_opt_rewards the reward of every index of a range (m = 0: every link is a prefix link)
+//   k_opt_landscape, k_opt_landscape_reduce  the search's walk, kept as a histogram of all rewards and their sum
+//                 (v2x_opt_landscape; described above its kernels)
 //   k_opt_bound_* the same optimum by branch and bound (v2x_opt_search_bound; described above its kernels)
 //   k_opt_local_* a near-optimal allocation for up to 128 links by multi-start local search (v2x_opt_search_local; described
 //                 above its kernels), k_opt_rewards_actions: the reward of joint actions given as channel arrays
@@ -291,6 +293,132 @@ __global__ __launch_bounds__(OPT_BLOCK) void k_opt_rewards(OptParams q, const do
     opt_decode_prefix(first + j, q.n, q.C, lo, hi);
     opt_prefix_init(q, tab, lo, hi, st, OPT_BLOCK);
     out[(int64_t)e * count + j] = opt_eval(q, tab, lo, hi, 0, st, OPT_BLOCK);
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------- reward landscape
+// v2x_opt_landscape: a histogram of ALL C^N rewards of a state over caller-given edges, and their fp64 sum.  The walk is
+// k_opt_search's (same plan, same LDS layout, same opt_decode_prefix / opt_prefix_init / opt_eval calls), so every reward
+// has the bits v2x_opt_rewards returns for its index.
+//
+// Slots: slot(r) = number of edges j with edges[j] <= r, i.e. 0 .. n_edges; a NaN reward takes slot n_edges + 1 (a NaN edge
+// never satisfies <=).  nb = n_edges + 2 <= 64 slots.
+//
+// Counting is integer only and needs neither LDS nor atomics: lane b of every wave owns the 64-bit counter of slot b.
+// Per evaluated action each lane computes its slot (edge k is kept in lane k and read with v_readlane: no memory access
+// in the loop), then for b = 0 .. nb - 1
+// the wave takes popcount(ballot(slot == b)) and lane b adds it.  Because a lane owns a counter whether or not it has
+// a prefix to walk, the grid-stride loop runs per WAVE (its base prefix is wave-uniform): every lane iterates while lane 0
+// of the wave has work, and a lane past n_pre evaluates nothing and votes slot -1, which matches no b.
+//
+// Sum: per thread in ascending index order, then a wave butterfly (the same bits in every lane), then wave 0 + wave 1: one
+// partial per workgroup; k_opt_landscape_reduce adds the partials per thread in ascending order, then the same butterfly
+// and the waves in order.  The order depends on the plan (hence on E) and on nothing else.
+
+__device__ __forceinline__ uint64_t opt_suffix_next(uint64_t s, int m, int C) {   // odometer step, link n - 1 fastest
+  for (int d = m - 1; d >= 0; --d) {
+    if (opt_sdigit(s, d) + 1 < C) return s + (1ull << (4 * d));
+    s &= ~(15ull << (4 * d));
+  }
+  return s;
+}
+
+__device__ __forceinline__ double opt_wave_sum(double x) {
+#pragma clang fp contract(off)
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) x += __shfl_xor(x, off, 64);
+  return x;
+}
+
+// grid (wgs, E), LDS as k_opt_search.  part_c [E][wgs][64], part_s [E][wgs].
+__global__ __launch_bounds__(OPT_BLOCK) void k_opt_landscape(OptParams q, const double* __restrict__ tabs, int64_t n_pre,
+                                                             int64_t n_suf, const double* __restrict__ edges, int n_edges,
+                                                             int64_t* part_c, double* part_s) {
+#pragma clang fp contract(off)
+  extern __shared__ double opt_lds[];
+  const int e = blockIdx.y;
+  const double* src = tabs + (int64_t)e * q.tab;
+  for (int64_t i = threadIdx.x; i < q.tab; i += OPT_BLOCK) opt_lds[i] = src[i];
+  __syncthreads();
+  const int64_t tab_pad = (q.tab + 1) & ~1ll;
+  double* st = opt_lds + tab_pad + threadIdx.x;
+  const double* ed = edges + (int64_t)e * n_edges;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int nb = n_edges + 2;
+  const double my_edge = lane < n_edges ? ed[lane] : 0.0;   // edge k lives in lane k: read back wave-uniformly below
+  const int edge_lo = __double2loint(my_edge), edge_hi = __double2hiint(my_edge);
+  int64_t cnt = 0;                                       // the counter of slot `lane`
+  double sum = 0.0;
+  const int64_t stride = (int64_t)gridDim.x * OPT_BLOCK;
+  for (int64_t tb = (int64_t)blockIdx.x * OPT_BLOCK + wave * 64; tb < n_pre; tb += stride) {   // wave-uniform
+    const int64_t t = tb + lane;
+    const bool work = t < n_pre;
+    uint64_t lo = 0, hi = 0;
+    if (work) {
+      opt_decode_prefix(t, q.p, q.C, lo, hi);
+      opt_prefix_init(q, opt_lds, lo, hi, st, OPT_BLOCK);
+    }
+    uint64_t s = 0;
+    for (int64_t j = 0; j < n_suf; ++j) {
+      int slot = -1;
+      if (work) {
+        const double r = opt_eval(q, opt_lds, lo, hi, s, st, OPT_BLOCK);
+        sum += r;
+        if (r != r) {
+          slot = n_edges + 1;
+        } else {
+          slot = 0;
+          for (int k = 0; k < n_edges; ++k)
+            slot += __hiloint2double(__builtin_amdgcn_readlane(edge_hi, k), __builtin_amdgcn_readlane(edge_lo, k)) <= r ? 1 : 0;
+        }
+      }
+      for (int b = 0; b < nb; ++b) {
+        const int c = __popcll(__ballot(slot == b));
+        if (lane == b) cnt += c;
+      }
+      s = opt_suffix_next(s, q.m, q.C);
+    }
+  }
+  sum = opt_wave_sum(sum);
+  // wave 1 hands its counters and its sum to wave 0 through the thread slots, which nobody reads any more (at least
+  // n + C >= 3 slots of OPT_BLOCK doubles; counters travel as bit patterns)
+  __syncthreads();
+  double* hand = opt_lds + tab_pad;
+  if (wave == 1) {
+    hand[lane] = __longlong_as_double((long long)cnt);
+    if (lane == 0) hand[64] = sum;
+  }
+  __syncthreads();
+  if (wave == 0) {
+    const int64_t w = (int64_t)e * gridDim.x + blockIdx.x;
+    part_c[w * 64 + lane] = cnt + (int64_t)__double_as_longlong(hand[lane]);
+    if (lane == 0) part_s[w] = sum + hand[64];
+  }
+}
+
+// grid E: counts[e][b] = sum over the workgroups' partials (integers: any order), sums[e] in a fixed order
+__global__ __launch_bounds__(OPT_REDUCE_BLOCK) void k_opt_landscape_reduce(const int64_t* part_c, const double* part_s, int wgs,
+                                                                           int nb, int64_t* counts, double* sums) {
+#pragma clang fp contract(off)
+  __shared__ int64_t sc[OPT_REDUCE_BLOCK];
+  __shared__ double ss[OPT_REDUCE_BLOCK / 64];
+  const int e = blockIdx.x;
+  const int b = threadIdx.x & 63, part = threadIdx.x >> 6;
+  int64_t c = 0;
+  for (int w = part; w < wgs; w += OPT_REDUCE_BLOCK / 64) c += part_c[((int64_t)e * wgs + w) * 64 + b];
+  sc[threadIdx.x] = c;
+  double x = 0.0;
+  for (int w = threadIdx.x; w < wgs; w += OPT_REDUCE_BLOCK) x += part_s[(int64_t)e * wgs + w];
+  x = opt_wave_sum(x);
+  if (b == 0) ss[part] = x;
+  __syncthreads();
+  if (part == 0 && b < nb) {
+    for (int k = 1; k < OPT_REDUCE_BLOCK / 64; ++k) c += sc[k * 64 + b];
+    counts[(int64_t)e * nb + b] = c;
+  }
+  if (threadIdx.x == 0 && sums) {
+    for (int k = 1; k < OPT_REDUCE_BLOCK / 64; ++k) x += ss[k];
+    sums[e] = x;
   }
 }
 
@@ -839,6 +967,55 @@ int v2x_opt_rewards(const v2x_opt_problem* p, void* workspace, int64_t first, in
                      count, out);
   hipError_t err = hipGetLastError();
   if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_rewards: launch failed: %s", hipGetErrorString(err));
+  return V2X_OK;
+}
+
+}  // extern "C"
+
+// ---- reward landscape: workspace = tables | per-workgroup counters [E][wgs][64] | per-workgroup sums [E][wgs]
+namespace {
+
+int opt_landscape_plan(const v2x_opt_problem* p, int32_t n_edges, const char* who, OptPlan& pl) {
+  int rc = opt_plan(p, who, pl);
+  if (rc != V2X_OK) return rc;
+  if (n_edges < 1 || n_edges > 62) OPT_FAIL(V2X_EINVAL, "%s: n_edges = %d (1..62)", who, n_edges);
+  if (pl.total < 0 || pl.total > OPT_MAX_SEARCH)
+    OPT_FAIL(V2X_EINVAL, "%s: %d^%d joint actions exceed the search limit of 2^36", who, pl.q.C, pl.q.n);
+  if (pl.lds > OPT_LDS_CAP) OPT_FAIL(V2X_EINVAL, "%s: %zu bytes of LDS needed (n = %d, rb = %d)", who, pl.lds, pl.q.n, pl.q.C);
+  return V2X_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t v2x_opt_landscape_workspace_bytes(const v2x_opt_problem* p, int32_t n_edges) {
+  OptPlan pl;
+  if (opt_landscape_plan(p, n_edges, "opt_landscape_workspace_bytes", pl) != V2X_OK) return V2X_EINVAL;
+  return opt_tables_bytes(p, pl) + (int64_t)p->E * pl.wgs * (int64_t)(64 * sizeof(int64_t) + sizeof(double));
+}
+
+int v2x_opt_landscape(const v2x_opt_problem* p, void* workspace, const double* edges, int32_t n_edges, int64_t* counts,
+                      double* sums, void* stream) {
+  OptPlan pl;
+  int rc = opt_landscape_plan(p, n_edges, "opt_landscape", pl);
+  if (rc != V2X_OK) return rc;
+  if (!edges) OPT_FAIL(V2X_EINVAL, "opt_landscape: null edges");
+  if (!counts) OPT_FAIL(V2X_EINVAL, "opt_landscape: null output");
+  hipStream_t s = (hipStream_t)stream;
+  rc = opt_prep(p, pl, workspace, s, "opt_landscape");
+  if (rc != V2X_OK) return rc;
+  const double* tabs = (const double*)workspace;
+  int64_t* part_c = (int64_t*)((char*)workspace + opt_tables_bytes(p, pl));
+  double* part_s = (double*)(part_c + (int64_t)p->E * pl.wgs * 64);
+  hipLaunchKernelGGL(k_opt_landscape, dim3((unsigned)pl.wgs, (unsigned)p->E), dim3(OPT_BLOCK), pl.lds, s, pl.q, tabs, pl.n_pre,
+                     pl.n_suf, edges, (int)n_edges, part_c, part_s);
+  hipError_t err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_landscape: landscape launch failed: %s", hipGetErrorString(err));
+  hipLaunchKernelGGL(k_opt_landscape_reduce, dim3((unsigned)p->E), dim3(OPT_REDUCE_BLOCK), 0, s, part_c, part_s, pl.wgs,
+                     (int)n_edges + 2, counts, sums);
+  err = hipGetLastError();
+  if (err != hipSuccess) OPT_FAIL(V2X_EHIP, "opt_landscape: reduce launch failed: %s", hipGetErrorString(err));
   return V2X_OK;
 }
 

@@ -130,6 +130,8 @@ SYMBOLS = [
     ("v2x_opt_workspace_bytes", _L, [C.POINTER(OptProblem)]),
     ("v2x_opt_search", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P]),
     ("v2x_opt_rewards", C.c_int, [C.POINTER(OptProblem), _P, _L, _L, _P, _P]),
+    ("v2x_opt_landscape_workspace_bytes", _L, [C.POINTER(OptProblem), C.c_int32]),
+    ("v2x_opt_landscape", C.c_int, [C.POINTER(OptProblem), _P, _P, C.c_int32, _P, _P, _P]),
     ("v2x_opt_bound_workspace_bytes", _L, [C.POINTER(OptProblem), _L]),
     ("v2x_opt_search_bound", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, C.POINTER(_L), _P]),
     ("v2x_opt_search_bound_seeded", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, _P, C.POINTER(_L), _P]),

@@ -847,14 +847,30 @@ class Agent(object):
         opt = OptimalAllocation()
         return lambda: self._brute_force_device(opt, bound)
 
-    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None):
+    def _rank_search(self):
+        """-> a callable (actions [1, A, N]) -> OptimalAllocation.rank_of of the CURRENT simulator state (opt_rank of
+        test_run); the refusals of opt_backend='device'."""
+        from .optimum import OptimalAllocation
+        OptimalAllocation.check_size(self.num_D2D, self.num_CH)
+        if self.num_Neighbor != 1:
+            raise ValueError("opt_rank supports one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor)
+        opt = OptimalAllocation()
+        return lambda actions: opt.rank_of(self.env, self.v2v_weight, self.v2i_weight, actions)
+
+    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None, opt_rank=False):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
         :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
         rl/optimum.py, or up to 32 links with opt_backend='bound': the same optimum by branch and bound on the GPU).
         opt_backend='local' (up to 128 links) records in the optimum's place the allocation of a multi-start local search
         on the GPU with opt_restarts restarts: a lower bound on the optimum, not the optimum.  Same return tuple as the
-        reference: 15 arrays with opt_flag, 10 without."""
+        reference: 15 arrays with opt_flag, 10 without.
+        opt_rank (C^N <= 2^36, one receiver per link; with or without opt_flag, any opt_backend): before every step the
+        random scheme's action and the greedy action are ranked among ALL C^N joint actions of the state on the GPU
+        (OptimalAllocation.rank_of), into `self.rank_book`: arrays [episodes, steps] `better` / `equal` (the greedy
+        action), `ra_better` / `ra_equal` (the random one), `total` (C^N) and `uniform_mean_reward` (the mean reward over
+        all joint actions: the exact expectation of the random scheme).  The returned tuple, the RNG draws and every
+        recorded array are those of opt_rank=False."""
         _check_opt_backend(opt_backend)
         n, C = self.num_D2D, self.num_CH
         self.num_Episodes, self.num_Test_Step = num_episodes, num_test_step
@@ -874,10 +890,16 @@ class Agent(object):
         rl, ra, opt = book(), book(), book()
         if opt_flag:
             optimum = self._optimum_search(opt_backend, opt_restarts)
+        if opt_rank:
+            ranker = self._rank_search()
+            shape = (num_episodes, num_test_step)
+            self.rank_book = {k: np.zeros(shape, np.int64) for k in ('better', 'equal', 'ra_better', 'ra_equal', 'total')}
+            self.rank_book['uniform_mean_reward'] = np.zeros(shape)
         for ep in range(num_episodes):
             self.env.new_random_game(self.num_D2D)
             for st in range(num_test_step):
-                record(ra, ep, st, *self.dump_act(self.select_action_random(None)))
+                ra_action = self.select_action_random(None)
+                record(ra, ep, st, *self.dump_act(ra_action))
                 if opt_flag:
                     best, reward, res = optimum()
                     if reward > 0:                                                        # at least one feasible solution
@@ -885,6 +907,13 @@ class Agent(object):
                 d2d_state, adj = self.observe()
                 q = self._predict(d2d_state[None], adj[None])[:, 0, :]
                 action = np.argmax(q, axis=1).reshape(n, self.num_Neighbor).astype(int)
+                if opt_rank:                                                              # the state both actions were chosen in
+                    rk = ranker(np.stack([np.asarray(ra_action).reshape(n), action.reshape(n)])[None])
+                    b = self.rank_book
+                    b['ra_better'][ep, st], b['better'][ep, st] = rk['better'][0]
+                    b['ra_equal'][ep, st], b['equal'][ep, st] = rk['equal'][0]
+                    b['total'][ep, st] = rk['total']
+                    b['uniform_mean_reward'][ep, st] = rk['mean_reward'][0]
                 record(rl, ep, st, *self.act(action))
         return tuple(rl + ra + opt) if opt_flag else tuple(rl + ra)
 

@@ -21,6 +21,11 @@ baseline there: a multi-start best-response local search (v2x_opt_search_local, 
 BOUND on the optimum -- a 1-opt allocation, in practice the optimum itself at the sizes where that can be checked
  -- as an array of channel numbers, not an index.  `rewards_of` scores given joint actions at any of those
 sizes, and `search_bound(..., incumbent='local')` starts the exact search from the local search's result.
+
+Where an allocation stands among ALL C^N joint actions of its state (C^N <= 2^36) is what `landscape` and `rank_of` answer:
+a histogram of every reward over given edges and the rewards' sum, reduced on the device (v2x_opt_landscape), and from it
+the number of joint actions strictly better than / exactly equal to given ones, and the exact mean of the landscape -- the
+expectation of the random-action scheme.
 """
 import ctypes as C
 
@@ -84,6 +89,69 @@ def encode(actions, rb):
     for l in range(n):
         out = out * int(rb) + a[..., l].astype(np.int64)
     return out
+
+
+MAX_EDGES = 62                      # edges of one landscape call (v2x_opt_landscape: 64 slots, one per lane of a wave)
+MAX_RANKED = MAX_EDGES // 2         # joint actions per state one rank_of call ranks (two edges each)
+
+
+def check_edges(edges, E=None):
+    """The argument checks of landscape (ValueError): edges [K] or [E, K] floats, 1 <= K <= 62, every row ascending (equal
+    neighbours allowed) -> float64 [E, K] (or [1, K] for E None and a single row)."""
+    ed = np.asarray(edges, np.float64)
+    if ed.ndim not in (1, 2):
+        raise ValueError("edges of shape [K] or [E, K] expected, got %s" % list(ed.shape))
+    ed = np.atleast_2d(ed)
+    K = ed.shape[1]
+    if not 1 <= K <= MAX_EDGES:
+        raise ValueError("the landscape takes 1..%d edges, got %d" % (MAX_EDGES, K))
+    if np.any(ed[:, 1:] < ed[:, :-1]):
+        raise ValueError("every row of edges must be ascending")
+    if E is not None:
+        if ed.shape[0] not in (1, E):
+            raise ValueError("edges of shape [%d] or [%d, %d] expected, got %s" % (K, E, K, list(np.shape(edges))))
+        ed = np.broadcast_to(ed, (E, K))
+    return np.array(ed, np.float64, order='C')                              # a writable copy
+
+
+def rank_edges(rewards):
+    """rewards [E, A] (A <= 31) -> edges float64 [E, 2 A] for landscape(): per row the sorted distinct values of
+    {v, nextafter(v, +inf)} over the row's rewards v, padded with +inf.  The bin [v, nextafter(v)) then holds exactly
+    the joint actions whose reward equals v, and the bins above it those that are strictly better (rank_from_counts).
+    NaN rewards get no edge."""
+    r = np.atleast_2d(np.asarray(rewards, np.float64))
+    E, A = r.shape
+    if not 1 <= A <= MAX_RANKED:
+        raise ValueError("1..%d rewards per state can be ranked in one call, got %d" % (MAX_RANKED, A))
+    out = np.full((E, 2 * A), np.inf)
+    for e in range(E):
+        v = r[e][~np.isnan(r[e])]
+        u = np.unique(np.concatenate([v, np.nextafter(v, np.inf)]))
+        out[e, :u.size] = u
+    return out
+
+
+def rank_from_counts(counts, edges, rewards):
+    """counts [E, K + 2] of landscape(edges = rank_edges(rewards)), edges [E, K], rewards [E, A] -> (better, equal) int64
+    [E, A]: the joint actions of the state with a strictly larger / an exactly equal reward.  `equal` is the count of the
+    bin [v, nextafter(v)), `better` the sum of the bins above it; the NaN slot is excluded.  -1 / -1 for a NaN reward."""
+    c = np.atleast_2d(np.asarray(counts, np.int64))
+    ed = np.atleast_2d(np.asarray(edges, np.float64))
+    r = np.atleast_2d(np.asarray(rewards, np.float64))
+    E, A = r.shape
+    K = ed.shape[1]
+    if c.shape != (E, K + 2) or ed.shape[0] != E:
+        raise ValueError("counts [%d, %d] and edges [%d, %d] expected, got %s and %s"
+                         % (E, K + 2, E, K, list(c.shape), list(ed.shape)))
+    better, equal = np.full((E, A), -1, np.int64), np.full((E, A), -1, np.int64)
+    for e in range(E):
+        above = np.concatenate([np.cumsum(c[e, K::-1])[::-1], [0]])          # above[s] = counts of slots s .. K
+        for a in range(A):
+            if r[e, a] == r[e, a]:
+                s = int(np.searchsorted(ed[e], r[e, a], side='right'))
+                equal[e, a] = c[e, s]
+                better[e, a] = above[s + 1]
+    return better, equal
 
 
 class BoundBudgetExceeded(RuntimeError):
@@ -217,9 +285,9 @@ class OptimalAllocation(object):
             raise ValueError("channel outside [0, %d) in the joint actions" % rb)
         return np.ascontiguousarray(a.reshape(E, -1, n), np.int32), a.ndim == 3
 
-    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None):
+    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None, n_edges=None):
         """max_nodes not None: the problem of search_bound (its checks, its workspace); local = (restarts, max_sweeps): of
-        search_local / rewards_of."""
+        search_local / rewards_of; n_edges: of landscape."""
         v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
         E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
         if local is not None:
@@ -236,6 +304,8 @@ class OptimalAllocation(object):
                           w_v2i=float(v2i_weight), **const)
         if local is not None:
             need = int(self._lib.v2x_opt_local_workspace_bytes(C.byref(prob), int(local[0])))
+        elif n_edges is not None:
+            need = int(self._lib.v2x_opt_landscape_workspace_bytes(C.byref(prob), int(n_edges)))
         elif max_nodes is None:
             need = int(self._lib.v2x_opt_workspace_bytes(C.byref(prob)))
         else:
@@ -406,6 +476,55 @@ class OptimalAllocation(object):
     def rewards(self, env, v2v_weight, v2i_weight, first=0, count=None):
         """rewards_device() copied to the host: float64 [E, count] (the reference's Curr_Feasible_Reward vector)."""
         return self.rewards_device(env, v2v_weight, v2i_weight, first, count).cpu().numpy()
+
+    def landscape_device(self, env, v2v_weight, v2i_weight, edges):
+        """landscape() with the results left on the device: (counts int64 [E, K + 2], sums float64 [E]) torch tensors."""
+        n, rb = _sizes(env)
+        E = env.E if hasattr(env, 'E') else 1
+        ed = check_edges(edges, E)
+        self.check_size(n, rb)
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_SEARCH, n_edges=ed.shape[1])
+        t = self.torch
+        K = ed.shape[1]
+        dev = t.from_numpy(ed).to(self.device)
+        counts = t.empty((E, K + 2), dtype=t.int64, device=self.device)
+        sums = t.empty(E, dtype=t.float64, device=self.device)
+        check(self._lib, self._lib.v2x_opt_landscape(C.byref(prob), self._ws.data_ptr(), dev.data_ptr(), K, counts.data_ptr(),
+                                                     sums.data_ptr(), self._stream()))
+        self._keep = self._keep + [dev]
+        return counts, sums
+
+    def landscape(self, env, v2v_weight, v2i_weight, edges):
+        """The histogram of ALL rb^n rewards of every state (rb^n <= 2^36, as search) over `edges` -- [K] for every state or
+        [E, K], 1 <= K <= 62, rows ascending -- reduced on the device, never downloaded:
+        -> (counts int64 [E, K + 2], sums float64 [E]).  counts[e, s] for s <= K: joint actions whose reward r has
+        np.searchsorted(edges[e], r, side='right') == s, each reward with the bits rewards() returns; counts[e, K + 1]:
+        NaN rewards; a row sums to rb^n.  sums[e]: the sum of the state's rewards, so sums / rb^n is the exact expectation
+        of the random-action scheme (uniform, independent per link).  Counts are exact; the sum is reproducible call to
+        call, but may differ in its last bits between a stacked and a single-state call."""
+        counts, sums = self.landscape_device(env, v2v_weight, v2i_weight, edges)
+        return counts.cpu().numpy(), sums.cpu().numpy()
+
+    def rank_of(self, env, v2v_weight, v2i_weight, actions):
+        """Where given joint actions stand among all rb^n of their state: actions [E, A, n] (A <= 31) or [E, n], channel
+        numbers -> dict of `better` / `equal` (int64: joint actions with a strictly larger / an exactly equal reward, the
+        action itself included in `equal`), `reward` (rewards_of(actions)), each [E, A] or [E]; `total` (rb^n) and
+        `mean_reward` (float64 [E]: the mean over all joint actions).  better == 0: an optimum; better / total: the share
+        of joint actions strictly better than the given one.  One rewards_of and one landscape call."""
+        n, rb = _sizes(env)
+        self.check_size(n, rb)
+        E = env.E if hasattr(env, 'E') else 1
+        host, had_k = self._check_actions(actions, E, n, rb)
+        if host.shape[1] > MAX_RANKED:
+            raise ValueError("1..%d joint actions per state can be ranked in one call, got %d" % (MAX_RANKED, host.shape[1]))
+        reward = self.rewards_of(env, v2v_weight, v2i_weight, host)
+        edges = rank_edges(reward)
+        counts, sums = self.landscape(env, v2v_weight, v2i_weight, edges)
+        better, equal = rank_from_counts(counts, edges, reward)
+        total = rb ** n
+        if not had_k:
+            better, equal, reward = better[:, 0], equal[:, 0], reward[:, 0]
+        return dict(better=better, equal=equal, total=total, mean_reward=sums / float(total), reward=reward)
 
     @staticmethod
     def decode(index, n, rb):

@@ -4,7 +4,7 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local]
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] [--opt-rank]
 """
 import argparse
 import json
@@ -33,18 +33,28 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
     return agent
 
 
-def run_test(cfg, agent, opt_backend='host', opt_restarts=None):
+def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False):
     """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme.  opt_backend: where the
     optimum is searched ('host': numpy over every joint action; 'device' / 'bound': the GPU searches of rl/optimum.py;
-    'local': its local search with opt_restarts restarts -- a lower bound on the optimum, not the optimum)."""
+    'local': its local search with opt_restarts restarts -- a lower bound on the optimum, not the optimum).  opt_rank: also
+    rank every step's greedy and random action among all C^N joint actions of its state (agent.rank_book; rank_summary)."""
     out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend,
-                         opt_restarts=opt_restarts)
+                         opt_restarts=opt_restarts, opt_rank=opt_rank)
     names = ['Expect_Return', 'Reward', 'Per_V2V_Rate', 'Per_V2I_Rate', 'Per_V2B_Interference']
     res = {}
     for prefix, chunk in zip(('', 'RA_', 'Opt_'), (out[0:5], out[5:10], out[10:15])):
         for name, arr in zip(names, chunk):
             res[prefix + name] = arr
     return res
+
+
+def rank_summary(book):
+    """The --opt-rank entries of the JSON summary from Agent.rank_book."""
+    total = book['total'].astype(np.float64)
+    return {"share_states_gnn_optimal": float(np.mean(book['better'] == 0)),
+            "median_share_better_gnn": float(np.median(book['better'] / total)),
+            "median_share_better_random": float(np.median(book['ra_better'] / total)),
+            "mean_reward_uniform_exact": float(book['uniform_mean_reward'].mean())}
 
 
 def main(argv=None):
@@ -63,6 +73,9 @@ def main(argv=None):
                     help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4);\n                         local: NOT the optimum but a lower bound on it, the best of --opt-restarts local searches on the GPU\n                         (up to 128 links, e.g. 100 x 4)")
     ap.add_argument("--opt-restarts", type=int, default=None,
                     help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
+    ap.add_argument("--opt-rank", action="store_true",
+                    help="rank every step's greedy and random action among ALL C^N joint actions of its state on the GPU "
+                         "(C^N <= 2^36; with or without --opt, any --opt-backend) and add the shares to the summary")
     ap.add_argument("--seed", type=int, default=11)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
@@ -77,11 +90,13 @@ def main(argv=None):
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = start_env(args.links)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed)
-    res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts)
+    res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,
                "mean_reward_gnn": float(res['Reward'].mean()), "mean_reward_random": float(res['RA_Reward'].mean())}
     if args.opt:
         summary["mean_reward_optimal"] = float(res['Opt_Reward'].mean())
+    if args.opt_rank:
+        summary.update(rank_summary(agent.rank_book))
     print(json.dumps(summary))
     return 0
 

@@ -345,6 +345,19 @@ int  v2x_opt_search(const v2x_opt_problem* p, void* workspace, int64_t* best_ind
 /* out[E][count]: the reward of every index in [first, first + count) (the reference's Curr_Feasible_Reward vector); the
  * same device arithmetic as the search, so out[best_index - first] == best_reward bit for bit */
 int  v2x_opt_rewards(const v2x_opt_problem* p, void* workspace, int64_t first, int64_t count, double* out, void* stream);
+/* The reward landscape of every state over ALL rb^n joint actions (rb^n <= 2^36, the limits of v2x_opt_search).
+ * edges [dev] [E][n_edges] doubles, 1 <= n_edges <= 62.  For a reward r, bin(r) = number of j with edges[e][j] <= r
+ * (for ascending edges: np.searchsorted(edges[e], r, side='right')); a NaN edge is legal and never satisfies <=.
+ * counts [dev] [E][n_edges + 2] int64: slots 0..n_edges count the joint actions per bin, slot n_edges + 1 counts NaN
+ * rewards; the slots of a state sum to rb^n.  Every reward has the bits v2x_opt_rewards returns for its index, and the
+ * counts are exact integers: a state's counts do not depend on the states stacked around it.  sums [dev] [E] (may be
+ * NULL): the fp64 sum of the state's rewards (NaN if any reward is), added in a fixed order: bit-identical from call to
+ * call for the same problem, but the order follows the launch plan, which depends on E, so the last bits may differ
+ * between a stacked and a single-state call.  Asynchronous on `stream`, three launches, no allocation, no
+ * synchronisation (capturable). */
+int64_t v2x_opt_landscape_workspace_bytes(const v2x_opt_problem* p, int32_t n_edges);
+int  v2x_opt_landscape(const v2x_opt_problem* p, void* workspace, const double* edges, int32_t n_edges,
+                       int64_t* counts, double* sums, void* stream);
 /* The same optimum by branch and bound (a depth-first search with an admissible upper bound on every completion of a
  * partial assignment; csrc/v2xopt.hip): no cap on rb^n beyond the 64-bit index (rb^n <= 2^62), so 20 links x 4 channels and
  * more.  Bit for bit the pair v2x_opt_search defines: leaves are scored with the same arithmetic, and nothing is pruned

@@ -17,6 +17,12 @@ restart, the share of restarts that end at the winner; hits and worst gap agains
 100 links against random actions and against 8 x the restarts; search_bound seeded with the local search against unseeded.
 
     python tools/opt_search_timing.py --local [--out profiles/opt_local_timing.json] [--states 10]
+
+With --landscape: the reward landscape (landscape, v2x_opt_landscape) with 2, 16 and 62 edges at 8, 12 and 16 links x 4 RBs on
+the seeded states of --bound, beside search() on the same states, the four taken in turn in the same run: wall and kernel
+time per state and the ratio of the landscape's kernel time to the search's.
+
+    python tools/opt_search_timing.py --landscape [--out profiles/opt_landscape_timing.json] [--states 10] [--reps 5]
 """
 import argparse
 import json
@@ -308,13 +314,97 @@ def main_local(args):
     return 0
 
 
+LANDSCAPE_EDGES = (2, 16, 62)
+
+
+def landscape_rows(opt, n, states, reps):
+    """search() and landscape() with 2 / 16 / 62 edges on `states` seeded states of n links x 4 RBs, one state per call, the
+    four in turn `reps` times per state: wall of the Python call (upload, launches, download) and the time between HIP
+    events around the C entry point alone (inputs on the device); the median over the reps of a state, then min / median /
+    max over the states.  The edges are evenly spaced over [0, best reward]."""
+    import ctypes
+    import torch
+    from v2xgnn.rl.optimum import MAX_SEARCH
+    w_v2v, w_v2i = 1.0, 0.1
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    cases = ("search",) + tuple("landscape_%d" % k for k in LANDSCAPE_EDGES)
+    wall = {c: [] for c in cases}
+    kern = {c: [] for c in cases}
+    ratio = {k: [] for k in LANDSCAPE_EDGES}
+    for seed in range(states):
+        env = _state(n, seed)
+        index, best = opt.search(env, w_v2v, w_v2i)
+        edges = {k: np.linspace(0.0, float(best[0]), k + 1)[1:] for k in LANDSCAPE_EDGES}
+        for k in LANDSCAPE_EDGES:                                   # warm-up: the workspace of each size
+            counts, sums = opt.landscape(env, w_v2v, w_v2i, edges[k])
+            assert int(counts.sum()) == 4 ** n and int(counts[0, k]) >= 1 and int(counts[0, k + 1]) == 0
+        w = {c: [] for c in cases}
+        t = {c: [] for c in cases}
+        for _ in range(reps):
+            for c in cases:
+                k = None if c == "search" else int(c.split("_")[1])
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                if k is None:
+                    opt.search(env, w_v2v, w_v2i)
+                else:
+                    opt.landscape(env, w_v2v, w_v2i, edges[k])
+                w[c].append((time.perf_counter() - t0) * 1e3)
+                prob, _, _, _ = opt._setup(env, w_v2v, w_v2i, MAX_SEARCH, n_edges=k)
+                if k is None:
+                    ix = torch.empty(1, dtype=torch.int64, device=opt.device)
+                    rw = torch.empty(1, dtype=torch.float64, device=opt.device)
+                    ev[0].record()
+                    rc = opt._lib.v2x_opt_search(ctypes.byref(prob), opt._ws.data_ptr(), ix.data_ptr(), rw.data_ptr(), opt._stream())
+                else:
+                    ed = torch.from_numpy(edges[k]).to(opt.device)
+                    cn = torch.empty(k + 2, dtype=torch.int64, device=opt.device)
+                    sm = torch.empty(1, dtype=torch.float64, device=opt.device)
+                    ev[0].record()
+                    rc = opt._lib.v2x_opt_landscape(ctypes.byref(prob), opt._ws.data_ptr(), ed.data_ptr(), k, cn.data_ptr(),
+                                                    sm.data_ptr(), opt._stream())
+                ev[1].record()
+                assert rc == 0
+                torch.cuda.synchronize()
+                t[c].append(ev[0].elapsed_time(ev[1]))
+        for c in cases:
+            wall[c].append(float(np.median(w[c])))
+            kern[c].append(float(np.median(t[c])))
+        for k in LANDSCAPE_EDGES:
+            ratio[k].append(kern["landscape_%d" % k][-1] / kern["search"][-1])
+        print(json.dumps({"n": n, "seed": seed, "kernel_ms": {c: round(kern[c][-1], 4) for c in cases},
+                          "wall_ms": {c: round(wall[c][-1], 4) for c in cases}}), flush=True)
+    return {"case": "landscape %d links" % n, "n": n, "rb": 4, "states": states, "reps": reps, "joint_actions_per_state": 4 ** n,
+            "wall_ms_per_state": {c: _mmm(wall[c]) for c in cases}, "kernel_ms_per_state": {c: _mmm(kern[c]) for c in cases},
+            "kernel_ratio_to_search": {str(k): _mmm(ratio[k]) for k in LANDSCAPE_EDGES}}
+
+
+def main_landscape(args):
+    import torch
+    from v2xgnn.rl import OptimalAllocation
+    opt = OptimalAllocation()
+    opt.search(_state(8), 1.0, 0.1)                                    # warm-up: code objects
+    opt.landscape(_state(8), 1.0, 0.1, [1.0])
+    rows = []
+    for n in (8, 12, 16):
+        rows.append(landscape_rows(opt, n, args.states if n < 16 else min(args.states, 3), args.reps if n < 16 else min(args.reps, 2)))
+        print(json.dumps(rows[-1]), flush=True)
+    out = {"device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--bound", action="store_true", help="measure the branch-and-bound search instead")
     ap.add_argument("--local", action="store_true", help="measure the multi-start local search instead")
-    ap.add_argument("--states", type=int, default=10, help="--bound / --local: seeded states per size")
+    ap.add_argument("--landscape", action="store_true", help="measure the reward landscape beside search() instead")
+    ap.add_argument("--states", type=int, default=10, help="--bound / --local / --landscape: seeded states per size")
     ap.add_argument("--links", type=int, nargs="+", default=[12, 16, 20, 24], help="--bound / --local: sizes against the exact optimum")
     args = ap.parse_args(argv)
     import torch
@@ -324,6 +414,8 @@ def main(argv=None):
         return main_bound(args)
     if args.local:
         return main_local(args)
+    if args.landscape:
+        return main_landscape(args)
     from v2xgnn.rl import OptimalAllocation
     opt = OptimalAllocation()
     rows = []
