@@ -79,6 +79,7 @@ struct v2x_model {
   float* loss_part = nullptr;  // 64 partial sums + the arrival counter of the split loss reduction
   float* zero_buf = nullptr;   // 4 KiB of zeros
   float* slab = nullptr; int slab_cap = 0;
+  int reduce_groups = 0;        // AdamArgs::groups of the last launch_reduce_adam (v2x_debug_layer_slabs)
   // staging for host-side inputs
   DevBuf st_xe, st_nbr, st_goff, st_rp, st_ci, st_y, st_q;
   DevBuf adj_mask;              // adjacency bit masks of the current batch (dense-graph aggregation)
@@ -108,7 +109,7 @@ struct v2x_model {
   // hipGraph cache
   // a captured step + the per-layer slab counts its weight-gradient launches write (host state that the launches
   // OUTSIDE the graph -- the Adam / slab-sum kernel of train_step -- depend on)
-  struct GraphEntry { hipGraphExec_t exec; std::vector<int> n_slabs; bool frag_live; };
+  struct GraphEntry { hipGraphExec_t exec; std::vector<int> n_slabs; bool frag_live; int reduce_groups; };
   int64_t ws_gen = 0;           // bumped whenever a workspace buffer is re-allocated (keys of graphs that bake in ANOTHER model's workspace)
   std::map<GraphKey, GraphEntry> graphs;
   bool capturing = false;
@@ -1344,6 +1345,7 @@ int launch_reduce_adam(v2x_model* m, hipStream_t st, int n_slabs, bool do_adam, 
   for (int l = 0; l < a.n_layers; ++l) max_slabs_used = std::max(max_slabs_used, a.layer_slabs[l]);
   a.groups = 1;
   if (a.slab && a.n4 < 256 * 1024 && max_slabs_used >= 16) a.groups = a.n4 < 64 * 1024 ? 16 : 4;
+  m->reduce_groups = a.groups;
   const int cols = 256 / a.groups;
   int blocks = (int)((a.range_end4 - a.range_begin4 + a.range2_end4 - a.range2_begin4 + cols - 1) / cols);
   if (blocks > 2048) blocks = 2048;
@@ -1885,6 +1887,7 @@ int run_maybe_graph(v2x_model* m, hipStream_t& st, const GraphKey& key, Body bod
     for (auto* v : {&m->gnn, &m->dense})
       for (LayerDesc& ld : *v) ld.n_slabs = it->second.n_slabs[i++];
     m->frag_live = it->second.frag_live;            // ... and in the model (layout of the saved h_L / a_L / gha)
+    m->reduce_groups = it->second.reduce_groups;
     HIPCHK(m, hipGraphLaunch(it->second.exec, st));
     return V2X_OK;
   }
@@ -1909,6 +1912,7 @@ int run_maybe_graph(v2x_model* m, hipStream_t& st, const GraphKey& key, Body bod
   v2x_model::GraphEntry entry;
   entry.exec = ge;
   entry.frag_live = m->frag_live;
+  entry.reduce_groups = m->reduce_groups;
   for (auto* v : {&m->gnn, &m->dense})
     for (const LayerDesc& ld : *v) entry.n_slabs.push_back(ld.n_slabs);
   m->graphs[key] = entry;
@@ -2733,6 +2737,18 @@ int v2x_debug_ragged_plan(v2x_model* m, int32_t* out, int n) {
   HIPCHK(m, hipDeviceSynchronize());
   HIPCHK(m, hipMemcpy(out, m->plan_buf.p, (size_t)std::min(n, m->plan_len) * 4, hipMemcpyDeviceToHost));
   return m->plan_len;
+}
+
+int v2x_debug_layer_slabs(v2x_model* m, int32_t* out, int n) {
+  if (!m || !out || n < 0) FAIL(m, V2X_EINVAL, "null argument");
+  const int want = (int)(m->gnn.size() + m->dense.size()) + 1;
+  if (n < want) FAIL(m, V2X_EINVAL, "layer_slabs: room for %d values needed", want);
+  HIPCHK(m, hipDeviceSynchronize());
+  int k = 0;
+  for (auto* v : {&m->gnn, &m->dense})
+    for (const LayerDesc& ld : *v) out[k++] = ld.n_slabs;
+  out[k++] = m->reduce_groups;
+  return k;
 }
 
 int v2x_profile_enable(v2x_model* m, int enable) {

@@ -418,6 +418,11 @@ int  v2x_debug_phase_stamps(v2x_model* m, int64_t* out, int n);
  * w = 0 .. n - 1 (entries past the plan's length are left alone); returns the plan's length (launched workgroups + 1) or a
  * negative error code.  [host] out. */
 int  v2x_debug_ragged_plan(v2x_model* m, int32_t* out, int n);
+/* Tests: how the last backward pass cut its weight gradients -- the partial-sum slabs written per layer, graph layers 0 .. L
+ * (0 = the embed layer) and then Dense 0 .. 3 (0 slabs: the layer's gradient was written in place), followed by the threads per
+ * column (1, 4 or 16) of the last slab sum / Adam launch.  n >= L + 6; returns the number of values written (L + 6) or a
+ * negative error code.  Launches nothing.  [host] out. */
+int  v2x_debug_layer_slabs(v2x_model* m, int32_t* out, int n);
 int  v2x_profile_read(v2x_model* m, char* names_out, int names_cap, double* ms_out, int64_t* calls_out,
                       int max_entries);   /* returns number of entries, names '\n'-separated */
 
