@@ -14,12 +14,7 @@
 #include <stdlib.h>
 #include <string.h>
 #include "../../include/v2xsim.h"
-
-#define TWOPI 6.283185307179586476925286766559
-
-static const double V2V_H = 1.5, FC = 2.0, V2V_DECORR = 10.0, V2V_SHADOW_STD = 3.0;
-static const double V2I_H_BS = 25.0, V2I_H_MS = 1.5, V2I_DECORR = 50.0, V2I_SHADOW_STD = 8.0;
-static const double BS_X = 750.0 / 2, BS_Y = 1299.0 / 2;
+#include "../../include/v2xsim_const.h"   /* V2V_H, FC, ... TWOPI: shared with the device counterpart, csrc/v2xsimdev.hip */
 
 int v2xsim_abi(void) { return 3; }
 /* ---- the thread pool --------------------------------------------------------------------------------------------------

@@ -139,6 +139,9 @@ SYMBOLS = [
     ("v2x_opt_local_workspace_bytes", _L, [C.POINTER(OptProblem), C.c_int32]),
     ("v2x_opt_search_local", C.c_int, [C.POINTER(OptProblem), _P, C.c_int32, C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("v2x_opt_rewards_actions", C.c_int, [C.POINTER(OptProblem), _P, _P, _L, _P, _P]),
+    ("v2x_sim_channels", C.c_int, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    ("v2x_sim_observe", C.c_int, [_I, _I, _I, _P, _P, _P] + [C.c_double] * 5 + [_P] * 7),
+    ("v2x_sim_rates", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P, _P, _P, _P]),
 ]
 
 

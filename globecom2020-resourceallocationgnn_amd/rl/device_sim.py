@@ -1,0 +1,508 @@
+"""The simulator's channel step, observation and rates on the GPU (csrc/v2xsimdev.hip, the v2x_sim_* entry points of
+include/v2xgnn.h): the device counterpart of rl/native_sim.py's channels / interference_db / observe_packed / reward.
+
+`DeviceChannels` owns the arrays of E simulator states of n links and rb resource blocks as torch tensors in HBM --
+shadowing, path loss + shadowing, fast fading, observation, rates -- and issues the three launches on torch's current
+stream.  Only small things cross the bus: the uniforms of a step go up (one pinned staging buffer), the packed
+observation (xe / mask / col / regular) and the rates come down.
+
+    dc = DeviceChannels(E, n, rb)
+    dc.upload('v2i_shadow', s_i); dc.upload('v2v_shadow', s_v)
+    dc.step(u, vel, pos)                        # u [E, n_u] uniforms of the step: v2x_sim_channels
+    dc.observe(dest)                            # v2x_sim_observe
+    xe, mask, col, regular = dc.fetch_observation()
+    dc.rates(actions)                           # v2x_sim_rates
+    r = dc.fetch_rates()                        # dict: v2v_rate, v2i_rate, interference, v2i_interf, v2v_interf
+    index, reward = OptimalAllocation().search(dc, 1.0, 0.1)        # on the device arrays, no upload
+
+`DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: mobility and the MT19937 streams stay on
+the host (libv2xsim.so), the channel update, the observable interference, the observation and the rates run on the device.
+The host simulator stays the default and the definition; the two agree to the rounding of the two math libraries
+(tests/test_gpu_device_sim.py).  There is no CPU fallback: without a GPU every device call raises.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import native_sim
+from ..lib import OptProblem, check, load_library
+from .batched_env import BatchedEnviron
+
+MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
+OBSERVE_MIN_LINKS, OBSERVE_MAX_LINKS, XE_WIDTH = 3, 31, 16
+
+# the radio constants of BatchedEnviron (Environment.py:183-212)
+DEFAULT_CONSTANTS = dict(p_v2v=10.0, p_v2i=23.0, veh_gain=3.0, bs_gain=8.0, bs_nf=5.0, veh_nf=9.0, sig2=10 ** (-114 / 10))
+
+_CHANNEL_TENSORS = ('v2i_shadow', 'v2v_shadow', 'v2v_abs', 'v2i_abs', 'v2v_ff', 'v2i_ff')
+
+
+def uniforms_per_step(n, rb):
+    """uniforms one channel update of a state consumes: n + n^2 shadowing draws, 2 n rb + 2 n^2 rb Rayleigh draws (even)"""
+    return n + n * n + 2 * n * rb + 2 * n * n * rb
+
+
+def _align(x, a=64):
+    return (x + a - 1) // a * a
+
+
+class DeviceChannels(object):
+    """The device arrays of E simulator states and the v2x_sim_* calls on them.  Argument checks (ValueError) come before any
+    device work; the device is touched at the first call that needs it."""
+
+    n_Neighbor = 1                                       # (what OptimalAllocation asks of a simulator)
+
+    def __init__(self, E, n, rb, device=0, constants=None):
+        E, n, rb = int(E), int(n), int(rb)
+        if not 1 <= E <= MAX_STATES or not 1 <= n <= MAX_LINKS or not 1 <= rb <= MAX_RB:
+            raise ValueError("DeviceChannels supports 1..%d states, 1..%d links and 1..%d resource blocks, got E = %d, n = %d, "
+                             "rb = %d" % (MAX_STATES, MAX_LINKS, MAX_RB, E, n, rb))
+        self.E, self.n, self.rb = E, n, rb
+        self.n_Veh, self.n_RB = n, rb
+        self.n_u = uniforms_per_step(n, rb)
+        self.device_index = int(device)
+        self.constants = dict(DEFAULT_CONSTANTS)
+        if constants:
+            unknown = set(constants) - set(DEFAULT_CONSTANTS)
+            if unknown:
+                raise ValueError("unknown constants %s" % sorted(unknown))
+            self.constants.update({k: float(v) for k, v in constants.items()})
+        self.torch = None
+        self._t = {}                                     # name -> device tensor
+        self._obs_ready = False
+        self._h2d_done = None
+
+    # ------------------------------------------------------------------ shapes and checks
+    def shapes(self):
+        E, n, rb, m = self.E, self.n, self.rb, min(self.rb, self.n)
+        return {'u': (E, self.n_u), 'vel': (E, n), 'pos': (E, n, 2), 'v2i_shadow': (E, n), 'v2v_shadow': (E, n, n),
+                'v2v_abs': (E, n, n), 'v2i_abs': (E, n), 'v2v_ff': (E, n, n, rb), 'v2i_ff': (E, n, rb), 'dest': (E, n),
+                'actions': (E, n), 'interf_db': (E, n, rb), 'state': (E, n, 3 * rb + 1), 'xe': (E, n, XE_WIDTH), 'mask': (E, n),
+                'col': (E, n * max(n - 2, 0)), 'regular': (E,), 'v2v_rate': (E, n), 'v2i_rate': (E, m), 'interference': (E, rb),
+                'v2i_interf': (E, rb), 'v2v_interf': (E, n)}
+
+    @staticmethod
+    def check_observe(n, C, rb=None):
+        """The limits of v2x_sim_observe (those of v2xsim_observe_packed)."""
+        if not OBSERVE_MIN_LINKS <= n <= OBSERVE_MAX_LINKS:
+            raise ValueError("the device observation supports %d..%d links, got %d" % (OBSERVE_MIN_LINKS, OBSERVE_MAX_LINKS, n))
+        if rb is not None and C != rb:
+            raise ValueError("the device observation is built for n_channels == n_RB (%d), got %d" % (rb, C))
+        if C > n:
+            raise ValueError("the device observation needs n_RB <= links (block r's V2I transmitter is vehicle r), got %d > %d"
+                             % (C, n))
+        if 3 * C + 1 > XE_WIDTH:
+            raise ValueError("an observation row of 3 * %d + 1 values exceeds the packed width of %d" % (C, XE_WIDTH))
+
+    def _check_input(self, name, a, dtype_kind='f'):
+        """a host array or device tensor for slot `name` -> ('host', contiguous numpy array) or ('dev', tensor)"""
+        shape = self.shapes()[name]
+        if hasattr(a, 'data_ptr'):
+            if tuple(a.shape) != shape:
+                raise ValueError("%s: a tensor of shape %s expected, got %s" % (name, list(shape), list(a.shape)))
+            want = {'f': 'torch.float64', 'i': 'torch.int64', 'a': 'torch.int32'}[dtype_kind]
+            if str(a.dtype) != want or not a.is_contiguous():
+                raise ValueError("%s: a contiguous %s tensor expected, got %s" % (name, want, a.dtype))
+            return 'dev', a
+        a = np.asarray(a)
+        if dtype_kind in 'ia' and a.dtype.kind not in 'iu':
+            raise ValueError("%s must be integers, got dtype %s" % (name, a.dtype))
+        if dtype_kind == 'f' and a.dtype.kind not in 'fiu':
+            raise ValueError("%s must be real numbers, got dtype %s" % (name, a.dtype))
+        if name == 'actions' and a.shape == shape + (1,):
+            a = a.reshape(shape)
+        if a.shape != shape and not (name in ('v2v_ff', 'interf_db') and a.size == int(np.prod(shape))):
+            raise ValueError("%s: an array of shape %s expected, got %s" % (name, list(shape), list(a.shape)))
+        return 'host', np.ascontiguousarray(a.reshape(shape), {'f': np.float64, 'i': np.int64, 'a': np.int32}[dtype_kind])
+
+    # ------------------------------------------------------------------ device side
+    def _init_device(self):
+        if self.torch is not None:
+            return
+        import torch
+        if not torch.cuda.is_available():
+            raise RuntimeError("DeviceChannels needs a GPU (there is no CPU fallback; the host path is rl/native_sim.py)")
+        self._lib = load_library()
+        self.device = torch.device('cuda', self.device_index)
+        self._pin = True
+        self.torch = torch
+        self._allocate()
+
+    def _allocate(self):
+        t, sh = self.torch, self.shapes()
+        f64 = t.float64
+        # the inputs of a step: ONE staging buffer (page-locked) and one device buffer, u | vel | pos
+        sizes = [int(np.prod(sh[k])) for k in ('u', 'vel', 'pos')]
+        self._in_host = t.empty(sum(sizes), dtype=f64, pin_memory=self._pin)
+        self._in_dev = t.empty(sum(sizes), dtype=f64, device=self.device)
+        o = 0
+        self._in_np = {}
+        for k, s in zip(('u', 'vel', 'pos'), sizes):
+            self._t[k] = self._in_dev[o:o + s].view(sh[k])
+            self._in_np[k] = self._in_host[o:o + s].view(sh[k]).numpy()
+            o += s
+        for k in _CHANNEL_TENSORS + ('interf_db', 'state'):
+            self._t[k] = t.zeros(sh[k], dtype=f64, device=self.device)
+        self._t['dest'] = t.zeros(sh['dest'], dtype=t.int64, device=self.device)
+        self._t['actions'] = t.zeros(sh['actions'], dtype=t.int32, device=self.device)
+        # the small results, each group one device buffer and one page-locked copy (one download per group)
+        self._obs_dev, self._obs_host, self._obs_np = self._group((('xe', t.float32), ('mask', t.int32), ('col', t.int32),
+                                                                   ('regular', t.uint8)))
+        self._rates_dev, self._rates_host, self._rates_np = self._group(tuple(
+            (k, f64) for k in ('v2v_rate', 'v2i_rate', 'interference', 'v2i_interf', 'v2v_interf')))
+
+    def _group(self, fields):
+        t, sh = self.torch, self.shapes()
+        offs, o = [], 0
+        for k, dt in fields:
+            nbytes = int(np.prod(sh[k])) * t.empty(0, dtype=dt).element_size()
+            offs.append((k, dt, o, nbytes))
+            o = _align(o + nbytes)
+        dev = t.zeros(max(o, 64), dtype=t.uint8, device=self.device)
+        host = t.zeros(max(o, 64), dtype=t.uint8, pin_memory=self._pin)
+        views = {}
+        for k, dt, o, nbytes in offs:
+            self._t[k] = dev[o:o + nbytes].view(dt).view(sh[k])
+            views[k] = host[o:o + nbytes].view(dt).view(sh[k]).numpy()
+        return dev, host, views
+
+    def _stream(self):
+        return self.torch.cuda.current_stream(self.device).cuda_stream
+
+    def _sync(self):
+        self.torch.cuda.current_stream(self.device).synchronize()
+
+    def _staging_free(self):
+        """the last upload out of the staging buffer has left it"""
+        if self._h2d_done is not None:
+            self._h2d_done.synchronize()
+
+    def _staging_sent(self):
+        if self._pin:
+            if self._h2d_done is None:
+                self._h2d_done = self.torch.cuda.Event()
+            self._h2d_done.record(self.torch.cuda.current_stream(self.device))
+
+    def tensor(self, name):
+        """the device tensor behind `name` (see shapes()); valid for the life of this object"""
+        self._init_device()
+        return self._t[name]
+
+    def upload(self, name, array):
+        """host array -> the device tensor `name` (shadowing states, channel arrays, dest, ...)"""
+        kind = 'i' if name == 'dest' else 'a' if name == 'actions' else 'f'
+        where, a = self._check_input(name, array, kind)
+        self._init_device()
+        if where == 'dev':
+            self._t[name].copy_(a)
+        else:
+            self._t[name].copy_(self.torch.from_numpy(a))
+        return self._t[name]
+
+    def download(self, *names):
+        """host copies (numpy) of the named device tensors, in order; no names: the six channel arrays"""
+        self._init_device()
+        names = names or _CHANNEL_TENSORS
+        out = [self._t[k].cpu().numpy() for k in names]
+        return out[0] if len(out) == 1 else tuple(out)
+
+    # ------------------------------------------------------------------ the three calls
+    def step(self, u, vel=None, pos=None):
+        """One channel update of every state (v2x_sim_channels) from the step's uniforms u [E, n_u]; vel [E, n] and pos
+        [E, n, 2] (None: what the device holds).  Host arrays travel through the page-locked staging buffer in one copy;
+        device tensors (float64, contiguous) are read where they are.  Shadowing is updated in place."""
+        given = {'u': u, 'vel': vel, 'pos': pos}
+        checked = {k: self._check_input(k, v) for k, v in given.items() if v is not None}
+        self._init_device()
+        host = [k for k in ('u', 'vel', 'pos') if k in checked and checked[k][0] == 'host']
+        if host:
+            self._staging_free()
+            for k in host:
+                self._in_np[k][...] = checked[k][1]
+            if len(host) == 3:
+                self._in_dev.copy_(self._in_host, non_blocking=True)
+            else:
+                o = 0
+                for k in ('u', 'vel', 'pos'):
+                    s = self._t[k].numel()
+                    if k in host:
+                        self._in_dev[o:o + s].copy_(self._in_host[o:o + s], non_blocking=True)
+                    o += s
+            self._staging_sent()
+        src = {k: (checked[k][1] if k in checked and checked[k][0] == 'dev' else self._t[k]) for k in ('u', 'vel', 'pos')}
+        self._keep = src                                 # the launch is asynchronous: its inputs stay alive
+        T = self._t
+        check(self._lib, self._lib.v2x_sim_channels(
+            self.E, self.n, self.rb, src['u'].data_ptr(), self.n_u, src['vel'].data_ptr(), src['pos'].data_ptr(),
+            T['v2i_shadow'].data_ptr(), T['v2v_shadow'].data_ptr(), T['v2v_abs'].data_ptr(), T['v2i_abs'].data_ptr(),
+            T['v2v_ff'].data_ptr(), T['v2i_ff'].data_ptr(), self._stream()))
+        self._obs_ready = False
+
+    def observe(self, dest=None, power=None):
+        """Observable interference + packed observation of the current channels (v2x_sim_observe) for n_channels = rb.
+        dest [E, n]: the receivers (host integers or an int64 device tensor; None: what the device holds); power: the V2V
+        power entry of the observation (default: the constants' p_v2v).  Results stay on the device (tensor('interf_db'),
+        'state', 'xe', 'mask', 'col', 'regular'); fetch_observation() brings the packed part to the host."""
+        self.check_observe(self.n, self.rb)
+        where = None
+        if dest is not None:
+            where, d = self._check_input('dest', dest, 'i')
+        self._init_device()
+        if where is not None:
+            self._t['dest'].copy_(d if where == 'dev' else self.torch.from_numpy(d))
+        T, c = self._t, self.constants
+        check(self._lib, self._lib.v2x_sim_observe(
+            self.E, self.n, self.rb, T['dest'].data_ptr(), T['v2v_ff'].data_ptr(), T['v2i_ff'].data_ptr(), c['p_v2i'],
+            c['veh_gain'], c['veh_nf'], c['sig2'], float(c['p_v2v'] if power is None else power), T['interf_db'].data_ptr(),
+            T['state'].data_ptr(), T['xe'].data_ptr(), T['mask'].data_ptr(), T['col'].data_ptr(), T['regular'].data_ptr(),
+            self._stream()))
+        self._obs_ready = True
+
+    def fetch_observation(self):
+        """-> (xe [E, n, 16] float32, mask [E, n] int32, col [E, n (n-2)] int32, regular [E] bool) of the last observe():
+        one download, fresh host arrays."""
+        self._init_device()
+        if not self._obs_ready:
+            raise RuntimeError("fetch_observation: no observe() since the last step()")
+        self._obs_host.copy_(self._obs_dev, non_blocking=True)
+        self._sync()
+        v = self._obs_np
+        return v['xe'].copy(), v['mask'].copy(), v['col'].copy(), v['regular'].astype(bool)
+
+    def rates(self, actions, dest=None):
+        """The rates of one joint action per state (v2x_sim_rates): actions [E, n] (or [E, n, 1]) channel numbers, host
+        integers or an int32 device tensor.  A channel outside [0, rb) gives that state NaN rates.  Results stay on the
+        device (tensor('v2v_rate'), ...); fetch_rates() brings them to the host."""
+        where, a = self._check_input('actions', actions, 'a')
+        dwhere = None
+        if dest is not None:
+            dwhere, d = self._check_input('dest', dest, 'i')
+        self._init_device()
+        if dwhere is not None:
+            self._t['dest'].copy_(d if dwhere == 'dev' else self.torch.from_numpy(d))
+        if where == 'host':
+            self._t['actions'].copy_(self.torch.from_numpy(a))
+            a = self._t['actions']
+        self._keep_actions = a
+        T = self._t
+        prob = self.problem()
+        check(self._lib, self._lib.v2x_sim_rates(
+            C.byref(prob), a.data_ptr(), T['v2v_rate'].data_ptr(), T['v2i_rate'].data_ptr(), T['interference'].data_ptr(),
+            T['v2i_interf'].data_ptr(), T['v2v_interf'].data_ptr(), self._stream()))
+
+    def fetch_rates(self):
+        """-> dict of host arrays of the last rates(): v2v_rate [E, n], v2i_rate [E, min(rb, n)], interference [E, rb] (without
+        noise), v2i_interf [E, rb] and v2v_interf [E, n] (with noise); one download."""
+        self._init_device()
+        self._rates_host.copy_(self._rates_dev, non_blocking=True)
+        self._sync()
+        return {k: v.copy() for k, v in self._rates_np.items()}
+
+    # ------------------------------------------------------------------ for OptimalAllocation
+    def problem(self, v2v_weight=0.0, v2i_weight=0.0):
+        """the v2x_opt_problem of the device arrays"""
+        self._init_device()
+        T = self._t
+        return OptProblem(E=self.E, n=self.n, rb=self.rb, pad_=0, v2v_ff=T['v2v_ff'].data_ptr(), v2i_ff=T['v2i_ff'].data_ptr(),
+                          v2i_abs=T['v2i_abs'].data_ptr(), dest=T['dest'].data_ptr(), w_v2v=float(v2v_weight),
+                          w_v2i=float(v2i_weight), **self.constants)
+
+    def problem_tensors(self, device=None):
+        """-> ([v2v_ff, v2i_ff, v2i_abs, dest] device tensors, constants): what OptimalAllocation uploads for a host simulator"""
+        self._init_device()
+        if device is not None and device != self.device:
+            raise ValueError("the simulator state lives on %s, the search runs on %s" % (self.device, device))
+        return [self._t[k] for k in ('v2v_ff', 'v2i_ff', 'v2i_abs', 'dest')], dict(self.constants)
+
+
+# attribute of BatchedEnviron -> (device tensor, host shape from (E, n, rb))
+_DEVICE_ARRAYS = {
+    '_v2i_shadow': ('v2i_shadow', lambda E, n, rb: (E, n)),
+    '_v2v_shadow': ('v2v_shadow', lambda E, n, rb: (E, n, n)),
+    'V2V_channels_abs': ('v2v_abs', lambda E, n, rb: (E, n, n)),
+    'V2I_channels_abs': ('v2i_abs', lambda E, n, rb: (E, n)),
+    'V2V_channels_with_fastfading': ('v2v_ff', lambda E, n, rb: (E, n, n, rb)),
+    'V2I_channels_with_fastfading': ('v2i_ff', lambda E, n, rb: (E, n, rb)),
+    'V2V_Interference_all': ('interf_db', lambda E, n, rb: (E, n, 1, rb)),
+}
+
+
+def _device_array(attr):
+    tensor, shape_of = _DEVICE_ARRAYS[attr]
+
+    def get(self):
+        a = self._host.get(attr)
+        if a is None:
+            if attr not in self._on_device:
+                raise AttributeError(attr)
+            dc = self.device_channels
+            a = dc.download(tensor).reshape(shape_of(dc.E, dc.n, dc.rb))
+            self._host[attr] = a
+        # the caller may write into the array it was handed (new_random_game does): it goes up again before the next device call
+        self._dirty.add(attr)
+        return a
+
+    def set(self, value):
+        self._host[attr] = np.asarray(value, np.float64)
+        self._dirty.add(attr)
+
+    return property(get, set)
+
+
+class DeviceBatchedEnviron(BatchedEnviron):
+    """BatchedEnviron with the channel update, the observable interference, the packed observation and the rates on the GPU
+    (DeviceChannels).  Same constructor and public surface.  Mobility, receivers and the MT19937 streams stay on the host
+    (libv2xsim.so), so positions, directions, receivers and stream states are those of the host simulator bit for bit; the
+    channel arrays and rates agree with it to the rounding of the two math libraries.  Per step the uniforms go up and
+    xe / mask / col / regular, the rates and the interference side outputs come down.  The six large channel arrays and
+    V2V_Interference_all are properties: reading one downloads it (once per step), assigning one uploads it before the next
+    device call -- inherited code keeps working, only slower.  The step is the three-call path (no v2xsim_advance, no
+    look-ahead: lookahead=True is refused)."""
+
+    def __init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=1, seeds=None, workers=None,
+                 native=None, lookahead=False, device=0):
+        if lookahead:
+            raise ValueError("DeviceBatchedEnviron has no look-ahead step (the channel update runs on the GPU); lookahead=True "
+                             "is refused")
+        if seeds is None:
+            raise ValueError("DeviceBatchedEnviron needs one seed per environment (its streams advance in libv2xsim.so)")
+        if native is not None and not native:
+            raise ValueError("DeviceBatchedEnviron keeps mobility and the random streams in libv2xsim.so: native=False is refused")
+        if not native_sim.available():
+            raise RuntimeError("DeviceBatchedEnviron needs libv2xsim.so (python -c 'import __graft_entry__ as g; g.build()')")
+        self._host, self._dirty, self._on_device = {}, set(), set()
+        self._dc = None
+        self._dev_obs = None
+        self.device_index = int(device)
+        BatchedEnviron.__init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=n_envs, seeds=seeds,
+                                workers=workers, native=True, lookahead=False)
+
+    lookahead = property(lambda self: False, lambda self, v: DeviceBatchedEnviron._no_lookahead(v))
+
+    @staticmethod
+    def _no_lookahead(v):
+        if v:
+            raise ValueError("DeviceBatchedEnviron has no look-ahead step; lookahead=True is refused")
+
+    def _one_call_step(self):
+        return False
+
+    def _check_sizes(self, n=None):
+        n = self.n_Veh if n is None else n
+        DeviceChannels.check_observe(int(n), int(self.n_RB))
+        if uniforms_per_step(n, self.n_RB) & 1:
+            raise NotImplementedError("odd number of draws per step")
+
+    def _constants(self):
+        return dict(p_v2v=float(self.V2V_power_dB_List[self.fixed_v2v_power_index]), p_v2i=float(self.V2I_power_dB),
+                    veh_gain=float(self.vehAntGain), bs_gain=float(self.bsAntGain), bs_nf=float(self.bsNoiseFigure),
+                    veh_nf=float(self.vehNoiseFigure), sig2=float(self.sig2))
+
+    @property
+    def device_channels(self):
+        """the DeviceChannels of the current (E, n_Veh, n_RB), every assigned array uploaded"""
+        return self._flush()
+
+    def _flush(self):
+        E, n, rb = self.E, self.n_Veh, self.n_RB
+        dc = self._dc
+        if dc is None or (dc.E, dc.n, dc.rb) != (E, n, rb):
+            self._check_sizes()
+            dc = self._dc = DeviceChannels(E, n, rb, device=self.device_index, constants=self._constants())
+            self._on_device = set()
+            self._dirty = set(k for k in self._host if self._host[k] is not None)
+        for attr in sorted(self._dirty):
+            tensor, shape_of = _DEVICE_ARRAYS[attr]
+            a = self._host[attr]
+            if a.size != int(np.prod(shape_of(E, n, rb))):
+                if attr in ('_v2i_shadow', '_v2v_shadow'):
+                    raise ValueError("%s of shape %s does not fit %d environments of %d links" % (attr, list(a.shape), E, n))
+                self._host.pop(attr)                       # an array of an earlier episode shape: nothing to keep
+                continue
+            dc.upload(tensor, a.reshape(dc.shapes()[tensor]))
+            self._on_device.add(attr)
+        self._dirty = set()
+        return dc
+
+    # ------------------------------------------------------------------ the overridden steps
+    def new_random_game(self, n_Veh=0):
+        self._check_sizes(n_Veh if n_Veh > 0 else self.n_Veh)
+        self._dev_obs = None
+        if n_Veh > 0 and n_Veh != self.n_Veh:
+            self._host, self._dirty, self._on_device, self._dc = {}, set(), set(), None
+        BatchedEnviron.new_random_game(self, n_Veh)
+        self._dev_obs = None                                   # new receivers
+
+    def renew_channels_fastfading(self):
+        """renew_channel + fast fading for all environments on the device: the streams' uniforms go up, nothing comes down"""
+        n, rb = self.n_Veh, self.n_RB
+        self._check_sizes()
+        self._drop_lookahead()
+        self._obs = None
+        self._dev_obs = None
+        with self._rng() as rs:
+            if any(s.gauss_next is not None for s in rs):
+                raise RuntimeError("a stream holds a cached gauss value")
+            u = native_sim.mt_uniforms(self._mt_keys, self._mt_pos, uniforms_per_step(n, rb))
+        dc = self._flush()
+        dc.step(u, self.vel, self.pos)
+        for attr in _DEVICE_ARRAYS:
+            self._host.pop(attr, None)
+            if attr != 'V2V_Interference_all':
+                self._on_device.add(attr)
+        self._on_device.discard('V2V_Interference_all')
+
+    def _observe_device(self):
+        dc = self._flush()
+        dc.observe(self.dest)
+        self._host.pop('V2V_Interference_all', None)
+        self._on_device.add('V2V_Interference_all')
+        self._dev_obs = dc.fetch_observation()
+        return self._dev_obs
+
+    def Compute_Interference(self, actions):
+        """the observable interference in dB (V2V_Interference_all, left on the device) -- and, from the same launch, the
+        packed observation the agent asks for next"""
+        self.finish_step()
+        self._observe_device()
+
+    def observe_packed(self, n_channels=4):
+        self.finish_step()
+        DeviceChannels.check_observe(self.n_Veh, int(n_channels), self.n_RB)
+        if self._dev_obs is None or self._dirty:
+            self._observe_device()
+        return self._dev_obs
+
+    def packed_ok(self, n_channels=4):
+        return bool(n_channels == self.n_RB and 2 < self.n_Veh <= 31 and self.n_RB <= self.n_Veh and 3 * n_channels + 1 <= 16)
+
+    def compute_reward_with_channel_selection(self, actions):
+        self.finish_step()
+        E, n = self.E, self.n_Veh
+        a = np.asarray(actions)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("actions must be integers, got dtype %s" % a.dtype)
+        if a.size != E * n:
+            raise ValueError("actions of shape [%d, %d] or [%d, %d, 1] expected, got %s" % (E, n, E, n, list(a.shape)))
+        self._check_sizes()
+        dc = self._flush()
+        dc.rates(a.reshape(E, n), dest=self.dest)
+        r = dc.fetch_rates()
+        self.V2I_Interference = r['v2i_interf']
+        self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
+        return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
+
+    # ------------------------------------------------------------------ for OptimalAllocation
+    def problem_tensors(self, device=None):
+        """the current state's device arrays for OptimalAllocation (no download, no upload but the receivers)"""
+        self.finish_step()
+        if not np.all(np.asarray(self.activate_links)):
+            raise ValueError("the optimal-allocation search needs every link active")
+        dc = self._flush()
+        dc.upload('dest', self.dest)
+        return dc.problem_tensors(device)
+
+
+for _attr in _DEVICE_ARRAYS:
+    setattr(DeviceBatchedEnviron, _attr, _device_array(_attr))
+del _attr

@@ -9,6 +9,8 @@ among exactly equal rewards the lowest index wins, like np.argmax.
 
     opt = OptimalAllocation()
     index, reward = opt.search(env, agent.v2v_weight, agent.v2i_weight)      # env: Environ (E = 1) or BatchedEnviron
+                                                                               # (or a DeviceChannels / DeviceBatchedEnviron of
+                                                                               #  rl/device_sim.py: its device arrays, no upload)
     actions = opt.decode(index, n, C)                                          # [E, N]
 
 `search` enumerates all C^N joint actions (C^N <= 2^36: 18 links x 4 channels).  `search_bound` finds the same pair by
@@ -288,8 +290,12 @@ class OptimalAllocation(object):
     def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None, n_edges=None):
         """max_nodes not None: the problem of search_bound (its checks, its workspace); local = (restarts, max_sweeps): of
         search_local / rewards_of; n_edges: of landscape."""
-        v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
-        E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
+        on_device = hasattr(env, 'problem_tensors')       # DeviceChannels / DeviceBatchedEnviron (rl/device_sim.py): no upload
+        if on_device:
+            E, (n, rb) = env.E, _sizes(env)
+        else:
+            v2v, v2i, v2i_abs, dest, const = problem_arrays(env)
+            E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
         if local is not None:
             self.check_local(n, rb, *local)
         elif max_nodes is None:
@@ -298,7 +304,10 @@ class OptimalAllocation(object):
             self.check_bound(n, rb, v2v_weight, v2i_weight, max_nodes)
         self._init_device()
         t = self.torch
-        dev = [t.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (v2v, v2i, v2i_abs, dest)]
+        if on_device:
+            dev, const = env.problem_tensors(self.device)
+        else:
+            dev = [t.from_numpy(np.ascontiguousarray(a)).to(self.device) for a in (v2v, v2i, v2i_abs, dest)]
         prob = OptProblem(E=E, n=n, rb=rb, pad_=0, v2v_ff=dev[0].data_ptr(), v2i_ff=dev[1].data_ptr(),
                           v2i_abs=dev[2].data_ptr(), dest=dev[3].data_ptr(), w_v2v=float(v2v_weight),
                           w_v2i=float(v2i_weight), **const)

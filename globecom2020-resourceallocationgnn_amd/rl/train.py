@@ -38,10 +38,12 @@ def start_env(n_links=None):
     return env
 
 
-def start_env_batched(n_links, n_envs, seed, lookahead=None):
+def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", device=0):
     """E environments on the same lane grid, environment e seeded with seed + 104729 e (rl/batched_env.py).
     lookahead: compute every next simulator step on the library's worker thread while the agent scores and replays (same
-    trajectories, see BatchedEnviron); default on, V2X_SIM_LOOKAHEAD=0 switches it off."""
+    trajectories, see BatchedEnviron); default on, V2X_SIM_LOOKAHEAD=0 switches it off.
+    backend: "host" (the default: BatchedEnviron) or "device" (rl/device_sim.py: channel update, observation and rates on the
+    GPU `device`; it has no look-ahead)."""
     import os
     if lookahead is None:
         lookahead = os.environ.get("V2X_SIM_LOOKAHEAD", "1") != "0"
@@ -50,6 +52,14 @@ def start_env_batched(n_links, n_envs, seed, lookahead=None):
     down_lanes = [250 - 3.5 - 3.5 / 2, 250 - 3.5 / 2, 500 - 3.5 - 3.5 / 2, 500 - 3.5 / 2, 750 - 3.5 - 3.5 / 2, 750 - 3.5 / 2]
     left_lanes = [3.5 / 2, 3.5 / 2 + 3.5, 433 + 3.5 / 2, 433 + 3.5 + 3.5 / 2, 866 + 3.5 / 2, 866 + 3.5 + 3.5 / 2]
     right_lanes = [433 - 3.5 - 3.5 / 2, 433 - 3.5 / 2, 866 - 3.5 - 3.5 / 2, 866 - 3.5 / 2, 1299 - 3.5 - 3.5 / 2, 1299 - 3.5 / 2]
+    if backend not in ("host", "device"):
+        raise ValueError("backend must be 'host' or 'device', got %r" % (backend,))
+    if backend == "device":
+        from .device_sim import DeviceBatchedEnviron
+        env = DeviceBatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
+                                   seeds=[seed + 104729 * e for e in range(n_envs)], device=device)
+        env.new_random_game(n_links)
+        return env
     env = BatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
                          seeds=[seed + 104729 * e for e in range(n_envs)])
     env.lookahead = bool(lookahead) and env.native
@@ -64,7 +74,7 @@ def run_train(env, cfg, brain=None, save_dir=None, verbose=False, **brain_kwargs
     return agent, out
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--links", type=int, default=4)
     ap.add_argument("--feedback", type=int, default=16)
@@ -80,7 +90,17 @@ def main(argv=None):
     ap.add_argument("--rollouts", choices=["replicated", "sharded"], default="replicated",
                     help="data-parallel runs: every rank steps the same simulator (bit-identical to one process) or every "
                          "rank its own, contributing 50/G transitions per train step (Agent docstring)")
+    ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
+                    help="with --envs: where the simulators' channel update, observation and rates run -- libv2xsim.so on the "
+                         "host (the default, and the definition) or the GPU (rl/device_sim.py)")
+    return ap
+
+
+def main(argv=None):
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.sim_backend == "device" and args.envs < 1:
+        ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:
         # the simulator drops vehicles in groups of four, one per direction (Environment.py:217-231), and the
         # observation divides by links - 2 (BS_brain.py:405)
@@ -105,8 +125,11 @@ def main(argv=None):
     cfg = RL_Config()
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)       # RL_Train_main.py:33-35,60
     cfg.Num_Episodes, cfg.Num_Train_Steps = args.episodes, args.train_steps
-    env = (start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0)) if args.envs > 0
-           else start_env(args.links))
+    if args.sim_backend == "device":
+        env = start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0), backend="device", device=local)
+    else:
+        env = (start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0)) if args.envs > 0
+               else start_env(args.links))
     t0 = time.perf_counter()
     import contextlib
     ctx = contextlib.nullcontext()

@@ -400,6 +400,51 @@ int  v2x_opt_search_local(const v2x_opt_problem* p, void* workspace, int32_t res
 int  v2x_opt_rewards_actions(const v2x_opt_problem* p, void* workspace, const int32_t* actions, int64_t K, double* out,
                              void* stream);
 
+/* ---- the simulator's channel step, observation and rates on the device (csrc/v2xsimdev.hip) ------------------------
+ * Device counterparts of the host simulator library (include/v2xsim.h, csrc/v2xsim.c: v2xsim_channels, v2xsim_interference +
+ * v2xsim_observe_packed, v2xsim_reward) for E independent simulator states of n vehicles = links and rb resource blocks
+ * whose arrays live in HBM, in the simulator's own layouts (C-contiguous, state major).  The host library stays the
+ * definition: the same expressions in the same order in fp64, no contraction, on the device math library, so results agree
+ * with it to the rounding of the two math libraries, and bit for bit where only sums, differences, divides and casts are
+ * involved (v2x_sim_observe's state / xe / mask / col / regular).  Mobility and the MT19937 streams stay on the host.
+ * All pointers [dev].  Every call is ONE launch, asynchronous on `stream`: no allocation, no synchronisation, no
+ * environment variable read (capturable).  A bad argument is V2X_EINVAL with text in v2x_last_error(NULL), before anything
+ * is launched.  E <= 65535.
+ *
+ * v2x_sim_channels: one channel update (renew_channel + renew_channels_fastfading, Environment.py:378-406 with the path loss
+ * of :94-146) from the step's uniforms u[E][n_u], n_u = n + n^2 + 2 n rb + 2 n^2 rb exactly (always even; anything else
+ * is V2X_EINVAL).  Gaussian k of a state is cos(2 pi u[k & ~1]) sqrt(-2 log(1 - u[k | 1])) for even k and the sin for odd k
+ * (random.gauss order); draw order: V2I shadowing (n), V2V shadowing (n^2, row-major i n + j), V2I fast fading real then
+ * imaginary (n rb each), V2V fast fading real then imaginary (n^2 rb each).  vel[E][n], pos[E][n][2].  v2i_shadow[E][n] and
+ * v2v_shadow[E][n][n] are read and updated IN PLACE; written: v2v_abs[E][n][n] (path loss + shadowing, + 50 on the diagonal),
+ * v2i_abs[E][n], v2v_ff[E][n][n][rb] and v2i_ff[E][n][rb] (abs - 20 log10 |(re + j im) / sqrt 2|).  The outputs must not
+ * overlap each other or the inputs.  1 <= n <= 128, 1 <= rb <= 16.                                                          */
+int  v2x_sim_channels(int32_t E, int32_t n, int32_t rb, const double* u, int32_t n_u, const double* vel, const double* pos,
+                      double* v2i_shadow, double* v2v_shadow, double* v2v_abs, double* v2i_abs, double* v2v_ff,
+                      double* v2i_ff, void* stream);
+/* v2x_sim_observe: Compute_Interference (Environment.py:460-493, the observable part) and Agent.observe (BS_brain.py:389-407,
+ * :441-445, :458-467) in the engine's packed form, for C = rb channels.  dest[E][n]: the receiver of every link;
+ * v2v_ff[E][n][n][C], v2i_ff[E][n][C].  Written: interf_db[E][n][C] = 10 log10(sig2 + the V2I transmitter of block r
+ * (vehicle r) at link k's receiver); state[E][n][3 C + 1] fp64 = [V2V gain | V2I gain | power | edge gain], the sum over
+ * senders p taken in ascending p; xe[E][n][16] float32 = the state row cast to float32, zero padded; mask[E][n]: bit p of
+ * mask[e][q] set when p sends to q (every p but q and q's receiver); col[E][n (n - 2)]: the CSR sources ascending per
+ * destination, all zeros for a state where some dest[k] == k; regular[E] (bytes): 1 unless some dest[k] == k.  A receiver
+ * outside [0, n) is never used as an index: that state's interf_db / state / xe rows are NaN and its regular flag is 0.
+ * 3 <= n <= 31, 1 <= C <= n, 3 C + 1 <= 16 (the limits of v2xsim_observe_packed).                                          */
+int  v2x_sim_observe(int32_t E, int32_t n, int32_t C, const int64_t* dest, const double* v2v_ff, const double* v2i_ff,
+                     double p_v2i, double veh_gain, double veh_nf, double sig2, double power, double* interf_db,
+                     double* state, float* xe, int32_t* mask, int32_t* col, uint8_t* regular, void* stream);
+/* v2x_sim_rates: compute_reward_with_channel_selection (Environment.py:408-458; every link active, one receiver per link)
+ * of ONE joint action per state, ch[E][n] channel numbers, on the arrays and constants of a v2x_opt_problem (w_v2v / w_v2i
+ * unused).  Written: v2v_rate[E][n], v2i_rate[E][min(rb, n)]; may be NULL: interference[E][rb] (V2V power received at the
+ * base station per block, without noise), v2i_interf[E][rb] and v2v_interf[E][n] (with noise).  Fold orders of the host
+ * library: the base-station sum over ascending k per block; at a receiver the V2I transmitter's term first, then the
+ * co-channel links in ascending j.  A channel outside [0, rb) anywhere in a state makes all outputs of that state NaN, a
+ * receiver outside [0, n) those of its link; neither is used as an index.  1 <= n <= 128, 1 <= rb <= 16.                   */
+int  v2x_sim_rates(const v2x_opt_problem* p, const int32_t* ch /*[E][n]*/, double* v2v_rate /*[E][n]*/,
+                   double* v2i_rate /*[E][min(rb,n)]*/, double* interference /*[E][rb]*/, double* v2i_interf /*[E][rb]*/,
+                   double* v2v_interf /*[E][n]*/, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

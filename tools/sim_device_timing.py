@@ -1,0 +1,197 @@
+"""Cost of a simulator step on the device (v2xgnn.rl.DeviceChannels / DeviceBatchedEnviron, csrc/v2xsimdev.hip) next to the host
+library (libv2xsim.so at its default thread count) on the same box, 20 links x 4 resource blocks, E = 1, 50 and 200 simulators:
+
+  device leg  per simulator step of all E states, the wall time of rates + step + observe on DeviceChannels with the uniforms'
+              upload and the small downloads (rates, xe / mask / col / regular) included, and the three kernels' time between
+              HIP events with every input already on the device;
+  host leg    native_sim.advance (mobility + uniforms + channels + interference + observation) from the same state, and
+              env.act() of both environments (rates + the whole step, mobility and MT19937 on the host either way);
+  loop leg    python -m v2xgnn.rl.train --links 20 --feedback 64 --batch 4096 --train-steps 20 --use-graph --envs 50 with both
+              backends, the two taken in turn: ms per train step of the whole run (start-up included), and of the steady
+              state as the difference between a 3-episode and a 1-episode run over their 40 extra train steps (the driver's
+              clock starts after the environment exists, so the device runs have initialised the GPU before it and the host
+              runs after it: only the difference compares like with like); and the same loop with both environments in ONE
+              process, warmed up, Agent.train(1, 20) timed in turn.
+
+Medians over --reps timed steps after --warmup untimed ones; the box's usable CPUs are recorded.
+
+    python tools/sim_device_timing.py [--out profiles/sim_device_timing.json] [--reps 200] [--loop-reps 3] [--no-loop]
+"""
+import argparse
+import json
+import os
+import subprocess
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+LINKS, RB = 20, 4
+
+
+def _median_ms(xs):
+    return round(float(np.median(xs)) * 1e3, 4)
+
+
+def step_legs(E, reps, warmup):
+    import torch
+    from v2xgnn.rl import native_sim
+    from v2xgnn.rl.train import start_env_batched
+    host = start_env_batched(LINKS, E, 7, lookahead=False)
+    dev = start_env_batched(LINKS, E, 7, backend="device")
+    dc = dev.device_channels
+    rng = np.random.default_rng(3)
+    pool = [rng.random((E, dc.n_u)) for _ in range(8)]
+    actions = [rng.integers(0, RB, size=(E, LINKS, 1)) for _ in range(8)]
+    a32 = [a.reshape(E, LINKS).astype(np.int32) for a in actions]
+
+    def device_step(k):
+        dc.rates(a32[k % 8], dest=dev.dest)
+        dc.fetch_rates()
+        dc.step(pool[k % 8], dev.vel, dev.pos)
+        dc.observe(dev.dest)
+        dc.fetch_observation()
+
+    for k in range(warmup):
+        device_step(k)
+    torch.cuda.synchronize()
+    wall = []
+    for k in range(reps):
+        t0 = time.perf_counter()
+        device_step(k)                                            # ends in the observation's download: synchronised
+        wall.append(time.perf_counter() - t0)
+
+    # the three kernels alone: inputs on the device, HIP events around the launches
+    u_t = torch.from_numpy(pool[0]).to(dc.device)
+    vel_t, pos_t = dc.tensor('vel'), dc.tensor('pos')
+    a_t = torch.from_numpy(a32[0]).to(dc.device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    kern = []
+    for k in range(warmup + reps):
+        ev[0].record()
+        dc.step(u_t, vel_t, pos_t)
+        dc.observe()
+        dc.rates(a_t)
+        ev[1].record()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            kern.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+
+    # host: the one-call step of the library from the current state (results dropped: the state does not move)
+    for k in range(warmup):
+        host._start_job(False)
+    adv = []
+    for k in range(reps):
+        t0 = time.perf_counter()
+        host._start_job(False)
+        adv.append(time.perf_counter() - t0)
+
+    def act_times(env):
+        for k in range(warmup):
+            env.act(actions[k % 8])
+            env.observe_packed(RB)
+        out = []
+        for k in range(reps):
+            t0 = time.perf_counter()
+            env.act(actions[k % 8])
+            env.observe_packed(RB)
+            out.append(time.perf_counter() - t0)
+        return out
+
+    act_host, act_dev = act_times(host), act_times(dev)
+    return {"simulators": E, "links": LINKS, "rb": RB, "uniforms_uploaded_bytes": int(pool[0].nbytes),
+            "device_step_wall_ms": _median_ms(wall), "device_step_wall_us_per_simulator": round(_median_ms(wall) * 1e3 / E, 2),
+            "device_kernels_ms": _median_ms(kern), "host_advance_ms": _median_ms(adv),
+            "host_advance_us_per_simulator": round(_median_ms(adv) * 1e3 / E, 2), "host_threads": native_sim._load().v2xsim_max_threads(),
+            "act_host_env_ms": _median_ms(act_host), "act_device_env_ms": _median_ms(act_dev)}
+
+
+def loop_leg(loop_reps):
+    base = [sys.executable, "-m", "v2xgnn.rl.train", "--links", "20", "--feedback", "64", "--batch", "4096", "--train-steps", "20",
+            "--use-graph", "--envs", "50"]
+    runs = {b: {1: [], 3: []} for b in ("host", "device")}
+    for rep in range(loop_reps):
+        for episodes in (1, 3):
+            for backend in ("host", "device"):                      # taken in turn: the box's load drifts
+                cmd = base + ["--episodes", str(episodes), "--sim-backend", backend]
+                done = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+                if done.returncode != 0:
+                    raise RuntimeError("%s failed (%d):\n%s" % (" ".join(cmd), done.returncode, done.stdout[-2000:]))
+                line = [x for x in done.stdout.splitlines() if x.startswith("{")][-1]
+                runs[backend][episodes].append(float(json.loads(line)["wall_s"]))
+    out = {"command": " ".join(base[1:]) + " --sim-backend {host,device}", "runs_per_setting": loop_reps}
+    for b in ("host", "device"):
+        w1, w3 = float(np.median(runs[b][1])), float(np.median(runs[b][3]))
+        out[b] = {"wall_s_1_episode": runs[b][1], "wall_s_3_episodes": runs[b][3],
+                  "ms_per_train_step_whole_run": round(w1 * 1e3 / 20, 3),
+                  "ms_per_train_step_steady": round((w3 - w1) * 1e3 / 40, 3)}
+    return out
+
+
+def loop_in_process(reps):
+    """The same loop with both environments alive in ONE process, so that start-up (device context, library load, replay
+    allocation, captures) is outside the timed region for both alike: one untimed Agent.train(1, 20) each, then `reps` timed
+    ones each, the two backends taken in turn; ms per train step = wall of the call / 20 (one episode reset included)."""
+    import random
+    import torch
+    from v2xgnn.rl import Agent, RL_Config
+    from v2xgnn.rl.train import start_env_batched
+    agents, walls = {}, {"host": [], "device": []}
+    with torch.cuda.stream(torch.cuda.Stream(device=0)):
+        for backend in ("host", "device"):
+            random.seed(1001)
+            np.random.seed(1001)
+            cfg = RL_Config()
+            cfg.set_train_value(64, 0.5, 4096, 1, 0.1)
+            cfg.Num_Episodes, cfg.Num_Train_Steps = 1, 20
+            env = start_env_batched(LINKS, 50, 1001, backend=backend)
+            agents[backend] = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True)
+            agents[backend].train(1, 20)                              # warm-up, untimed
+        torch.cuda.synchronize()
+        for rep in range(reps):
+            for backend in ("host", "device"):
+                t0 = time.perf_counter()
+                agents[backend].train(1, 20)
+                torch.cuda.synchronize()
+                walls[backend].append(time.perf_counter() - t0)
+    return {b: {"wall_s_per_call": [round(w, 4) for w in walls[b]], "ms_per_train_step": round(float(np.median(walls[b])) * 1e3 / 20, 3)}
+            for b in walls}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sim_device_timing.json"))
+    ap.add_argument("--reps", type=int, default=200)
+    ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--loop-reps", type=int, default=3)
+    ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--simulators", type=int, nargs="+", default=[1, 50, 200])
+    args = ap.parse_args()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("sim_device_timing needs a GPU: nothing is measured without one")
+    from v2xgnn.rl.batched_env import _usable_cpus
+    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
+              "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
+    for row in result["steps"]:
+        print(json.dumps(row))
+    if not args.no_loop:
+        result["loop"] = loop_leg(args.loop_reps)
+        print(json.dumps(result["loop"]))
+        try:
+            result["loop_in_process"] = loop_in_process(max(3, args.loop_reps))
+        except Exception as exc:                                       # the legs above are still worth writing down
+            result["loop_in_process"] = {"error": "%s: %s" % (type(exc).__name__, exc)}
+        print(json.dumps(result["loop_in_process"]))
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
