@@ -63,6 +63,17 @@ class OptProblem(C.Structure):
         [(k, C.c_double) for k in ("p_v2v", "p_v2i", "veh_gain", "bs_gain", "bs_nf", "veh_nf", "sig2", "w_v2v", "w_v2i")]
 
 
+class SimStep(C.Structure):
+    """v2x_sim_step of include/v2xgnn.h"""
+    _fields_ = [("problem", OptProblem)] + \
+        [(k, C.c_void_p) for k in ("keys", "mtpos", "xy", "dirs", "vel", "lanes", "u")] + \
+        [("n_lanes", C.c_int32), ("n_u", C.c_int32), ("timestep", C.c_double), ("width", C.c_double), ("height", C.c_double)] + \
+        [(k, C.c_void_p) for k in ("v2i_shadow", "v2v_shadow", "v2v_abs", "v2i_abs", "v2v_ff", "v2i_ff")] + \
+        [("power", C.c_double)] + \
+        [(k, C.c_void_p) for k in ("interf_db", "state", "xe", "mask", "col", "regular", "v2v_rate", "v2i_rate", "interference",
+                                   "v2i_interf", "v2v_interf", "actions")]
+
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -142,6 +153,8 @@ SYMBOLS = [
     ("v2x_sim_channels", C.c_int, [_I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     ("v2x_sim_observe", C.c_int, [_I, _I, _I, _P, _P, _P] + [C.c_double] * 5 + [_P] * 7),
     ("v2x_sim_rates", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P, _P, _P, _P]),
+    ("v2x_sim_stream", C.c_int, [_I, _I, _P, _P, _P, _P, _P, C.c_double, _I, _P, C.c_double, C.c_double, _P, _I, _P]),
+    ("v2x_sim_advance", C.c_int, [C.POINTER(SimStep), _P]),
 ]
 
 

@@ -15,8 +15,18 @@ observation (xe / mask / col / regular) and the rates come down.
     r = dc.fetch_rates()                        # dict: v2v_rate, v2i_rate, interference, v2i_interf, v2v_interf
     index, reward = OptimalAllocation().search(dc, 1.0, 0.1)        # on the device arrays, no upload
 
-`DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: mobility and the MT19937 streams stay on
-the host (libv2xsim.so), the channel update, the observable interference, the observation and the rates run on the device.
+Mobility and the MT19937 streams have a device form too (v2x_sim_stream), and a whole step is one call that needs nothing
+from the host but the actions (v2x_sim_advance: rates, stream, channels, observation -- four launches, capturable):
+
+    dc.set_grid((up, down, left, right), width, height, timestep)
+    dc.upload('keys', keys); dc.upload('mtpos', mtpos); dc.upload('pos', xy); dc.upload('dirs', dirs); dc.upload('vel', vel)
+    dc.stream(mobility=True)                    # moves the vehicles, then the step's uniforms into tensor('u')
+    dc.advance(actions)                         # or all of a step at once
+    dc.traffic                                  # {'bytes_up': ..., 'bytes_down': ...}: every byte this object sent over the bus
+
+`DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
+interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
+(libv2xsim.so) by default and move to the device with streams='device'.
 The host simulator stays the default and the definition; the two agree to the rounding of the two math libraries
 (tests/test_gpu_device_sim.py).  There is no CPU fallback: without a GPU every device call raises.
 """
@@ -25,11 +35,12 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import OptProblem, check, load_library
+from ..lib import OptProblem, SimStep, check, load_library
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
 OBSERVE_MIN_LINKS, OBSERVE_MAX_LINKS, XE_WIDTH = 3, 31, 16
+MT_WORDS, MAX_LANES = 624, 64                            # v2x_sim_stream
 
 # the radio constants of BatchedEnviron (Environment.py:183-212)
 DEFAULT_CONSTANTS = dict(p_v2v=10.0, p_v2i=23.0, veh_gain=3.0, bs_gain=8.0, bs_nf=5.0, veh_nf=9.0, sig2=10 ** (-114 / 10))
@@ -71,6 +82,9 @@ class DeviceChannels(object):
         self._t = {}                                     # name -> device tensor
         self._obs_ready = False
         self._h2d_done = None
+        self._grid = None                                # set_grid(): (lanes [4, n_lanes] float64, width, height, timestep)
+        self._grid_sent = False
+        self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
 
     # ------------------------------------------------------------------ shapes and checks
     def shapes(self):
@@ -79,7 +93,7 @@ class DeviceChannels(object):
                 'v2v_abs': (E, n, n), 'v2i_abs': (E, n), 'v2v_ff': (E, n, n, rb), 'v2i_ff': (E, n, rb), 'dest': (E, n),
                 'actions': (E, n), 'interf_db': (E, n, rb), 'state': (E, n, 3 * rb + 1), 'xe': (E, n, XE_WIDTH), 'mask': (E, n),
                 'col': (E, n * max(n - 2, 0)), 'regular': (E,), 'v2v_rate': (E, n), 'v2i_rate': (E, m), 'interference': (E, rb),
-                'v2i_interf': (E, rb), 'v2v_interf': (E, n)}
+                'v2i_interf': (E, rb), 'v2v_interf': (E, n), 'keys': (E, MT_WORDS), 'mtpos': (E,), 'dirs': (E, n)}
 
     @staticmethod
     def check_observe(n, C, rb=None):
@@ -100,20 +114,25 @@ class DeviceChannels(object):
         if hasattr(a, 'data_ptr'):
             if tuple(a.shape) != shape:
                 raise ValueError("%s: a tensor of shape %s expected, got %s" % (name, list(shape), list(a.shape)))
-            want = {'f': 'torch.float64', 'i': 'torch.int64', 'a': 'torch.int32'}[dtype_kind]
+            want = {'f': 'torch.float64', 'i': 'torch.int64', 'a': 'torch.int32', 'k': 'torch.int32', 'b': 'torch.int8'}[dtype_kind]
             if str(a.dtype) != want or not a.is_contiguous():
                 raise ValueError("%s: a contiguous %s tensor expected, got %s" % (name, want, a.dtype))
             return 'dev', a
         a = np.asarray(a)
-        if dtype_kind in 'ia' and a.dtype.kind not in 'iu':
+        if dtype_kind in 'iakb' and a.dtype.kind not in 'iu':
             raise ValueError("%s must be integers, got dtype %s" % (name, a.dtype))
+        if dtype_kind == 'k' and name == 'keys' and a.dtype.itemsize != 4:
+            raise ValueError("keys must be 32-bit words (uint32, the layout of RandomState.get_state()), got dtype %s" % a.dtype)
         if dtype_kind == 'f' and a.dtype.kind not in 'fiu':
             raise ValueError("%s must be real numbers, got dtype %s" % (name, a.dtype))
         if name == 'actions' and a.shape == shape + (1,):
             a = a.reshape(shape)
         if a.shape != shape and not (name in ('v2v_ff', 'interf_db') and a.size == int(np.prod(shape))):
             raise ValueError("%s: an array of shape %s expected, got %s" % (name, list(shape), list(a.shape)))
-        return 'host', np.ascontiguousarray(a.reshape(shape), {'f': np.float64, 'i': np.int64, 'a': np.int32}[dtype_kind])
+        if dtype_kind == 'k' and name == 'keys':
+            return 'host', np.ascontiguousarray(a.reshape(shape)).view(np.int32)       # (the bits: torch has no uint32 copies)
+        return 'host', np.ascontiguousarray(a.reshape(shape), {'f': np.float64, 'i': np.int64, 'a': np.int32, 'k': np.int32,
+                                                               'b': np.int8}[dtype_kind])
 
     # ------------------------------------------------------------------ device side
     def _init_device(self):
@@ -145,6 +164,12 @@ class DeviceChannels(object):
             self._t[k] = t.zeros(sh[k], dtype=f64, device=self.device)
         self._t['dest'] = t.zeros(sh['dest'], dtype=t.int64, device=self.device)
         self._t['actions'] = t.zeros(sh['actions'], dtype=t.int32, device=self.device)
+        # the stream state of v2x_sim_stream: key words as int32 bits, positions (624: "block used up", nothing to read yet)
+        self._t['keys'] = t.zeros(sh['keys'], dtype=t.int32, device=self.device)
+        self._t['mtpos'] = t.full(sh['mtpos'], MT_WORDS, dtype=t.int32, device=self.device)
+        self._t['dirs'] = t.zeros(sh['dirs'], dtype=t.int8, device=self.device)
+        if self._grid is not None:
+            self._send_grid()
         # the small results, each group one device buffer and one page-locked copy (one download per group)
         self._obs_dev, self._obs_host, self._obs_np = self._group((('xe', t.float32), ('mask', t.int32), ('col', t.int32),
                                                                    ('regular', t.uint8)))
@@ -188,22 +213,34 @@ class DeviceChannels(object):
         self._init_device()
         return self._t[name]
 
+    _KINDS = {'dest': 'i', 'actions': 'a', 'keys': 'k', 'mtpos': 'k', 'dirs': 'b'}
+
+    def _up(self, tensor, host_array):
+        """one host -> device copy, counted"""
+        src = self.torch.from_numpy(host_array)
+        tensor.copy_(src)
+        self.traffic['bytes_up'] += src.numel() * src.element_size()
+
     def upload(self, name, array):
-        """host array -> the device tensor `name` (shadowing states, channel arrays, dest, ...)"""
-        kind = 'i' if name == 'dest' else 'a' if name == 'actions' else 'f'
-        where, a = self._check_input(name, array, kind)
+        """host array -> the device tensor `name` (shadowing states, channel arrays, dest, keys, mtpos, dirs, ...)"""
+        where, a = self._check_input(name, array, self._KINDS.get(name, 'f'))
         self._init_device()
         if where == 'dev':
             self._t[name].copy_(a)
         else:
-            self._t[name].copy_(self.torch.from_numpy(a))
+            self._up(self._t[name], a)
         return self._t[name]
 
     def download(self, *names):
-        """host copies (numpy) of the named device tensors, in order; no names: the six channel arrays"""
+        """host copies (numpy) of the named device tensors, in order; no names: the six channel arrays.  keys come back as
+        uint32 (the layout of RandomState.get_state())."""
         self._init_device()
         names = names or _CHANNEL_TENSORS
-        out = [self._t[k].cpu().numpy() for k in names]
+        out = []
+        for k in names:
+            a = self._t[k].cpu().numpy()
+            self.traffic['bytes_down'] += a.nbytes
+            out.append(a.view(np.uint32) if k == 'keys' else a)
         return out[0] if len(out) == 1 else tuple(out)
 
     # ------------------------------------------------------------------ the three calls
@@ -219,6 +256,7 @@ class DeviceChannels(object):
             self._staging_free()
             for k in host:
                 self._in_np[k][...] = checked[k][1]
+            self.traffic['bytes_up'] += 8 * sum(self._t[k].numel() for k in host)
             if len(host) == 3:
                 self._in_dev.copy_(self._in_host, non_blocking=True)
             else:
@@ -248,8 +286,10 @@ class DeviceChannels(object):
         if dest is not None:
             where, d = self._check_input('dest', dest, 'i')
         self._init_device()
-        if where is not None:
-            self._t['dest'].copy_(d if where == 'dev' else self.torch.from_numpy(d))
+        if where == 'dev':
+            self._t['dest'].copy_(d)
+        elif where is not None:
+            self._up(self._t['dest'], d)
         T, c = self._t, self.constants
         check(self._lib, self._lib.v2x_sim_observe(
             self.E, self.n, self.rb, T['dest'].data_ptr(), T['v2v_ff'].data_ptr(), T['v2i_ff'].data_ptr(), c['p_v2i'],
@@ -265,6 +305,7 @@ class DeviceChannels(object):
         if not self._obs_ready:
             raise RuntimeError("fetch_observation: no observe() since the last step()")
         self._obs_host.copy_(self._obs_dev, non_blocking=True)
+        self.traffic['bytes_down'] += self._obs_host.numel()
         self._sync()
         v = self._obs_np
         return v['xe'].copy(), v['mask'].copy(), v['col'].copy(), v['regular'].astype(bool)
@@ -278,10 +319,12 @@ class DeviceChannels(object):
         if dest is not None:
             dwhere, d = self._check_input('dest', dest, 'i')
         self._init_device()
-        if dwhere is not None:
-            self._t['dest'].copy_(d if dwhere == 'dev' else self.torch.from_numpy(d))
+        if dwhere == 'dev':
+            self._t['dest'].copy_(d)
+        elif dwhere is not None:
+            self._up(self._t['dest'], d)
         if where == 'host':
-            self._t['actions'].copy_(self.torch.from_numpy(a))
+            self._up(self._t['actions'], a)
             a = self._t['actions']
         self._keep_actions = a
         T = self._t
@@ -295,8 +338,85 @@ class DeviceChannels(object):
         noise), v2i_interf [E, rb] and v2v_interf [E, n] (with noise); one download."""
         self._init_device()
         self._rates_host.copy_(self._rates_dev, non_blocking=True)
+        self.traffic['bytes_down'] += self._rates_host.numel()
         self._sync()
         return {k: v.copy() for k, v in self._rates_np.items()}
+
+    # ------------------------------------------------------------------ mobility, streams and the one-call step
+    def set_grid(self, lanes, width, height, timestep):
+        """The lane grid of the mobility rule: lanes = the (up, down, left, right) tables, [4, n_lanes] coordinates (the order
+        of native_sim.positions); the map is [0, width] x [0, height]; timestep: seconds per step.  Goes up once: now, or when
+        the device is first touched."""
+        try:
+            tab = np.ascontiguousarray(np.asarray(lanes, dtype=np.float64))
+        except (TypeError, ValueError):
+            raise ValueError("set_grid: lanes must be four tables of equal length (up, down, left, right)")
+        if tab.ndim != 2 or tab.shape[0] != 4 or not 1 <= tab.shape[1] <= MAX_LANES:
+            raise ValueError("set_grid: lanes of shape [4, 1..%d] expected (up, down, left, right), got %s"
+                             % (MAX_LANES, list(tab.shape)))
+        vals = (float(width), float(height), float(timestep))
+        if not np.all(np.isfinite(tab)) or not all(np.isfinite(v) for v in vals):
+            raise ValueError("set_grid: lanes, width, height and timestep must be finite")
+        self._grid = (tab,) + vals
+        self._grid_sent = False
+        if self.torch is not None:                       # (not inside the next call, which may be under stream capture)
+            self._send_grid()
+
+    def _send_grid(self):
+        if not self._grid_sent:
+            tab = self._grid[0]
+            if 'lanes' not in self._t or tuple(self._t['lanes'].shape) != tab.shape:
+                self._t['lanes'] = self.torch.zeros(tab.shape, dtype=self.torch.float64, device=self.device)
+            self._up(self._t['lanes'], tab)
+            self._grid_sent = True
+
+    def _check_mobility(self, who, mobility):
+        if not isinstance(mobility, (bool, np.bool_)):
+            raise ValueError("%s: mobility must be True or False, got %r" % (who, mobility))
+        if mobility and self._grid is None:
+            raise ValueError("%s: mobility needs the lane grid (set_grid) first" % who)
+
+    def stream(self, mobility=True):
+        """v2x_sim_stream on the resident state: one renew_positions step of every vehicle (mobility=True; needs set_grid and
+        the resident keys / mtpos / pos / dirs / vel), then the next n_u uniforms of every stream into tensor('u') -- what
+        step(dc.tensor('u')) consumes.  Bit for bit native_sim.positions followed by native_sim.mt_uniforms."""
+        self._check_mobility("stream", mobility)
+        self._init_device()
+        T = self._t
+        tab, width, height, timestep = self._grid if mobility else (None, 0.0, 0.0, 0.0)
+        if mobility:
+            self._send_grid()
+        check(self._lib, self._lib.v2x_sim_stream(
+            self.E, self.n, T['keys'].data_ptr(), T['mtpos'].data_ptr(), T['pos'].data_ptr() if mobility else None,
+            T['dirs'].data_ptr(), T['vel'].data_ptr(), timestep, tab.shape[1] if mobility else 0,
+            T['lanes'].data_ptr() if mobility else None, width, height, T['u'].data_ptr(), self.n_u, self._stream()))
+
+    def advance(self, actions=None, power=None):
+        """One whole simulator step in one call (v2x_sim_advance): the rates of `actions` on the current channels (None: no
+        rates), mobility and the step's uniforms, the channel update, the observation -- all on the resident state, so the
+        actions ([E, n] or [E, n, 1] host integers, or an int32 device tensor) are the only thing that goes up.  Results as
+        after rates() / step() / observe(): fetch_rates(), fetch_observation()."""
+        where = None
+        if actions is not None:
+            where, a = self._check_input('actions', actions, 'a')
+        self.check_observe(self.n, self.rb)
+        self._check_mobility("advance", True)
+        self._init_device()
+        self._send_grid()
+        T, c = self._t, self.constants
+        if where == 'host':
+            self._up(T['actions'], a)
+            a = T['actions']
+        self._keep_actions = a if actions is not None else None
+        tab, width, height, timestep = self._grid
+        s = SimStep(problem=self.problem(), n_lanes=tab.shape[1], n_u=self.n_u, timestep=timestep, width=width, height=height,
+                    power=float(c['p_v2v'] if power is None else power), xy=T['pos'].data_ptr(),
+                    actions=a.data_ptr() if actions is not None else None,
+                    **{k: T[k].data_ptr() for k in ('keys', 'mtpos', 'dirs', 'vel', 'lanes', 'u') + _CHANNEL_TENSORS + (
+                        'interf_db', 'state', 'xe', 'mask', 'col', 'regular', 'v2v_rate', 'v2i_rate', 'interference', 'v2i_interf',
+                        'v2v_interf')})
+        check(self._lib, self._lib.v2x_sim_advance(C.byref(s), self._stream()))
+        self._obs_ready = True
 
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
@@ -349,6 +469,29 @@ def _device_array(attr):
     return property(get, set)
 
 
+# the state v2x_sim_stream advances: attribute of BatchedEnviron -> device tensor
+_STREAM_ARRAYS = {'_mt_keys': 'keys', '_mt_pos': 'mtpos', 'pos': 'pos', 'dirs': 'dirs'}
+
+
+def _stream_array(attr):
+    def get(self):
+        self._settle_streams()
+        if self.stream_backend == 'device':
+            # (as above: the caller may write into what it is handed -- the library's draws of a reset do, MTStream does)
+            self._streams_dirty = True
+        try:
+            return self._stream_host[attr]
+        except KeyError:
+            raise AttributeError(attr)
+
+    def set(self, value):
+        self._settle_streams()
+        self._stream_host[attr] = value
+        self._streams_dirty = True
+
+    return property(get, set)
+
+
 class DeviceBatchedEnviron(BatchedEnviron):
     """BatchedEnviron with the channel update, the observable interference, the packed observation and the rates on the GPU
     (DeviceChannels).  Same constructor and public surface.  Mobility, receivers and the MT19937 streams stay on the host
@@ -357,10 +500,43 @@ class DeviceBatchedEnviron(BatchedEnviron):
     xe / mask / col / regular, the rates and the interference side outputs come down.  The six large channel arrays and
     V2V_Interference_all are properties: reading one downloads it (once per step), assigning one uploads it before the next
     device call -- inherited code keeps working, only slower.  The step is the three-call path (no v2xsim_advance, no
-    look-ahead: lookahead=True is refused)."""
+    look-ahead: lookahead=True is refused).
+
+    streams='device': mobility and the MT19937 streams live on the device as well (v2x_sim_stream), and act() is ONE
+    enqueue, DeviceChannels.advance(actions), followed by the download of the rates and of the observation; per step only
+    the actions go up.  Velocities, receivers and the lane grid go up when they change: at a reset (assign `vel` / `dest`
+    anywhere else and call new_random_game, or upload them through device_channels).  _mt_keys, _mt_pos, pos and dirs become
+    pull-on-read like the channel arrays: a read after a device step downloads all four into the same numpy arrays, in
+    place (the MTStream objects are attached to rows of _mt_keys), and marks them as possibly written, so they go up again
+    before the next device call.  The host draws of a reset (reset_vehicles, mt_uniforms, sample_dest, anything through an
+    MTStream) therefore cost one pull and one push; a step costs none.  Trajectories are those of streams='host' bit for bit.
+
+    Who holds the newer copy of the stream state (keys, positions in the stream, vehicle positions, directions), with
+    streams='device' (with streams='host' the host always does and the flags below stay False):
+
+      _streams_ahead   the device's copy is newer: a device step ran.  Set by act() and by the device channel update; cleared
+                       by _settle_streams(), which downloads into the same host arrays.
+      _streams_dirty   the host's copy may be newer: somebody was handed one of the four arrays (a read settles first, so
+                       the two flags are never set together).  Cleared by _flush(), which uploads before a device call.
+      _move_pending    renew_positions() was called and its walk has not been made: the next device channel update makes
+                       it (stream(mobility=True)); a read of the four arrays, a flush for anything else or a second
+                       renew_positions() makes it on the host instead (_settle_streams, after the download if one is due).
+      _static_dirty    velocities, receivers or the lane grid changed (a reset, a new DeviceChannels): _flush() uploads them.
+      _in_reset        new_random_game() is running: its draws are the host's, so its channel update takes uniforms,
+                       velocities and positions from the host like streams='host' and _flush() uploads no stream state
+                       (everything goes up once, at the first device call after the reset).
+
+      event                                   ahead  dirty   copies moved
+      read / assign one of the four arrays    -> F   -> T    download if ahead (then the pending move, on the host)
+      MTStream draw (on_touch)                -> F   -> T    the same
+      _flush() before a device call           F      -> F    upload if dirty (not during a reset)
+      act(), device channel update            -> T   F       none: the device advances its own copy
+      new_random_game()                       -> F   -> T    download if ahead; the upload waits for the next device call"""
 
     def __init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=1, seeds=None, workers=None,
-                 native=None, lookahead=False, device=0):
+                 native=None, lookahead=False, device=0, streams='host'):
+        if streams not in ('host', 'device'):
+            raise ValueError("streams must be 'host' or 'device', got %r" % (streams,))
         if lookahead:
             raise ValueError("DeviceBatchedEnviron has no look-ahead step (the channel update runs on the GPU); lookahead=True "
                              "is refused")
@@ -374,8 +550,18 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._dc = None
         self._dev_obs = None
         self.device_index = int(device)
+        self.stream_backend = streams                          # ('streams' is the list of MTStream objects)
+        self._stream_host = {}                                 # the host copies of _STREAM_ARRAYS
+        self._streams_dirty = False                            # ... may have been written since they last went up
+        self._streams_ahead = False                            # ... are older than the device's (a device step ran)
+        self._static_dirty = True                              # vel / dest / the lane grid changed (a reset)
+        self._move_pending = False                             # renew_positions() waits for the stream call of the channel update
+        self._in_reset = False
         BatchedEnviron.__init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=n_envs, seeds=seeds,
                                 workers=workers, native=True, lookahead=False)
+        if streams == 'device':
+            for st in self.streams:                            # a draw through an MTStream reads its row of _mt_keys: pull first
+                st.on_touch = self._touch_streams
 
     lookahead = property(lambda self: False, lambda self, v: DeviceBatchedEnviron._no_lookahead(v))
 
@@ -403,14 +589,48 @@ class DeviceBatchedEnviron(BatchedEnviron):
         """the DeviceChannels of the current (E, n_Veh, n_RB), every assigned array uploaded"""
         return self._flush()
 
-    def _flush(self):
+    # ------------------------------------------------------------------ streams='device': who holds the newer stream state
+    def _touch_streams(self):
+        self._drop_lookahead()
+        self._settle_streams()
+        self._streams_dirty = True
+
+    def _settle_streams(self):
+        """the host copies of keys / positions / directions are current: a pending move is made, the device's newer state is
+        downloaded IN PLACE"""
+        if self._streams_ahead:
+            self._streams_ahead = False
+            got = self._dc.download(*[_STREAM_ARRAYS[k] for k in ('_mt_keys', '_mt_pos', 'pos', 'dirs')])
+            for k, a in zip(('_mt_keys', '_mt_pos', 'pos', 'dirs'), got):
+                self._stream_host[k][...] = a.reshape(self._stream_host[k].shape)
+        if self._move_pending:                                 # renew_positions() without its channel update: the host's walk
+            self._move_pending = False
+            BatchedEnviron.renew_positions(self)
+
+    def _flush(self, settle=True):
         E, n, rb = self.E, self.n_Veh, self.n_RB
+        if settle and self._move_pending:
+            self._settle_streams()
         dc = self._dc
         if dc is None or (dc.E, dc.n, dc.rb) != (E, n, rb):
             self._check_sizes()
+            if self._streams_ahead:                            # (the old shape's device state is the newer one: keep it)
+                self._settle_streams()
             dc = self._dc = DeviceChannels(E, n, rb, device=self.device_index, constants=self._constants())
             self._on_device = set()
             self._dirty = set(k for k in self._host if self._host[k] is not None)
+            self._streams_dirty = self._static_dirty = True
+        if self.stream_backend == 'device' and not self._in_reset:   # (a reset's channel update takes everything from the host)
+            if self._static_dirty:
+                p = self._proto
+                dc.set_grid((p.up_lanes, p.down_lanes, p.left_lanes, p.right_lanes), p.width, p.height, p.timestep)
+                dc.upload('vel', self.vel)
+                dc.upload('dest', self.dest)
+                self._static_dirty = False
+            if self._streams_dirty and not self._streams_ahead:
+                for k in ('_mt_keys', '_mt_pos', 'pos', 'dirs'):
+                    dc.upload(_STREAM_ARRAYS[k], self._stream_host[k])
+                self._streams_dirty = False
         for attr in sorted(self._dirty):
             tensor, shape_of = _DEVICE_ARRAYS[attr]
             a = self._host[attr]
@@ -428,29 +648,87 @@ class DeviceBatchedEnviron(BatchedEnviron):
     def new_random_game(self, n_Veh=0):
         self._check_sizes(n_Veh if n_Veh > 0 else self.n_Veh)
         self._dev_obs = None
+        self._settle_streams()                                 # the reset draws on the host: its copy of the streams first
         if n_Veh > 0 and n_Veh != self.n_Veh:
             self._host, self._dirty, self._on_device, self._dc = {}, set(), set(), None
-        BatchedEnviron.new_random_game(self, n_Veh)
+        self._in_reset = True
+        try:
+            BatchedEnviron.new_random_game(self, n_Veh)
+        finally:
+            self._in_reset = False
+        self._static_dirty = True                              # new velocities and receivers
         self._dev_obs = None                                   # new receivers
 
+    def renew_positions(self):
+        if self.stream_backend != 'device':
+            return BatchedEnviron.renew_positions(self)
+        # the walk rides on the stream call of the channel update that follows (v2x_sim_stream moves, then draws); anything
+        # that looks at the streams or the positions first gets the host's walk (_settle_streams)
+        self._drop_lookahead()
+        if self._move_pending:                                 # a second move with no channel update in between: the first
+            self._settle_streams()                             # one is made on the host (one pull); otherwise nothing moves
+        self._move_pending = True
+
+    def _channels_updated(self):
+        for attr in _DEVICE_ARRAYS:
+            self._host.pop(attr, None)
+            if attr != 'V2V_Interference_all':
+                self._on_device.add(attr)
+        self._on_device.discard('V2V_Interference_all')
+
     def renew_channels_fastfading(self):
-        """renew_channel + fast fading for all environments on the device: the streams' uniforms go up, nothing comes down"""
+        """renew_channel + fast fading for all environments on the device: the streams' uniforms go up, nothing comes down
+        (streams='device': they are drawn there, nothing goes up; during a reset, whose other draws are the host's, they are
+        drawn on the host like with streams='host')"""
         n, rb = self.n_Veh, self.n_RB
         self._check_sizes()
         self._drop_lookahead()
         self._obs = None
         self._dev_obs = None
+        if self.stream_backend == 'device' and not self._in_reset:
+            if any(s.gauss_next is not None for s in self.streams):
+                raise RuntimeError("a stream holds a cached gauss value")
+            move, self._move_pending = self._move_pending, False
+            dc = self._flush(settle=False)
+            dc.stream(mobility=move)
+            dc.step(dc.tensor('u'))
+            self._streams_ahead = True
+            self._channels_updated()
+            return
         with self._rng() as rs:
             if any(s.gauss_next is not None for s in rs):
                 raise RuntimeError("a stream holds a cached gauss value")
             u = native_sim.mt_uniforms(self._mt_keys, self._mt_pos, uniforms_per_step(n, rb))
         dc = self._flush()
         dc.step(u, self.vel, self.pos)
-        for attr in _DEVICE_ARRAYS:
-            self._host.pop(attr, None)
-            if attr != 'V2V_Interference_all':
-                self._on_device.add(attr)
-        self._on_device.discard('V2V_Interference_all')
+        self._channels_updated()
+
+    def act(self, actions):
+        """rates under `actions`, then one simulator step.  streams='device': one enqueue (DeviceChannels.advance) and the
+        downloads of the rates and of the observation; the actions are all that goes up."""
+        if self.stream_backend != 'device':
+            return BatchedEnviron.act(self, actions)
+        self.finish_step()
+        E, n = self.E, self.n_Veh
+        a = np.asarray(actions)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("actions must be integers, got dtype %s" % a.dtype)
+        if a.size != E * n:
+            raise ValueError("actions of shape [%d, %d] or [%d, %d, 1] expected, got %s" % (E, n, E, n, list(a.shape)))
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        self._obs = None
+        dc = self._flush()
+        dc.advance(a.reshape(E, n))
+        self._streams_ahead = True
+        self._channels_updated()
+        self._on_device.add('V2V_Interference_all')
+        r = dc.fetch_rates()
+        self._dev_obs = dc.fetch_observation()
+        self.V2I_Interference = r['v2i_interf']
+        self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
+        return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
 
     def _observe_device(self):
         dc = self._flush()
@@ -505,4 +783,6 @@ class DeviceBatchedEnviron(BatchedEnviron):
 
 for _attr in _DEVICE_ARRAYS:
     setattr(DeviceBatchedEnviron, _attr, _device_array(_attr))
+for _attr in _STREAM_ARRAYS:
+    setattr(DeviceBatchedEnviron, _attr, _stream_array(_attr))
 del _attr

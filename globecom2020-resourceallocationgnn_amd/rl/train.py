@@ -38,12 +38,14 @@ def start_env(n_links=None):
     return env
 
 
-def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", device=0):
+def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", device=0, streams="host"):
     """E environments on the same lane grid, environment e seeded with seed + 104729 e (rl/batched_env.py).
     lookahead: compute every next simulator step on the library's worker thread while the agent scores and replays (same
     trajectories, see BatchedEnviron); default on, V2X_SIM_LOOKAHEAD=0 switches it off.
     backend: "host" (the default: BatchedEnviron) or "device" (rl/device_sim.py: channel update, observation and rates on the
-    GPU `device`; it has no look-ahead)."""
+    GPU `device`; it has no look-ahead).
+    streams: with backend="device", where mobility and the MT19937 streams advance: "host" (libv2xsim.so, the default) or
+    "device" (a step is then one enqueue that takes only the actions from the host)."""
     import os
     if lookahead is None:
         lookahead = os.environ.get("V2X_SIM_LOOKAHEAD", "1") != "0"
@@ -54,10 +56,14 @@ def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", dev
     right_lanes = [433 - 3.5 - 3.5 / 2, 433 - 3.5 / 2, 866 - 3.5 - 3.5 / 2, 866 - 3.5 / 2, 1299 - 3.5 - 3.5 / 2, 1299 - 3.5 / 2]
     if backend not in ("host", "device"):
         raise ValueError("backend must be 'host' or 'device', got %r" % (backend,))
+    if streams not in ("host", "device"):
+        raise ValueError("streams must be 'host' or 'device', got %r" % (streams,))
+    if streams == "device" and backend != "device":
+        raise ValueError("streams='device' needs backend='device' (the host simulator's streams live in libv2xsim.so)")
     if backend == "device":
         from .device_sim import DeviceBatchedEnviron
         env = DeviceBatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
-                                   seeds=[seed + 104729 * e for e in range(n_envs)], device=device)
+                                   seeds=[seed + 104729 * e for e in range(n_envs)], device=device, streams=streams)
         env.new_random_game(n_links)
         return env
     env = BatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
@@ -93,12 +99,17 @@ def build_parser():
     ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
                     help="with --envs: where the simulators' channel update, observation and rates run -- libv2xsim.so on the "
                          "host (the default, and the definition) or the GPU (rl/device_sim.py)")
+    ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
+                    help="with --sim-backend device: where mobility and the simulators' MT19937 streams advance -- libv2xsim.so "
+                         "(the default) or the GPU, where a step is one enqueue that takes only the actions from the host")
     return ap
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.sim_streams == "device" and args.sim_backend != "device":
+        ap.error("--sim-streams device needs --sim-backend device")
     if args.sim_backend == "device" and args.envs < 1:
         ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:
@@ -126,7 +137,8 @@ def main(argv=None):
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)       # RL_Train_main.py:33-35,60
     cfg.Num_Episodes, cfg.Num_Train_Steps = args.episodes, args.train_steps
     if args.sim_backend == "device":
-        env = start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0), backend="device", device=local)
+        env = start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0), backend="device", device=local,
+                                streams=args.sim_streams)
     else:
         env = (start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0)) if args.envs > 0
                else start_env(args.links))

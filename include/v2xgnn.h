@@ -406,10 +406,11 @@ int  v2x_opt_rewards_actions(const v2x_opt_problem* p, void* workspace, const in
  * whose arrays live in HBM, in the simulator's own layouts (C-contiguous, state major).  The host library stays the
  * definition: the same expressions in the same order in fp64, no contraction, on the device math library, so results agree
  * with it to the rounding of the two math libraries, and bit for bit where only sums, differences, divides and casts are
- * involved (v2x_sim_observe's state / xe / mask / col / regular).  Mobility and the MT19937 streams stay on the host.
- * All pointers [dev].  Every call is ONE launch, asynchronous on `stream`: no allocation, no synchronisation, no
- * environment variable read (capturable).  A bad argument is V2X_EINVAL with text in v2x_last_error(NULL), before anything
- * is launched.  E <= 65535.
+ * involved (v2x_sim_observe's state / xe / mask / col / regular; v2x_sim_stream's positions, directions, stream states and
+ * uniforms).  Mobility and the MT19937 streams may stay on the host (a step then receives its uniforms) or live in HBM too
+ * (v2x_sim_stream, v2x_sim_advance).  All pointers [dev].  Every call is ONE launch (v2x_sim_advance: four), asynchronous on
+ * `stream`: no allocation, no synchronisation, no environment variable read (capturable).  A bad argument is V2X_EINVAL
+ * with text in v2x_last_error(NULL), before anything is launched.  E <= 65535.
  *
  * v2x_sim_channels: one channel update (renew_channel + renew_channels_fastfading, Environment.py:378-406 with the path loss
  * of :94-146) from the step's uniforms u[E][n_u], n_u = n + n^2 + 2 n rb + 2 n^2 rb exactly (always even; anything else
@@ -444,6 +445,48 @@ int  v2x_sim_observe(int32_t E, int32_t n, int32_t C, const int64_t* dest, const
 int  v2x_sim_rates(const v2x_opt_problem* p, const int32_t* ch /*[E][n]*/, double* v2v_rate /*[E][n]*/,
                    double* v2i_rate /*[E][min(rb,n)]*/, double* interference /*[E][rb]*/, double* v2i_interf /*[E][rb]*/,
                    double* v2v_interf /*[E][n]*/, void* stream);
+/* v2x_sim_stream: mobility and the random streams of E states (v2xsim_positions, then v2xsim_mt_uniforms), bit for bit the
+ * host library's.  keys[E][624] / mtpos[E]: the MT19937 states in numpy's RandomState layout, advanced in place; a block of
+ * 624 words is regenerated only when a word is needed and the position is 624, never eagerly, so after a call that ends
+ * exactly at a block's end mtpos is 624 and keys is the block just used up (what RandomState.get_state() reports).  A
+ * position outside [0, 624] reads as 624.  xy[E][n][2] / dirs[E][n] (0 up, 1 down, 2 left, 3 right) / vel[E][n]: one
+ * renew_positions step of `timestep` seconds (Environment.py:236-345): vehicles in index order, the crossing lanes of
+ * lanes[4][n_lanes] (tables up, down, left, right) in the reference's checking order, one 53-bit draw per reached lane (turn
+ * when it is < 0.4), then re-entry of the vehicles that left [0, width] x [0, height].  xy == NULL: no mobility (dirs, vel
+ * and lanes are not read).  Then u[E][n_u] = the next n_u doubles of every stream, (a >> 5, b >> 6) -> (a 2^26 + b) / 2^53 of
+ * consecutive tempered words.  1 <= n <= 128, 1 <= n_lanes <= 64, n_u even and >= 2.                                         */
+int  v2x_sim_stream(int32_t E, int32_t n, uint32_t* keys /*[E][624]*/, int32_t* mtpos /*[E]*/,
+                    double* xy /*[E][n][2] or NULL: no mobility*/, int8_t* dirs /*[E][n]*/, const double* vel /*[E][n]*/,
+                    double timestep, int32_t n_lanes, const double* lanes /*[4][n_lanes]: up, down, left, right*/,
+                    double width, double height, double* u /*[E][n_u]*/, int32_t n_u, void* stream);
+/* v2x_sim_advance: one whole simulator step of E states from nothing but the actions -- the device counterpart of
+ * v2xsim_advance (include/v2xsim.h).  Enqueues, in this order, v2x_sim_rates of `actions` on the CURRENT channels (skipped
+ * when actions is NULL), v2x_sim_stream (mobility, then the step's n_u uniforms into u), v2x_sim_channels on the moved
+ * positions and v2x_sim_observe with C = rb: four launches on one stream, no parallel branches (capturable).  Every
+ * argument check of the four calls is made before the first launch.  problem: E, n, rb, the constants, dest, and v2v_ff /
+ * v2i_ff / v2i_abs, which must be the step's own arrays of the same names.  Limits: those of v2x_sim_observe (3..31 links,
+ * rb <= n, 3 rb + 1 <= 16) and n_u == n + n^2 + 2 n rb + 2 n^2 rb, even.                                                      */
+typedef struct v2x_sim_step {
+  v2x_opt_problem problem;
+  uint32_t* keys;          /* [E][624]  */
+  int32_t* mtpos;          /* [E]       */
+  double* xy;              /* [E][n][2] */
+  int8_t* dirs;            /* [E][n]    */
+  const double* vel;       /* [E][n]    */
+  const double* lanes;     /* [4][n_lanes] */
+  double* u;               /* [E][n_u]: the uniforms of the step (written, then read by the channel update) */
+  int32_t n_lanes, n_u;
+  double timestep, width, height;
+  double *v2i_shadow, *v2v_shadow, *v2v_abs, *v2i_abs, *v2v_ff, *v2i_ff;        /* as v2x_sim_channels */
+  double power;                                                                   /* as v2x_sim_observe  */
+  double *interf_db, *state;
+  float* xe;
+  int32_t *mask, *col;
+  uint8_t* regular;
+  double *v2v_rate, *v2i_rate, *interference, *v2i_interf, *v2v_interf;          /* as v2x_sim_rates; the last three may be NULL */
+  const int32_t* actions;  /* [E][n]; NULL: no rates */
+} v2x_sim_step;
+int  v2x_sim_advance(const v2x_sim_step* s, void* stream);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream

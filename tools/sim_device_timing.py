@@ -16,6 +16,13 @@ library (libv2xsim.so at its default thread count) on the same box, 20 links x 4
 Medians over --reps timed steps after --warmup untimed ones; the box's usable CPUs are recorded.
 
     python tools/sim_device_timing.py [--out profiles/sim_device_timing.json] [--reps 200] [--loop-reps 3] [--no-loop]
+
+--mode streams measures the device environment with mobility and the MT19937 streams on the device too (streams='device':
+one v2x_sim_advance per step) against the same environment with host streams and against the host simulator, all three alive
+in one process: env.act() + observe_packed() wall time, the bytes each device environment moves per step (DeviceChannels.traffic),
+the four launches of v2x_sim_advance between HIP events, and the DQN loop of the in-process leg above for the three of them.
+
+    python tools/sim_device_timing.py --mode streams [--out profiles/sim_device_streams_timing.json]
 """
 import argparse
 import json
@@ -161,9 +168,101 @@ def loop_in_process(reps):
             for b in walls}
 
 
+SETTINGS = {"host": dict(backend="host"), "device_host_streams": dict(backend="device", streams="host"),
+            "device_device_streams": dict(backend="device", streams="device")}
+
+
+def streams_legs(E, reps, warmup):
+    import torch
+    from v2xgnn.rl.train import start_env_batched
+    envs = {"host": start_env_batched(LINKS, E, 7, lookahead=False)}
+    for name in ("device_host_streams", "device_device_streams"):
+        envs[name] = start_env_batched(LINKS, E, 7, **SETTINGS[name])
+    rng = np.random.default_rng(3)
+    actions = [rng.integers(0, RB, size=(E, LINKS, 1)) for _ in range(8)]
+    walls = {name: [] for name in envs}
+    traffic = {}
+    for k in range(warmup):
+        for env in envs.values():
+            env.act(actions[k % 8])
+            env.observe_packed(RB)
+    for name in ("device_host_streams", "device_device_streams"):
+        traffic[name] = dict(envs[name].device_channels.traffic)
+    for k in range(reps):
+        for name, env in envs.items():                              # taken in turn: the box's load drifts
+            t0 = time.perf_counter()
+            env.act(actions[k % 8])
+            env.observe_packed(RB)                                  # (what the agent reads next: ends synchronised)
+            walls[name].append(time.perf_counter() - t0)
+    row = {"simulators": E, "links": LINKS, "rb": RB}
+    for name in envs:
+        row["act_%s_ms" % name] = _median_ms(walls[name])
+    for name, before in traffic.items():
+        after = envs[name].device_channels.traffic
+        for k in ("bytes_up", "bytes_down"):
+            row["%s_%s_per_step" % (name, k)] = (after[k] - before[k]) // reps
+    # the four launches of one v2x_sim_advance alone: actions on the device, HIP events around the call
+    dc = envs["device_device_streams"].device_channels
+    a_t = torch.from_numpy(actions[0].reshape(E, LINKS).astype(np.int32)).to(dc.device)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    kern = []
+    for k in range(warmup + reps):
+        ev[0].record()
+        dc.advance(a_t)
+        ev[1].record()
+        torch.cuda.synchronize()
+        if k >= warmup:
+            kern.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+    row["advance_kernels_ms"] = _median_ms(kern)
+    return row
+
+
+def loop_in_process_streams(reps):
+    """loop_in_process for the host simulator (with look-ahead), the device environment with host streams and the device
+    environment with device streams: all three alive and warmed up in ONE process, Agent.train(1, 20) timed in turn"""
+    import random
+    import torch
+    from v2xgnn.rl import Agent, RL_Config
+    from v2xgnn.rl.train import start_env_batched
+    agents, walls = {}, {name: [] for name in SETTINGS}
+    with torch.cuda.stream(torch.cuda.Stream(device=0)):
+        for name, kw in SETTINGS.items():
+            random.seed(1001)
+            np.random.seed(1001)
+            cfg = RL_Config()
+            cfg.set_train_value(64, 0.5, 4096, 1, 0.1)
+            cfg.Num_Episodes, cfg.Num_Train_Steps = 1, 20
+            env = start_env_batched(LINKS, 50, 1001, **kw)
+            agents[name] = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True)
+            agents[name].train(1, 20)                                 # warm-up, untimed
+        torch.cuda.synchronize()
+        for rep in range(reps):
+            for name in SETTINGS:
+                t0 = time.perf_counter()
+                agents[name].train(1, 20)
+                torch.cuda.synchronize()
+                walls[name].append(time.perf_counter() - t0)
+    return {b: {"wall_s_per_call": [round(w, 4) for w in walls[b]], "ms_per_train_step": round(float(np.median(walls[b])) * 1e3 / 20, 3)}
+            for b in walls}
+
+
+def main_streams(args):
+    import torch
+    from v2xgnn.rl.batched_env import _usable_cpus
+    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
+              "steps": [streams_legs(E, args.reps, args.warmup) for E in args.simulators]}
+    for row in result["steps"]:
+        print(json.dumps(row))
+    if not args.no_loop:
+        result["loop_in_process"] = loop_in_process_streams(max(3, args.loop_reps))
+        print(json.dumps(result["loop_in_process"]))
+    return result
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sim_device_timing.json"))
+    ap.add_argument("--mode", choices=["channels", "streams"], default="channels")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--loop-reps", type=int, default=3)
@@ -173,12 +272,17 @@ def main():
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("sim_device_timing needs a GPU: nothing is measured without one")
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "sim_device_streams_timing.json" if args.mode == "streams" else "sim_device_timing.json")
     from v2xgnn.rl.batched_env import _usable_cpus
-    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
-              "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
-    for row in result["steps"]:
-        print(json.dumps(row))
-    if not args.no_loop:
+    if args.mode == "streams":
+        result = main_streams(args)
+    else:
+        result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
+                  "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
+        for row in result["steps"]:
+            print(json.dumps(row))
+    if args.mode != "streams" and not args.no_loop:
         result["loop"] = loop_leg(args.loop_reps)
         print(json.dumps(result["loop"]))
         try:
