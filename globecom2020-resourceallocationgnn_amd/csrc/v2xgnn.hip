@@ -1970,6 +1970,11 @@ int presize_rows(v2x_model* m, int n_rows) {
 // the v2x_last_error(NULL) text, for the entry points of the other translation units (v2xopt.hip)
 namespace v2x {
 void set_global_error(const char* text) { g_err = text; }
+// links, channels and whether the graphs may differ in size: what v2x_rollout_step (v2xsimdev.hip) checks a batch against
+// before it launches anything
+void model_dims(const v2x_model* m, int* n_nodes, int* n_channels, int* variable_graphs) {
+  *n_nodes = m->N; *n_channels = m->C; *variable_graphs = m->cfg.variable_graphs;
+}
 }
 
 // ======================================================================================= C ABI

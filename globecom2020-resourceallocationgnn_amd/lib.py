@@ -74,6 +74,15 @@ class SimStep(C.Structure):
                                    "v2i_interf", "v2v_interf", "actions")]
 
 
+class Rollout(C.Structure):
+    """v2x_rollout of include/v2xgnn.h"""
+    _fields_ = [("model", C.c_void_p), ("batch", Batch)] + \
+        [(k, C.c_void_p) for k in ("q", "explore", "random_actions", "actions")] + \
+        [("step", SimStep), ("w_v2v", C.c_double), ("w_v2i", C.c_double)] + \
+        [(k, C.c_void_p) for k in ("rep_xe", "rep_xe_next", "rep_col", "rep_mask", "rep_action", "rep_reward")] + \
+        [("head", C.c_int64), ("capacity", C.c_int64), ("result_reward", C.c_void_p), ("result_regular", C.c_void_p)]
+
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -155,6 +164,9 @@ SYMBOLS = [
     ("v2x_sim_rates", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P, _P, _P, _P]),
     ("v2x_sim_stream", C.c_int, [_I, _I, _P, _P, _P, _P, _P, C.c_double, _I, _P, C.c_double, C.c_double, _P, _I, _P]),
     ("v2x_sim_advance", C.c_int, [C.POINTER(SimStep), _P]),
+    ("v2x_rollout_pick", C.c_int, [_I, _I, _I] + [_P] * 11 + [_L, _L, _P, _P]),
+    ("v2x_rollout_store", C.c_int, [_I, _I, _I, _P, _P, C.c_double, C.c_double] + [_P] * 6 + [_L, _L, _P, _P, _P]),
+    ("v2x_rollout_step", C.c_int, [C.POINTER(Rollout), _P]),
 ]
 
 

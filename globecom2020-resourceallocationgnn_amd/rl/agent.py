@@ -25,6 +25,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 
 OPT_BACKENDS = ('host', 'device', 'bound', 'local')
+ROLLOUT_BACKENDS = ('host', 'device')
 
 
 def _check_opt_backend(opt_backend):
@@ -75,8 +76,15 @@ class Memory(object):
 
 class Agent(object):
     def __init__(self, num_d2d, num_ch, num_neighbor, num_d2d_feedback, environment, curr_rl_config, brain=None,
-                 device_replay='auto', rollouts='replicated', **brain_kwargs):
-        """device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
+                 device_replay='auto', rollouts='replicated', rollout_backend='host', **brain_kwargs):
+        """rollout_backend: 'host' (the default: _packed_iteration -- the observation comes down, is scored, the actions go up,
+        the transitions go up again) or 'device': a whole rollout iteration is ONE call on the resident state (v2x_rollout_step:
+        score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
+        needs a DeviceBatchedEnviron with streams='device', the HBM replay memory, the gfx950 engine, one receiver per link and
+        no data parallelism; anything else is a ValueError here.  Same transitions, rewards and numpy draws as 'host', bit for
+        bit (tests/test_gpu_rollout_device.py).
+
+        device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
         visiting the host; 'auto' = whenever the brain runs on the gfx950 engine.
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
@@ -131,6 +139,30 @@ class Agent(object):
             if not on_gpu:
                 raise ValueError("device_replay needs a brain on the gfx950 engine")
             self.device_replay = DeviceReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device)
+        self._check_rollout_backend(rollout_backend, on_gpu)
+        self.rollout_backend = rollout_backend
+        self._lazy_rewards = None
+
+    def _check_rollout_backend(self, rollout_backend, on_gpu):
+        if rollout_backend not in ROLLOUT_BACKENDS:
+            raise ValueError("rollout_backend must be one of %s, got %r" % (ROLLOUT_BACKENDS, rollout_backend))
+        if rollout_backend == 'host':
+            return
+        why = None
+        if not hasattr(self.env, 'rollout_step'):
+            why = "a DeviceBatchedEnviron (the simulator state must live in HBM), got %s" % type(self.env).__name__
+        elif getattr(self.env, 'stream_backend', None) != 'device':
+            why = "streams='device' on the DeviceBatchedEnviron (mobility and the MT19937 streams advance inside the call)"
+        elif self.num_Neighbor != 1:
+            why = "one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor
+        elif not on_gpu:
+            why = "a brain on the gfx950 engine"
+        elif self.device_replay is None:
+            why = "the replay memory in HBM (device_replay)"
+        elif self._trainer() is not None:
+            why = "a single GPU (no data parallelism)"
+        if why is not None:
+            raise ValueError("rollout_backend='device' needs " + why)
 
     def _trainer(self):
         return getattr(getattr(self.brain, 'model', None), 'trainer', None)
@@ -302,6 +334,22 @@ class Agent(object):
         packed = self._packed_rollouts()
         if packed and E == 1 and self._native_rollout_ok():
             return self._rollout_one_simulator(num_transitions)
+        if self.rollout_backend == 'device':
+            if not packed:
+                raise RuntimeError("rollout_backend='device' takes the packed observation of the simulator (n_channels == n_RB, "
+                                   "3..31 links, V2X_RL_PACKED unset)")
+            rows = []
+            for it in range(n_iter):
+                r = self._device_iteration(last=it == n_iter - 1)
+                if hasattr(r, 'resolve'):
+                    rows.append((it, r))                   # a result row on its way: the rewards are read when it has arrived
+                else:
+                    rewards[it * E:(it + 1) * E] = r
+            out = rewards[:num_transitions] if n_iter * E == num_transitions else rewards
+            self._lazy_rewards = (out, rewards, rows, E)
+            if not getattr(self, '_predraw_ok', False):    # (inside Agent.train the step's replay resolves the rows first)
+                self._resolve_rewards()
+            return out
         for it in range(n_iter):
             if packed:
                 rewards[it * E:(it + 1) * E] = self._packed_iteration(last=it == n_iter - 1)
@@ -338,7 +386,63 @@ class Agent(object):
                                         np.concatenate((nxt[e].reshape(1, -1), adj[e].reshape(1, -1)), axis=-1)])
         return rewards[:num_transitions] if n_iter * E == num_transitions else rewards
 
-    def _packed_iteration(self, last=False, force_greedy=False):
+    def _resolve_rewards(self):
+        """the rewards of the device iterations of the last rollout, read from their result rows (waits for rows still on
+        their way) into the array generate_d2d_transition returned; -> that array, or None when nothing was pending"""
+        lazy, self._lazy_rewards = self._lazy_rewards, None
+        if lazy is None:
+            return None
+        out, rewards, rows, E = lazy
+        for it, row in rows:
+            rewards[it * E:(it + 1) * E] = row.resolve().reward
+        return out
+
+    def _policy_draws(self):
+        """the epsilon-greedy draws of one batched iteration, as _packed_iteration's loop takes them: per state one uniform
+        draw, and randint for each exploring state right after its draw -> (actions [E, n, 1] int, greedy states)"""
+        E, n, C = self.env.E, self.num_D2D, self.num_CH
+        steps = self.num_Episodes * 0.8 * self.num_Train_Step * self.num_transition
+        per_step = (MAX_EPSILON - MIN_EPSILON) / steps
+        actions = np.zeros((E, n, 1), int)
+        greedy = []
+        draw, base = np.random.random, self.num_step
+        for e in range(E):
+            step_no = base + e
+            self.epsilon = MAX_EPSILON - per_step * step_no if step_no < steps else MIN_EPSILON
+            if draw() < self.epsilon:
+                actions[e] = _random_channels(n, 1, C)
+            else:
+                greedy.append(e)
+        return actions, greedy
+
+    def _device_iteration(self, last=False):
+        """_packed_iteration as ONE call on the resident state (rollout_backend='device'): the same numpy draws in the same
+        order, then the policy buffer goes up, DeviceBatchedEnviron.rollout_step scores, picks, steps and stores, and the
+        replay memory commits the block.  -> the RolloutRow (rewards once it has arrived).  The replay's own draws are made at
+        replay time: nothing here is drawn ahead, so the process-wide stream sees the reference's order.
+        A state whose graph is not regular (a link that is its own receiver) cannot be scored from the fixed-degree CSR: when
+        somebody is greedy the flags of the current observation are read first (from the previous iteration's result row --
+        inside Agent.train the replay has resolved it already; after a reset one small download), and an iteration with such
+        a state runs through _packed_iteration with the draws already taken."""
+        env, rep = self.env, self.device_replay
+        E, C = env.E, self.num_CH
+        actions, greedy = self._policy_draws()
+        if greedy and not env.resident_regular(C).all():
+            return self._packed_iteration(last=last, drawn=(actions, greedy))
+        explore = np.ones(E, np.uint8)
+        explore[greedy] = 0
+        head = rep.reserve(E)
+        row = env.rollout_step(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
+                               engine=self.brain.model.engine if greedy else None, row_ptr=rep.row_ptr(E) if greedy else None)
+        rep.commit(E, row)
+        self.num_step += E
+        samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x E)
+        samples.extend([None] * E)
+        if len(samples) > self.memory.capacity:
+            del samples[:len(samples) - self.memory.capacity]
+        return row
+
+    def _packed_iteration(self, last=False, force_greedy=False, drawn=None):
         """One iteration of _generate_batched on packed observations: same epsilon draws in the same order, same Q-values
         (the same kernels on the same float32 rows and CSR), same stored transitions.
         While the GPU is still busy with the previous fit (the predict below has to wait for it anyway) the host does what
@@ -350,7 +454,9 @@ class Agent(object):
         xe, mask, col, regular = env.observe_packed(C)
         steps = self.num_Episodes * 0.8 * self.num_Train_Step * self.num_transition
         per_step = (MAX_EPSILON - MIN_EPSILON) / steps
-        if (not force_greedy and E >= 4 and os.environ.get("V2X_RL_NATIVE_POLICY", "0") == "1" and native_sim.available()):
+        if drawn is not None:                          # (the device rollout took this iteration's draws and found a graph it cannot score)
+            actions, greedy = drawn
+        elif (not force_greedy and E >= 4 and os.environ.get("V2X_RL_NATIVE_POLICY", "0") == "1" and native_sim.available()):
             # the E epsilon draws and the exploring simulators' randint draws in one library call on numpy's own generator state
             # (draw for draw the loop below).  OFF by default: measured at 50 simulators, batch 4096 -- 0.87-0.93 ms per train step
             # with it, 0.88 without: this part of the rollout runs while the GPU is still fitting and is not on the critical path
@@ -517,6 +623,12 @@ class Agent(object):
             xe, _, col, regular = self.env.observe_packed(self.num_CH)
             if regular.all():
                 self._predict_packed(xe, col)
+                if self.rollout_backend == 'device':       # ... and the forward of the resident batch
+                    rep = self.device_replay
+                    if rep.n_edges is None:
+                        rep.n_edges = self.num_D2D * (self.num_D2D - 2)
+                    dc = self.env.device_channels
+                    self.brain.model.engine.forward(dc.rollout_batch(rep.row_ptr(self.env.E)), out=dc.rollout_buffers()['q'])
 
     def _predict_packed(self, xe, col):
         """Q-values [E, N, C] (float32, a view of a pinned buffer: valid until the next call) of all environments from their
@@ -735,6 +847,8 @@ class Agent(object):
             for it in range(num_train_steps):
                 reward_step[ep, it, :] = self.generate_d2d_transition(self.num_transition)
                 out = self._replay_on_device(defer=True) if defer else self.replay()
+                if self._lazy_rewards is not None:         # device rollout: the replay has waited for the result rows
+                    reward_step[ep, it, :] = self._resolve_rewards()
                 if defer and len(out) == 2:
                     pending.append(out)
                 else:

@@ -35,7 +35,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import OptProblem, SimStep, check, load_library
+from ..lib import OptProblem, Rollout, SimStep, check, load_library
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -55,6 +55,27 @@ def uniforms_per_step(n, rb):
 
 def _align(x, a=64):
     return (x + a - 1) // a * a
+
+
+class RolloutRow(object):
+    """The result row of one resident rollout iteration (DeviceChannels.rollout_step): the rewards [E] and the regularity flags
+    of the stored observation and of the next one, [2, E].  The row is on its way to a page-locked buffer when this object is
+    handed out; resolve() waits for the event recorded behind that copy (once), keeps plain copies in .reward / .regular and
+    gives the buffer back."""
+
+    def __init__(self, owner, event, pin, E):
+        self._owner, self._event, self._pin, self.E = owner, event, pin, E
+        self.reward = self.regular = None
+
+    def resolve(self):
+        if self._pin is not None:
+            self._event.synchronize()
+            raw = self._pin.numpy()
+            self.reward = raw[:8 * self.E].view(np.float64).copy()
+            self.regular = raw[8 * self.E:10 * self.E].reshape(2, self.E).astype(bool)
+            self._owner._rows_free.append(self._pin)
+            self._pin = self._event = None
+        return self
 
 
 class DeviceChannels(object):
@@ -403,20 +424,153 @@ class DeviceChannels(object):
         self._check_mobility("advance", True)
         self._init_device()
         self._send_grid()
-        T, c = self._t, self.constants
+        T = self._t
         if where == 'host':
             self._up(T['actions'], a)
             a = T['actions']
         self._keep_actions = a if actions is not None else None
-        tab, width, height, timestep = self._grid
-        s = SimStep(problem=self.problem(), n_lanes=tab.shape[1], n_u=self.n_u, timestep=timestep, width=width, height=height,
-                    power=float(c['p_v2v'] if power is None else power), xy=T['pos'].data_ptr(),
-                    actions=a.data_ptr() if actions is not None else None,
-                    **{k: T[k].data_ptr() for k in ('keys', 'mtpos', 'dirs', 'vel', 'lanes', 'u') + _CHANNEL_TENSORS + (
-                        'interf_db', 'state', 'xe', 'mask', 'col', 'regular', 'v2v_rate', 'v2i_rate', 'interference', 'v2i_interf',
-                        'v2v_interf')})
+        s = self._sim_step(a.data_ptr() if actions is not None else None, power)
         check(self._lib, self._lib.v2x_sim_advance(C.byref(s), self._stream()))
         self._obs_ready = True
+
+    def _sim_step(self, actions_ptr, power=None):
+        T, c = self._t, self.constants
+        tab, width, height, timestep = self._grid
+        return SimStep(problem=self.problem(), n_lanes=tab.shape[1], n_u=self.n_u, timestep=timestep, width=width, height=height,
+                       power=float(c['p_v2v'] if power is None else power), xy=T['pos'].data_ptr(), actions=actions_ptr,
+                       **{k: T[k].data_ptr() for k in ('keys', 'mtpos', 'dirs', 'vel', 'lanes', 'u') + _CHANNEL_TENSORS + (
+                           'interf_db', 'state', 'xe', 'mask', 'col', 'regular', 'v2v_rate', 'v2i_rate', 'interference',
+                           'v2i_interf', 'v2v_interf')})
+
+    # ------------------------------------------------------------------ one DQN rollout iteration on the resident state
+    @property
+    def rollout_policy_bytes(self):
+        """bytes of the one buffer a rollout iteration uploads: random_actions [E, n] int32, then explore [E] bytes"""
+        return _align(4 * self.E * self.n + self.E, 4)
+
+    @property
+    def rollout_result_bytes(self):
+        """bytes of the result row a rollout iteration downloads: reward [E] float64, then regular [2, E] bytes"""
+        return _align(10 * self.E, 8)
+
+    def check_rollout(self, explore, random_actions, storage, head, capacity):
+        """ValueError unless the arguments of rollout_step() fit this object; -> (explore [E] uint8, random_actions [E, n] int32)"""
+        E, n = self.E, self.n
+        self.check_observe(n, self.rb)
+        self._check_mobility("rollout_step", True)
+        ex = np.asarray(explore)
+        if ex.shape != (E,) or ex.dtype.kind not in 'biu':
+            raise ValueError("explore: %d flags expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
+        ra = np.asarray(random_actions)
+        if ra.dtype.kind not in 'iu':
+            raise ValueError("random_actions must be integers, got dtype %s" % ra.dtype)
+        if ra.shape == (E, n, 1):
+            ra = ra.reshape(E, n)
+        if ra.shape != (E, n):
+            raise ValueError("random_actions: an array of shape %s expected, got %s" % ([E, n], list(ra.shape)))
+        head, capacity = int(head), int(capacity)
+        if not E <= capacity or not 0 <= head < capacity:
+            raise ValueError("rollout_step: E <= capacity and 0 <= head < capacity needed, got E = %d, head = %d, capacity = %d"
+                             % (E, head, capacity))
+        want = {'xe': (n, XE_WIDTH), 'xe_next': (n, XE_WIDTH), 'col': (n * (n - 2),), 'mask': (n,), 'action': (n,), 'reward': ()}
+        for k, tail in want.items():
+            t = storage.get(k)
+            if t is None or tuple(t.shape[1:]) != tail or not t.is_contiguous():
+                raise ValueError("rollout_step: replay storage %r of shape [slots] + %s expected" % (k, list(tail)))
+            if t.shape[0] < (capacity if head + E > capacity else head + E):      # (a block that wraps touches the last slot)
+                raise ValueError("rollout_step: replay storage %r has %d slots, the block at %d needs more" % (k, t.shape[0], head))
+        return ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32)
+
+    def rollout_buffers(self):
+        """the device buffers of rollout_step(): policy_dev (random_actions [E, n] int32 | explore [E] bytes), result_dev (reward [E]
+        float64 | regular [2, E] bytes), q [E n, rb] float32"""
+        self._init_device()
+        io = getattr(self, '_roll', None)
+        if io is None:
+            t, E, n = self.torch, self.E, self.n
+            nb = self.rollout_policy_bytes
+            io = self._roll = {
+                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
+                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
+                'result_dev': t.zeros(self.rollout_result_bytes, dtype=t.uint8, device=self.device),
+                'q': t.zeros((E * n, self.rb), dtype=t.float32, device=self.device), 'batch': {}}
+            self._rows_free = []
+        return io
+
+    def rollout_batch(self, row_ptr):
+        """the resident observation as the engine's batch: E graphs of n rows, xe and the CSR sources where v2x_sim_observe writes
+        them (every state regular: n - 2 sources per row, row_ptr the constant pointer of E n rows)"""
+        from ..engine import DeviceBatch
+        self._init_device()
+        io = self.rollout_buffers()
+        db = io['batch'].get(row_ptr.data_ptr())
+        if db is None:
+            E, n, T = self.E, self.n, self._t
+            db = DeviceBatch.from_tensors(E, n, T['xe'].view(E * n, XE_WIDTH), row_ptr, T['col'].view(-1), n * (n - 2))
+            io['batch'] = {row_ptr.data_ptr(): db}
+            io['row_ptr'] = row_ptr
+        return db
+
+    def rollout_struct(self, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+        """the v2x_rollout of the resident tensors (what rollout_step() passes to the library): the policy comes from
+        rollout_buffers()['policy_dev'], the result row goes to ['result_dev'], the actions to tensor('actions')"""
+        self._init_device()
+        self._send_grid()
+        T, E, n = self._t, self.E, self.n
+        io = self.rollout_buffers()
+        base = io['policy_dev'].data_ptr()
+        r = Rollout(model=None, q=io['q'].data_ptr(), explore=base + 4 * E * n, random_actions=base, actions=T['actions'].data_ptr(),
+                    step=self._sim_step(T['actions'].data_ptr(), power), w_v2v=float(v2v_weight), w_v2i=float(v2i_weight),
+                    rep_xe=storage['xe'].data_ptr(), rep_xe_next=storage['xe_next'].data_ptr(), rep_col=storage['col'].data_ptr(),
+                    rep_mask=storage['mask'].data_ptr(), rep_action=storage['action'].data_ptr(),
+                    rep_reward=storage['reward'].data_ptr(), head=int(head), capacity=int(capacity),
+                    result_reward=io['result_dev'].data_ptr(), result_regular=io['result_dev'].data_ptr() + 8 * E)
+        if engine is not None:
+            from ..engine import _batch_struct
+            r.model = engine._h
+            r.batch = _batch_struct(self.rollout_batch(row_ptr))
+        return r
+
+    def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
+                     power=None):
+        """One DQN rollout iteration in one call (v2x_rollout_step) on the resident state: the Q-values of the resident
+        observation (engine: a GnnEngine, with row_ptr the constant CSR pointer of E n rows; None: nobody is greedy, no
+        forward), the actions (explore [E] flags, random_actions [E, n]: the host's epsilon-greedy draws, uploaded as one small
+        buffer), the simulator step, the reward v2v_weight * sum(V2V rates) + v2i_weight * sum(V2I rates) in numpy's order, and
+        the transitions into slots (head + e) % capacity of `storage` (the replay's device tensors xe, xe_next, col, mask,
+        action, reward).  The current observation must be on the device (observe() / advance() / a previous rollout_step).
+        -> a RolloutRow whose download is in flight.  Afterwards as after advance(): fetch_rates(), fetch_observation()."""
+        ex, ra = self.check_rollout(explore, random_actions, storage, head, capacity)
+        if engine is not None and row_ptr is None:
+            raise ValueError("rollout_step: scoring needs the CSR row pointer of the resident batch")
+        self._init_device()
+        if not self._obs_ready:
+            raise RuntimeError("rollout_step: no observe() since the last step()")
+        self._send_grid()
+        t, T, E, n = self.torch, self._t, self.E, self.n
+        io = self.rollout_buffers()
+        i = io['next']
+        io['next'] = (i + 1) % 4
+        if io['policy_ev'][i] is not None:
+            io['policy_ev'][i].synchronize()
+        pin = io['policy_pin'][i].numpy()
+        pin[:4 * E * n].view(np.int32)[:] = ra.reshape(-1)
+        pin[4 * E * n:4 * E * n + E] = ex
+        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
+        self.traffic['bytes_up'] += io['policy_dev'].numel()
+        if io['policy_ev'][i] is None:
+            io['policy_ev'][i] = t.cuda.Event()
+        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
+        r = self.rollout_struct(storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
+        self._keep_actions = T['actions']
+        check(self._lib, self._lib.v2x_rollout_step(C.byref(r), self._stream()))
+        self._obs_ready = True
+        pinned = self._rows_free.pop() if self._rows_free else t.zeros(self.rollout_result_bytes, dtype=t.uint8, pin_memory=self._pin)
+        pinned.copy_(io['result_dev'], non_blocking=True)
+        self.traffic['bytes_down'] += pinned.numel()
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return RolloutRow(self, ev, pinned, E)
 
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
@@ -557,6 +711,9 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._static_dirty = True                              # vel / dest / the lane grid changed (a reset)
         self._move_pending = False                             # renew_positions() waits for the stream call of the channel update
         self._in_reset = False
+        self._rate_host = {}                                   # V2I_Interference / V2V_Interference as last computed or assigned
+        self._rates_pending = False                            # ... are older than the device's (a resident rollout step ran)
+        self._resident_row = None                              # the RolloutRow of the step that made the current observation
         BatchedEnviron.__init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=n_envs, seeds=seeds,
                                 workers=workers, native=True, lookahead=False)
         if streams == 'device':
@@ -626,6 +783,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
                 dc.set_grid((p.up_lanes, p.down_lanes, p.left_lanes, p.right_lanes), p.width, p.height, p.timestep)
                 dc.upload('vel', self.vel)
                 dc.upload('dest', self.dest)
+                dc._obs_ready = False                          # (new receivers: the resident observation is of the old ones)
                 self._static_dirty = False
             if self._streams_dirty and not self._streams_ahead:
                 for k in ('_mt_keys', '_mt_pos', 'pos', 'dirs'):
@@ -648,6 +806,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
     def new_random_game(self, n_Veh=0):
         self._check_sizes(n_Veh if n_Veh > 0 else self.n_Veh)
         self._dev_obs = None
+        self._resident_row = None
         self._settle_streams()                                 # the reset draws on the host: its copy of the streams first
         if n_Veh > 0 and n_Veh != self.n_Veh:
             self._host, self._dirty, self._on_device, self._dc = {}, set(), set(), None
@@ -685,6 +844,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._drop_lookahead()
         self._obs = None
         self._dev_obs = None
+        self._resident_row = None
         if self.stream_backend == 'device' and not self._in_reset:
             if any(s.gauss_next is not None for s in self.streams):
                 raise RuntimeError("a stream holds a cached gauss value")
@@ -719,16 +879,61 @@ class DeviceBatchedEnviron(BatchedEnviron):
         if any(s.gauss_next is not None for s in self.streams):
             raise RuntimeError("a stream holds a cached gauss value")
         self._obs = None
+        self._resident_row = None
         dc = self._flush()
         dc.advance(a.reshape(E, n))
         self._streams_ahead = True
         self._channels_updated()
         self._on_device.add('V2V_Interference_all')
         r = dc.fetch_rates()
+        self._rates_pending = False
         self._dev_obs = dc.fetch_observation()
         self.V2I_Interference = r['v2i_interf']
         self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
+
+    def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None):
+        """act() of a whole DQN rollout iteration without the host in the loop (streams='device' only; DeviceChannels.rollout_step):
+        the resident observation is scored (engine given), the actions are picked from the host's policy draws, the simulators
+        step, and the transitions land in the replay slots -- one call, nothing comes back but the result row (-> RolloutRow, its
+        download in flight).  The bookkeeping is act()'s: the device holds the newer streams and channel arrays, the observable
+        interference is on the device, no host copy of the observation exists; V2I_Interference / V2V_Interference download
+        the rates when they are next read."""
+        if self.stream_backend != 'device':
+            raise ValueError("rollout_step needs streams='device' (mobility and the MT19937 streams advance inside the call)")
+        self.finish_step()
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        stale = bool(self._dirty)
+        dc = self._flush()
+        dc.check_rollout(explore, random_actions, storage, head, capacity)
+        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
+            dc.observe(self.dest)
+        self._obs = None
+        row = dc.rollout_step(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr)
+        self._streams_ahead = True
+        self._channels_updated()
+        self._on_device.add('V2V_Interference_all')
+        self._dev_obs = None
+        self._rates_pending = True
+        self._resident_row = row
+        return row
+
+    def resident_regular(self, n_channels=4):
+        """the regularity flags [E] of the CURRENT observation, from wherever they are known without a device call: the host copy
+        of the observation, or the result row of the resident step that made it (waits for that row); otherwise one download"""
+        if self._dev_obs is not None and not self._dirty:
+            return self._dev_obs[3]
+        if self._resident_row is not None and not self._dirty:
+            return self._resident_row.resolve().regular[1]
+        return self.observe_packed(n_channels)[3]
+
+    def _pull_rates(self):
+        self._rates_pending = False
+        r = self._dc.fetch_rates()
+        self._rate_host['V2I_Interference'] = r['v2i_interf']
+        self._rate_host['V2V_Interference'] = r['v2v_interf'].reshape(self.E, self.n_Veh, 1)
 
     def _observe_device(self):
         dc = self._flush()
@@ -766,6 +971,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
         dc = self._flush()
         dc.rates(a.reshape(E, n), dest=self.dest)
         r = dc.fetch_rates()
+        self._rates_pending = False
         self.V2I_Interference = r['v2i_interf']
         self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
@@ -781,6 +987,23 @@ class DeviceBatchedEnviron(BatchedEnviron):
         return dc.problem_tensors(device)
 
 
+def _rate_array(attr):
+    def get(self):
+        if self._rates_pending:
+            self._pull_rates()
+        try:
+            return self._rate_host[attr]
+        except KeyError:
+            raise AttributeError(attr)
+
+    def set(self, value):
+        self._rate_host[attr] = value
+
+    return property(get, set)
+
+
+for _attr in ('V2I_Interference', 'V2V_Interference'):
+    setattr(DeviceBatchedEnviron, _attr, _rate_array(_attr))
 for _attr in _DEVICE_ARRAYS:
     setattr(DeviceBatchedEnviron, _attr, _device_array(_attr))
 for _attr in _STREAM_ARRAYS:

@@ -45,6 +45,7 @@ class DeviceReplay(object):
         self._regular = np.ones(0, bool)       # host-side: slot holds a graph with in-degree n-2 everywhere
         self._early = None                     # stage_early(): (slot, xe, col, mask) already copied for the next packed block
         self._db_cache = {}
+        self._pending = []                     # commit(): (first slot, K, RolloutRow) blocks whose flags are still on their way
 
     # ------------------------------------------------------------------ storage
     def _grow(self, need):
@@ -153,6 +154,49 @@ class DeviceReplay(object):
         self._early = (pos, xe, col, mask)
         return True
 
+    # ------------------------------------------------------------------ transitions written by the device (v2x_rollout_step)
+    def storage(self):
+        """the storage tensors by name, for a call that writes transitions into their slots on the device"""
+        return {'xe': self.xe, 'xe_next': self.xe_next, 'col': self.col, 'mask': self.mask, 'action': self.action,
+                'reward': self.reward}
+
+    def reserve(self, K):
+        """-> the first slot of a block of K transitions the DEVICE is about to write (slot (head + e) % capacity for
+        transition e: a block may wrap, the kernels take the modulo).  Flushes anything staged and grows the storage; nothing
+        is stored until commit()."""
+        K = int(K)
+        if not 1 <= K <= self.capacity:
+            raise ValueError("reserve: 1..%d transitions, got %d" % (self.capacity, K))
+        if self.n > self.MAX_LINKS:
+            raise ValueError("DeviceReplay keeps the adjacency as one 32-bit source mask per link: at most 31 links")
+        if self.n_edges is None:
+            self.n_edges = self.n * (self.n - 2)
+        self.flush()
+        self._early = None
+        self._grow(min(self.capacity, self.size + K))
+        return self.head
+
+    def commit(self, K, row):
+        """The block reserve(K) handed out has been enqueued: head and size advance at once.  row: the RolloutRow of the call
+        (its .regular[0] are the flags of the stored observations); it is resolved -- one wait for work already enqueued --
+        when the flags are first needed (sample())."""
+        K = int(K)
+        self._pending.append((self.head, K, row))
+        self.head = (self.head + K) % self.capacity
+        self.size = min(self.capacity, self.size + K)
+
+    def _resolve_pending(self):
+        """the regularity flags of every committed block are in _regular"""
+        if self._pending:
+            for first, K, row in self._pending:
+                self._regular[(first + np.arange(K)) % self.capacity] = row.resolve().regular[0]
+            self._pending = []
+
+    def regular_flags(self):
+        """[allocated slots] bool: the slot holds a graph with in-degree n - 2 everywhere (pending device blocks resolved)"""
+        self._resolve_pending()
+        return self._regular
+
     def prefetch_indices(self, idx, K):
         """Upload the slots of a minibatch drawn AHEAD: idx are positions in the FIFO order as it will be once K more
         transitions are stored.  -> what sample(idx, pre=...) takes, or None when the ring wraps by then."""
@@ -189,6 +233,7 @@ class DeviceReplay(object):
         """Staged transitions -> HBM (one copy per tensor; ring wrap handled by splitting at the end of the storage)."""
         if not self._stage:
             return
+        self._resolve_pending()                      # (flags of older blocks first: a ring that wraps may overwrite their slots)
         torch = self.torch
         k = self._n_staged
         self._grow(min(self.capacity, self.size + k))
@@ -327,6 +372,7 @@ class DeviceReplay(object):
         else:
             slots = self.logical_to_slot(idx)
             idx_dev = self._upload_indices(slots)
+        self._resolve_pending()        # the one wait of a device rollout: after the draws, for work that is already enqueued
         regular = bool(self._regular[slots].all())
         xe, xe_next, action, reward, last = self._gather_many(
             [(self.xe, 'xe'), (self.xe_next, 'xe_next'), (self.action, 'action'), (self.reward, 'reward'),

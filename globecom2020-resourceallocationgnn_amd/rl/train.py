@@ -102,6 +102,10 @@ def build_parser():
     ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
                     help="with --sim-backend device: where mobility and the simulators' MT19937 streams advance -- libv2xsim.so "
                          "(the default) or the GPU, where a step is one enqueue that takes only the actions from the host")
+    ap.add_argument("--rollout", choices=["host", "device"], default="host",
+                    help="with --sim-backend device --sim-streams device: 'device' runs a whole rollout iteration (score, pick, "
+                         "step, reward, store) as one call on the state resident in HBM; 'host' (the default) scores and stores "
+                         "through the host")
     return ap
 
 
@@ -110,6 +114,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
+    if args.rollout == "device" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--rollout device needs --sim-backend device --sim-streams device")
     if args.sim_backend == "device" and args.envs < 1:
         ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:
@@ -154,7 +160,7 @@ def main(argv=None):
         agent, (loss, reward_step, reward_ep, q_mean, q_max, _, _) = run_train(
             env, cfg, save_dir=args.save_dir if rank == 0 else None, verbose=rank == 0,
             device=local, seed=args.seed, use_graph=args.use_graph, data_parallel=world > 1 or force_dp,
-            rollouts=args.rollouts)
+            rollouts=args.rollouts, rollout_backend=args.rollout)
     dt = time.perf_counter() - t0
     if rank == 0:
         n_fit = args.episodes * args.train_steps

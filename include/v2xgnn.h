@@ -488,6 +488,62 @@ typedef struct v2x_sim_step {
 } v2x_sim_step;
 int  v2x_sim_advance(const v2x_sim_step* s, void* stream);
 
+/* ---- one DQN rollout iteration on the resident state (csrc/v2xsimdev.hip) --------------------------------------------
+ * Agent._packed_iteration (BS_brain.py:308-352 inside :409-553) for E simulator states whose observation, simulator arrays and
+ * replay memory all live in HBM: score, pick the actions, step the simulators, compute the reward, write the transitions into
+ * their replay slots.  The host contributes the draws of the epsilon-greedy policy (which do not depend on device state) and
+ * reads one small result row back.  Same rules as the v2x_sim_* calls: all pointers [dev], one asynchronous launch per
+ * kernel on `stream`, no allocation, no synchronisation, no environment variable read; a bad argument is V2X_EINVAL with
+ * text in v2x_last_error(NULL), before anything is launched.  Limits: those of v2x_sim_observe (3 <= n <= 31, 1 <= C <= n,
+ * 3 C + 1 <= 16) and 1 <= E <= capacity.  State e's transition goes to replay slot (head + e) % capacity: a block may wrap.
+ *
+ * v2x_rollout_pick (before the simulator step): actions[e][k] = explore[e] ? random_actions[e][k] : argmax_c q[e n + k][c],
+ * np.argmax's argmax (the first maximiser in ascending c; the first NaN wins over any number).  q == NULL: nobody is greedy,
+ * explore is not read and every state takes its random actions.  The same launch copies the state's observation half --
+ * xe[e] ([n][16] float32), col[e] ([n (n - 2)] int32) and mask[e] ([n] int32) -- to its slot of rep_xe / rep_col / rep_mask,
+ * because the step overwrites it, and regular[e] to regular_out[e].
+ *
+ * v2x_rollout_store (after the step): reward[e] = w_v2v * S(v2v_rate[e][0..n)) + w_v2i * S(v2i_rate[e][0..min(rb, n))) in
+ * fp64, no contraction, S being numpy's summation of a contiguous row (fewer than 8 terms: left to right; otherwise eight
+ * accumulators r[j] = a[j], r[j] += a[i + j] over the whole groups of eight, ((r0 + r1) + (r2 + r3)) + ((r4 + r5) + (r6 + r7)),
+ * then the remaining terms one by one), so it equals w * v2v.sum(axis=(1, 2)) + w * v2i.sum(axis=1) bit for bit.  Written to
+ * the state's slot: xe[e] (now the next observation) to rep_xe_next, actions[e] to rep_action, reward[e] to rep_reward; and
+ * reward[e] to reward_out[e], regular[e] (of the next observation) to regular_out[e].                                        */
+int  v2x_rollout_pick(int32_t E, int32_t n, int32_t C, const float* q /*[E n][C] or NULL*/, const uint8_t* explore /*[E]*/,
+                      const int32_t* random_actions /*[E][n]*/, int32_t* actions /*[E][n], written*/, const float* xe,
+                      const int32_t* col, const int32_t* mask, const uint8_t* regular, float* rep_xe, int32_t* rep_col,
+                      int32_t* rep_mask, int64_t head, int64_t capacity, uint8_t* regular_out /*[E]*/, void* stream);
+int  v2x_rollout_store(int32_t E, int32_t n, int32_t rb, const double* v2v_rate /*[E][n]*/,
+                       const double* v2i_rate /*[E][min(rb,n)]*/, double w_v2v, double w_v2i, const float* xe,
+                       const int32_t* actions, const uint8_t* regular, float* rep_xe_next, int32_t* rep_action,
+                       double* rep_reward, int64_t head, int64_t capacity, double* reward_out /*[E]*/,
+                       uint8_t* regular_out /*[E]*/, void* stream);
+/* v2x_rollout_step: the iteration.  Enqueues, in this order on one stream with no parallel branches, v2x_forward of `batch`
+ * on `model` into q (skipped when model is NULL: nobody is greedy), v2x_rollout_pick, the four launches of v2x_sim_advance
+ * with `actions` as the step's actions, and v2x_rollout_store.  Every check of every part is made before the first launch.
+ * batch: on_device = 1, n_graphs = E fixed-size graphs of n nodes, xe = step.xe, col_idx = step.col (the resident
+ * observation; every state must be regular: the CSR has n - 2 sources per row), a model of n nodes and rb channels.
+ * step.actions must be NULL or `actions`.  The result row: result_reward[E] doubles, result_regular[2][E] bytes (the flags
+ * of the stored observation, then those of the next one).  Capturable once the model's workspaces exist (one eager call
+ * first) on a model created without use_graph.                                                                             */
+typedef struct v2x_rollout {
+  v2x_model* model;                /* the online network, or NULL */
+  v2x_batch batch;
+  float* q;                        /* [E n][rb] Q workspace (required with a model) */
+  const uint8_t* explore;          /* [E]    */
+  const int32_t* random_actions;   /* [E][n] */
+  int32_t* actions;                /* [E][n]: written by the pick, read by the step and the store */
+  v2x_sim_step step;
+  double w_v2v, w_v2i;
+  float *rep_xe, *rep_xe_next;     /* [capacity][n][16]     */
+  int32_t *rep_col, *rep_mask, *rep_action;   /* [capacity][n (n - 2)], [capacity][n], [capacity][n] */
+  double* rep_reward;              /* [capacity] */
+  int64_t head, capacity;
+  double* result_reward;           /* [E]    */
+  uint8_t* result_regular;         /* [2][E] */
+} v2x_rollout;
+int  v2x_rollout_step(const v2x_rollout* r, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

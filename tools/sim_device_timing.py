@@ -23,6 +23,15 @@ in one process: env.act() + observe_packed() wall time, the bytes each device en
 the four launches of v2x_sim_advance between HIP events, and the DQN loop of the in-process leg above for the three of them.
 
     python tools/sim_device_timing.py --mode streams [--out profiles/sim_device_streams_timing.json]
+
+--mode rollout measures the device-resident rollout iteration (Agent(rollout_backend='device'): v2x_rollout_step) with the recipe
+of --mode streams: the iteration alone at 1, 50 and 200 simulators (Agent.generate_d2d_transition(E) wall time, epsilon held near
+0.5, and the bytes DeviceChannels.traffic counts per iteration) next to the host rollout on the same kind of environment, and the
+DQN loop at 50 simulators -- the device rollout, the host rollout on device streams and the host simulator with look-ahead, all
+alive in one process, Agent.train(1, 20) timed in turn; and the call alone between HIP events, issued eagerly and replayed from
+a graph the tool captures itself (the agent issues it eagerly: head moves with every block).
+
+    python tools/sim_device_timing.py --mode rollout [--out profiles/rollout_device_timing.json]
 """
 import argparse
 import json
@@ -246,6 +255,124 @@ def loop_in_process_streams(reps):
             for b in walls}
 
 
+ROLLOUT_SETTINGS = {"host_lookahead": (dict(backend="host"), "host"),
+                    "device_streams_host_rollout": (dict(backend="device", streams="device"), "host"),
+                    "device_streams_device_rollout": (dict(backend="device", streams="device"), "device")}
+
+
+def _rollout_agent(E, kw, rollout, batch=4096):
+    import random
+    from v2xgnn.rl import Agent, RL_Config
+    from v2xgnn.rl.train import start_env_batched
+    random.seed(1001)
+    np.random.seed(1001)
+    cfg = RL_Config()
+    cfg.set_train_value(64, 0.5, batch, 1, 0.1)
+    cfg.Num_Episodes, cfg.Num_Train_Steps = 1, 20
+    env = start_env_batched(LINKS, E, 1001, **kw)
+    return Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True, rollout_backend=rollout)
+
+
+def rollout_legs(E, reps, warmup):
+    """one rollout iteration of E simulators alone (no replay in between): wall time per iteration with epsilon held near 0.5,
+    the host synchronised at the end of every iteration (the result row is read), and the bytes moved per iteration"""
+    import torch
+    agents = {name: _rollout_agent(E, kw, rollout) for name, (kw, rollout) in ROLLOUT_SETTINGS.items() if name != "host_lookahead"}
+    walls = {name: [] for name in agents}
+    traffic = {}
+    for ag in agents.values():
+        ag.num_Train_Step = 20
+    for k in range(warmup + reps):
+        if k == warmup:
+            traffic = {name: dict(ag.env.device_channels.traffic) for name, ag in agents.items()}
+        for name, ag in agents.items():                              # taken in turn: the box's load drifts
+            ag.num_step = 10 * ag.num_transition                       # epsilon = 1 - 0.99 * 500 / 800: both branches every iteration
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ag.generate_d2d_transition(E)
+            if k >= warmup:
+                walls[name].append(time.perf_counter() - t0)
+    row = {"simulators": E, "links": LINKS, "rb": RB}
+    for name, ag in agents.items():
+        row["iteration_%s_ms" % name] = _median_ms(walls[name])
+        after = ag.env.device_channels.traffic
+        for key in ("bytes_up", "bytes_down"):
+            row["%s_%s_per_iteration" % (name, key)] = (after[key] - traffic[name][key]) // reps
+    # the call alone between HIP events, eagerly and replayed from a captured graph (policy already on the device)
+    ag = agents["device_streams_device_rollout"]
+    dc, rep = ag.env.device_channels, ag.device_replay
+    engine, rp = ag.brain.model.engine, rep.row_ptr(E)
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    from v2xgnn.lib import check
+    import ctypes
+    out = {}
+    side = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(side):
+        head = rep.reserve(E)
+        r = dc.rollout_struct(rep.storage(), head, rep.capacity, 1.0, 0.1, engine=engine, row_ptr=rp)
+        call = lambda: check(dc._lib, dc._lib.v2x_rollout_step(ctypes.byref(r), torch.cuda.current_stream().cuda_stream))   # noqa: E731
+        call()
+        torch.cuda.synchronize()
+        graph, captured = torch.cuda.CUDAGraph(), None
+        try:
+            with torch.cuda.graph(graph, stream=side):
+                call()
+            captured = graph.replay
+        except Exception as exc:                                       # written down, not hidden
+            out["graph_error"] = "%s: %s" % (type(exc).__name__, exc)
+        for tag, fn in (("eager", call), ("graph", captured)):
+            if fn is None:
+                continue
+            gpu, host = [], []
+            for k in range(warmup + reps):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ev[0].record()
+                fn()
+                ev[1].record()
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                if k >= warmup:
+                    gpu.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+                    host.append(t1 - t0)
+            out["call_%s_gpu_ms" % tag], out["call_%s_enqueue_ms" % tag] = _median_ms(gpu), _median_ms(host)
+    row.update(out)
+    return row
+
+
+def loop_in_process_rollout(reps):
+    """loop_in_process_streams for the three settings of ROLLOUT_SETTINGS at 50 simulators, batch 4096"""
+    import torch
+    agents, walls = {}, {name: [] for name in ROLLOUT_SETTINGS}
+    with torch.cuda.stream(torch.cuda.Stream(device=0)):
+        for name, (kw, rollout) in ROLLOUT_SETTINGS.items():
+            agents[name] = _rollout_agent(50, kw, rollout)
+            agents[name].train(1, 20)                                 # warm-up, untimed
+        torch.cuda.synchronize()
+        for rep in range(reps):
+            for name in ROLLOUT_SETTINGS:
+                t0 = time.perf_counter()
+                agents[name].train(1, 20)
+                torch.cuda.synchronize()
+                walls[name].append(time.perf_counter() - t0)
+    return {b: {"wall_s_per_call": [round(w, 4) for w in walls[b]], "ms_per_train_step": round(float(np.median(walls[b])) * 1e3 / 20, 3)}
+            for b in walls}
+
+
+def main_rollout(args):
+    import torch
+    from v2xgnn.rl.batched_env import _usable_cpus
+    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
+              "iterations": [rollout_legs(E, args.reps, args.warmup) for E in args.simulators]}
+    for row in result["iterations"]:
+        print(json.dumps(row))
+    if not args.no_loop:
+        result["loop_in_process"] = loop_in_process_rollout(max(3, args.loop_reps))
+        print(json.dumps(result["loop_in_process"]))
+    return result
+
+
 def main_streams(args):
     import torch
     from v2xgnn.rl.batched_env import _usable_cpus
@@ -261,7 +388,7 @@ def main_streams(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["channels", "streams"], default="channels")
+    ap.add_argument("--mode", choices=["channels", "streams", "rollout"], default="channels")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -273,16 +400,19 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("sim_device_timing needs a GPU: nothing is measured without one")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "sim_device_streams_timing.json" if args.mode == "streams" else "sim_device_timing.json")
+        args.out = os.path.join(ROOT, "profiles", {"streams": "sim_device_streams_timing.json", "rollout": "rollout_device_timing.json"}.get(
+            args.mode, "sim_device_timing.json"))
     from v2xgnn.rl.batched_env import _usable_cpus
     if args.mode == "streams":
         result = main_streams(args)
+    elif args.mode == "rollout":
+        result = main_rollout(args)
     else:
         result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
                   "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
         for row in result["steps"]:
             print(json.dumps(row))
-    if args.mode != "streams" and not args.no_loop:
+    if args.mode == "channels" and not args.no_loop:
         result["loop"] = loop_leg(args.loop_reps)
         print(json.dumps(result["loop"]))
         try:
