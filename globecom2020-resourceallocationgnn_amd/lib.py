@@ -83,6 +83,12 @@ class Rollout(C.Structure):
         [("head", C.c_int64), ("capacity", C.c_int64), ("result_reward", C.c_void_p), ("result_regular", C.c_void_p)]
 
 
+class RolloutTraj(C.Structure):
+    """v2x_rollout_traj of include/v2xgnn.h"""
+    _fields_ = [("r", Rollout), ("T", C.c_int32), ("pad_", C.c_int32)] + \
+        [(k, C.c_void_p) for k in ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")]
+
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -167,6 +173,8 @@ SYMBOLS = [
     ("v2x_rollout_pick", C.c_int, [_I, _I, _I] + [_P] * 11 + [_L, _L, _P, _P]),
     ("v2x_rollout_store", C.c_int, [_I, _I, _I, _P, _P, C.c_double, C.c_double] + [_P] * 6 + [_L, _L, _P, _P, _P]),
     ("v2x_rollout_step", C.c_int, [C.POINTER(Rollout), _P]),
+    ("v2x_rollout_steps_workspace_bytes", _L, [_I, _I, _I, _I]),
+    ("v2x_rollout_steps", C.c_int, [C.POINTER(RolloutTraj), _P]),
 ]
 
 

@@ -25,7 +25,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 
 OPT_BACKENDS = ('host', 'device', 'bound', 'local')
-ROLLOUT_BACKENDS = ('host', 'device')
+ROLLOUT_BACKENDS = ('host', 'device', 'trajectory')
 
 
 def _check_opt_backend(opt_backend):
@@ -82,7 +82,10 @@ class Agent(object):
         score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
         needs a DeviceBatchedEnviron with streams='device', the HBM replay memory, the gfx950 engine, one receiver per link and
         no data parallelism; anything else is a ValueError here.  Same transitions, rewards and numpy draws as 'host', bit for
-        bit (tests/test_gpu_rollout_device.py).
+        bit (tests/test_gpu_rollout_device.py).  'trajectory': the same prerequisites; ALL iterations of a rollout are one call
+        (v2x_rollout_steps: one kernel walks every simulator through its steps, one forward scores all observations, one
+        kernel picks, pays and stores) -- the policy draws of the whole rollout are taken first, in the order 'device' takes
+        them; bit for bit 'device' (tests/test_gpu_rollout_trajectory.py).
 
         device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
         visiting the host; 'auto' = whenever the brain runs on the gfx950 engine.
@@ -162,7 +165,7 @@ class Agent(object):
         elif self._trainer() is not None:
             why = "a single GPU (no data parallelism)"
         if why is not None:
-            raise ValueError("rollout_backend='device' needs " + why)
+            raise ValueError("rollout_backend=%r needs %s" % (rollout_backend, why))
 
     def _trainer(self):
         return getattr(getattr(self.brain, 'model', None), 'trainer', None)
@@ -334,17 +337,23 @@ class Agent(object):
         packed = self._packed_rollouts()
         if packed and E == 1 and self._native_rollout_ok():
             return self._rollout_one_simulator(num_transitions)
-        if self.rollout_backend == 'device':
+        if self.rollout_backend in ('device', 'trajectory'):
             if not packed:
-                raise RuntimeError("rollout_backend='device' takes the packed observation of the simulator (n_channels == n_RB, "
-                                   "3..31 links, V2X_RL_PACKED unset)")
-            rows = []
-            for it in range(n_iter):
-                r = self._device_iteration(last=it == n_iter - 1)
-                if hasattr(r, 'resolve'):
-                    rows.append((it, r))                   # a result row on its way: the rewards are read when it has arrived
-                else:
-                    rewards[it * E:(it + 1) * E] = r
+                raise RuntimeError("rollout_backend=%r takes the packed observation of the simulator (n_channels == n_RB, "
+                                   "3..31 links, V2X_RL_PACKED unset)" % self.rollout_backend)
+            rows, drawn, block = [], None, None
+            if self.rollout_backend == 'trajectory':       # the draws of the whole rollout first, then (if it can be) one call
+                drawn = self._draw_rollout_ahead(n_iter)
+                block = self._trajectory_rollout(drawn)
+            if block is not None:
+                rows.append((0, block))
+            else:
+                for it in range(n_iter):
+                    r = self._device_iteration(last=it == n_iter - 1, drawn=None if drawn is None else drawn[it])
+                    if hasattr(r, 'resolve'):
+                        rows.append((it, r))               # a result row on its way: the rewards are read when it has arrived
+                    else:
+                        rewards[it * E:(it + 1) * E] = r
             out = rewards[:num_transitions] if n_iter * E == num_transitions else rewards
             self._lazy_rewards = (out, rewards, rows, E)
             if not getattr(self, '_predraw_ok', False):    # (inside Agent.train the step's replay resolves the rows first)
@@ -393,8 +402,9 @@ class Agent(object):
         if lazy is None:
             return None
         out, rewards, rows, E = lazy
-        for it, row in rows:
-            rewards[it * E:(it + 1) * E] = row.resolve().reward
+        for it, row in rows:                               # (a RolloutRow: E rewards; a RolloutBlock: T x E from iteration `it` on)
+            r = row.resolve().reward.reshape(-1)
+            rewards[it * E:it * E + r.size] = r
         return out
 
     def _policy_draws(self):
@@ -415,7 +425,48 @@ class Agent(object):
                 greedy.append(e)
         return actions, greedy
 
-    def _device_iteration(self, last=False):
+    def _draw_rollout_ahead(self, n_iter):
+        """the policy draws of n_iter iterations, taken before the first of them runs: n_iter calls of _policy_draws with num_step
+        advanced by E between them (and put back: the iterations advance it).  Nothing else draws between the device iterations
+        of a rollout, so the process-wide stream sees the order of the per-iteration path; epsilon ends at the last iteration's
+        value.  -> [(actions [E, n, 1], greedy states)] per iteration"""
+        base, drawn = self.num_step, []
+        try:
+            for _ in range(n_iter):
+                drawn.append(self._policy_draws())
+                self.num_step += self.env.E
+        finally:
+            self.num_step = base
+        return drawn
+
+    def _trajectory_rollout(self, drawn):
+        """All iterations of a rollout as ONE call on the resident state (rollout_backend='trajectory'): one reserve, one
+        DeviceBatchedEnviron.rollout_steps, one commit, the FIFO bookkeeping of len(drawn) x E transitions.  -> the RolloutBlock
+        (rewards once it has arrived), or None when the per-iteration path has to run with these draws: somebody is greedy and a
+        resident graph is not regular (receivers are fixed within a rollout: one look suffices), or the block does not fit the
+        replay ring."""
+        env, rep = self.env, self.device_replay
+        E, n, C, T = env.E, self.num_D2D, self.num_CH, len(drawn)
+        K = T * E
+        anybody = any(len(g) > 0 for _, g in drawn)
+        if K > rep.capacity or (anybody and not env.resident_regular(C).all()):
+            return None
+        explore = np.ones((T, E), np.uint8)
+        for it, (_, greedy) in enumerate(drawn):
+            explore[it, greedy] = 0
+        actions = np.stack([a for a, _ in drawn]).reshape(T, E, n)
+        head = rep.reserve(K)
+        block = env.rollout_steps(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
+                                  engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None)
+        rep.commit(K, block)
+        self.num_step += K
+        samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
+        samples.extend([None] * K)
+        if len(samples) > self.memory.capacity:
+            del samples[:len(samples) - self.memory.capacity]
+        return block
+
+    def _device_iteration(self, last=False, drawn=None):
         """_packed_iteration as ONE call on the resident state (rollout_backend='device'): the same numpy draws in the same
         order, then the policy buffer goes up, DeviceBatchedEnviron.rollout_step scores, picks, steps and stores, and the
         replay memory commits the block.  -> the RolloutRow (rewards once it has arrived).  The replay's own draws are made at
@@ -423,10 +474,11 @@ class Agent(object):
         A state whose graph is not regular (a link that is its own receiver) cannot be scored from the fixed-degree CSR: when
         somebody is greedy the flags of the current observation are read first (from the previous iteration's result row --
         inside Agent.train the replay has resolved it already; after a reset one small download), and an iteration with such
-        a state runs through _packed_iteration with the draws already taken."""
+        a state runs through _packed_iteration with the draws already taken.  drawn: this iteration's draws, taken ahead
+        (_draw_rollout_ahead)."""
         env, rep = self.env, self.device_replay
         E, C = env.E, self.num_CH
-        actions, greedy = self._policy_draws()
+        actions, greedy = self._policy_draws() if drawn is None else drawn
         if greedy and not env.resident_regular(C).all():
             return self._packed_iteration(last=last, drawn=(actions, greedy))
         explore = np.ones(E, np.uint8)
@@ -623,7 +675,7 @@ class Agent(object):
             xe, _, col, regular = self.env.observe_packed(self.num_CH)
             if regular.all():
                 self._predict_packed(xe, col)
-                if self.rollout_backend == 'device':       # ... and the forward of the resident batch
+                if self.rollout_backend in ('device', 'trajectory'):      # ... and the forward of the resident batch
                     rep = self.device_replay
                     if rep.n_edges is None:
                         rep.n_edges = self.num_D2D * (self.num_D2D - 2)

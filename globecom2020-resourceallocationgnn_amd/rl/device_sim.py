@@ -35,7 +35,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import OptProblem, Rollout, SimStep, check, load_library
+from ..lib import OptProblem, Rollout, RolloutTraj, SimStep, check, load_library
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -74,6 +74,38 @@ class RolloutRow(object):
             self.reward = raw[:8 * self.E].view(np.float64).copy()
             self.regular = raw[8 * self.E:10 * self.E].reshape(2, self.E).astype(bool)
             self._owner._rows_free.append(self._pin)
+            self._pin = self._event = None
+        return self
+
+
+def trajectory_workspace_layout(E, n, rb, T):
+    """-> (the byte offsets of traj_xe, traj_col, traj_mask, traj_regular, traj_v2v_ff, traj_v2i_ff, traj_v2i_abs in the one
+    workspace of v2x_rollout_steps, its size): the formula of include/v2xgnn.h, every array rounded up to 256 bytes"""
+    parts = (4 * (T + 1) * E * n * XE_WIDTH, 4 * (T + 1) * E * n * (n - 2), 4 * (T + 1) * E * n, (T + 1) * E,
+             8 * T * E * n * n * rb, 8 * T * E * n * rb, 8 * T * E * n)
+    offs, o = [], 0
+    for b in parts:
+        offs.append(o)
+        o += _align(b, 256)
+    return dict(zip(('traj_xe', 'traj_col', 'traj_mask', 'traj_regular', 'traj_v2v_ff', 'traj_v2i_ff', 'traj_v2i_abs'), offs)), o
+
+
+class RolloutBlock(object):
+    """The result rows of T resident rollout iterations made in one call (DeviceChannels.rollout_steps): after resolve(),
+    .reward [T, E] and .regular [T, 2, E] (row t: the flags of the observation stored by iteration t, then of the next one).
+    Like RolloutRow the block is on its way to a page-locked buffer when this object is handed out."""
+
+    def __init__(self, free, event, pin, T, E):
+        self._free, self._event, self._pin, self.T, self.E = free, event, pin, T, E
+        self.reward = self.regular = None
+
+    def resolve(self):
+        if self._pin is not None:
+            self._event.synchronize()
+            raw, K = self._pin.numpy(), self.T * self.E
+            self.reward = raw[:8 * K].view(np.float64).reshape(self.T, self.E).copy()
+            self.regular = raw[8 * K:10 * K].reshape(self.T, 2, self.E).astype(bool)
+            self._free.append(self._pin)
             self._pin = self._event = None
         return self
 
@@ -572,6 +604,143 @@ class DeviceChannels(object):
         ev.record(t.cuda.current_stream(self.device))
         return RolloutRow(self, ev, pinned, E)
 
+    # ------------------------------------------------------------------ T rollout iterations in one call
+    def rollout_steps_policy_bytes(self, T):
+        """bytes of the one buffer rollout_steps() uploads: random_actions [T, E, n] int32, then explore [T, E] bytes"""
+        return _align(4 * T * self.E * self.n + T * self.E, 4)
+
+    def rollout_steps_result_bytes(self, T):
+        """bytes of the result block rollout_steps() downloads: reward [T, E] float64, then regular [T, 2, E] bytes"""
+        return _align(10 * T * self.E, 8)
+
+    def check_rollout_steps(self, explore, random_actions, storage, head, capacity):
+        """ValueError unless the arguments of rollout_steps() fit this object; -> (T, explore [T, E] uint8, random_actions
+        [T, E, n] int32)"""
+        E, n = self.E, self.n
+        self.check_observe(n, self.rb)
+        self._check_mobility("rollout_steps", True)
+        ex = np.asarray(explore)
+        if ex.ndim != 2 or ex.shape[0] < 1 or ex.shape[1] != E or ex.dtype.kind not in 'biu':
+            raise ValueError("explore: [T, %d] flags with T >= 1 expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
+        T = ex.shape[0]
+        ra = np.asarray(random_actions)
+        if ra.dtype.kind not in 'iu':
+            raise ValueError("random_actions must be integers, got dtype %s" % ra.dtype)
+        if ra.shape == (T, E, n, 1):
+            ra = ra.reshape(T, E, n)
+        if ra.shape != (T, E, n):
+            raise ValueError("random_actions: an array of shape %s expected, got %s" % ([T, E, n], list(ra.shape)))
+        head, capacity = int(head), int(capacity)
+        K = T * E
+        if not K <= capacity or not 0 <= head < capacity:
+            raise ValueError("rollout_steps: T E <= capacity and 0 <= head < capacity needed, got T = %d, E = %d, head = %d, "
+                             "capacity = %d" % (T, E, head, capacity))
+        want = {'xe': (n, XE_WIDTH), 'xe_next': (n, XE_WIDTH), 'col': (n * (n - 2),), 'mask': (n,), 'action': (n,), 'reward': ()}
+        for k, tail in want.items():
+            t = storage.get(k)
+            if t is None or tuple(t.shape[1:]) != tail or not t.is_contiguous():
+                raise ValueError("rollout_steps: replay storage %r of shape [slots] + %s expected" % (k, list(tail)))
+            if t.shape[0] < (capacity if head + K > capacity else head + K):      # (a block that wraps touches the last slot)
+                raise ValueError("rollout_steps: replay storage %r has %d slots, the block at %d needs more" % (k, t.shape[0], head))
+        return T, ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32)
+
+    def rollout_steps_buffers(self, T):
+        """the device buffers of rollout_steps() for blocks of T iterations, made once per T: workspace (the trajectory, carved
+        by trajectory_workspace_layout), policy_dev (random_actions [T, E, n] int32 | explore [T, E] bytes), result_dev (reward
+        [T, E] float64 | regular [T, 2, E] bytes), q [T E n, rb] float32"""
+        self._init_device()
+        cache = self.__dict__.setdefault('_traj', {})
+        io = cache.get(T)
+        if io is None:
+            t, E, n, rb = self.torch, self.E, self.n, self.rb
+            offs, size = trajectory_workspace_layout(E, n, rb, T)
+            need = self._lib.v2x_rollout_steps_workspace_bytes(E, n, rb, T)
+            if need != size:
+                raise ValueError("rollout_steps: the library sizes the trajectory workspace of E = %d, n = %d, rb = %d, T = %d at %d "
+                                 "bytes, the documented layout at %d" % (E, n, rb, T, need, size))
+            nb = self.rollout_steps_policy_bytes(T)
+            io = cache[T] = {
+                'workspace': t.zeros(size, dtype=t.uint8, device=self.device), 'offsets': offs,
+                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
+                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
+                'result_dev': t.zeros(self.rollout_steps_result_bytes(T), dtype=t.uint8, device=self.device),
+                'q': t.zeros((T * E * n, rb), dtype=t.float32, device=self.device), 'batch': {}, 'rows_free': []}
+        return io
+
+    def rollout_steps_batch(self, T, row_ptr):
+        """entries 0..T-1 of the trajectory as the engine's batch: T E graphs of n rows, xe and the CSR sources where
+        k_sim_trajectory writes them (row_ptr: the constant pointer of T E n rows, n - 2 sources each)"""
+        from ..engine import DeviceBatch
+        io = self.rollout_steps_buffers(T)
+        db = io['batch'].get(row_ptr.data_ptr())
+        if db is None:
+            E, n, ws, offs = self.E, self.n, io['workspace'], io['offsets']
+            K, t = T * E, self.torch
+            xe = ws[offs['traj_xe']:offs['traj_xe'] + 4 * K * n * XE_WIDTH].view(t.float32).view(K * n, XE_WIDTH)
+            col = ws[offs['traj_col']:offs['traj_col'] + 4 * K * n * (n - 2)].view(t.int32)
+            db = DeviceBatch.from_tensors(K, n, xe, row_ptr, col, n * (n - 2))
+            io['batch'] = {row_ptr.data_ptr(): db}
+            io['row_ptr'] = row_ptr
+        return db
+
+    def rollout_steps_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+        """the v2x_rollout_traj of the resident tensors and the buffers of rollout_steps_buffers(T)"""
+        self._init_device()
+        self._send_grid()
+        E, n = self.E, self.n
+        io = self.rollout_steps_buffers(T)
+        r = self.rollout_struct(storage, head, capacity, v2v_weight, v2i_weight, None, None, power)
+        base, res = io['policy_dev'].data_ptr(), io['result_dev'].data_ptr()
+        r.q, r.random_actions, r.explore = io['q'].data_ptr(), base, base + 4 * T * E * n
+        r.result_reward, r.result_regular = res, res + 8 * T * E
+        if engine is not None:
+            from ..engine import _batch_struct
+            r.model = engine._h
+            r.batch = _batch_struct(self.rollout_steps_batch(T, row_ptr))
+        ws = io['workspace'].data_ptr()
+        return RolloutTraj(r=r, T=T, pad_=0, **{k: ws + o for k, o in io['offsets'].items()})
+
+    def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
+                      power=None):
+        """T DQN rollout iterations in ONE call (v2x_rollout_steps) on the resident state: every simulator walks its T steps in
+        one kernel, one forward scores all T E observations (engine: a GnnEngine, with row_ptr the constant CSR pointer of
+        T E n rows; None: nobody is greedy anywhere in the block, no forward), and one kernel picks (explore [T, E] flags,
+        random_actions [T, E, n]: the host's draws, one upload), pays and stores the T E transitions into slots
+        (head + t E + e) % capacity of `storage`.  Bit for bit T calls of rollout_step().  -> a RolloutBlock whose download
+        (one) is in flight.  Afterwards as after the last rollout_step: fetch_rates(), fetch_observation()."""
+        T, ex, ra = self.check_rollout_steps(explore, random_actions, storage, head, capacity)
+        if engine is not None and row_ptr is None:
+            raise ValueError("rollout_steps: scoring needs the CSR row pointer of the trajectory's batch")
+        self._init_device()
+        if not self._obs_ready:
+            raise RuntimeError("rollout_steps: no observe() since the last step()")
+        self._send_grid()
+        t, E, n = self.torch, self.E, self.n
+        io = self.rollout_steps_buffers(T)
+        i = io['next']
+        io['next'] = (i + 1) % 4
+        if io['policy_ev'][i] is not None:
+            io['policy_ev'][i].synchronize()
+        pin = io['policy_pin'][i].numpy()
+        pin[:4 * T * E * n].view(np.int32)[:] = ra.reshape(-1)
+        pin[4 * T * E * n:4 * T * E * n + T * E] = ex.reshape(-1)
+        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
+        self.traffic['bytes_up'] += io['policy_dev'].numel()
+        if io['policy_ev'][i] is None:
+            io['policy_ev'][i] = t.cuda.Event()
+        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
+        r = self.rollout_steps_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
+        self._keep_actions = self._t['actions']
+        check(self._lib, self._lib.v2x_rollout_steps(C.byref(r), self._stream()))
+        self._obs_ready = True
+        free = io['rows_free']
+        pinned = free.pop() if free else t.zeros(self.rollout_steps_result_bytes(T), dtype=t.uint8, pin_memory=self._pin)
+        pinned.copy_(io['result_dev'], non_blocking=True)
+        self.traffic['bytes_down'] += pinned.numel()
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return RolloutBlock(free, ev, pinned, T, E)
+
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
         """the v2x_opt_problem of the device arrays"""
@@ -920,13 +1089,39 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._resident_row = row
         return row
 
+    def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None):
+        """T iterations of rollout_step() in one call (explore [T, E], random_actions [T, E, n]; DeviceChannels.rollout_steps):
+        the same bookkeeping, once.  -> the RolloutBlock, its download in flight."""
+        if self.stream_backend != 'device':
+            raise ValueError("rollout_steps needs streams='device' (mobility and the MT19937 streams advance inside the call)")
+        self.finish_step()
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        stale = bool(self._dirty)
+        dc = self._flush()
+        dc.check_rollout_steps(explore, random_actions, storage, head, capacity)
+        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
+            dc.observe(self.dest)
+        self._obs = None
+        block = dc.rollout_steps(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
+                                 row_ptr=row_ptr)
+        self._streams_ahead = True
+        self._channels_updated()
+        self._on_device.add('V2V_Interference_all')
+        self._dev_obs = None
+        self._rates_pending = True
+        self._resident_row = block
+        return block
+
     def resident_regular(self, n_channels=4):
         """the regularity flags [E] of the CURRENT observation, from wherever they are known without a device call: the host copy
         of the observation, or the result row of the resident step that made it (waits for that row); otherwise one download"""
         if self._dev_obs is not None and not self._dirty:
             return self._dev_obs[3]
         if self._resident_row is not None and not self._dirty:
-            return self._resident_row.resolve().regular[1]
+            flags = self._resident_row.resolve().regular       # a row [2, E], or the block [T, 2, E] of rollout_steps
+            return flags[1] if flags.ndim == 2 else flags[-1, 1]
         return self.observe_packed(n_channels)[3]
 
     def _pull_rates(self):

@@ -178,7 +178,8 @@ class DeviceReplay(object):
 
     def commit(self, K, row):
         """The block reserve(K) handed out has been enqueued: head and size advance at once.  row: the RolloutRow of the call
-        (its .regular[0] are the flags of the stored observations); it is resolved -- one wait for work already enqueued --
+        (its .regular[0] are the flags of the stored observations) or the RolloutBlock of T iterations made at once (K = T E,
+        .regular[:, 0, :] in slot order); it is resolved -- one wait for work already enqueued --
         when the flags are first needed (sample())."""
         K = int(K)
         self._pending.append((self.head, K, row))
@@ -189,7 +190,8 @@ class DeviceReplay(object):
         """the regularity flags of every committed block are in _regular"""
         if self._pending:
             for first, K, row in self._pending:
-                self._regular[(first + np.arange(K)) % self.capacity] = row.resolve().regular[0]
+                flags = row.resolve().regular                # a row [2, E], or T rows [T, 2, E] (slot order: t major)
+                self._regular[(first + np.arange(K)) % self.capacity] = flags[0] if flags.ndim == 2 else flags[:, 0, :].reshape(-1)
             self._pending = []
 
     def regular_flags(self):

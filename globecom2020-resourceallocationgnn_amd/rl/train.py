@@ -102,10 +102,11 @@ def build_parser():
     ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
                     help="with --sim-backend device: where mobility and the simulators' MT19937 streams advance -- libv2xsim.so "
                          "(the default) or the GPU, where a step is one enqueue that takes only the actions from the host")
-    ap.add_argument("--rollout", choices=["host", "device"], default="host",
+    ap.add_argument("--rollout", choices=["host", "device", "trajectory"], default="host",
                     help="with --sim-backend device --sim-streams device: 'device' runs a whole rollout iteration (score, pick, "
-                         "step, reward, store) as one call on the state resident in HBM; 'host' (the default) scores and stores "
-                         "through the host")
+                         "step, reward, store) as one call on the state resident in HBM, 'trajectory' all iterations of a "
+                         "rollout as one call (one kernel walks the simulators, one forward scores every observation, one kernel "
+                         "picks, pays and stores); 'host' (the default) scores and stores through the host")
     return ap
 
 
@@ -114,8 +115,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
-    if args.rollout == "device" and (args.sim_backend != "device" or args.sim_streams != "device"):
-        ap.error("--rollout device needs --sim-backend device --sim-streams device")
+    if args.rollout != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--rollout %s needs --sim-backend device --sim-streams device" % args.rollout)
     if args.sim_backend == "device" and args.envs < 1:
         ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:

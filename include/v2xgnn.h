@@ -544,6 +544,43 @@ typedef struct v2x_rollout {
 } v2x_rollout;
 int  v2x_rollout_step(const v2x_rollout* r, void* stream);
 
+/* v2x_rollout_steps: T iterations of v2x_rollout_step in one call.  Nothing in a simulator step depends on the actions except
+ * the rates paid for them, and the network does not change inside a rollout: all T observations are known before any action
+ * is.  Enqueues, in this order on one stream with no parallel branches,
+ *   k_sim_trajectory  grid (E), 256 threads: every state walks its T steps (stream, channels, observation: the device functions
+ *                     of the single-step kernels, so the same bits), the MT19937 key array in LDS throughout.  It leaves the
+ *                     resident arrays as T calls of v2x_sim_advance leave them and writes the trajectory: the observation at
+ *                     entry and after every step (entries 0..T), and what the rates read before every step (snapshots 0..T-1);
+ *   v2x_forward       of the T E observations of entries 0..T-1 (`r.batch`: on_device, T E graphs of n rows, xe = traj_xe,
+ *                     col_idx = traj_col, n - 2 sources per row) into r.q -- skipped when r.model is NULL (nobody is greedy);
+ *   k_rollout_finish  grid (T E), one wave per transition (t, e): the pick of v2x_rollout_pick, the rates of v2x_sim_rates on
+ *                     snapshot t (same fold orders), the reward of v2x_rollout_store, and the transition -- xe / col / mask of
+ *                     entry t, xe_next of entry t + 1, actions, reward -- into slot (head + t E + e) % capacity.  The
+ *                     transitions of t = T - 1 also leave actions / v2v_rate / v2i_rate / interference / v2i_interf /
+ *                     v2v_interf in the resident arrays.
+ * In `r`: explore is [T][E], random_actions [T][E][n], q [T E n][rb], result_reward [T][E], result_regular [T][2][E] (row t:
+ * the flags of the stored observation, then of the next one); everything else as for v2x_rollout_step.  Same rules: all
+ * pointers [dev], asynchronous, no allocation, no synchronisation, no environment variable read; every check of every part
+ * before the first launch (V2X_EINVAL, text in v2x_last_error(NULL)).  Limits: those of v2x_rollout_step, 1 <= T,
+ * T E <= capacity (every transition of the block has its own slot), T E n (n - 2) < 2^31, non-NULL workspaces.
+ * The trajectory workspace is seven arrays; one allocation of v2x_rollout_steps_workspace_bytes(E, n, rb, T) bytes holds
+ * them back to back in the order of the struct, each rounded up to a multiple of 256 bytes:
+ *   A(4 (T+1) E n 16) + A(4 (T+1) E n (n-2)) + A(4 (T+1) E n) + A((T+1) E) + A(8 T E n n rb) + A(8 T E n rb) + A(8 T E n),
+ *   A(x) = ceil(x / 256) * 256.  A negative V2X_E* code on sizes outside the limits.                                          */
+typedef struct v2x_rollout_traj {
+  v2x_rollout r;
+  int32_t T, pad_;
+  float* traj_xe;                  /* [T+1][E][n][16]      */
+  int32_t* traj_col;               /* [T+1][E][n (n - 2)]  */
+  int32_t* traj_mask;              /* [T+1][E][n]          */
+  uint8_t* traj_regular;           /* [T+1][E]             */
+  double* traj_v2v_ff;             /* [T][E][n][n][rb]     */
+  double* traj_v2i_ff;             /* [T][E][n][rb]        */
+  double* traj_v2i_abs;            /* [T][E][n]            */
+} v2x_rollout_traj;
+int64_t v2x_rollout_steps_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
+int  v2x_rollout_steps(const v2x_rollout_traj* r, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

@@ -32,6 +32,14 @@ alive in one process, Agent.train(1, 20) timed in turn; and the call alone betwe
 a graph the tool captures itself (the agent issues it eagerly: head moves with every block).
 
     python tools/sim_device_timing.py --mode rollout [--out profiles/rollout_device_timing.json]
+
+--mode trajectory measures the whole-rollout call (Agent(rollout_backend='trajectory'): v2x_rollout_steps) with the same recipe at
+E = 1, 5, 10, 25 and 50 simulators: a 50-transition rollout (Agent.generate_d2d_transition(50), epsilon held near 0.4) for
+'trajectory', for 'device' (one v2x_rollout_step per iteration) and, at E = 1, for the host simulator's single-call native
+rollout; the bytes each moves per rollout; the one call alone between HIP events and its host enqueue time; and the DQN loop
+Agent.train(1, 20) per train step for the same backends, all agents of one E alive in one process and taken in turn.
+
+    python tools/sim_device_timing.py --mode trajectory [--out profiles/rollout_trajectory_timing.json]
 """
 import argparse
 import json
@@ -360,6 +368,89 @@ def loop_in_process_rollout(reps):
             for b in walls}
 
 
+TRAJECTORY_SETTINGS = {"trajectory": (dict(backend="device", streams="device"), "trajectory"),
+                       "device": (dict(backend="device", streams="device"), "device"),
+                       "host_native_rollout": (dict(backend="host"), "host")}            # (E = 1 only: the single-call v2xsim_rollout)
+
+
+def trajectory_legs(E, reps, warmup, loop_reps):
+    """a 50-transition rollout of E simulators alone (no replay in between), the one call between HIP events, and the DQN loop"""
+    import ctypes
+    import torch
+    from v2xgnn.lib import check
+    names = [k for k in TRAJECTORY_SETTINGS if k != "host_native_rollout" or E == 1]
+    row = {"simulators": E, "links": LINKS, "rb": RB, "transitions": 50, "iterations": -(-50 // E)}
+    with torch.cuda.stream(torch.cuda.Stream(device=0)):
+        agents = {k: _rollout_agent(E, *TRAJECTORY_SETTINGS[k]) for k in names}
+        walls, traffic = {k: [] for k in names}, {}
+        for ag in agents.values():
+            ag.num_Train_Step = 20
+        for k in range(warmup + reps):
+            if k == warmup:
+                traffic = {name: dict(ag.env.device_channels.traffic) for name, ag in agents.items() if name != "host_native_rollout"}
+            for name, ag in agents.items():                          # taken in turn: the box's load drifts
+                ag.num_step = 10 * 50                                  # epsilon = 1 - 0.99 * 500 / 800: both branches in every rollout
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ag.generate_d2d_transition(50)
+                torch.cuda.synchronize()
+                if k >= warmup:
+                    walls[name].append(time.perf_counter() - t0)
+        for name, ag in agents.items():
+            row["rollout_%s_ms" % name] = _median_ms(walls[name])
+            if name in traffic:
+                after = ag.env.device_channels.traffic
+                for key in ("bytes_up", "bytes_down"):
+                    row["%s_%s_per_rollout" % (name, key)] = (after[key] - traffic[name][key]) // reps
+        # the call alone between HIP events (policy already on the device), and what the host spends enqueueing it
+        ag = agents["trajectory"]
+        dc, rep, T = ag.env.device_channels, ag.device_replay, -(-50 // E)
+        engine, rp = ag.brain.model.engine, rep.row_ptr(T * E)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+        head = rep.reserve(T * E)
+        r = dc.rollout_steps_struct(T, rep.storage(), head, rep.capacity, 1.0, 0.1, engine=engine, row_ptr=rp)
+        gpu, host = [], []
+        for k in range(warmup + reps):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ev[0].record()
+            check(dc._lib, dc._lib.v2x_rollout_steps(ctypes.byref(r), torch.cuda.current_stream().cuda_stream))
+            ev[1].record()
+            t1 = time.perf_counter()
+            torch.cuda.synchronize()
+            if k >= warmup:
+                gpu.append(ev[0].elapsed_time(ev[1]) * 1e-3)
+                host.append(t1 - t0)
+        row["call_gpu_ms"], row["call_enqueue_ms"] = _median_ms(gpu), _median_ms(host)
+        # the loop: Agent.train(1, 20), the agents taken in turn
+        loop = {k: [] for k in names}
+        for ag in agents.values():
+            ag.train(1, 20)                                            # warm-up, untimed
+        torch.cuda.synchronize()
+        for _ in range(loop_reps):
+            for name, ag in agents.items():
+                t0 = time.perf_counter()
+                ag.train(1, 20)
+                torch.cuda.synchronize()
+                loop[name].append(time.perf_counter() - t0)
+        for name in names:
+            row["loop_%s_ms_per_train_step" % name] = round(float(np.median(loop[name])) * 1e3 / 20, 3)
+        for ag in agents.values():
+            ag.brain.close()
+    return row
+
+
+def main_trajectory(args):
+    import torch
+    from v2xgnn.rl.batched_env import _usable_cpus
+    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
+              "loop_reps": max(3, args.loop_reps), "rollouts": []}
+    for E in args.simulators:
+        result["rollouts"].append(trajectory_legs(E, args.reps, args.warmup, max(3, args.loop_reps)))
+        print(json.dumps(result["rollouts"][-1]), flush=True)
+    return result
+
+
 def main_rollout(args):
     import torch
     from v2xgnn.rl.batched_env import _usable_cpus
@@ -388,25 +479,30 @@ def main_streams(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["channels", "streams", "rollout"], default="channels")
+    ap.add_argument("--mode", choices=["channels", "streams", "rollout", "trajectory"], default="channels")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--loop-reps", type=int, default=3)
     ap.add_argument("--no-loop", action="store_true")
-    ap.add_argument("--simulators", type=int, nargs="+", default=[1, 50, 200])
+    ap.add_argument("--simulators", type=int, nargs="+", default=None)
     args = ap.parse_args()
+    if args.simulators is None:
+        args.simulators = [1, 5, 10, 25, 50] if args.mode == "trajectory" else [1, 50, 200]
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("sim_device_timing needs a GPU: nothing is measured without one")
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", {"streams": "sim_device_streams_timing.json", "rollout": "rollout_device_timing.json"}.get(
+        args.out = os.path.join(ROOT, "profiles", {"streams": "sim_device_streams_timing.json", "rollout": "rollout_device_timing.json",
+                                                           "trajectory": "rollout_trajectory_timing.json"}.get(
             args.mode, "sim_device_timing.json"))
     from v2xgnn.rl.batched_env import _usable_cpus
     if args.mode == "streams":
         result = main_streams(args)
     elif args.mode == "rollout":
         result = main_rollout(args)
+    elif args.mode == "trajectory":
+        result = main_trajectory(args)
     else:
         result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
                   "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
