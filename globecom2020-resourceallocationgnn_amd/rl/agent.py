@@ -341,19 +341,20 @@ class Agent(object):
             if not packed:
                 raise RuntimeError("rollout_backend=%r takes the packed observation of the simulator (n_channels == n_RB, "
                                    "3..31 links, V2X_RL_PACKED unset)" % self.rollout_backend)
-            rows, drawn, block = [], None, None
+            rows, drawn, block = [], None, None            # rows: results on their way (the rewards are read when they have arrived)
             if self.rollout_backend == 'trajectory':       # the draws of the whole rollout first, then (if it can be) one call
                 drawn = self._draw_rollout_ahead(n_iter)
-                block = self._trajectory_rollout(drawn)
+                block = self._resident_rollout(drawn, whole=True)
             if block is not None:
                 rows.append((0, block))
             else:
                 for it in range(n_iter):
-                    r = self._device_iteration(last=it == n_iter - 1, drawn=None if drawn is None else drawn[it])
-                    if hasattr(r, 'resolve'):
-                        rows.append((it, r))               # a result row on its way: the rewards are read when it has arrived
-                    else:
-                        rewards[it * E:(it + 1) * E] = r
+                    d = self._policy_draws() if drawn is None else drawn[it]
+                    r = self._resident_rollout([d], whole=False)
+                    if r is not None:
+                        rows.append((it, r))
+                    else:                                  # a graph the fixed-degree CSR cannot score: the host's iteration, these draws
+                        rewards[it * E:(it + 1) * E] = self._packed_iteration(last=it == n_iter - 1, drawn=d)
             out = rewards[:num_transitions] if n_iter * E == num_transitions else rewards
             self._lazy_rewards = (out, rewards, rows, E)
             if not getattr(self, '_predraw_ok', False):    # (inside Agent.train the step's replay resolves the rows first)
@@ -402,7 +403,7 @@ class Agent(object):
         if lazy is None:
             return None
         out, rewards, rows, E = lazy
-        for it, row in rows:                               # (a RolloutRow: E rewards; a RolloutBlock: T x E from iteration `it` on)
+        for it, row in rows:                               # (a RolloutResult: E rewards, or T x E from iteration `it` on)
             r = row.resolve().reward.reshape(-1)
             rewards[it * E:it * E + r.size] = r
         return out
@@ -439,60 +440,39 @@ class Agent(object):
             self.num_step = base
         return drawn
 
-    def _trajectory_rollout(self, drawn):
-        """All iterations of a rollout as ONE call on the resident state (rollout_backend='trajectory'): one reserve, one
-        DeviceBatchedEnviron.rollout_steps, one commit, the FIFO bookkeeping of len(drawn) x E transitions.  -> the RolloutBlock
-        (rewards once it has arrived), or None when the per-iteration path has to run with these draws: somebody is greedy and a
-        resident graph is not regular (receivers are fixed within a rollout: one look suffices), or the block does not fit the
-        replay ring."""
+    def _resident_rollout(self, drawn, whole):
+        """The iterations `drawn` ([(actions [E, n, 1], greedy states)], _policy_draws each) on the resident state: one reserve, one
+        call -- DeviceBatchedEnviron.rollout_steps for a whole rollout (rollout_backend='trajectory'), rollout_step for the one
+        iteration of 'device' or of a rollout that cannot be made whole -- one commit, the FIFO bookkeeping of len(drawn) x E
+        transitions.  The same numpy draws in the same order as _packed_iteration; the replay's own draws are made at replay time.
+        -> the RolloutResult (rewards once it has arrived), or None when the next smaller path has to run with these draws:
+        somebody is greedy and a resident graph is not regular (a link that is its own receiver cannot be scored from the
+        fixed-degree CSR; receivers are fixed within a rollout, so one look suffices: the flags come from the previous result --
+        inside Agent.train the replay has resolved it already -- or after a reset from one small download), or a whole rollout
+        does not fit the replay ring."""
         env, rep = self.env, self.device_replay
-        E, n, C, T = env.E, self.num_D2D, self.num_CH, len(drawn)
+        E, n, T = env.E, self.num_D2D, len(drawn)
         K = T * E
         anybody = any(len(g) > 0 for _, g in drawn)
-        if K > rep.capacity or (anybody and not env.resident_regular(C).all()):
+        if (whole and K > rep.capacity) or (anybody and not env.resident_regular(self.num_CH).all()):
             return None
         explore = np.ones((T, E), np.uint8)
-        for it, (_, greedy) in enumerate(drawn):
-            explore[it, greedy] = 0
-        actions = np.stack([a for a, _ in drawn]).reshape(T, E, n)
+        for row, (_, greedy) in zip(explore, drawn):
+            row[greedy] = 0
+        if whole:
+            call, actions = env.rollout_steps, np.stack([a for a, _ in drawn]).reshape(T, E, n)
+        else:                                          # one iteration: no leading axis
+            call, explore, actions = env.rollout_step, explore[0], drawn[0][0]
         head = rep.reserve(K)
-        block = env.rollout_steps(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
-                                  engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None)
-        rep.commit(K, block)
+        result = call(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
+                      engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None)
+        rep.commit(K, result)
         self.num_step += K
         samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
         samples.extend([None] * K)
         if len(samples) > self.memory.capacity:
             del samples[:len(samples) - self.memory.capacity]
-        return block
-
-    def _device_iteration(self, last=False, drawn=None):
-        """_packed_iteration as ONE call on the resident state (rollout_backend='device'): the same numpy draws in the same
-        order, then the policy buffer goes up, DeviceBatchedEnviron.rollout_step scores, picks, steps and stores, and the
-        replay memory commits the block.  -> the RolloutRow (rewards once it has arrived).  The replay's own draws are made at
-        replay time: nothing here is drawn ahead, so the process-wide stream sees the reference's order.
-        A state whose graph is not regular (a link that is its own receiver) cannot be scored from the fixed-degree CSR: when
-        somebody is greedy the flags of the current observation are read first (from the previous iteration's result row --
-        inside Agent.train the replay has resolved it already; after a reset one small download), and an iteration with such
-        a state runs through _packed_iteration with the draws already taken.  drawn: this iteration's draws, taken ahead
-        (_draw_rollout_ahead)."""
-        env, rep = self.env, self.device_replay
-        E, C = env.E, self.num_CH
-        actions, greedy = self._policy_draws() if drawn is None else drawn
-        if greedy and not env.resident_regular(C).all():
-            return self._packed_iteration(last=last, drawn=(actions, greedy))
-        explore = np.ones(E, np.uint8)
-        explore[greedy] = 0
-        head = rep.reserve(E)
-        row = env.rollout_step(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
-                               engine=self.brain.model.engine if greedy else None, row_ptr=rep.row_ptr(E) if greedy else None)
-        rep.commit(E, row)
-        self.num_step += E
-        samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x E)
-        samples.extend([None] * E)
-        if len(samples) > self.memory.capacity:
-            del samples[:len(samples) - self.memory.capacity]
-        return row
+        return result
 
     def _packed_iteration(self, last=False, force_greedy=False, drawn=None):
         """One iteration of _generate_batched on packed observations: same epsilon draws in the same order, same Q-values

@@ -24,6 +24,16 @@ from the host but the actions (v2x_sim_advance: rates, stream, channels, observa
     dc.advance(actions)                         # or all of a step at once
     dc.traffic                                  # {'bytes_up': ..., 'bytes_down': ...}: every byte this object sent over the bus
 
+A DQN rollout runs on the resident state as well, one iteration per call (v2x_rollout_step) or T of them in one call
+(v2x_rollout_steps).  The two calls are ONE host path -- one argument check, one set of buffers per T (T = None: the single
+iteration), one policy upload through a ring of page-locked copies, one struct builder, one result download -- that ends in
+the entry point of its name; both hand out a RolloutResult:
+
+    res = dc.rollout_step(explore, random_actions, storage, head, capacity, w_v2v, w_v2i, engine, row_ptr)      # [E], [E, n]
+    res = dc.rollout_steps(explore, random_actions, storage, head, capacity, w_v2v, w_v2i, engine, row_ptr)     # [T, E], [T, E, n]
+    res.resolve().reward, res.regular           # [E], [2, E] / [T, E], [T, 2, E]
+    res.stored_regular, res.resident_regular    # the flags of the stored slots [T E]; of the observation left resident [E]
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -57,27 +67,6 @@ def _align(x, a=64):
     return (x + a - 1) // a * a
 
 
-class RolloutRow(object):
-    """The result row of one resident rollout iteration (DeviceChannels.rollout_step): the rewards [E] and the regularity flags
-    of the stored observation and of the next one, [2, E].  The row is on its way to a page-locked buffer when this object is
-    handed out; resolve() waits for the event recorded behind that copy (once), keeps plain copies in .reward / .regular and
-    gives the buffer back."""
-
-    def __init__(self, owner, event, pin, E):
-        self._owner, self._event, self._pin, self.E = owner, event, pin, E
-        self.reward = self.regular = None
-
-    def resolve(self):
-        if self._pin is not None:
-            self._event.synchronize()
-            raw = self._pin.numpy()
-            self.reward = raw[:8 * self.E].view(np.float64).copy()
-            self.regular = raw[8 * self.E:10 * self.E].reshape(2, self.E).astype(bool)
-            self._owner._rows_free.append(self._pin)
-            self._pin = self._event = None
-        return self
-
-
 def trajectory_workspace_layout(E, n, rb, T):
     """-> (the byte offsets of traj_xe, traj_col, traj_mask, traj_regular, traj_v2v_ff, traj_v2i_ff, traj_v2i_abs in the one
     workspace of v2x_rollout_steps, its size): the formula of include/v2xgnn.h, every array rounded up to 256 bytes"""
@@ -90,24 +79,42 @@ def trajectory_workspace_layout(E, n, rb, T):
     return dict(zip(('traj_xe', 'traj_col', 'traj_mask', 'traj_regular', 'traj_v2v_ff', 'traj_v2i_ff', 'traj_v2i_abs'), offs)), o
 
 
-class RolloutBlock(object):
-    """The result rows of T resident rollout iterations made in one call (DeviceChannels.rollout_steps): after resolve(),
-    .reward [T, E] and .regular [T, 2, E] (row t: the flags of the observation stored by iteration t, then of the next one).
-    Like RolloutRow the block is on its way to a page-locked buffer when this object is handed out."""
+class RolloutResult(object):
+    """What a resident rollout call brings back: from DeviceChannels.rollout_step (T None) the rewards [E] and the regularity
+    flags [2, E] of the stored observation and of the next one; from rollout_steps the same per iteration, [T, E] and
+    [T, 2, E].  The bytes are on their way to a page-locked buffer when this object is handed out; resolve() waits for the
+    event recorded behind that copy (once), keeps plain copies in .reward / .regular and gives the buffer back to `free`."""
 
-    def __init__(self, free, event, pin, T, E):
-        self._free, self._event, self._pin, self.T, self.E = free, event, pin, T, E
+    def __init__(self, free, event, pin, E, T=None):
+        self._free, self._event, self._pin, self.E, self.T = free, event, pin, E, T
         self.reward = self.regular = None
 
     def resolve(self):
         if self._pin is not None:
             self._event.synchronize()
-            raw, K = self._pin.numpy(), self.T * self.E
-            self.reward = raw[:8 * K].view(np.float64).reshape(self.T, self.E).copy()
-            self.regular = raw[8 * K:10 * K].reshape(self.T, 2, self.E).astype(bool)
+            lead = () if self.T is None else (self.T,)
+            raw, K = self._pin.numpy(), (self.T or 1) * self.E
+            self.reward = raw[:8 * K].view(np.float64).reshape(lead + (self.E,)).copy()
+            self.regular = raw[8 * K:10 * K].reshape(lead + (2, self.E)).astype(bool)
             self._free.append(self._pin)
             self._pin = self._event = None
         return self
+
+    @property
+    def stored_regular(self):
+        """the flags of the stored observations in slot order (t major, e minor), flat [T E]"""
+        return self.resolve().regular.reshape(-1, 2, self.E)[:, 0, :].reshape(-1)
+
+    @property
+    def resident_regular(self):
+        """the flags [E] of the observation the call left resident"""
+        return self.resolve().regular.reshape(-1, 2, self.E)[-1, 1]
+
+
+def _block_length(explore):
+    """T of the explore flags [T, E] of a block (0: not a block, refused by the check)"""
+    shape = np.shape(explore)
+    return shape[0] if len(shape) == 2 else 0
 
 
 class DeviceChannels(object):
@@ -138,6 +145,7 @@ class DeviceChannels(object):
         self._grid = None                                # set_grid(): (lanes [4, n_lanes] float64, width, height, timestep)
         self._grid_sent = False
         self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
+        self._roll = {}                                  # _rollout_io(): None (rollout_step) or T (rollout_steps) -> its buffers
 
     # ------------------------------------------------------------------ shapes and checks
     def shapes(self):
@@ -474,94 +482,199 @@ class DeviceChannels(object):
                            'interf_db', 'state', 'xe', 'mask', 'col', 'regular', 'v2v_rate', 'v2i_rate', 'interference',
                            'v2i_interf', 'v2v_interf')})
 
-    # ------------------------------------------------------------------ one DQN rollout iteration on the resident state
+    # ------------------------------------------------------------------ DQN rollouts on the resident state
+    # One host path with two entry points: rollout_step() makes one iteration (v2x_rollout_step), rollout_steps() T of them
+    # (v2x_rollout_steps).  Everything around the library call is shared and takes T = None for the one iteration (no leading
+    # axis, the resident observation is the batch) or the T of a block (a leading axis of T, the trajectory workspace).
+    def rollout_steps_policy_bytes(self, T):
+        """bytes of the one buffer rollout_steps() uploads: random_actions [T, E, n] int32, then explore [T, E] bytes"""
+        return _align(4 * T * self.E * self.n + T * self.E, 4)
+
+    def rollout_steps_result_bytes(self, T):
+        """bytes of the result block rollout_steps() downloads: reward [T, E] float64, then regular [T, 2, E] bytes"""
+        return _align(10 * T * self.E, 8)
+
     @property
     def rollout_policy_bytes(self):
-        """bytes of the one buffer a rollout iteration uploads: random_actions [E, n] int32, then explore [E] bytes"""
-        return _align(4 * self.E * self.n + self.E, 4)
+        """bytes of the one buffer rollout_step() uploads: random_actions [E, n] int32, then explore [E] bytes"""
+        return self.rollout_steps_policy_bytes(1)
 
     @property
     def rollout_result_bytes(self):
-        """bytes of the result row a rollout iteration downloads: reward [E] float64, then regular [2, E] bytes"""
-        return _align(10 * self.E, 8)
+        """bytes of the result row rollout_step() downloads: reward [E] float64, then regular [2, E] bytes"""
+        return self.rollout_steps_result_bytes(1)
 
-    def check_rollout(self, explore, random_actions, storage, head, capacity):
-        """ValueError unless the arguments of rollout_step() fit this object; -> (explore [E] uint8, random_actions [E, n] int32)"""
+    def _check_rollout(self, who, T, explore, random_actions, storage, head, capacity):
+        """ValueError unless the arguments of rollout_step() (T None) / rollout_steps() fit this object; -> (explore uint8,
+        random_actions int32) of shapes [E] and [E, n], under a leading axis of T for a block"""
         E, n = self.E, self.n
+        lead, K = (() if T is None else (T,)), (E if T is None else T * E)
         self.check_observe(n, self.rb)
-        self._check_mobility("rollout_step", True)
+        self._check_mobility(who, True)
         ex = np.asarray(explore)
-        if ex.shape != (E,) or ex.dtype.kind not in 'biu':
-            raise ValueError("explore: %d flags expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
+        if K < 1 or ex.shape != lead + (E,) or ex.dtype.kind not in 'biu':
+            raise ValueError("explore: %s flags expected, got shape %s of dtype %s"
+                             % (E if T is None else "[T, %d] with T >= 1" % E, list(ex.shape), ex.dtype))
         ra = np.asarray(random_actions)
         if ra.dtype.kind not in 'iu':
             raise ValueError("random_actions must be integers, got dtype %s" % ra.dtype)
-        if ra.shape == (E, n, 1):
-            ra = ra.reshape(E, n)
-        if ra.shape != (E, n):
-            raise ValueError("random_actions: an array of shape %s expected, got %s" % ([E, n], list(ra.shape)))
+        if ra.shape == lead + (E, n, 1):
+            ra = ra.reshape(lead + (E, n))
+        if ra.shape != lead + (E, n):
+            raise ValueError("random_actions: an array of shape %s expected, got %s" % (list(lead + (E, n)), list(ra.shape)))
         head, capacity = int(head), int(capacity)
-        if not E <= capacity or not 0 <= head < capacity:
-            raise ValueError("rollout_step: E <= capacity and 0 <= head < capacity needed, got E = %d, head = %d, capacity = %d"
-                             % (E, head, capacity))
+        if not K <= capacity or not 0 <= head < capacity:
+            raise ValueError("%s: %sE <= capacity and 0 <= head < capacity needed, got %sE = %d, head = %d, capacity = %d"
+                             % (who, "" if T is None else "T ", "" if T is None else "T = %d, " % T, E, head, capacity))
         want = {'xe': (n, XE_WIDTH), 'xe_next': (n, XE_WIDTH), 'col': (n * (n - 2),), 'mask': (n,), 'action': (n,), 'reward': ()}
         for k, tail in want.items():
             t = storage.get(k)
             if t is None or tuple(t.shape[1:]) != tail or not t.is_contiguous():
-                raise ValueError("rollout_step: replay storage %r of shape [slots] + %s expected" % (k, list(tail)))
-            if t.shape[0] < (capacity if head + E > capacity else head + E):      # (a block that wraps touches the last slot)
-                raise ValueError("rollout_step: replay storage %r has %d slots, the block at %d needs more" % (k, t.shape[0], head))
+                raise ValueError("%s: replay storage %r of shape [slots] + %s expected" % (who, k, list(tail)))
+            if t.shape[0] < (capacity if head + K > capacity else head + K):      # (a block that wraps touches the last slot)
+                raise ValueError("%s: replay storage %r has %d slots, the block at %d needs more" % (who, k, t.shape[0], head))
         return ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32)
+
+    def check_rollout(self, explore, random_actions, storage, head, capacity):
+        """ValueError unless the arguments of rollout_step() fit this object; -> (explore [E] uint8, random_actions [E, n] int32)"""
+        return self._check_rollout("rollout_step", None, explore, random_actions, storage, head, capacity)
+
+    def check_rollout_steps(self, explore, random_actions, storage, head, capacity):
+        """ValueError unless the arguments of rollout_steps() fit this object; -> (T, explore [T, E] uint8, random_actions
+        [T, E, n] int32)"""
+        T = _block_length(explore)
+        return (T,) + self._check_rollout("rollout_steps", T, explore, random_actions, storage, head, capacity)
+
+    def _rollout_io(self, T):
+        """the buffers of rollout_step() (T None) or of rollout_steps() for blocks of T iterations, made once per T: policy_dev
+        (random_actions int32 | explore bytes) behind a ring of four page-locked copies with their events, result_dev (reward
+        float64 | regular bytes) with the free list of its page-locked copies, q [graphs n, rb] float32, the observations a
+        model scores (xe, col of `graphs` graphs) with the cached DeviceBatch, and for a block the trajectory workspace"""
+        self._init_device()
+        io = self._roll.get(T)
+        if io is None:
+            t, E, n, rb = self.torch, self.E, self.n, self.rb
+            K = (T or 1) * E
+            nb = self.rollout_steps_policy_bytes(T or 1)
+            io = self._roll[T] = {
+                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
+                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
+                'result_dev': t.zeros(self.rollout_steps_result_bytes(T or 1), dtype=t.uint8, device=self.device), 'free': [],
+                'q': t.zeros((K * n, rb), dtype=t.float32, device=self.device), 'graphs': K, 'batch': {}}
+            if T is None:
+                io['xe'], io['col'] = self._t['xe'].view(E * n, XE_WIDTH), self._t['col'].view(-1)
+            else:
+                offs, size = trajectory_workspace_layout(E, n, rb, T)
+                need = self._lib.v2x_rollout_steps_workspace_bytes(E, n, rb, T)
+                if need != size:
+                    raise ValueError("rollout_steps: the library sizes the trajectory workspace of E = %d, n = %d, rb = %d, T = %d at "
+                                     "%d bytes, the documented layout at %d" % (E, n, rb, T, need, size))
+                ws = io['workspace'] = t.zeros(size, dtype=t.uint8, device=self.device)
+                io['offsets'] = offs
+                # entries 0..T-1 of the trajectory, where k_sim_trajectory writes them
+                io['xe'] = ws[offs['traj_xe']:offs['traj_xe'] + 4 * K * n * XE_WIDTH].view(t.float32).view(K * n, XE_WIDTH)
+                io['col'] = ws[offs['traj_col']:offs['traj_col'] + 4 * K * n * (n - 2)].view(t.int32)
+        return io
 
     def rollout_buffers(self):
         """the device buffers of rollout_step(): policy_dev (random_actions [E, n] int32 | explore [E] bytes), result_dev (reward [E]
         float64 | regular [2, E] bytes), q [E n, rb] float32"""
-        self._init_device()
-        io = getattr(self, '_roll', None)
-        if io is None:
-            t, E, n = self.torch, self.E, self.n
-            nb = self.rollout_policy_bytes
-            io = self._roll = {
-                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
-                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
-                'result_dev': t.zeros(self.rollout_result_bytes, dtype=t.uint8, device=self.device),
-                'q': t.zeros((E * n, self.rb), dtype=t.float32, device=self.device), 'batch': {}}
-            self._rows_free = []
-        return io
+        return self._rollout_io(None)
 
-    def rollout_batch(self, row_ptr):
-        """the resident observation as the engine's batch: E graphs of n rows, xe and the CSR sources where v2x_sim_observe writes
-        them (every state regular: n - 2 sources per row, row_ptr the constant pointer of E n rows)"""
+    def rollout_steps_buffers(self, T):
+        """the device buffers of rollout_steps() for blocks of T iterations: workspace (the trajectory, carved by
+        trajectory_workspace_layout), policy_dev (random_actions [T, E, n] int32 | explore [T, E] bytes), result_dev (reward
+        [T, E] float64 | regular [T, 2, E] bytes), q [T E n, rb] float32"""
+        return self._rollout_io(T)
+
+    def _rollout_batch(self, io, graphs, xe, col, row_ptr):
+        """`graphs` observations of n rows as the engine's batch, xe and the CSR sources where the kernels write them (every
+        state regular: n - 2 sources per row, row_ptr the constant pointer of graphs n rows); kept in io for the next call"""
         from ..engine import DeviceBatch
-        self._init_device()
-        io = self.rollout_buffers()
         db = io['batch'].get(row_ptr.data_ptr())
         if db is None:
-            E, n, T = self.E, self.n, self._t
-            db = DeviceBatch.from_tensors(E, n, T['xe'].view(E * n, XE_WIDTH), row_ptr, T['col'].view(-1), n * (n - 2))
+            db = DeviceBatch.from_tensors(graphs, self.n, xe, row_ptr, col, self.n * (self.n - 2))
             io['batch'] = {row_ptr.data_ptr(): db}
             io['row_ptr'] = row_ptr
         return db
 
-    def rollout_struct(self, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
-        """the v2x_rollout of the resident tensors (what rollout_step() passes to the library): the policy comes from
-        rollout_buffers()['policy_dev'], the result row goes to ['result_dev'], the actions to tensor('actions')"""
-        self._init_device()
+    def rollout_batch(self, row_ptr):
+        """the resident observation as the engine's batch: E graphs of n rows, where v2x_sim_observe writes them"""
+        io = self._rollout_io(None)
+        return self._rollout_batch(io, io['graphs'], io['xe'], io['col'], row_ptr)
+
+    def _rollout_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power):
+        """what the library takes: the v2x_rollout of the resident tensors and the buffers of _rollout_io(T) -- the policy comes
+        from policy_dev, the result goes to result_dev, the actions to tensor('actions') -- and around it, for a block, the
+        v2x_rollout_traj with the workspace"""
+        io = self._rollout_io(T)
         self._send_grid()
-        T, E, n = self._t, self.E, self.n
-        io = self.rollout_buffers()
-        base = io['policy_dev'].data_ptr()
-        r = Rollout(model=None, q=io['q'].data_ptr(), explore=base + 4 * E * n, random_actions=base, actions=T['actions'].data_ptr(),
-                    step=self._sim_step(T['actions'].data_ptr(), power), w_v2v=float(v2v_weight), w_v2i=float(v2i_weight),
+        t, K = self._t, io['graphs']
+        base, res = io['policy_dev'].data_ptr(), io['result_dev'].data_ptr()
+        r = Rollout(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * self.n, random_actions=base, actions=t['actions'].data_ptr(),
+                    step=self._sim_step(t['actions'].data_ptr(), power), w_v2v=float(v2v_weight), w_v2i=float(v2i_weight),
                     rep_xe=storage['xe'].data_ptr(), rep_xe_next=storage['xe_next'].data_ptr(), rep_col=storage['col'].data_ptr(),
                     rep_mask=storage['mask'].data_ptr(), rep_action=storage['action'].data_ptr(),
                     rep_reward=storage['reward'].data_ptr(), head=int(head), capacity=int(capacity),
-                    result_reward=io['result_dev'].data_ptr(), result_regular=io['result_dev'].data_ptr() + 8 * E)
+                    result_reward=res, result_regular=res + 8 * K)
         if engine is not None:
             from ..engine import _batch_struct
             r.model = engine._h
-            r.batch = _batch_struct(self.rollout_batch(row_ptr))
-        return r
+            r.batch = _batch_struct(self._rollout_batch(io, K, io['xe'], io['col'], row_ptr))
+        if T is None:
+            return r
+        ws = io['workspace'].data_ptr()
+        return RolloutTraj(r=r, T=T, pad_=0, **{k: ws + o for k, o in io['offsets'].items()})
+
+    def rollout_struct(self, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+        """the v2x_rollout of the resident tensors and rollout_buffers() (what rollout_step() passes to the library)"""
+        return self._rollout_struct(None, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
+
+    def rollout_steps_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+        """the v2x_rollout_traj of the resident tensors and rollout_steps_buffers(T) (what rollout_steps() passes to the library)"""
+        return self._rollout_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
+
+    def _upload_policy(self, io, random_actions, explore):
+        """the host's draws -> io['policy_dev'] through the next of the four page-locked copies (its event guards the reuse)"""
+        t, i = self.torch, io['next']
+        io['next'] = (i + 1) % 4
+        if io['policy_ev'][i] is not None:
+            io['policy_ev'][i].synchronize()
+        pin, nb = io['policy_pin'][i].numpy(), 4 * random_actions.size
+        pin[:nb].view(np.int32)[:] = random_actions.reshape(-1)
+        pin[nb:nb + explore.size] = explore.reshape(-1)
+        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
+        self.traffic['bytes_up'] += io['policy_dev'].numel()
+        if io['policy_ev'][i] is None:
+            io['policy_ev'][i] = t.cuda.Event()
+        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
+
+    def _download_result(self, io, T):
+        """io['result_dev'] -> a page-locked copy (a returned one, or a new one); -> the RolloutResult, its download in flight"""
+        t, free = self.torch, io['free']
+        pinned = free.pop() if free else t.zeros(io['result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
+        pinned.copy_(io['result_dev'], non_blocking=True)
+        self.traffic['bytes_down'] += pinned.numel()
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return RolloutResult(free, ev, pinned, self.E, T)
+
+    def _rollout(self, who, T, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power):
+        """rollout_step() (T None) / rollout_steps(): check, upload the policy, the one library call, start the download"""
+        ex, ra = self._check_rollout(who, T, explore, random_actions, storage, head, capacity)
+        if engine is not None and row_ptr is None:
+            raise ValueError("%s: scoring needs the CSR row pointer of the %s batch" % (who, "resident" if T is None else "trajectory's"))
+        self._init_device()
+        if not self._obs_ready:
+            raise RuntimeError("%s: no observe() since the last step()" % who)
+        io = self._rollout_io(T)
+        self._upload_policy(io, ra, ex)
+        r = self._rollout_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
+        self._keep_actions = self._t['actions']
+        call = self._lib.v2x_rollout_step if T is None else self._lib.v2x_rollout_steps
+        check(self._lib, call(C.byref(r), self._stream()))
+        self._obs_ready = True
+        return self._download_result(io, T)
 
     def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                      power=None):
@@ -571,134 +684,9 @@ class DeviceChannels(object):
         buffer), the simulator step, the reward v2v_weight * sum(V2V rates) + v2i_weight * sum(V2I rates) in numpy's order, and
         the transitions into slots (head + e) % capacity of `storage` (the replay's device tensors xe, xe_next, col, mask,
         action, reward).  The current observation must be on the device (observe() / advance() / a previous rollout_step).
-        -> a RolloutRow whose download is in flight.  Afterwards as after advance(): fetch_rates(), fetch_observation()."""
-        ex, ra = self.check_rollout(explore, random_actions, storage, head, capacity)
-        if engine is not None and row_ptr is None:
-            raise ValueError("rollout_step: scoring needs the CSR row pointer of the resident batch")
-        self._init_device()
-        if not self._obs_ready:
-            raise RuntimeError("rollout_step: no observe() since the last step()")
-        self._send_grid()
-        t, T, E, n = self.torch, self._t, self.E, self.n
-        io = self.rollout_buffers()
-        i = io['next']
-        io['next'] = (i + 1) % 4
-        if io['policy_ev'][i] is not None:
-            io['policy_ev'][i].synchronize()
-        pin = io['policy_pin'][i].numpy()
-        pin[:4 * E * n].view(np.int32)[:] = ra.reshape(-1)
-        pin[4 * E * n:4 * E * n + E] = ex
-        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
-        self.traffic['bytes_up'] += io['policy_dev'].numel()
-        if io['policy_ev'][i] is None:
-            io['policy_ev'][i] = t.cuda.Event()
-        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
-        r = self.rollout_struct(storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
-        self._keep_actions = T['actions']
-        check(self._lib, self._lib.v2x_rollout_step(C.byref(r), self._stream()))
-        self._obs_ready = True
-        pinned = self._rows_free.pop() if self._rows_free else t.zeros(self.rollout_result_bytes, dtype=t.uint8, pin_memory=self._pin)
-        pinned.copy_(io['result_dev'], non_blocking=True)
-        self.traffic['bytes_down'] += pinned.numel()
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return RolloutRow(self, ev, pinned, E)
-
-    # ------------------------------------------------------------------ T rollout iterations in one call
-    def rollout_steps_policy_bytes(self, T):
-        """bytes of the one buffer rollout_steps() uploads: random_actions [T, E, n] int32, then explore [T, E] bytes"""
-        return _align(4 * T * self.E * self.n + T * self.E, 4)
-
-    def rollout_steps_result_bytes(self, T):
-        """bytes of the result block rollout_steps() downloads: reward [T, E] float64, then regular [T, 2, E] bytes"""
-        return _align(10 * T * self.E, 8)
-
-    def check_rollout_steps(self, explore, random_actions, storage, head, capacity):
-        """ValueError unless the arguments of rollout_steps() fit this object; -> (T, explore [T, E] uint8, random_actions
-        [T, E, n] int32)"""
-        E, n = self.E, self.n
-        self.check_observe(n, self.rb)
-        self._check_mobility("rollout_steps", True)
-        ex = np.asarray(explore)
-        if ex.ndim != 2 or ex.shape[0] < 1 or ex.shape[1] != E or ex.dtype.kind not in 'biu':
-            raise ValueError("explore: [T, %d] flags with T >= 1 expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
-        T = ex.shape[0]
-        ra = np.asarray(random_actions)
-        if ra.dtype.kind not in 'iu':
-            raise ValueError("random_actions must be integers, got dtype %s" % ra.dtype)
-        if ra.shape == (T, E, n, 1):
-            ra = ra.reshape(T, E, n)
-        if ra.shape != (T, E, n):
-            raise ValueError("random_actions: an array of shape %s expected, got %s" % ([T, E, n], list(ra.shape)))
-        head, capacity = int(head), int(capacity)
-        K = T * E
-        if not K <= capacity or not 0 <= head < capacity:
-            raise ValueError("rollout_steps: T E <= capacity and 0 <= head < capacity needed, got T = %d, E = %d, head = %d, "
-                             "capacity = %d" % (T, E, head, capacity))
-        want = {'xe': (n, XE_WIDTH), 'xe_next': (n, XE_WIDTH), 'col': (n * (n - 2),), 'mask': (n,), 'action': (n,), 'reward': ()}
-        for k, tail in want.items():
-            t = storage.get(k)
-            if t is None or tuple(t.shape[1:]) != tail or not t.is_contiguous():
-                raise ValueError("rollout_steps: replay storage %r of shape [slots] + %s expected" % (k, list(tail)))
-            if t.shape[0] < (capacity if head + K > capacity else head + K):      # (a block that wraps touches the last slot)
-                raise ValueError("rollout_steps: replay storage %r has %d slots, the block at %d needs more" % (k, t.shape[0], head))
-        return T, ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32)
-
-    def rollout_steps_buffers(self, T):
-        """the device buffers of rollout_steps() for blocks of T iterations, made once per T: workspace (the trajectory, carved
-        by trajectory_workspace_layout), policy_dev (random_actions [T, E, n] int32 | explore [T, E] bytes), result_dev (reward
-        [T, E] float64 | regular [T, 2, E] bytes), q [T E n, rb] float32"""
-        self._init_device()
-        cache = self.__dict__.setdefault('_traj', {})
-        io = cache.get(T)
-        if io is None:
-            t, E, n, rb = self.torch, self.E, self.n, self.rb
-            offs, size = trajectory_workspace_layout(E, n, rb, T)
-            need = self._lib.v2x_rollout_steps_workspace_bytes(E, n, rb, T)
-            if need != size:
-                raise ValueError("rollout_steps: the library sizes the trajectory workspace of E = %d, n = %d, rb = %d, T = %d at %d "
-                                 "bytes, the documented layout at %d" % (E, n, rb, T, need, size))
-            nb = self.rollout_steps_policy_bytes(T)
-            io = cache[T] = {
-                'workspace': t.zeros(size, dtype=t.uint8, device=self.device), 'offsets': offs,
-                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
-                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
-                'result_dev': t.zeros(self.rollout_steps_result_bytes(T), dtype=t.uint8, device=self.device),
-                'q': t.zeros((T * E * n, rb), dtype=t.float32, device=self.device), 'batch': {}, 'rows_free': []}
-        return io
-
-    def rollout_steps_batch(self, T, row_ptr):
-        """entries 0..T-1 of the trajectory as the engine's batch: T E graphs of n rows, xe and the CSR sources where
-        k_sim_trajectory writes them (row_ptr: the constant pointer of T E n rows, n - 2 sources each)"""
-        from ..engine import DeviceBatch
-        io = self.rollout_steps_buffers(T)
-        db = io['batch'].get(row_ptr.data_ptr())
-        if db is None:
-            E, n, ws, offs = self.E, self.n, io['workspace'], io['offsets']
-            K, t = T * E, self.torch
-            xe = ws[offs['traj_xe']:offs['traj_xe'] + 4 * K * n * XE_WIDTH].view(t.float32).view(K * n, XE_WIDTH)
-            col = ws[offs['traj_col']:offs['traj_col'] + 4 * K * n * (n - 2)].view(t.int32)
-            db = DeviceBatch.from_tensors(K, n, xe, row_ptr, col, n * (n - 2))
-            io['batch'] = {row_ptr.data_ptr(): db}
-            io['row_ptr'] = row_ptr
-        return db
-
-    def rollout_steps_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
-        """the v2x_rollout_traj of the resident tensors and the buffers of rollout_steps_buffers(T)"""
-        self._init_device()
-        self._send_grid()
-        E, n = self.E, self.n
-        io = self.rollout_steps_buffers(T)
-        r = self.rollout_struct(storage, head, capacity, v2v_weight, v2i_weight, None, None, power)
-        base, res = io['policy_dev'].data_ptr(), io['result_dev'].data_ptr()
-        r.q, r.random_actions, r.explore = io['q'].data_ptr(), base, base + 4 * T * E * n
-        r.result_reward, r.result_regular = res, res + 8 * T * E
-        if engine is not None:
-            from ..engine import _batch_struct
-            r.model = engine._h
-            r.batch = _batch_struct(self.rollout_steps_batch(T, row_ptr))
-        ws = io['workspace'].data_ptr()
-        return RolloutTraj(r=r, T=T, pad_=0, **{k: ws + o for k, o in io['offsets'].items()})
+        -> a RolloutResult whose download is in flight.  Afterwards as after advance(): fetch_rates(), fetch_observation()."""
+        return self._rollout("rollout_step", None, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
+                             row_ptr, power)
 
     def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                       power=None):
@@ -706,40 +694,10 @@ class DeviceChannels(object):
         one kernel, one forward scores all T E observations (engine: a GnnEngine, with row_ptr the constant CSR pointer of
         T E n rows; None: nobody is greedy anywhere in the block, no forward), and one kernel picks (explore [T, E] flags,
         random_actions [T, E, n]: the host's draws, one upload), pays and stores the T E transitions into slots
-        (head + t E + e) % capacity of `storage`.  Bit for bit T calls of rollout_step().  -> a RolloutBlock whose download
+        (head + t E + e) % capacity of `storage`.  Bit for bit T calls of rollout_step().  -> a RolloutResult whose download
         (one) is in flight.  Afterwards as after the last rollout_step: fetch_rates(), fetch_observation()."""
-        T, ex, ra = self.check_rollout_steps(explore, random_actions, storage, head, capacity)
-        if engine is not None and row_ptr is None:
-            raise ValueError("rollout_steps: scoring needs the CSR row pointer of the trajectory's batch")
-        self._init_device()
-        if not self._obs_ready:
-            raise RuntimeError("rollout_steps: no observe() since the last step()")
-        self._send_grid()
-        t, E, n = self.torch, self.E, self.n
-        io = self.rollout_steps_buffers(T)
-        i = io['next']
-        io['next'] = (i + 1) % 4
-        if io['policy_ev'][i] is not None:
-            io['policy_ev'][i].synchronize()
-        pin = io['policy_pin'][i].numpy()
-        pin[:4 * T * E * n].view(np.int32)[:] = ra.reshape(-1)
-        pin[4 * T * E * n:4 * T * E * n + T * E] = ex.reshape(-1)
-        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
-        self.traffic['bytes_up'] += io['policy_dev'].numel()
-        if io['policy_ev'][i] is None:
-            io['policy_ev'][i] = t.cuda.Event()
-        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
-        r = self.rollout_steps_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
-        self._keep_actions = self._t['actions']
-        check(self._lib, self._lib.v2x_rollout_steps(C.byref(r), self._stream()))
-        self._obs_ready = True
-        free = io['rows_free']
-        pinned = free.pop() if free else t.zeros(self.rollout_steps_result_bytes(T), dtype=t.uint8, pin_memory=self._pin)
-        pinned.copy_(io['result_dev'], non_blocking=True)
-        self.traffic['bytes_down'] += pinned.numel()
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return RolloutBlock(free, ev, pinned, T, E)
+        return self._rollout("rollout_steps", _block_length(explore), explore, random_actions, storage, head, capacity, v2v_weight,
+                             v2i_weight, engine, row_ptr, power)
 
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
@@ -882,7 +840,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._in_reset = False
         self._rate_host = {}                                   # V2I_Interference / V2V_Interference as last computed or assigned
         self._rates_pending = False                            # ... are older than the device's (a resident rollout step ran)
-        self._resident_row = None                              # the RolloutRow of the step that made the current observation
+        self._resident_row = None                              # the RolloutResult of the call that made the current observation
         BatchedEnviron.__init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=n_envs, seeds=seeds,
                                 workers=workers, native=True, lookahead=False)
         if streams == 'device':
@@ -1061,58 +1019,46 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
 
+    def _resident_rollout(self, steps, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr):
+        """rollout_step() / rollout_steps() (steps): DeviceChannels' call of that name with act()'s bookkeeping around it -- the
+        device holds the newer streams and channel arrays, the observable interference is on the device, no host copy of the
+        observation exists; V2I_Interference / V2V_Interference download the rates when they are next read"""
+        if self.stream_backend != 'device':
+            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)"
+                             % ('rollout_steps' if steps else 'rollout_step'))
+        self.finish_step()
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        stale = bool(self._dirty)
+        dc = self._flush()
+        check_args, call = (dc.check_rollout_steps, dc.rollout_steps) if steps else (dc.check_rollout, dc.rollout_step)
+        check_args(explore, random_actions, storage, head, capacity)
+        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
+            dc.observe(self.dest)
+        self._obs = None
+        result = call(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr)
+        self._streams_ahead = True
+        self._channels_updated()
+        self._on_device.add('V2V_Interference_all')
+        self._dev_obs = None
+        self._rates_pending = True
+        self._resident_row = result
+        return result
+
     def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None):
         """act() of a whole DQN rollout iteration without the host in the loop (streams='device' only; DeviceChannels.rollout_step):
         the resident observation is scored (engine given), the actions are picked from the host's policy draws, the simulators
-        step, and the transitions land in the replay slots -- one call, nothing comes back but the result row (-> RolloutRow, its
-        download in flight).  The bookkeeping is act()'s: the device holds the newer streams and channel arrays, the observable
-        interference is on the device, no host copy of the observation exists; V2I_Interference / V2V_Interference download
-        the rates when they are next read."""
-        if self.stream_backend != 'device':
-            raise ValueError("rollout_step needs streams='device' (mobility and the MT19937 streams advance inside the call)")
-        self.finish_step()
-        self._check_sizes()
-        if any(s.gauss_next is not None for s in self.streams):
-            raise RuntimeError("a stream holds a cached gauss value")
-        stale = bool(self._dirty)
-        dc = self._flush()
-        dc.check_rollout(explore, random_actions, storage, head, capacity)
-        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
-            dc.observe(self.dest)
-        self._obs = None
-        row = dc.rollout_step(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr)
-        self._streams_ahead = True
-        self._channels_updated()
-        self._on_device.add('V2V_Interference_all')
-        self._dev_obs = None
-        self._rates_pending = True
-        self._resident_row = row
-        return row
+        step, and the transitions land in the replay slots -- one call, nothing comes back but the result row (-> RolloutResult,
+        its download in flight)."""
+        return self._resident_rollout(False, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
+                                      row_ptr)
 
     def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None):
         """T iterations of rollout_step() in one call (explore [T, E], random_actions [T, E, n]; DeviceChannels.rollout_steps):
-        the same bookkeeping, once.  -> the RolloutBlock, its download in flight."""
-        if self.stream_backend != 'device':
-            raise ValueError("rollout_steps needs streams='device' (mobility and the MT19937 streams advance inside the call)")
-        self.finish_step()
-        self._check_sizes()
-        if any(s.gauss_next is not None for s in self.streams):
-            raise RuntimeError("a stream holds a cached gauss value")
-        stale = bool(self._dirty)
-        dc = self._flush()
-        dc.check_rollout_steps(explore, random_actions, storage, head, capacity)
-        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
-            dc.observe(self.dest)
-        self._obs = None
-        block = dc.rollout_steps(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
-                                 row_ptr=row_ptr)
-        self._streams_ahead = True
-        self._channels_updated()
-        self._on_device.add('V2V_Interference_all')
-        self._dev_obs = None
-        self._rates_pending = True
-        self._resident_row = block
-        return block
+        the same bookkeeping, once.  -> the RolloutResult of the block, its download in flight."""
+        return self._resident_rollout(True, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
+                                      row_ptr)
 
     def resident_regular(self, n_channels=4):
         """the regularity flags [E] of the CURRENT observation, from wherever they are known without a device call: the host copy
@@ -1120,8 +1066,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
         if self._dev_obs is not None and not self._dirty:
             return self._dev_obs[3]
         if self._resident_row is not None and not self._dirty:
-            flags = self._resident_row.resolve().regular       # a row [2, E], or the block [T, 2, E] of rollout_steps
-            return flags[1] if flags.ndim == 2 else flags[-1, 1]
+            return self._resident_row.resident_regular
         return self.observe_packed(n_channels)[3]
 
     def _pull_rates(self):

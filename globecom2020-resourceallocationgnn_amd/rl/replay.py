@@ -45,7 +45,7 @@ class DeviceReplay(object):
         self._regular = np.ones(0, bool)       # host-side: slot holds a graph with in-degree n-2 everywhere
         self._early = None                     # stage_early(): (slot, xe, col, mask) already copied for the next packed block
         self._db_cache = {}
-        self._pending = []                     # commit(): (first slot, K, RolloutRow) blocks whose flags are still on their way
+        self._pending = []                     # commit(): (first slot, K, RolloutResult) blocks whose flags are still on their way
 
     # ------------------------------------------------------------------ storage
     def _grow(self, need):
@@ -177,10 +177,9 @@ class DeviceReplay(object):
         return self.head
 
     def commit(self, K, row):
-        """The block reserve(K) handed out has been enqueued: head and size advance at once.  row: the RolloutRow of the call
-        (its .regular[0] are the flags of the stored observations) or the RolloutBlock of T iterations made at once (K = T E,
-        .regular[:, 0, :] in slot order); it is resolved -- one wait for work already enqueued --
-        when the flags are first needed (sample())."""
+        """The block reserve(K) handed out has been enqueued: head and size advance at once.  row: the RolloutResult of the
+        call (its .stored_regular are the flags of the K stored observations in slot order); it is resolved -- one wait for
+        work already enqueued -- when the flags are first needed (sample())."""
         K = int(K)
         self._pending.append((self.head, K, row))
         self.head = (self.head + K) % self.capacity
@@ -190,8 +189,7 @@ class DeviceReplay(object):
         """the regularity flags of every committed block are in _regular"""
         if self._pending:
             for first, K, row in self._pending:
-                flags = row.resolve().regular                # a row [2, E], or T rows [T, 2, E] (slot order: t major)
-                self._regular[(first + np.arange(K)) % self.capacity] = flags[0] if flags.ndim == 2 else flags[:, 0, :].reshape(-1)
+                self._regular[(first + np.arange(K)) % self.capacity] = row.stored_regular
             self._pending = []
 
     def regular_flags(self):

@@ -228,6 +228,61 @@ def test_a_refused_call_leaves_the_state_and_the_storage_alone():
     eng.close()
 
 
+@pytest.mark.parametrize("use_model", [False, True])
+def test_blocks_and_single_iterations_mixed_on_one_state_leave_what_five_single_iterations_leave(use_model):
+    """rollout_steps (T = 2), rollout_step, rollout_steps (T = 2) on ONE DeviceChannels -- the two entry points share their host
+    path, and their buffers must neither alias nor be made twice -- against five rollout_step calls on a twin: E = 3, n = 4,
+    rb = 4, the smallest shape with more than one state, an odd E and a ring that wraps inside the single iteration."""
+    E, n, rb, T = 3, 4, 4, 2
+    capacity, head = 5 * E + 3, 3 * E + 2                                # slots 11..16 | 17, 0, 1 | 2..7
+    eng = _engine(n) if use_model else None
+    rp_one, rp_all = _row_ptr(E, n), _row_ptr(T * E, n)
+    explore, rand = _policy(E, n, rb, 5, np.random.default_rng(41), use_model)
+    if use_model:
+        explore[2] = (0, 1, 0)                                           # the single iteration scores somebody too
+        assert not explore[:2].all() and not explore[3:].all()
+    st = start_state(E, n, 512, [0, 623, 624])
+    at = lambda t: (head + t * E) % capacity                             # noqa: E731
+
+    ref, st_ref = start_channels(E, n, rb, st), _storage(capacity, n)
+    rows = [ref.rollout_step(explore[t], rand[t], st_ref, at(t), capacity, 1.0, 0.1, engine=eng, row_ptr=rp_one) for t in range(5)]
+    want = _snapshot(ref, st_ref)
+    want_reward = np.stack([r.resolve().reward for r in rows])
+    want_regular = np.stack([r.resolve().regular for r in rows])
+
+    dc, st_got = start_channels(E, n, rb, st), _storage(capacity, n)
+    before = dict(dc.traffic)
+    first = dc.rollout_steps(explore[:2], rand[:2], st_got, at(0), capacity, 1.0, 0.1, engine=eng, row_ptr=rp_all if eng else None)
+    ptrs = {k: dc.rollout_steps_buffers(T)[k].data_ptr() for k in ('policy_dev', 'result_dev', 'workspace', 'q')}
+    one = dc.rollout_step(explore[2], rand[2], st_got, at(2), capacity, 1.0, 0.1, engine=eng, row_ptr=rp_one)
+    last = dc.rollout_steps(explore[3:], rand[3:], st_got, at(3), capacity, 1.0, 0.1, engine=eng, row_ptr=rp_all if eng else None)
+    got = _snapshot(dc, st_got)
+    for name in want:
+        assert got[name] == want[name], name
+    got_reward = np.concatenate([first.resolve().reward, one.resolve().reward[None], last.resolve().reward])
+    got_regular = np.concatenate([first.regular, one.regular[None], last.regular])
+    assert first.reward.shape == last.reward.shape == (T, E) and one.reward.shape == (E,) and one.regular.shape == (2, E)
+    assert got_reward.tobytes() == want_reward.tobytes() and got_regular.tobytes() == want_regular.tobytes()
+    assert np.all(np.isfinite(want_reward)) and len(set(want_reward.reshape(-1).tolist())) == 5 * E
+    for res, t0 in ((first, 0), (one, 2), (last, 3)):
+        k = res.stored_regular.size // E
+        assert np.array_equal(res.stored_regular, want_regular[t0:t0 + k, 0].reshape(-1))
+        assert np.array_equal(res.resident_regular, want_regular[t0 + k - 1, 1])
+    # the second block reused the first one's buffers, and the single iteration has its own
+    again, single = dc.rollout_steps_buffers(T), dc.rollout_buffers()
+    assert {k: again[k].data_ptr() for k in ptrs} == ptrs
+    assert not set(ptrs.values()) & {single[k].data_ptr() for k in ('policy_dev', 'result_dev', 'q')}
+    assert {k: dc.traffic[k] - before[k] for k in before} == {
+        'bytes_up': 2 * dc.rollout_steps_policy_bytes(T) + dc.rollout_policy_bytes,
+        'bytes_down': 2 * dc.rollout_steps_result_bytes(T) + dc.rollout_result_bytes}
+    rest = np.setdiff1d(np.arange(capacity), (head + np.arange(5 * E)) % capacity)
+    assert len(rest) == 3 and all(np.all(t.cpu().numpy()[rest] == MARK) for t in st_got.values())
+    if eng is not None:
+        acts = st_got['action'].cpu().numpy()[(head + np.arange(5 * E)) % capacity].reshape(5, E, n)
+        assert np.array_equal(acts[explore != 0], rand[explore != 0]) and not np.array_equal(acts[1], rand[1])
+        eng.close()
+
+
 # ------------------------------------------------------------------------------------------------------- the agent
 def _agent(E, seed, backend, n=4, capacity=None, irregular=None):
     random.seed(seed)

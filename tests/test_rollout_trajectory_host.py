@@ -204,6 +204,114 @@ def test_environment_and_channels_refuse_bad_block_arguments_before_any_device_w
     assert dc.rollout_steps_policy_bytes(1) == dc.rollout_policy_bytes and dc.rollout_steps_result_bytes(1) == dc.rollout_result_bytes
 
 
+# ------------------------------------------------------------------------------------------------------- one host path
+def _cpu_storage(slots, n=4, **other):
+    """replay storage on the host: the checks look at shapes and contiguity only"""
+    import torch
+    st = {'xe': torch.zeros(slots, n, 16), 'xe_next': torch.zeros(slots, n, 16), 'col': torch.zeros(slots, n * (n - 2), dtype=torch.int32),
+          'mask': torch.zeros(slots, n, dtype=torch.int32), 'action': torch.zeros(slots, n, dtype=torch.int32),
+          'reward': torch.zeros(slots, dtype=torch.float64)}
+    st.update(other)
+    return st
+
+
+def test_the_one_step_check_is_the_block_check_with_T_equal_1():
+    """check_rollout(ex, ra, ...) and check_rollout_steps(ex[None], ra[None], ...) accept and refuse the same arguments (the bad
+    ones of this file and of test_rollout_device_host.py, at one iteration), and what they return differs by the leading axis"""
+    import torch
+    E, n = 2, 4
+    rng = np.random.default_rng(3)
+    ex, ra, full = rng.integers(0, 2, E).astype(bool), rng.integers(0, 4, (E, n)), _cpu_storage(8)
+    dc = DeviceChannels(E, n, 4)
+    for check, a, b in ((dc.check_rollout, ex, ra), (dc.check_rollout_steps, ex[None], ra[None])):
+        with pytest.raises(ValueError, match="set_grid"):
+            check(a, b, full, 0, 8)
+    dc.set_grid(LANES, 750, 1299, 0.01)
+    good = [(ex, ra, full, 0, 8), (ex.astype(np.uint8), ra.astype(np.int32), full, 7, 8), (ex.astype(int), ra[:, :, None], full, 6, 8),
+            (ex, ra, _cpu_storage(5), 3, 100), (ex, ra, _cpu_storage(2), 0, 2)]
+    for e, r, st, head, capacity in good:
+        e1, r1 = dc.check_rollout(e, r, st, head, capacity)
+        T, eT, rT = dc.check_rollout_steps(np.asarray(e)[None], np.asarray(r)[None], st, head, capacity)
+        assert T == 1 and eT.shape == (1, E) and rT.shape == (1, E, n)
+        assert e1.dtype == eT.dtype == np.uint8 and r1.dtype == rT.dtype == np.int32 and r1.flags.c_contiguous and rT.flags.c_contiguous
+        assert np.array_equal(e1, eT[0]) and np.array_equal(r1, rT[0])
+        assert np.array_equal(e1, np.asarray(e).astype(np.uint8)) and np.array_equal(r1, np.asarray(r).reshape(E, n))
+    bad = [(np.zeros(3, bool), ra, full, 0, 8, "explore"), (np.zeros(2), ra, full, 0, 8, "explore"),
+           (ex, np.zeros((2, 4)), full, 0, 8, "integers"), (ex, np.zeros((2, 5), int), full, 0, 8, "shape"),
+           (ex, np.zeros(2, int), full, 0, 8, "shape"), (ex, np.zeros((3, 4), int), full, 0, 8, "shape"),
+           (ex, ra, full, 0, 1, "capacity"), (ex, ra, full, 8, 8, "capacity"), (ex, ra, full, -1, 8, "capacity"),
+           (ex, ra, {}, 0, 8, "storage"), (ex, ra, _cpu_storage(8, mask=torch.zeros(8, 5, dtype=torch.int32)), 0, 8, "storage"),
+           (ex, ra, _cpu_storage(8, xe=torch.zeros(8, 4, 32)[:, :, ::2]), 0, 8, "storage"),
+           (ex, ra, _cpu_storage(4), 3, 8, "slots"), (ex, ra, _cpu_storage(7), 7, 8, "slots")]
+    for e, r, st, head, capacity, word in bad:
+        with pytest.raises(ValueError, match=word) as one:
+            dc.check_rollout(e, r, st, head, capacity)
+        with pytest.raises(ValueError, match=word) as block:
+            dc.check_rollout_steps(e[None], r[None], st, head, capacity)
+        assert "rollout_steps" not in str(one.value) and "rollout_step:" not in str(block.value)
+    wide = DeviceChannels(2, 32, 4)
+    wide.set_grid(LANES, 750, 1299, 0.01)
+    for check, a, b in ((wide.check_rollout, ex, np.zeros((2, 32), int)), (wide.check_rollout_steps, ex[None], np.zeros((1, 2, 32), int))):
+        with pytest.raises(ValueError, match="links"):
+            check(a, b, _cpu_storage(8, n=32), 0, 8)
+    assert dc.torch is None and dc.traffic == {'bytes_up': 0, 'bytes_down': 0}
+
+
+class _Event(object):
+    def __init__(self):
+        self.waits = 0
+
+    def synchronize(self):
+        self.waits += 1
+
+
+@pytest.mark.parametrize("T", [None, 2])
+def test_rollout_result_on_host_storage(T):
+    """RolloutResult on a host buffer in the downloaded layout (reward float64 | regular bytes) and a stub event: shapes and
+    values per entry point, the two flat views, and resolve() waits once and returns the buffer once"""
+    import torch
+    from v2xgnn.rl.device_sim import RolloutResult
+    E = 3
+    lead = () if T is None else (T,)
+    K = (T or 1) * E
+    rng = np.random.default_rng(17)
+    reward = rng.normal(size=lead + (E,))
+    regular = rng.integers(0, 2, size=lead + (2, E)).astype(np.uint8)
+    blocks = regular.reshape(-1, 2, E)
+    blocks[0, 0], blocks[-1, 1] = (1, 0, 1), (0, 1, 1)                   # (stored and resident flags that differ from each other)
+    pin = torch.zeros(-(-10 * K // 8) * 8, dtype=torch.uint8)
+    pin.numpy()[:8 * K] = np.frombuffer(reward.tobytes(), np.uint8)
+    pin.numpy()[8 * K:10 * K] = regular.reshape(-1)
+    free, ev = [], _Event()
+    res = RolloutResult(free, ev, pin, E, T)
+    assert res.reward is None and res.regular is None and free == [] and ev.waits == 0
+    assert res.resolve() is res and ev.waits == 1 and len(free) == 1 and free[0] is pin
+    assert res.reward.shape == lead + (E,) and res.reward.dtype == np.float64 and res.reward.tobytes() == reward.tobytes()
+    assert res.regular.shape == lead + (2, E) and res.regular.dtype == bool and np.array_equal(res.regular, regular != 0)
+    pin.zero_()                                                          # the buffer is somebody else's now: plain copies were kept
+    assert res.resolve() is res and ev.waits == 1 and len(free) == 1
+    assert res.reward.tobytes() == reward.tobytes() and np.array_equal(res.regular, regular != 0)
+    stored, resident = res.stored_regular, res.resident_regular
+    assert stored.shape == (K,) and resident.shape == (E,) and ev.waits == 1 and len(free) == 1
+    if T is None:
+        assert np.array_equal(stored, regular[0] != 0) and np.array_equal(resident, regular[1] != 0)
+    else:
+        assert np.array_equal(stored, res.regular[:, 0, :].reshape(-1)) and np.array_equal(resident, res.regular[-1, 1])
+        assert np.array_equal(stored.reshape(T, E), regular[:, 0] != 0)  # (t major, e minor)
+    assert stored[:E].tolist() == [True, False, True] and resident.tolist() == [False, True, True]
+
+
+def test_the_views_resolve_a_result_that_nobody_resolved():
+    import torch
+    from v2xgnn.rl.device_sim import RolloutResult
+    free, ev = [], _Event()
+    pin = torch.zeros(24, dtype=torch.uint8)
+    pin[16:20] = torch.tensor([1, 0, 0, 1], dtype=torch.uint8)
+    res = RolloutResult(free, ev, pin, 2)
+    assert res.resident_regular.tolist() == [False, True] and res.stored_regular.tolist() == [True, False]
+    assert ev.waits == 1 and len(free) == 1 and free[0] is pin
+
+
 @pytest.mark.parametrize("argv", [["--envs", "2", "--rollout", "trajectory"],
                                   ["--envs", "2", "--sim-backend", "device", "--rollout", "trajectory"]])
 def test_rollout_trajectory_needs_the_device_simulator_and_streams_on_the_command_line(argv, capsys):
