@@ -89,6 +89,18 @@ class RolloutTraj(C.Structure):
         [(k, C.c_void_p) for k in ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")]
 
 
+TRAJ_WORKSPACES = ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")
+EVAL_RESULTS = ("result_actions", "result_v2v_rate", "result_v2i_rate", "result_interference", "result_reward", "result_regular")
+
+
+class Eval(C.Structure):
+    """v2x_eval of include/v2xgnn.h"""
+    _fields_ = [("model", C.c_void_p), ("batch", Batch)] + \
+        [(k, C.c_void_p) for k in ("q", "explore", "random_actions", "baseline_actions", "actions")] + \
+        [("step", SimStep), ("w_v2v", C.c_double), ("w_v2i", C.c_double), ("T", C.c_int32), ("pad_", C.c_int32)] + \
+        [(k, C.c_void_p) for k in TRAJ_WORKSPACES + EVAL_RESULTS]
+
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -175,6 +187,8 @@ SYMBOLS = [
     ("v2x_rollout_step", C.c_int, [C.POINTER(Rollout), _P]),
     ("v2x_rollout_steps_workspace_bytes", _L, [_I, _I, _I, _I]),
     ("v2x_rollout_steps", C.c_int, [C.POINTER(RolloutTraj), _P]),
+    ("v2x_eval_steps_result_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_eval_steps", C.c_int, [C.POINTER(Eval), _P]),
 ]
 
 

@@ -26,6 +26,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 
 OPT_BACKENDS = ('host', 'device', 'bound', 'local')
 ROLLOUT_BACKENDS = ('host', 'device', 'trajectory')
+EVAL_BACKENDS = ('host', 'device')
 
 
 def _check_opt_backend(opt_backend):
@@ -145,6 +146,7 @@ class Agent(object):
         self._check_rollout_backend(rollout_backend, on_gpu)
         self.rollout_backend = rollout_backend
         self._lazy_rewards = None
+        self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
     def _check_rollout_backend(self, rollout_backend, on_gpu):
         if rollout_backend not in ROLLOUT_BACKENDS:
@@ -1003,7 +1005,115 @@ class Agent(object):
         opt = OptimalAllocation()
         return lambda actions: opt.rank_of(self.env, self.v2v_weight, self.v2i_weight, actions)
 
-    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None, opt_rank=False):
+    # ------------------------------------------------------------------ evaluation on the resident state (eval_backend='device')
+    def _check_eval_backend(self, eval_backend):
+        """ValueError unless eval_backend is known and, for 'device', everything it needs is there; nothing is drawn or reset"""
+        if eval_backend not in EVAL_BACKENDS:
+            raise ValueError("eval_backend must be one of %s, got %r" % (EVAL_BACKENDS, eval_backend))
+        if eval_backend == 'host':
+            return
+        engine = getattr(getattr(self.brain, 'model', None), 'engine', None)
+        why = None
+        if not hasattr(self.env, 'evaluate_steps'):
+            why = "a DeviceBatchedEnviron (the simulator state must live in HBM), got %s" % type(self.env).__name__
+        elif getattr(self.env, 'stream_backend', None) != 'device':
+            why = "streams='device' on the DeviceBatchedEnviron (mobility and the MT19937 streams advance inside the call)"
+        elif self.env.E != 1:
+            why = "ONE simulator (E = 1), the environment holds %d" % self.env.E
+        elif self.num_Neighbor != 1:
+            why = "one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor
+        elif not hasattr(engine, '_h'):
+            why = "a brain on the gfx950 engine"
+        elif self._trainer() is not None:
+            why = "a single GPU (no data parallelism)"
+        if why is not None:
+            raise ValueError("eval_backend=%r needs %s" % (eval_backend, why))
+
+    def _draw_test_run_ahead(self, T):
+        """the host draws of T steps of test_run's loop, taken before the first step runs: one select_action_random per step
+        -> the random scheme's actions [T, n] int"""
+        return np.stack([np.asarray(self.select_action_random(None)).reshape(self.num_D2D) for _ in range(T)])
+
+    def _draw_trial_ahead(self, T, fixed_epsilon):
+        """the host draws of T steps of evaluate_training_diff_trials' loop in its order: per step the random scheme's action,
+        np.random.random(), and _random_channels when that draw is below fixed_epsilon
+        -> (the random scheme's actions [T, n], explore flags [T] uint8, the policy's random actions [T, n], zeros where greedy)"""
+        n, nn, C = self.num_D2D, self.num_Neighbor, self.num_CH
+        baseline, explore, rand = np.zeros((T, n), int), np.zeros(T, np.uint8), np.zeros((T, n), int)
+        for t in range(T):
+            baseline[t] = np.asarray(self.select_action_random(None)).reshape(n)
+            if np.random.random() < fixed_epsilon:
+                explore[t] = 1
+                rand[t] = _random_channels(n, nn, C).reshape(n)
+        return baseline, explore, rand
+
+    def _eval_optimiser(self):
+        """the OptimalAllocation (and its device workspace) the device episodes share"""
+        if getattr(self, '_eval_opt', None) is None:
+            from .optimum import OptimalAllocation
+            self._eval_opt = OptimalAllocation(getattr(self.env, 'device_index', 0))
+        return self._eval_opt
+
+    def _stacked_optimum(self, states, opt_backend, opt_restarts):
+        """_optimum_search for the T stacked states of an episode (DeviceBatchedEnviron.trajectory_states) in ONE search:
+        -> (index [T], reward [T] -- numpy's, of the recorded rates -- and the rates (v2v [T, n], v2i [T, C], interference [T, C])
+        from one rates() call).  'device' / 'bound' / 'local': the stacked searches of rl/optimum.py, 'bound' with the node budget
+        of T single calls.  'host': the host's argmax (np.argmax: the first maximiser) over the numpy rewards of all C^N joint
+        actions, whose rates come from C^N rates() calls on the stacked snapshots -- what _brute_force does state by state."""
+        from .optimum import DEFAULT_LOCAL_RESTARTS, DEFAULT_MAX_NODES, MAX_INDEX, decode, encode
+        T, n, C = states.E, self.num_D2D, self.num_CH
+        w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
+
+        def rewards_of(v2v, v2i):
+            return np.array([w_v2v * np.sum(v2v[t]) + w_v2i * np.sum(v2i[t]) for t in range(T)])
+
+        if opt_backend == 'host':
+            joint = self._joint_actions()
+            table = np.stack([rewards_of(*states.rates(np.tile(a, (T, 1)))[:2]) for a in joint])        # [C^N, T]
+            index = np.argmax(table, axis=0)
+            actions = joint[index]
+        elif opt_backend == 'local':
+            restarts = DEFAULT_LOCAL_RESTARTS if opt_restarts is None else opt_restarts
+            actions, _ = self._eval_optimiser().search_local(states, w_v2v, w_v2i, restarts=restarts)
+            index = encode(actions, C) if C ** n <= MAX_INDEX else np.full(T, -1, np.int64)
+        else:
+            opt = self._eval_optimiser()
+            if opt_backend == 'bound':
+                index, _ = opt.search_bound(states, w_v2v, w_v2i, max_nodes=T * DEFAULT_MAX_NODES)
+            else:
+                index, _ = opt.search(states, w_v2v, w_v2i)
+            actions = decode(index, n, C)
+        v2v, v2i, intf = states.rates(actions)
+        return index, rewards_of(v2v, v2i), (v2v, v2i, intf)
+
+    def _device_episode(self, explore, policy_random, baseline, optimum=None, rank=False):
+        """One evaluation episode of T steps on the resident state: one evaluate_steps call for the steps and both schemes, with
+        optimum = (opt_backend, opt_restarts) one stacked search and one rates() call, with rank one rank_of call.
+        -> dict: res (the resolved EvalResult), opt (_stacked_optimum's triple) and rank (rank_of's dict), where asked for"""
+        T, n = len(explore), self.num_D2D
+        explore = np.asarray(explore, np.uint8)
+        engine = None if explore.all() else self.brain.model.engine
+        res = self.env.evaluate_steps(explore.reshape(T, 1), np.asarray(policy_random).reshape(T, 1, n),
+                                      np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine)
+        out = {'res': res.resolve()}
+        if optimum is not None or rank:
+            states = self.env.trajectory_states(T)
+            if optimum is not None:
+                out['opt'] = self._stacked_optimum(states, *optimum)
+            if rank:
+                both = np.stack([np.asarray(baseline).reshape(T, n), res.actions[0, :, 0, :].astype(np.int64)], axis=1)   # [T, 2, n]
+                out['rank'] = self._eval_optimiser().rank_of(states, self.v2v_weight, self.v2i_weight, both)
+        self.num_step += T
+        self.eval_stats['device_episodes'] += 1
+        return out
+
+    def _device_episode_possible(self):
+        """after the reset of an episode: the new graph is regular (receivers are fixed within an episode, so one look is
+        enough); otherwise the episode runs through the host loop -- nothing has been drawn yet"""
+        return bool(np.all(self.env.resident_regular(self.num_CH)))
+
+    def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None, opt_rank=False,
+                 eval_backend='host'):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
         :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
@@ -1016,8 +1126,16 @@ class Agent(object):
         (OptimalAllocation.rank_of), into `self.rank_book`: arrays [episodes, steps] `better` / `equal` (the greedy
         action), `ra_better` / `ra_equal` (the random one), `total` (C^N) and `uniform_mean_reward` (the mean reward over
         all joint actions: the exact expectation of the random scheme).  The returned tuple, the RNG draws and every
-        recorded array are those of opt_rank=False."""
+        recorded array are those of opt_rank=False.
+        eval_backend='device' (a DeviceBatchedEnviron with streams='device' and E = 1, a brain on the gfx950 engine, one
+        receiver per link, no data parallelism; anything else is a ValueError before any draw or reset): an episode is one
+        evaluate_steps call -- the draws of its T steps are taken first, in this loop's order --, one stacked optimum search
+        over its T states (opt_backend as above; 'host': the host's argmax over rates computed on the stacked snapshots), one
+        rates() call and one rank_of call; the books are filled from the downloaded rates with the expressions below.  Same
+        arrays, RNG states, num_step and simulator state as 'host', bit for bit (tests/test_gpu_eval_device.py).  An episode
+        whose graph is not regular runs through the host loop; `self.eval_stats` counts both kinds."""
         _check_opt_backend(opt_backend)
+        self._check_eval_backend(eval_backend)
         n, C = self.num_D2D, self.num_CH
         self.num_Episodes, self.num_Test_Step = num_episodes, num_test_step
         w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
@@ -1041,8 +1159,29 @@ class Agent(object):
             shape = (num_episodes, num_test_step)
             self.rank_book = {k: np.zeros(shape, np.int64) for k in ('better', 'equal', 'ra_better', 'ra_equal', 'total')}
             self.rank_book['uniform_mean_reward'] = np.zeros(shape)
+        T = num_test_step
         for ep in range(num_episodes):
             self.env.new_random_game(self.num_D2D)
+            if eval_backend == 'device' and T > 0 and self._device_episode_possible():
+                baseline = self._draw_test_run_ahead(T)
+                got = self._device_episode(np.zeros(T, np.uint8), np.zeros((T, n), int), baseline,
+                                           optimum=(opt_backend, opt_restarts) if opt_flag else None, rank=opt_rank)
+                r = got['res']
+                for st in range(T):
+                    record(ra, ep, st, r.v2v_rate[1, st, 0][:, None], r.v2i_rate[1, st, 0], r.interference[1, st, 0])
+                    if opt_flag:
+                        _, reward, (v2v, v2i, intf) = got['opt']
+                        if reward[st] > 0:
+                            record(opt, ep, st, v2v[st][:, None], v2i[st], intf[st])
+                    if opt_rank:
+                        rk, b = got['rank'], self.rank_book
+                        b['ra_better'][ep, st], b['better'][ep, st] = rk['better'][st]
+                        b['ra_equal'][ep, st], b['equal'][ep, st] = rk['equal'][st]
+                        b['total'][ep, st] = rk['total']
+                        b['uniform_mean_reward'][ep, st] = rk['mean_reward'][st]
+                    record(rl, ep, st, r.v2v_rate[0, st, 0][:, None], r.v2i_rate[0, st, 0], r.interference[0, st, 0])
+                continue
+            self.eval_stats['host_episodes'] += 1
             for st in range(num_test_step):
                 ra_action = self.select_action_random(None)
                 record(ra, ep, st, *self.dump_act(ra_action))
@@ -1071,7 +1210,7 @@ class Agent(object):
 
     def evaluate_training_diff_trials(self, num_episodes, num_test_step, opt_flag, fixed_epsilon, num_evaluate_trials,
                                       model_dir=None, num_train_steps=20, load=True, opt_backend='host',
-                                      opt_restarts=None):
+                                      opt_restarts=None, eval_backend='host'):
         """Evaluation of the TRAINING PROCESS (BS_brain.py:1164-1451): for every saved checkpoint (one per 5 training
         episodes, :1218,:1228) and every trial, an episode under a FIXED epsilon-greedy policy (:1376-1397) next to the
         random-action baseline (:1330-1338) and -- per step of the first checkpoint -- the brute-force optimum (:1282-
@@ -1079,9 +1218,11 @@ class Agent(object):
         t + 1 before every episode (:1262-1265).  Same return tuples as the reference: 9 arrays with opt_flag, 5 without.
         model_dir: checkpoint folder (default: checkpoint_dir()); load=False evaluates the weights already in the brain
         for every checkpoint (tests with a recording brain).  opt_backend / opt_restarts: where the optimum is searched, as in
-        test_run ('local': a lower bound on the optimum, not the optimum)."""
+        test_run ('local': a lower bound on the optimum, not the optimum).  eval_backend: as in test_run; the optimum of an
+        episode's T states is searched once where this loop asks for it twice (the first checkpoint's ground truth and opt_flag)."""
         import random
         _check_opt_backend(opt_backend)
+        self._check_eval_backend(eval_backend)
         n, C, nn = self.num_D2D, self.num_CH, self.num_Neighbor
         self.num_Episodes = int(num_episodes // 5)
         self.num_Test_Step = num_test_step
@@ -1104,6 +1245,30 @@ class Agent(object):
                 random.seed(trial + 1)
                 np.random.seed(trial + 1)
                 self.env.new_random_game(self.num_D2D)
+                if eval_backend == 'device' and n_st > 0 and self._device_episode_possible():
+                    baseline, explore, rand = self._draw_trial_ahead(n_st, fixed_epsilon)
+                    got = self._device_episode(explore, rand, baseline,
+                                               optimum=(opt_backend, opt_restarts) if (ep == 0 or opt_flag) else None)
+                    r = got['res']
+                    for st in range(n_st):
+                        if ep == 0 or opt_flag:
+                            reward = got['opt'][1][st]
+                            v2v, v2i, intf = (a[st] for a in got['opt'][2])
+                        if ep == 0 and reward > 0:
+                            ev_opt_reward[trial, st] = reward
+                            ev_opt_return[trial] += reward
+                        ra_reward[trial, ep, st] = w_v2v * np.sum(r.v2v_rate[1, st, 0]) + w_v2i * np.sum(r.v2i_rate[1, st, 0])
+                        ra_return[trial, ep] += ra_reward[trial, ep, st]
+                        if opt_flag and reward > 0:
+                            opt_reward[trial, ep, st] = reward
+                            opt_return[trial, ep] += reward
+                            opt_v2v[trial, ep, st, :] = v2v
+                            opt_v2i[trial, ep, st, :] = v2i
+                            opt_intf[trial, ep, st, :] = intf
+                        rew[trial, ep, st] = w_v2v * np.sum(r.v2v_rate[0, st, 0]) + w_v2i * np.sum(r.v2i_rate[0, st, 0])
+                        ret[trial, ep] += rew[trial, ep, st]
+                    continue
+                self.eval_stats['host_episodes'] += 1
                 for st in range(n_st):
                     if ep == 0:                                  # ground truth once per trial (:1282)
                         _, reward, _ = optimum()

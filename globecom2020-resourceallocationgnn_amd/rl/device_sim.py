@@ -34,6 +34,14 @@ the entry point of its name; both hand out a RolloutResult:
     res.resolve().reward, res.regular           # [E], [2, E] / [T, E], [T, 2, E]
     res.stored_regular, res.resident_regular    # the flags of the stored slots [T E]; of the observation left resident [E]
 
+An evaluation episode runs the same way (v2x_eval_steps: no replay memory, the policy and a baseline scheme paid per state,
+rates instead of a reward alone), and the T snapshots it leaves are one stacked problem for OptimalAllocation:
+
+    res = dc.eval_steps(explore, policy_random, baseline_actions, w_v2v, w_v2i, engine)       # [T, E], [T, E, n], [T, E, n] or None
+    res.resolve().v2v_rate, res.v2i_rate, res.interference, res.reward, res.actions, res.regular     # [S, T, E, ...], [T + 1, E]
+    states = dc.trajectory_states(T)            # E' = T E states; valid until the next trajectory call of that T
+    index, reward = OptimalAllocation().search(states, 1.0, 0.1); states.rates(actions)
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -45,7 +53,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import OptProblem, Rollout, RolloutTraj, SimStep, check, load_library
+from ..lib import Eval, OptProblem, Rollout, RolloutTraj, SimStep, check, load_library
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -77,6 +85,106 @@ def trajectory_workspace_layout(E, n, rb, T):
         offs.append(o)
         o += _align(b, 256)
     return dict(zip(('traj_xe', 'traj_col', 'traj_mask', 'traj_regular', 'traj_v2v_ff', 'traj_v2i_ff', 'traj_v2i_abs'), offs)), o
+
+
+def eval_result_layout(E, n, rb, T, schemes):
+    """-> (the byte offsets of v2v_rate, v2i_rate, interference, reward, actions, regular in the result block of v2x_eval_steps,
+    its size): the layout of include/v2xgnn.h -- the doubles first, then the int32 actions, then the flags, back to back"""
+    K, m = schemes * T * E, min(rb, n)
+    parts = (('v2v_rate', 8 * K * n), ('v2i_rate', 8 * K * m), ('interference', 8 * K * rb), ('reward', 8 * K), ('actions', 4 * K * n),
+             ('regular', (T + 1) * E))
+    offs, o = {}, 0
+    for k, b in parts:
+        offs[k] = o
+        o += b
+    return offs, _align(o, 8)
+
+
+class EvalResult(object):
+    """What DeviceChannels.eval_steps brings back, scheme major (scheme 0 the policy, scheme 1 the baseline when one was given):
+    actions [S, T, E, n] int32, v2v_rate [S, T, E, n], v2i_rate [S, T, E, min(rb, n)], interference [S, T, E, rb], reward
+    [S, T, E] and regular [T + 1, E] (the flags of the observation at entry and after every step).  As with RolloutResult the
+    bytes are on their way when this object is handed out; resolve() waits (once) and keeps plain copies."""
+
+    FIELDS = ('v2v_rate', 'v2i_rate', 'interference', 'reward', 'actions', 'regular')
+
+    def __init__(self, free, event, pin, E, n, rb, T, schemes):
+        self._free, self._event, self._pin = free, event, pin
+        self.E, self.n, self.rb, self.T, self.schemes = E, n, rb, T, schemes
+        for k in self.FIELDS:
+            setattr(self, k, None)
+
+    def resolve(self):
+        if self._pin is not None:
+            self._event.synchronize()
+            E, n, rb, T, S = self.E, self.n, self.rb, self.T, self.schemes
+            offs, _ = eval_result_layout(E, n, rb, T, S)
+            raw, K = self._pin.numpy(), S * T * E
+            f64 = lambda k, w: raw[offs[k]:offs[k] + 8 * K * w].view(np.float64).copy()          # noqa: E731
+            self.v2v_rate = f64('v2v_rate', n).reshape(S, T, E, n)
+            self.v2i_rate = f64('v2i_rate', min(rb, n)).reshape(S, T, E, min(rb, n))
+            self.interference = f64('interference', rb).reshape(S, T, E, rb)
+            self.reward = f64('reward', 1).reshape(S, T, E)
+            self.actions = raw[offs['actions']:offs['actions'] + 4 * K * n].view(np.int32).reshape(S, T, E, n).copy()
+            self.regular = raw[offs['regular']:offs['regular'] + (T + 1) * E].reshape(T + 1, E).astype(bool)
+            self._free.append(self._pin)
+            self._pin = self._event = None
+        return self
+
+    @property
+    def resident_regular(self):
+        """the flags [E] of the observation the call left resident"""
+        return self.resolve().regular[-1]
+
+
+class TrajectoryStates(object):
+    """The T snapshots a trajectory call (rollout_steps / eval_steps) of block length T left in its workspace, as ONE stacked
+    problem of T E states for OptimalAllocation (state t E + e: simulator e before its step t).  The channel arrays are views
+    over the workspace, no copy; valid until the next trajectory call of that T on the same DeviceChannels."""
+
+    n_Neighbor = 1
+
+    def __init__(self, dc, T, io):
+        t, E, n, rb = dc.torch, dc.E, dc.n, dc.rb
+        K, ws, offs = T * E, io['workspace'], io['offsets']
+        self._dc, self.T = dc, T
+        self.E, self.n_Veh, self.n_RB = K, n, rb
+        view = lambda k, count, shape: ws[offs[k]:offs[k] + 8 * count].view(t.float64).view(shape)   # noqa: E731
+        self._tensors = [view('traj_v2v_ff', K * n * n * rb, (K, n, n, rb)), view('traj_v2i_ff', K * n * rb, (K, n, rb)),
+                         view('traj_v2i_abs', K * n, (K, n)), dc.tensor('dest').repeat(T, 1)]
+
+    def problem_tensors(self, device=None):
+        """-> ([v2v_ff [T E, n, n, rb], v2i_ff, v2i_abs, dest [T E, n]] device tensors, constants)"""
+        if device is not None and device != self._dc.device:
+            raise ValueError("the simulator state lives on %s, the search runs on %s" % (self._dc.device, device))
+        return list(self._tensors), dict(self._dc.constants)
+
+    def rates(self, actions):
+        """v2x_sim_rates of one joint action per snapshot: actions [T E, n] host integers -> (v2v_rate [T E, n], v2i_rate
+        [T E, min(rb, n)], interference [T E, rb]) host arrays; one upload, one launch, one download"""
+        dc, K, n, rb = self._dc, self.E, self.n_Veh, self.n_RB
+        m = min(rb, n)
+        a = np.asarray(actions)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("actions must be integers, got dtype %s" % a.dtype)
+        if a.shape == (K, n, 1):
+            a = a.reshape(K, n)
+        if a.shape != (K, n):
+            raise ValueError("actions: an array of shape %s expected, got %s" % ([K, n], list(a.shape)))
+        t = dc.torch
+        dev = t.empty((K, n), dtype=t.int32, device=dc.device)
+        dc._up(dev, np.ascontiguousarray(a, np.int32))
+        out = t.empty(K * (n + m + rb), dtype=t.float64, device=dc.device)
+        v = self._tensors
+        prob = OptProblem(E=K, n=n, rb=rb, pad_=0, v2v_ff=v[0].data_ptr(), v2i_ff=v[1].data_ptr(), v2i_abs=v[2].data_ptr(),
+                          dest=v[3].data_ptr(), w_v2v=0.0, w_v2i=0.0, **dc.constants)
+        base = out.data_ptr()
+        check(dc._lib, dc._lib.v2x_sim_rates(C.byref(prob), dev.data_ptr(), base, base + 8 * K * n, base + 8 * K * (n + m), None, None,
+                                             dc._stream()))
+        host = out.cpu().numpy()
+        dc.traffic['bytes_down'] += host.nbytes
+        return (host[:K * n].reshape(K, n).copy(), host[K * n:K * (n + m)].reshape(K, m).copy(),
+                host[K * (n + m):].reshape(K, rb).copy())
 
 
 class RolloutResult(object):
@@ -699,6 +807,132 @@ class DeviceChannels(object):
         return self._rollout("rollout_steps", _block_length(explore), explore, random_actions, storage, head, capacity, v2v_weight,
                              v2i_weight, engine, row_ptr, power)
 
+    # ------------------------------------------------------------------ an evaluation episode on the resident state
+    def eval_steps_policy_bytes(self, T, baseline=True):
+        """bytes of the one buffer eval_steps() uploads: policy_random [T, E, n] int32, explore [T, E] bytes (rounded up to 4),
+        then, with a baseline scheme, baseline_actions [T, E, n] int32"""
+        K = T * self.E
+        return _align(4 * K * self.n + K, 4) + (4 * K * self.n if baseline else 0)
+
+    def eval_steps_result_bytes(self, T, schemes=2):
+        """bytes of the result block eval_steps() downloads (eval_result_layout)"""
+        return eval_result_layout(self.E, self.n, self.rb, T, schemes)[1]
+
+    def check_eval_steps(self, explore, policy_random, baseline_actions):
+        """ValueError unless the arguments of eval_steps() fit this object; -> (T, explore [T, E] uint8, policy_random [T, E, n]
+        int32, baseline_actions [T, E, n] int32 or None)"""
+        E, n = self.E, self.n
+        self.check_observe(n, self.rb)
+        self._check_mobility("eval_steps", True)
+        T = _block_length(explore)
+        ex = np.asarray(explore)
+        if T < 1 or ex.shape != (T, E) or ex.dtype.kind not in 'biu':
+            raise ValueError("explore: [T, %d] flags with T >= 1 expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
+        if T * E > MAX_STATES:
+            raise ValueError("eval_steps: T E <= %d needed (the snapshots are one stacked search problem), got T = %d, E = %d"
+                             % (MAX_STATES, T, E))
+        out = []
+        for name, a in (('policy_random', policy_random), ('baseline_actions', baseline_actions)):
+            if a is None and name == 'baseline_actions':
+                out.append(None)
+                continue
+            a = np.asarray(a)
+            if a.dtype.kind not in 'iu':
+                raise ValueError("%s must be integers, got dtype %s" % (name, a.dtype))
+            if a.shape == (T, E, n, 1):
+                a = a.reshape(T, E, n)
+            if a.shape != (T, E, n):
+                raise ValueError("%s: an array of shape %s expected, got %s" % (name, [T, E, n], list(a.shape)))
+            out.append(np.ascontiguousarray(a, np.int32))
+        return T, ex.astype(np.uint8), out[0], out[1]
+
+    def _eval_io(self, T):
+        """_rollout_io(T) -- the trajectory workspace, q and the cached T E-graph batch are shared with rollout_steps() -- with
+        the evaluation's own policy buffer (ring of four page-locked copies) and result block added at the first use"""
+        io = self._rollout_io(T)
+        if 'eval_policy_dev' not in io:
+            t, nb = self.torch, self.eval_steps_policy_bytes(T)
+            io['eval_policy_dev'] = t.zeros(nb, dtype=t.uint8, device=self.device)
+            io['eval_policy_pin'] = [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)]
+            io['eval_policy_ev'], io['eval_next'] = [None] * 4, 0
+            io['eval_result_dev'] = t.zeros(self.eval_steps_result_bytes(T, 2), dtype=t.uint8, device=self.device)
+            io['eval_free'] = []
+        return io
+
+    def eval_steps_struct(self, T, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None, baseline=True):
+        """the v2x_eval of the resident tensors and the buffers of _eval_io(T) (what eval_steps() passes to the library)"""
+        io = self._eval_io(T)
+        self._send_grid()
+        t, K, n = self._t, T * self.E, self.n
+        base, res = io['eval_policy_dev'].data_ptr(), io['eval_result_dev'].data_ptr()
+        offs, _ = eval_result_layout(self.E, n, self.rb, T, 2 if baseline else 1)
+        ws = io['workspace'].data_ptr()
+        r = Eval(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * n, random_actions=base,
+                 baseline_actions=base + _align(4 * K * n + K, 4) if baseline else None, actions=t['actions'].data_ptr(),
+                 step=self._sim_step(t['actions'].data_ptr(), power), w_v2v=float(v2v_weight), w_v2i=float(v2i_weight), T=T, pad_=0,
+                 **{k: ws + o for k, o in io['offsets'].items()}, **{'result_' + k: res + o for k, o in offs.items()})
+        if engine is not None:
+            from ..engine import _batch_struct
+            if row_ptr is None:                          # the constant CSR pointer of T E n rows of n - 2 sources, made once per T
+                row_ptr = io.get('eval_row_ptr')
+                if row_ptr is None:
+                    row_ptr = io['eval_row_ptr'] = self.torch.arange(K * n + 1, dtype=self.torch.int32, device=self.device) * (n - 2)
+            r.model = engine._h
+            r.batch = _batch_struct(self._rollout_batch(io, K, io['xe'], io['col'], row_ptr))
+        return r
+
+    def eval_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+        """The T steps of an evaluation episode in ONE call (v2x_eval_steps) on the resident state: every simulator walks its T
+        steps in one kernel, one forward scores all T E observations (engine: a GnnEngine; row_ptr: the constant CSR pointer of
+        T E n rows, made here when None; engine None: nobody is greedy, no forward), and one kernel pays two schemes per state --
+        the policy (explore [T, E] flags, policy_random [T, E, n]) and the baseline (baseline_actions [T, E, n]; None: no
+        baseline scheme) -- on the step's snapshot.  No replay memory is touched.  One upload (the draws), one download (the
+        result block) -> an EvalResult whose download is in flight.  Afterwards the resident state is what T advance() calls
+        under the policy's actions leave, and trajectory_states(T) holds the T snapshots."""
+        T, ex, ra, ba = self.check_eval_steps(explore, policy_random, baseline_actions)
+        self._init_device()
+        if not self._obs_ready:
+            raise RuntimeError("eval_steps: no observe() since the last step()")
+        io = self._eval_io(T)
+        t, i = self.torch, io['eval_next']
+        io['eval_next'] = (i + 1) % 4
+        if io['eval_policy_ev'][i] is not None:
+            io['eval_policy_ev'][i].synchronize()
+        pin, K, n = io['eval_policy_pin'][i].numpy(), T * self.E, self.n
+        nb = self.eval_steps_policy_bytes(T, ba is not None)
+        pin[:4 * K * n].view(np.int32)[:] = ra.reshape(-1)
+        pin[4 * K * n:4 * K * n + K] = ex.reshape(-1)
+        if ba is not None:
+            pin[nb - 4 * K * n:nb].view(np.int32)[:] = ba.reshape(-1)
+        io['eval_policy_dev'][:nb].copy_(io['eval_policy_pin'][i][:nb], non_blocking=True)
+        self.traffic['bytes_up'] += nb
+        if io['eval_policy_ev'][i] is None:
+            io['eval_policy_ev'][i] = t.cuda.Event()
+        io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
+        r = self.eval_steps_struct(T, v2v_weight, v2i_weight, engine, row_ptr, power, ba is not None)
+        self._keep_actions = self._t['actions']
+        check(self._lib, self._lib.v2x_eval_steps(C.byref(r), self._stream()))
+        self._obs_ready = True
+        S = 2 if ba is not None else 1
+        size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
+        pinned = free.pop() if free else t.zeros(io['eval_result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
+        pinned[:size].copy_(io['eval_result_dev'][:size], non_blocking=True)
+        self.traffic['bytes_down'] += size
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return EvalResult(free, ev, pinned, self.E, n, self.rb, T, S)
+
+    def trajectory_states(self, T):
+        """-> TrajectoryStates: the T snapshots the last rollout_steps() / eval_steps() of block length T left in its workspace,
+        as one stacked problem of T E states (E = T self.E, n_Veh, n_RB, problem_tensors(), rates()) for OptimalAllocation.
+        Views over the workspace, no copy: valid until the next trajectory call of that T."""
+        T = int(T)
+        if T < 1 or T * self.E > MAX_STATES:
+            raise ValueError("trajectory_states: 1 <= T and T E <= %d needed, got T = %d, E = %d" % (MAX_STATES, T, self.E))
+        if self.torch is None or T not in self._roll:
+            raise RuntimeError("trajectory_states: no trajectory call of T = %d has run on this object" % T)
+        return TrajectoryStates(self, T, self._roll[T])
+
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
         """the v2x_opt_problem of the device arrays"""
@@ -1023,21 +1257,31 @@ class DeviceBatchedEnviron(BatchedEnviron):
         """rollout_step() / rollout_steps() (steps): DeviceChannels' call of that name with act()'s bookkeeping around it -- the
         device holds the newer streams and channel arrays, the observable interference is on the device, no host copy of the
         observation exists; V2I_Interference / V2V_Interference download the rates when they are next read"""
+        def check_args(dc):
+            (dc.check_rollout_steps if steps else dc.check_rollout)(explore, random_actions, storage, head, capacity)
+
+        def call(dc):
+            return (dc.rollout_steps if steps else dc.rollout_step)(explore, random_actions, storage, head, capacity, v2v_weight,
+                                                                    v2i_weight, engine=engine, row_ptr=row_ptr)
+
+        return self._resident_call('rollout_steps' if steps else 'rollout_step', check_args, call)
+
+    def _resident_call(self, who, check_args, call):
+        """the bookkeeping every call that steps the resident state shares (rollout_step / rollout_steps / evaluate_steps):
+        check_args(dc) raises ValueError before any device work of the call, call(dc) makes it -> its result object"""
         if self.stream_backend != 'device':
-            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)"
-                             % ('rollout_steps' if steps else 'rollout_step'))
+            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
         self.finish_step()
         self._check_sizes()
         if any(s.gauss_next is not None for s in self.streams):
             raise RuntimeError("a stream holds a cached gauss value")
         stale = bool(self._dirty)
         dc = self._flush()
-        check_args, call = (dc.check_rollout_steps, dc.rollout_steps) if steps else (dc.check_rollout, dc.rollout_step)
-        check_args(explore, random_actions, storage, head, capacity)
+        check_args(dc)
         if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
             dc.observe(self.dest)
         self._obs = None
-        result = call(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr)
+        result = call(dc)
         self._streams_ahead = True
         self._channels_updated()
         self._on_device.add('V2V_Interference_all')
@@ -1059,6 +1303,23 @@ class DeviceBatchedEnviron(BatchedEnviron):
         the same bookkeeping, once.  -> the RolloutResult of the block, its download in flight."""
         return self._resident_rollout(True, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
                                       row_ptr)
+
+    def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None):
+        """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
+        bookkeeping of rollout_steps() around it: explore [T, E], policy_random [T, E, n], baseline_actions [T, E, n] or None.
+        -> the EvalResult, its download in flight.  trajectory_states(T) then holds the T snapshots."""
+        return self._resident_call(
+            'evaluate_steps', lambda dc: dc.check_eval_steps(explore, policy_random, baseline_actions),
+            lambda dc: dc.eval_steps(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr))
+
+    def trajectory_states(self, T):
+        """the T snapshots of the last evaluate_steps() / rollout_steps() of block length T as one stacked search problem
+        (DeviceChannels.trajectory_states): valid until the next such call"""
+        if self._dc is None:
+            raise RuntimeError("trajectory_states: no trajectory call has run")
+        if not np.all(np.asarray(self.activate_links)):
+            raise ValueError("the optimal-allocation search needs every link active")
+        return self._dc.trajectory_states(T)
 
     def resident_regular(self, n_channels=4):
         """the regularity flags [E] of the CURRENT observation, from wherever they are known without a device call: the host copy

@@ -14,7 +14,7 @@ import numpy as np
 
 from .agent import Agent
 from .sim_config import RL_Config
-from .train import start_env
+from .run import add_sim_arguments, evaluation_env
 
 
 def main(argv=None):
@@ -35,6 +35,7 @@ def main(argv=None):
     ap.add_argument("--opt-restarts", type=int, default=None,
                     help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
     ap.add_argument("--seed", type=int, default=1)                # :22
+    add_sim_arguments(ap)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
         ap.error("--links must be a multiple of 4 and at least 4 (got %d)" % args.links)
@@ -42,11 +43,12 @@ def main(argv=None):
     np.random.seed(args.seed)
     cfg = RL_Config()
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
-    env = start_env(args.links)
+    env = evaluation_env(ap, args)
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False)
     out = agent.evaluate_training_diff_trials(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials,
                                               model_dir=args.save_dir, num_train_steps=args.train_steps,
-                                              opt_backend=args.opt_backend, opt_restarts=args.opt_restarts)
+                                              opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,
+                                              eval_backend=args.eval_backend)
     ret, ra = (out[0], out[2]) if args.opt else (out[1], out[3])
     summary = {"links": args.links, "checkpoints": int(ret.shape[1]), "trials": args.trials,
                "mean_return_per_checkpoint": [round(float(v), 4) for v in ret.mean(axis=0)],

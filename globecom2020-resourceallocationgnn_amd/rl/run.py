@@ -4,7 +4,8 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] [--opt-rank]
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] [--opt-rank] \\
+                              [--sim-backend device --sim-streams device --eval-backend device]
 """
 import argparse
 import json
@@ -15,7 +16,7 @@ import numpy as np
 
 from .agent import Agent
 from .sim_config import RL_Config
-from .train import start_env
+from .train import start_env, start_env_batched
 
 
 def weight_file_names(num_episodes, num_train_steps, batch_size):
@@ -33,13 +34,37 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
     return agent
 
 
-def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False):
+def add_sim_arguments(ap):
+    """--sim-backend / --sim-streams / --eval-backend of the two evaluation drivers"""
+    ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
+                    help="where the simulator's channel update, observation and rates run: the single host simulator (the "
+                         "default) or ONE batched simulator on the GPU (rl/device_sim.py)")
+    ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
+                    help="with --sim-backend device: where mobility and the simulator's MT19937 stream advance")
+    ap.add_argument("--eval-backend", choices=["host", "device"], default="host",
+                    help="with --sim-backend device --sim-streams device: 'device' runs an evaluation episode as one call for "
+                         "its steps and both schemes, one stacked optimum search and one rates call (Agent.test_run)")
+
+
+def evaluation_env(ap, args):
+    """the simulator the evaluation drivers step: start_env(links) unless --sim-backend device asks for the batched one (E = 1);
+    the argument errors are those of rl/train.py"""
+    if args.sim_streams == "device" and args.sim_backend != "device":
+        ap.error("--sim-streams device needs --sim-backend device")
+    if args.eval_backend != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
+    if args.sim_backend == "device":
+        return start_env_batched(args.links, 1, args.seed, backend="device", streams=args.sim_streams)
+    return start_env(args.links)
+
+
+def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False, eval_backend='host'):
     """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme.  opt_backend: where the
     optimum is searched ('host': numpy over every joint action; 'device' / 'bound': the GPU searches of rl/optimum.py;
     'local': its local search with opt_restarts restarts -- a lower bound on the optimum, not the optimum).  opt_rank: also
     rank every step's greedy and random action among all C^N joint actions of its state (agent.rank_book; rank_summary)."""
     out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend,
-                         opt_restarts=opt_restarts, opt_rank=opt_rank)
+                         opt_restarts=opt_restarts, opt_rank=opt_rank, eval_backend=eval_backend)
     names = ['Expect_Return', 'Reward', 'Per_V2V_Rate', 'Per_V2I_Rate', 'Per_V2B_Interference']
     res = {}
     for prefix, chunk in zip(('', 'RA_', 'Opt_'), (out[0:5], out[5:10], out[10:15])):
@@ -77,6 +102,7 @@ def main(argv=None):
                     help="rank every step's greedy and random action among ALL C^N joint actions of its state on the GPU "
                          "(C^N <= 2^36; with or without --opt, any --opt-backend) and add the shares to the summary")
     ap.add_argument("--seed", type=int, default=11)
+    add_sim_arguments(ap)
     args = ap.parse_args(argv)
     if args.links < 4 or args.links % 4:
         # the simulator drops vehicles in groups of four, one per direction (Environment.py:217-231), and the
@@ -88,9 +114,10 @@ def main(argv=None):
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
     cfg.Num_Episodes, cfg.Num_Train_Steps = args.episodes, args.train_steps
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
-    env = start_env(args.links)
+    env = evaluation_env(ap, args)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed)
-    res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank)
+    res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank,
+                   eval_backend=args.eval_backend)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,
                "mean_reward_gnn": float(res['Reward'].mean()), "mean_reward_random": float(res['RA_Reward'].mean())}
     if args.opt:

@@ -581,6 +581,58 @@ typedef struct v2x_rollout_traj {
 int64_t v2x_rollout_steps_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
 int  v2x_rollout_steps(const v2x_rollout_traj* r, void* stream);
 
+/* v2x_eval_steps: the T steps of an EVALUATION episode in one call -- v2x_rollout_steps without a replay memory, paying up to
+ * two schemes per state and returning their rates, not only a reward.  Enqueues, in this order on one stream with no parallel
+ * branches,
+ *   k_sim_trajectory  as in v2x_rollout_steps, unchanged;
+ *   v2x_forward       of the T E observations of entries 0..T-1 (`batch`: as in v2x_rollout_steps) into q -- skipped when model
+ *                     is NULL (the policy scheme then takes random_actions everywhere and explore is not read);
+ *   k_eval_finish     grid (S T E), one wave per (scheme, t, e), S = 2 with baseline_actions, else 1.  Scheme 0, the policy:
+ *                     link k takes random_actions[t][e][k] when explore[t][e], else np.argmax of its Q row (the rule of
+ *                     v2x_rollout_pick).  Scheme 1: baseline_actions[t][e].  Per scheme the rates of v2x_sim_rates on snapshot
+ *                     t (same fold orders; a channel outside [0, rb) makes that (scheme, t, e) NaN and is never an index) and
+ *                     reward = w_v2v * S(v2v_rate) + w_v2i * S(v2i_rate) in the summation order of v2x_rollout_store.  The
+ *                     policy scheme at t = T - 1 also leaves actions / v2v_rate / v2i_rate / interference / v2i_interf /
+ *                     v2v_interf in the resident arrays: after the call the resident state is what T calls of v2x_sim_advance
+ *                     under the policy's actions leave.
+ * Results, scheme major: result_actions [S][T][E][n], result_v2v_rate [S][T][E][n], result_v2i_rate [S][T][E][min(rb, n)],
+ * result_interference [S][T][E][rb] (V2V power at the base station, without noise), result_reward [S][T][E], and
+ * result_regular [T+1][E] (the flags of entries 0..T).  One allocation of v2x_eval_steps_result_bytes(E, n, rb, T, S) bytes
+ * holds them back to back, unpadded, in the order v2v_rate, v2i_rate, interference, reward (doubles), actions (int32), regular
+ * (bytes), the total rounded up to a multiple of 8: 8 S T E (n + min(rb, n) + rb + 1) + 4 S T E n + (T + 1) E.
+ * Same rules as v2x_rollout_steps: all pointers [dev], asynchronous, no allocation, no synchronisation, no environment variable
+ * read; every check of every part before the first launch (V2X_EINVAL, text in v2x_last_error(NULL)).  Limits: those of
+ * v2x_rollout_step (without a replay ring), 1 <= T, T E <= 65535 (the stacked searches of v2x_opt_* accept the T E snapshots as
+ * one problem), T E n (n - 2) < 2^31, non-NULL workspaces (layout and size: v2x_rollout_steps_workspace_bytes).
+ * step.actions must be NULL or `actions`.                                                                                    */
+typedef struct v2x_eval {
+  v2x_model* model;                /* the network, or NULL */
+  v2x_batch batch;
+  float* q;                        /* [T E n][rb] Q workspace (required with a model) */
+  const uint8_t* explore;          /* [T][E] (required with a model) */
+  const int32_t* random_actions;   /* [T][E][n]: the policy's random actions */
+  const int32_t* baseline_actions; /* [T][E][n], or NULL: no baseline scheme */
+  int32_t* actions;                /* [E][n]: the resident actions (written: the policy's of t = T - 1) */
+  v2x_sim_step step;
+  double w_v2v, w_v2i;
+  int32_t T, pad_;
+  float* traj_xe;                  /* [T+1][E][n][16]      */
+  int32_t* traj_col;               /* [T+1][E][n (n - 2)]  */
+  int32_t* traj_mask;              /* [T+1][E][n]          */
+  uint8_t* traj_regular;           /* [T+1][E]             */
+  double* traj_v2v_ff;             /* [T][E][n][n][rb]     */
+  double* traj_v2i_ff;             /* [T][E][n][rb]        */
+  double* traj_v2i_abs;            /* [T][E][n]            */
+  int32_t* result_actions;         /* [S][T][E][n]         */
+  double* result_v2v_rate;         /* [S][T][E][n]         */
+  double* result_v2i_rate;         /* [S][T][E][min(rb,n)] */
+  double* result_interference;     /* [S][T][E][rb]        */
+  double* result_reward;           /* [S][T][E]            */
+  uint8_t* result_regular;         /* [T+1][E]             */
+} v2x_eval;
+int64_t v2x_eval_steps_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
+int  v2x_eval_steps(const v2x_eval* r, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

@@ -40,6 +40,14 @@ rollout; the bytes each moves per rollout; the one call alone between HIP events
 Agent.train(1, 20) per train step for the same backends, all agents of one E alive in one process and taken in turn.
 
     python tools/sim_device_timing.py --mode trajectory [--out profiles/rollout_trajectory_timing.json]
+
+--mode evaluate measures an evaluation run, Agent.test_run(--episodes episodes, 50 steps), with eval_backend 'host' and 'device' on
+the same kind of device-streams environment (E = 1) and with the host loop on the host BatchedEnviron (E = 1), the three agents
+alive in one process and taken in turn, medians after warm-up: without the optimum at 20 links, with --opt-backend bound at 20
+links and with --opt-backend device at 12 links (--loop-reps timed runs each for the two with an optimum); and the bytes each
+device environment moves per episode (DeviceChannels.traffic).
+
+    python tools/sim_device_timing.py --mode evaluate [--out profiles/eval_device_timing.json] [--episodes 1]
 """
 import argparse
 import json
@@ -440,6 +448,63 @@ def trajectory_legs(E, reps, warmup, loop_reps):
     return row
 
 
+EVALUATE_CONFIGS = (("no_optimum", 20, False, "host"), ("optimum_bound", 20, True, "bound"), ("optimum_device", 12, True, "device"))
+# name -> (simulator backend, streams, eval_backend)
+EVALUATE_SETTINGS = {"device_eval": ("device", "device", "device"), "host_eval_device_streams": ("device", "device", "host"),
+                     "host_eval_host_simulator": ("host", "host", "host")}
+
+
+def _evaluate_agent(links, backend, streams):
+    import random
+    from v2xgnn.rl import Agent, RL_Config
+    from v2xgnn.rl.train import start_env_batched
+    random.seed(7)
+    np.random.seed(7)
+    env = start_env_batched(links, 1, 7, lookahead=False, backend=backend, streams=streams)
+    cfg = RL_Config()
+    cfg.set_train_value(64, 0.5, 4096, 1, 0.1)
+    return Agent(links, env.n_RB, env.n_Neighbor, 64, env, cfg, seed=7, device_replay=False)
+
+
+def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
+    """test_run(episodes, 50 steps) of the three agents, taken in turn"""
+    import torch
+    row = {"config": name, "links": links, "rb": RB, "episodes": episodes, "steps": 50, "opt_backend": opt_backend if opt_flag else None,
+           "reps": reps, "warmup": warmup}
+    agents = {k: _evaluate_agent(links, v[0], v[1]) for k, v in EVALUATE_SETTINGS.items()}
+    walls, traffic = {k: [] for k in agents}, {}
+    for k in range(warmup + reps):
+        if k == warmup:
+            traffic = {n: dict(ag.env.device_channels.traffic) for n, ag in agents.items() if EVALUATE_SETTINGS[n][0] == "device"}
+        for n, ag in agents.items():                                 # taken in turn: the box's load drifts
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            ag.test_run(episodes, 50, opt_flag, opt_backend=opt_backend, eval_backend=EVALUATE_SETTINGS[n][2])
+            torch.cuda.synchronize()
+            if k >= warmup:
+                walls[n].append(time.perf_counter() - t0)
+    for n, ag in agents.items():
+        row["%s_ms_per_episode" % n] = round(float(np.median(walls[n])) * 1e3 / episodes, 3)
+        if n in traffic:
+            after = ag.env.device_channels.traffic
+            for key in ("bytes_up", "bytes_down"):
+                row["%s_%s_per_episode" % (n, key)] = (after[key] - traffic[n][key]) // (reps * episodes)
+        row["%s_stats" % n] = dict(ag.eval_stats)
+        ag.brain.close()
+    return row
+
+
+def main_evaluate(args):
+    import torch
+    from v2xgnn.rl.batched_env import _usable_cpus
+    result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "runs": []}
+    for name, links, opt_flag, opt_backend in EVALUATE_CONFIGS:
+        reps, warmup = (max(3, args.loop_reps), 1) if opt_flag else (min(args.reps, 20), min(args.warmup, 3))
+        result["runs"].append(evaluate_legs(name, links, opt_flag, opt_backend, args.episodes, reps, warmup))
+        print(json.dumps(result["runs"][-1]), flush=True)
+    return result
+
+
 def main_trajectory(args):
     import torch
     from v2xgnn.rl.batched_env import _usable_cpus
@@ -479,7 +544,8 @@ def main_streams(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=["channels", "streams", "rollout", "trajectory"], default="channels")
+    ap.add_argument("--mode", choices=["channels", "streams", "rollout", "trajectory", "evaluate"], default="channels")
+    ap.add_argument("--episodes", type=int, default=1, help="--mode evaluate: episodes per timed test_run")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
@@ -494,7 +560,8 @@ def main():
         raise SystemExit("sim_device_timing needs a GPU: nothing is measured without one")
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", {"streams": "sim_device_streams_timing.json", "rollout": "rollout_device_timing.json",
-                                                           "trajectory": "rollout_trajectory_timing.json"}.get(
+                                                           "trajectory": "rollout_trajectory_timing.json",
+                                                           "evaluate": "eval_device_timing.json"}.get(
             args.mode, "sim_device_timing.json"))
     from v2xgnn.rl.batched_env import _usable_cpus
     if args.mode == "streams":
@@ -503,6 +570,8 @@ def main():
         result = main_rollout(args)
     elif args.mode == "trajectory":
         result = main_trajectory(args)
+    elif args.mode == "evaluate":
+        result = main_evaluate(args)
     else:
         result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "reps": args.reps, "warmup": args.warmup,
                   "steps": [step_legs(E, args.reps, args.warmup) for E in args.simulators]}
