@@ -14,6 +14,8 @@
 //   k_opt_landscape, k_opt_landscape_reduce  the search's walk, kept as a histogram of all rewards and their sum
 //                 (v2x_opt_landscape; described above its kernels)
 //   k_opt_bound_* the same optimum by branch and bound (v2x_opt_search_bound; described above its kernels)
+//   k_opt_count_* the joint actions above / at given thresholds, counted over the same tree (v2x_opt_count_bound; described
+//                 above its kernels)
 //   k_opt_local_* a near-optimal allocation for up to 128 links by multi-start local search (v2x_opt_search_local; described
 //                 above its kernels), k_opt_rewards_actions: the reward of joint actions given as channel arrays
 // Search and rewards call the same opt_prefix_init / opt_eval, and every sum is a left fold in ascending link order that
@@ -1032,10 +1034,13 @@ struct OptBoundPlan {
   int64_t off_ctrl, off_inc, off_idx, off_bits, off_qa, off_qb, off_cand, off_leaf, bytes;
 };
 
-int opt_bound_plan(const v2x_opt_problem* p, int64_t max_nodes, const char* who, OptPlan& pl, OptBoundPlan& bp) {
+// need_index: the caller returns a joint action as a 64-bit index (the search); the counting search names none
+int opt_bound_plan(const v2x_opt_problem* p, int64_t max_nodes, const char* who, OptPlan& pl, OptBoundPlan& bp,
+                   bool need_index = true) {
   int rc = opt_plan(p, who, pl);
   if (rc != V2X_OK) return rc;
-  if (pl.total < 0) OPT_FAIL(V2X_EINVAL, "%s: %d^%d joint actions exceed 2^62 (64-bit indices)", who, pl.q.C, pl.q.n);
+  if (need_index && pl.total < 0)
+    OPT_FAIL(V2X_EINVAL, "%s: %d^%d joint actions exceed 2^62 (64-bit indices)", who, pl.q.C, pl.q.n);
   if (max_nodes < 1) OPT_FAIL(V2X_EINVAL, "%s: max_nodes = %lld (>= 1)", who, (long long)max_nodes);
   if (!(p->w_v2v >= 0.0) || !(p->w_v2i >= 0.0))
     OPT_FAIL(V2X_EINVAL, "%s: weights %g / %g (the bound needs both >= 0)", who, p->w_v2v, p->w_v2i);
@@ -1177,6 +1182,431 @@ int v2x_opt_search_bound_seeded(const v2x_opt_problem* p, void* workspace, int64
                                 int64_t* best_index, double* best_reward, int64_t* nodes_visited, void* stream) {
   if (!start_actions) OPT_FAIL(V2X_EINVAL, "opt_search_bound_seeded: null start_actions");
   return opt_search_bound_impl(p, workspace, max_nodes, start_actions, best_index, best_reward, nodes_visited, stream);
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------- counting branch and bound
+// How many joint actions of a state score above / exactly at a threshold v (v2x_opt_count_bound): the search's tree, queue
+// and round loop with a FIXED threshold in the incumbent's place.  A node is pruned when
+//   ub * (1 + EPS) + EPS * (w_v2v + w_v2i) < v,  strictly
+// -- by the rounding margin above no leaf below it scores >= v as a leaf is scored, so no better and no equal action is
+// lost -- and every leaf that is reached is scored with opt_prefix_init / opt_eval and compared with v exactly.  What a
+// subtree contributes depends on the subtree and v alone, and the contributions are integers: `better` and `equal` do not
+// depend on the schedule.  There is no incumbent, hence no atomicMax, no candidates and no fold kernels; children are
+// visited in natural channel order (the order does not change a count).
+//
+// A work item is an OptItem whose pad_ holds the threshold slot: (state, slot) pairs are searched independently, E * n_thr
+// root items.  Per item end a lane adds its two integer counters to the (state, slot) totals with 64-bit integer
+// atomicAdd.  When the node budget is spent, k_opt_count_open books every item still in the queue into per-depth counts
+// of open subtrees -- the node it would visit next at depth d, and the untried siblings along its path d0 .. d - 1 at
+// their depths -- and k_opt_count_open_fold turns the counts into the 128-bit number of unexamined leaves
+// sum_k count[k] * C^(n - k), one lane per (state, slot) doing the carries (opt_open_leaves).
+//
+// The node state is that of the search (I[l][c] and B[r] in the lane's LDS slots, every slot a left fold over ascending
+// assigned k); the three helpers below are its slot arithmetic as functions.
+namespace {
+
+// slots of the prefix of d links
+__device__ __forceinline__ void opt_slots_init(const OptParams& q, const double* __restrict__ tab, uint64_t lo, uint64_t hi, int d,
+                                               const OptSlots& S) {
+  const int n = q.n, C = q.C, nr = q.nr;
+  const double* tx = tab + (int64_t)n * C;
+  const double* bs = tab + 2ll * n * C;
+  const double* cross = tab + 3ll * n * C;
+  for (int i = 0; i < n * C; ++i) S[i] = tx[i];
+  for (int k = 0; k < d; ++k) {
+    const int c = opt_digit(lo, hi, k);
+    for (int l = 0; l < n; ++l)
+      if (l != k) S[l * C + c] += cross[(l * n + k) * C + c];
+  }
+  for (int r = 0; r < C; ++r) {
+    double acc = 0.0;
+    if (r < nr)
+      for (int k = 0; k < d; ++k)
+        if (opt_digit(lo, hi, k) == r) acc += bs[k * C + r];
+    S[n * C + r] = acc;
+  }
+}
+
+// link k (the largest assigned one) joins channel c
+__device__ __forceinline__ void opt_slots_push(const OptParams& q, const double* __restrict__ tab, int k, int c, const OptSlots& S) {
+  const int n = q.n, C = q.C;
+  const double* bs = tab + 2ll * n * C;
+  const double* cross = tab + 3ll * n * C;
+  for (int l = 0; l < n; ++l)
+    if (l != k) S[l * C + c] += cross[(l * n + k) * C + c];
+  if (c < q.nr) S[n * C + c] += bs[k * C + c];
+}
+
+// column c again from scratch over the d assigned links (opt_row_fold's order)
+__device__ __forceinline__ void opt_slots_column(const OptParams& q, const double* __restrict__ tab, uint64_t lo, uint64_t hi, int d,
+                                                 int c, const OptSlots& S) {
+  const int n = q.n, C = q.C;
+  const double* tx = tab + (int64_t)n * C;
+  const double* bs = tab + 2ll * n * C;
+  const double* cross = tab + 3ll * n * C;
+  for (int l = 0; l < n; ++l) S[l * C + c] = tx[l * C + c];
+  for (int kk = 0; kk < d; ++kk)
+    if (opt_digit(lo, hi, kk) == c)
+      for (int l = 0; l < n; ++l)
+        if (l != kk) S[l * C + c] += cross[(l * n + kk) * C + c];
+  if (c < q.nr) {
+    double acc = 0.0;
+    for (int kk = 0; kk < d; ++kk)
+      if (opt_digit(lo, hi, kk) == c) acc += bs[kk * C + c];
+    S[n * C + c] = acc;
+  }
+}
+
+// the bound of the prefix of d links ("Bound of a prefix" above): two log2 per node
+__device__ __forceinline__ double opt_node_bound(const OptParams& q, const double* __restrict__ tab, uint64_t lo, uint64_t hi, int d,
+                                                 const OptSlots& S) {
+#pragma clang fp contract(off)
+  const int n = q.n, C = q.C, nr = q.nr;
+  const double* sig = tab;
+  const double* v2i = tab + 3ll * n * C + (int64_t)n * n * C;
+  double pv = 1.0, pi = 1.0;
+#pragma unroll 4
+  for (int l = 0; l < d; ++l) {
+    const int c = opt_digit(lo, hi, l);
+    pv *= 1.0 + sig[l * C + c] / (S[l * C + c] + q.sig2);
+  }
+  for (int l = d; l < n; ++l) {
+    double x = 0.0;
+#pragma unroll 4
+    for (int c = 0; c < C; ++c) x = fmax(x, sig[l * C + c] / (S[l * C + c] + q.sig2));
+    pv *= 1.0 + x;
+  }
+#pragma unroll 4
+  for (int r = 0; r < nr; ++r) pi *= 1.0 + v2i[r] / (S[n * C + r] + q.sig2);
+  return q.w_v2v * log2(pv) + q.w_v2i * log2(pi);
+}
+
+enum { OPTC_BAD = 5 };                // ctrl word beside OPTB_*: a threshold that is not a number was seen
+constexpr int OPTC_MAX_THR = 31;
+
+struct OptCountArgs {
+  OptParams q;                      // p = n, m = 0: the leaf's opt_prefix_init / opt_eval
+  const double* tabs;
+  const OptItem* qin;
+  OptItem* qout;
+  int n_in, cap, allow_split, n_thr;
+  unsigned long long* ctrl;         // OPTB_* counters
+  const double* thr;                // [E][n_thr]
+  unsigned long long* better;       // [E][n_thr] totals
+  unsigned long long* equal;
+  double* leaf;                     // [n + C][lanes] scratch of opt_prefix_init
+};
+
+// LDS as k_opt_bound_search: [the state's table when TAB_LDS (E = 1)] [n * C + C slots x 64 lanes]
+template <bool TAB_LDS>
+__global__ __launch_bounds__(OPTB_BLOCK) void k_opt_count_bound(OptCountArgs a) {
+#pragma clang fp contract(off)
+  extern __shared__ double opt_lds[];
+  const OptParams q = a.q;
+  const int n = q.n, C = q.C;
+  const int64_t lanes = (int64_t)gridDim.x * OPTB_BLOCK, lane = (int64_t)blockIdx.x * OPTB_BLOCK + threadIdx.x;
+  const int64_t tab_pad = TAB_LDS ? ((q.tab + 1) & ~1ll) : 0;
+  if constexpr (TAB_LDS) {
+    for (int64_t i = threadIdx.x; i < q.tab; i += OPTB_BLOCK) opt_lds[i] = a.tabs[i];
+    __syncthreads();
+  }
+  OptSlots S;
+  S.base = opt_lds + tab_pad + threadIdx.x;
+  double* lf = a.leaf + lane;
+  unsigned long long visited = 0;
+  for (;;) {                                                   // <= n_in items in all lanes together
+    const unsigned long long it = atomicAdd(&a.ctrl[OPTB_HEAD], 1ull);
+    if (it >= (unsigned long long)a.n_in) break;
+    const OptItem item = a.qin[it];
+    const int e = item.e, d0 = item.d0;
+    const int64_t slot = item.pad_;
+    int d = item.d;
+    uint64_t lo = item.lo, hi = item.hi;
+    const double* tab = TAB_LDS ? opt_lds : a.tabs + (int64_t)e * q.tab;
+    const double v = a.thr[(int64_t)e * a.n_thr + slot];
+    opt_slots_init(q, tab, lo, hi, d, S);
+    unsigned long long nb = 0, ne = 0;                         // leaves of this run of the item above / at the threshold
+    int cnt = 0;
+    bool visit = true, finished = false;
+    // every iteration visits a node (<= cap of them) or steps one level back (<= n in a row)
+    for (;;) {
+      if (visit) {
+        if (cnt >= a.cap) break;                               // suspended: the node at depth d is still to visit
+        ++cnt;
+        if (d == n) {                                          // leaf: the exhaustive search's own arithmetic
+          opt_prefix_init(q, tab, lo, hi, lf, (int)lanes);
+          const double r = opt_eval(q, tab, lo, hi, 0, lf, (int)lanes);
+          nb += r > v ? 1ull : 0ull;                           // (a reward that is not a number is neither)
+          ne += r == v ? 1ull : 0ull;
+          visit = false;
+          continue;
+        }
+        const double ub = opt_node_bound(q, tab, lo, hi, d, S);
+        if (ub * (1.0 + OPT_BOUND_EPS) + OPT_BOUND_EPS * (q.w_v2v + q.w_v2i) < v) {
+          visit = false;
+          continue;
+        }
+        opt_slots_push(q, tab, d, 0, S);
+        opt_set_digit(lo, hi, d, 0);
+        ++d;
+      } else {
+        if (d == d0) { finished = true; break; }
+        const int k = d - 1, c = opt_digit(lo, hi, k);
+        d = k;
+        opt_slots_column(q, tab, lo, hi, d, c, S);
+        if (c + 1 < C) {
+          opt_slots_push(q, tab, k, c + 1, S);
+          opt_set_digit(lo, hi, k, c + 1);
+          d = k + 1;
+          visit = true;
+        }
+      }
+    }
+    visited += (unsigned long long)cnt;
+    if (nb) atomicAdd(&a.better[(int64_t)e * a.n_thr + slot], nb);
+    if (ne) atomicAdd(&a.equal[(int64_t)e * a.n_thr + slot], ne);
+    OptItem back;
+    back.lo = lo;
+    back.hi = hi;
+    back.e = finished ? -1 : e;
+    back.d0 = (int16_t)d0;
+    back.d = (int16_t)d;
+    back.pad_ = slot;
+    if (!finished && a.allow_split && d > d0) {
+      // the untried siblings along the path d0 .. d - 1 (the channels above the one taken) become items of their own, the
+      // node at depth d its own root
+      int need = 0;
+      for (int j = d0; j < d; ++j) need += C - 1 - opt_digit(lo, hi, j);
+      const unsigned long long at = a.n_in + atomicAdd(&a.ctrl[OPTB_TAIL], (unsigned long long)need);
+      if (at + need <= (unsigned long long)OPTB_QCAP) {
+        unsigned long long w = at;
+        for (int j = d0; j < d; ++j)
+          for (int c = opt_digit(lo, hi, j) + 1; c < C; ++c) {
+            OptItem sib;
+            sib.lo = j < 16 ? (lo & ((1ull << (4 * j)) - 1)) : lo;
+            sib.hi = j < 16 ? 0ull : (hi & ((1ull << (4 * (j - 16))) - 1));
+            opt_set_digit(sib.lo, sib.hi, j, c);
+            sib.e = e;
+            sib.d0 = sib.d = (int16_t)(j + 1);
+            sib.pad_ = slot;
+            a.qout[w++] = sib;
+          }
+        back.d0 = (int16_t)d;
+      } else {                                                 // no room: holes where the reservation lies inside the queue
+        OptItem hole;
+        hole.lo = hole.hi = 0;
+        hole.e = -1;
+        hole.d0 = hole.d = 0;
+        hole.pad_ = 0;
+        for (unsigned long long w = at; w < at + need && w < (unsigned long long)OPTB_QCAP; ++w) a.qout[w] = hole;
+      }
+    }
+    a.qout[it] = back;
+  }
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) visited += __shfl_xor(visited, off, 64);
+  if (threadIdx.x == 0 && visited) atomicAdd(&a.ctrl[OPTB_NODES], visited);
+}
+
+// grid ceil(E * n_thr / 256): one root item per (state, slot), totals at zero; a threshold that is not a number is flagged
+__global__ __launch_bounds__(256) void k_opt_count_init(int E, int n_thr, const double* __restrict__ thr, OptItem* q0,
+                                                        unsigned long long* better, unsigned long long* equal,
+                                                        unsigned long long* ctrl) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= E * n_thr) return;
+  OptItem it;
+  it.lo = it.hi = 0;
+  it.e = i / n_thr;
+  it.d0 = it.d = 0;
+  it.pad_ = i % n_thr;
+  q0[i] = it;
+  better[i] = 0;
+  equal[i] = 0;
+  const double v = thr[i];
+  if (v != v) ctrl[OPTC_BAD] = 1;
+}
+
+// grid-stride over the items the budget left open: open subtrees per (state, slot) and depth, depth[(e * n_thr + slot)][n + 1]
+__global__ __launch_bounds__(256) void k_opt_count_open(int n_in, int n, int C, int n_thr, const OptItem* __restrict__ items,
+                                                        unsigned long long* depth) {
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n_in; i += gridDim.x * 256) {
+    const OptItem it = items[i];
+    if (it.e < 0) continue;
+    unsigned long long* row = depth + ((int64_t)it.e * n_thr + it.pad_) * (n + 1);
+    atomicAdd(&row[it.d], 1ull);                               // the node to visit next
+    for (int j = it.d0; j < it.d; ++j) {                       // the untried siblings of link j: subtrees rooted at depth j + 1
+      const int left = C - 1 - opt_digit(it.lo, it.hi, j);
+      if (left > 0) atomicAdd(&row[j + 1], (unsigned long long)left);
+    }
+  }
+}
+
+__host__ __device__ inline unsigned long long opt_mulhi64(unsigned long long x, unsigned long long y) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __umul64hi(x, y);
+#else
+  return (unsigned long long)(((unsigned __int128)x * y) >> 64);
+#endif
+}
+
+// sum_k count[k] * C^(n - k) as a 128-bit integer (modulo 2^128; C^n < 2^102 at every size the search accepts)
+__host__ __device__ inline void opt_open_leaves(const unsigned long long* count, int n, int C, unsigned long long& hi,
+                                                unsigned long long& lo) {
+  hi = 0;
+  lo = 0;
+  unsigned long long ph = 0, pl = 1;                           // C^(n - k)
+  for (int k = n; k >= 0; --k) {
+    const unsigned long long c = count[k];
+    if (c) {
+      const unsigned long long add_lo = c * pl, add_hi = opt_mulhi64(c, pl) + c * ph;
+      const unsigned long long s = lo + add_lo;
+      hi += add_hi + (s < lo ? 1ull : 0ull);
+      lo = s;
+    }
+    ph = ph * (unsigned long long)C + opt_mulhi64(pl, (unsigned long long)C);
+    pl = pl * (unsigned long long)C;
+  }
+}
+
+// grid ceil(E * n_thr / 256): a lane per (state, slot) does the carries
+__global__ __launch_bounds__(256) void k_opt_count_open_fold(int rows, int n, int C, const unsigned long long* __restrict__ depth,
+                                                             unsigned long long* open_hi, unsigned long long* open_lo) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= rows) return;
+  unsigned long long hi, lo;
+  opt_open_leaves(depth + (int64_t)i * (n + 1), n, C, hi, lo);
+  open_hi[i] = hi;
+  open_lo[i] = lo;
+}
+
+// workspace = that of v2x_opt_search_bound | per-depth open counts [E * n_thr][n + 1]
+int opt_count_plan(const v2x_opt_problem* p, int32_t n_thr, int64_t max_nodes, const char* who, OptPlan& pl, OptBoundPlan& bp,
+                   int64_t& off_depth, int64_t& bytes) {
+  int rc = opt_bound_plan(p, max_nodes, who, pl, bp, false);
+  if (rc != V2X_OK) return rc;
+  if (n_thr < 1 || n_thr > OPTC_MAX_THR) OPT_FAIL(V2X_EINVAL, "%s: n_thr = %d thresholds per state (1..%d)", who, n_thr, OPTC_MAX_THR);
+  if ((int64_t)p->E * n_thr > OPTB_QCAP)
+    OPT_FAIL(V2X_EINVAL, "%s: E * n_thr = %d * %d root items exceed the queue of %d", who, p->E, n_thr, OPTB_QCAP);
+  off_depth = bp.bytes;
+  bytes = bp.bytes + (((int64_t)p->E * n_thr * (pl.q.n + 1) * 8 + 255) & ~255ll);
+  return V2X_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t v2x_opt_count_bound_workspace_bytes(const v2x_opt_problem* p, int32_t n_thr, int64_t max_nodes) {
+  OptPlan pl;
+  OptBoundPlan bp;
+  int64_t off_depth, bytes;
+  if (opt_count_plan(p, n_thr, max_nodes, "opt_count_bound_workspace_bytes", pl, bp, off_depth, bytes) != V2X_OK) return V2X_EINVAL;
+  return bytes;
+}
+
+int v2x_opt_count_open_leaves(const uint64_t* depth_counts, int32_t n, int32_t rb, uint64_t* open_hi, uint64_t* open_lo) {
+  if (!depth_counts || !open_hi || !open_lo) OPT_FAIL(V2X_EINVAL, "opt_count_open_leaves: null argument");
+  if (n < 1 || n > OPT_MAX_N || rb < OPT_MIN_C || rb > OPT_MAX_C)
+    OPT_FAIL(V2X_EINVAL, "opt_count_open_leaves: %d links x %d channels (1..%d, %d..%d)", n, rb, OPT_MAX_N, OPT_MIN_C, OPT_MAX_C);
+  unsigned long long cnt[OPT_MAX_N + 1], hi, lo;
+  for (int k = 0; k <= n; ++k) cnt[k] = depth_counts[k];
+  opt_open_leaves(cnt, n, rb, hi, lo);
+  *open_hi = hi;
+  *open_lo = lo;
+  return V2X_OK;
+}
+
+int v2x_opt_count_bound(const v2x_opt_problem* p, void* workspace, const double* thresholds, int32_t n_thr, int64_t max_nodes,
+                        int64_t* better, int64_t* equal, uint64_t* open_hi, uint64_t* open_lo, int64_t* nodes_visited,
+                        void* stream) {
+  OptPlan pl;
+  OptBoundPlan bp;
+  int64_t off_depth, bytes;
+  int rc = opt_count_plan(p, n_thr, max_nodes, "opt_count_bound", pl, bp, off_depth, bytes);
+  if (rc != V2X_OK) return rc;
+  if (!thresholds) OPT_FAIL(V2X_EINVAL, "opt_count_bound: null thresholds");
+  if (!better || !equal || !open_hi || !open_lo) OPT_FAIL(V2X_EINVAL, "opt_count_bound: null output");
+  hipStream_t s = (hipStream_t)stream;
+  rc = opt_prep(p, pl, workspace, s, "opt_count_bound");
+  if (rc != V2X_OK) return rc;
+  char* ws = (char*)workspace;
+  unsigned long long* ctrl = (unsigned long long*)(ws + bp.off_ctrl);
+  unsigned long long* depth = (unsigned long long*)(ws + off_depth);
+  OptItem* qa = (OptItem*)(ws + bp.off_qa);
+  OptItem* qb = (OptItem*)(ws + bp.off_qb);
+  const int rows = p->E * n_thr;
+  const unsigned rgrid = (unsigned)((rows + 255) / 256);
+  hipError_t err;
+#define OPTC_LAUNCHED(what)                                                                                        \
+  if ((err = hipGetLastError()) != hipSuccess)                                                                     \
+  OPT_FAIL(V2X_EHIP, "opt_count_bound: %s failed: %s", what, hipGetErrorString(err))
+  if ((err = hipMemsetAsync(ctrl, 0, OPTB_CTRL * sizeof(unsigned long long), s)) != hipSuccess ||
+      (err = hipMemsetAsync(depth, 0, (size_t)rows * (pl.q.n + 1) * sizeof(unsigned long long), s)) != hipSuccess)
+    OPT_FAIL(V2X_EHIP, "opt_count_bound: counter reset failed: %s", hipGetErrorString(err));
+  hipLaunchKernelGGL(k_opt_count_init, dim3(rgrid), dim3(256), 0, s, p->E, (int)n_thr, thresholds, qa, (unsigned long long*)better,
+                     (unsigned long long*)equal, ctrl);
+  OPTC_LAUNCHED("init launch");
+  unsigned long long bad = 0;
+  if ((err = hipMemcpyAsync(&bad, ctrl + OPTC_BAD, sizeof(bad), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+      (err = hipStreamSynchronize(s)) != hipSuccess)
+    OPT_FAIL(V2X_EHIP, "opt_count_bound: threshold check failed: %s", hipGetErrorString(err));
+  if (bad) OPT_FAIL(V2X_EINVAL, "opt_count_bound: a threshold is not a number (NaN)");
+  OptCountArgs a;
+  a.q = pl.q;
+  a.tabs = (const double*)workspace;
+  a.qin = qa;
+  a.qout = qb;
+  a.n_thr = (int)n_thr;
+  a.ctrl = ctrl;
+  a.thr = thresholds;
+  a.better = (unsigned long long*)better;
+  a.equal = (unsigned long long*)equal;
+  a.leaf = (double*)(ws + bp.off_leaf);
+  if (bp.lds_bytes > 64 * 1024) {          // above the default dynamic-LDS size a kernel has to be told; the launch check decides
+    if (bp.tab_lds) (void)hipFuncSetAttribute((const void*)k_opt_count_bound<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.lds_bytes);
+    else (void)hipFuncSetAttribute((const void*)k_opt_count_bound<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bp.lds_bytes);
+    (void)hipGetLastError();
+  }
+  const int64_t short_of = (int64_t)bp.wgs * OPTB_BLOCK * OPTB_ITEMS_PER_LANE;
+  int64_t n_in = rows, nodes = 0;
+  // one round per pass; every round visits at least one node per item, so the node budget also bounds the rounds
+  for (int64_t round = 0; n_in > 0 && nodes < max_nodes; ++round) {
+    const bool few = n_in < short_of;
+    a.n_in = (int)n_in;
+    a.cap = round == 0 ? pl.q.n + 1 : (few ? OPTB_CAP_SEED : OPTB_CAP_RUN);
+    a.allow_split = few ? 1 : 0;
+    if ((err = hipMemsetAsync(ctrl, 0, 4 * sizeof(unsigned long long), s)) != hipSuccess)
+      OPT_FAIL(V2X_EHIP, "opt_count_bound: counter reset failed: %s", hipGetErrorString(err));
+    const unsigned wgs = (unsigned)std::min<int64_t>(bp.wgs, (n_in + OPTB_BLOCK - 1) / OPTB_BLOCK);
+    if (bp.tab_lds) hipLaunchKernelGGL(k_opt_count_bound<true>, dim3(wgs), dim3(OPTB_BLOCK), bp.lds_bytes, s, a);
+    else hipLaunchKernelGGL(k_opt_count_bound<false>, dim3(wgs), dim3(OPTB_BLOCK), bp.lds_bytes, s, a);
+    OPTC_LAUNCHED("count launch");
+    hipLaunchKernelGGL(k_opt_bound_compact, dim3(256), dim3(256), 0, s, a.n_in, ctrl, a.qout, qa);
+    OPTC_LAUNCHED("compact launch");
+    unsigned long long back[2];                                  // { items of the next round, nodes visited so far }
+    if ((err = hipMemcpyAsync(back, ctrl + OPTB_OUT, sizeof(back), hipMemcpyDeviceToHost, s)) != hipSuccess ||
+        (err = hipStreamSynchronize(s)) != hipSuccess)
+      OPT_FAIL(V2X_EHIP, "opt_count_bound: round %lld failed: %s", (long long)round, hipGetErrorString(err));
+    n_in = (int64_t)back[0];
+    nodes = (int64_t)back[1];
+  }
+  if (n_in > 0) {
+    hipLaunchKernelGGL(k_opt_count_open, dim3((unsigned)std::min<int64_t>(256, (n_in + 255) / 256)), dim3(256), 0, s, (int)n_in,
+                       pl.q.n, pl.q.C, (int)n_thr, qa, depth);
+    OPTC_LAUNCHED("open launch");
+  }
+  hipLaunchKernelGGL(k_opt_count_open_fold, dim3(rgrid), dim3(256), 0, s, rows, pl.q.n, pl.q.C, depth,
+                     (unsigned long long*)open_hi, (unsigned long long*)open_lo);
+  OPTC_LAUNCHED("open fold launch");
+#undef OPTC_LAUNCHED
+  if (nodes_visited) *nodes_visited = nodes;
+  if (n_in > 0)
+    OPT_FAIL(V2X_EBUDGET, "opt_count_bound: node budget spent at %d links x %d channels: %lld nodes visited (max_nodes = %lld), "
+             "%lld subtrees open; better / equal are lower bounds, open the leaves not examined", pl.q.n, pl.q.C, (long long)nodes,
+             (long long)max_nodes, (long long)n_in);
+  return V2X_OK;
 }
 
 }  // extern "C"

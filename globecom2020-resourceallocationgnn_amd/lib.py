@@ -174,6 +174,10 @@ SYMBOLS = [
     ("v2x_opt_bound_workspace_bytes", _L, [C.POINTER(OptProblem), _L]),
     ("v2x_opt_search_bound", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, C.POINTER(_L), _P]),
     ("v2x_opt_search_bound_seeded", C.c_int, [C.POINTER(OptProblem), _P, _L, _P, _P, _P, C.POINTER(_L), _P]),
+    ("v2x_opt_count_bound_workspace_bytes", _L, [C.POINTER(OptProblem), C.c_int32, _L]),
+    ("v2x_opt_count_bound", C.c_int, [C.POINTER(OptProblem), _P, _P, C.c_int32, _L, _P, _P, _P, _P, C.POINTER(_L), _P]),
+    ("v2x_opt_count_open_leaves", C.c_int, [C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                            C.POINTER(C.c_uint64)]),
     ("v2x_opt_local_workspace_bytes", _L, [C.POINTER(OptProblem), C.c_int32]),
     ("v2x_opt_search_local", C.c_int, [C.POINTER(OptProblem), _P, C.c_int32, C.c_uint64, C.c_int32, _P, _P, _P, _P, _P, _P]),
     ("v2x_opt_rewards_actions", C.c_int, [C.POINTER(OptProblem), _P, _P, _L, _P, _P]),

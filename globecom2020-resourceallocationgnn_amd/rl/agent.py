@@ -995,15 +995,52 @@ class Agent(object):
         opt = OptimalAllocation()
         return lambda: self._brute_force_device(opt, bound)
 
-    def _rank_search(self):
-        """-> a callable (actions [1, A, N]) -> OptimalAllocation.rank_of of the CURRENT simulator state (opt_rank of
-        test_run); the refusals of opt_backend='device'."""
-        from .optimum import OptimalAllocation
-        OptimalAllocation.check_size(self.num_D2D, self.num_CH)
+    def _check_rank_backend(self, rank_backend, rank_max_nodes):
+        """the refusals of opt_rank (ValueError, before any device work) -> the node budget of one ranked step"""
+        from .optimum import DEFAULT_RANK_MAX_NODES, RANK_BACKENDS, OptimalAllocation
+        if rank_backend not in RANK_BACKENDS:
+            raise ValueError("rank_backend must be one of %s, got %r" % (RANK_BACKENDS, rank_backend))
+        max_nodes = DEFAULT_RANK_MAX_NODES if rank_max_nodes is None else rank_max_nodes
+        if rank_backend == 'bound':
+            OptimalAllocation.check_count(self.num_D2D, self.num_CH, self.v2v_weight, self.v2i_weight, max_nodes, 2)
+        else:
+            OptimalAllocation.check_size(self.num_D2D, self.num_CH)
         if self.num_Neighbor != 1:
             raise ValueError("opt_rank supports one receiver per link (num_Neighbor = 1), got %d" % self.num_Neighbor)
+        return int(max_nodes)
+
+    def _rank_search(self, rank_backend='landscape', rank_max_nodes=None):
+        """-> a callable (actions [1, A, N]) -> OptimalAllocation.rank_of of the CURRENT simulator state (opt_rank of
+        test_run); the refusals of opt_backend='device', or with rank_backend='bound' those of count_better."""
+        from .optimum import OptimalAllocation
+        max_nodes = self._check_rank_backend(rank_backend, rank_max_nodes)
         opt = OptimalAllocation()
+        if rank_backend == 'bound':
+            return lambda actions: opt.rank_of(self.env, self.v2v_weight, self.v2i_weight, actions, backend='bound',
+                                               max_nodes=max_nodes)
         return lambda actions: opt.rank_of(self.env, self.v2v_weight, self.v2i_weight, actions)
+
+    def _new_rank_book(self, shape, rank_backend):
+        """the arrays [episodes, steps] opt_rank fills; with 'bound' also the brackets (Python ints: rb^n may pass 2^63)"""
+        book = {k: np.zeros(shape, np.int64) for k in ('better', 'equal', 'ra_better', 'ra_equal', 'total')}
+        book['uniform_mean_reward'] = np.zeros(shape)
+        if rank_backend == 'bound':
+            for k in ('total', 'better_max', 'ra_better_max'):
+                book[k] = np.zeros(shape, object)
+            book['exact'], book['ra_exact'] = np.zeros(shape, bool), np.zeros(shape, bool)
+        return book
+
+    def _book_rank(self, ep, st, rk, row):
+        """one ranked state into rank_book: rk of rank_of, row its entry of the state ([2]: the random action, the greedy one)"""
+        b = self.rank_book
+        b['ra_better'][ep, st], b['better'][ep, st] = rk['better'][row]
+        b['ra_equal'][ep, st], b['equal'][ep, st] = rk['equal'][row]
+        b['total'][ep, st] = rk['total']
+        if 'exact' in b:                                                      # rank_backend='bound': no landscape, no mean
+            b['ra_better_max'][ep, st], b['better_max'][ep, st] = rk['better_max'][row]
+            b['ra_exact'][ep, st], b['exact'][ep, st] = rk['exact'][row]
+        else:
+            b['uniform_mean_reward'][ep, st] = rk['mean_reward'][row]
 
     # ------------------------------------------------------------------ evaluation on the resident state (eval_backend='device')
     def _check_eval_backend(self, eval_backend):
@@ -1088,7 +1125,8 @@ class Agent(object):
 
     def _device_episode(self, explore, policy_random, baseline, optimum=None, rank=False):
         """One evaluation episode of T steps on the resident state: one evaluate_steps call for the steps and both schemes, with
-        optimum = (opt_backend, opt_restarts) one stacked search and one rates() call, with rank one rank_of call.
+        optimum = (opt_backend, opt_restarts) one stacked search and one rates() call, with rank (True, or (rank_backend, node
+        budget of one step): 'bound' gets the budget of T single calls) one rank_of call.
         -> dict: res (the resolved EvalResult), opt (_stacked_optimum's triple) and rank (rank_of's dict), where asked for"""
         T, n = len(explore), self.num_D2D
         explore = np.asarray(explore, np.uint8)
@@ -1102,7 +1140,11 @@ class Agent(object):
                 out['opt'] = self._stacked_optimum(states, *optimum)
             if rank:
                 both = np.stack([np.asarray(baseline).reshape(T, n), res.actions[0, :, 0, :].astype(np.int64)], axis=1)   # [T, 2, n]
-                out['rank'] = self._eval_optimiser().rank_of(states, self.v2v_weight, self.v2i_weight, both)
+                if rank is True or rank[0] == 'landscape':
+                    out['rank'] = self._eval_optimiser().rank_of(states, self.v2v_weight, self.v2i_weight, both)
+                else:
+                    out['rank'] = self._eval_optimiser().rank_of(states, self.v2v_weight, self.v2i_weight, both, backend=rank[0],
+                                                                 max_nodes=T * rank[1])
         self.num_step += T
         self.eval_stats['device_episodes'] += 1
         return out
@@ -1113,7 +1155,7 @@ class Agent(object):
         return bool(np.all(self.env.resident_regular(self.num_CH)))
 
     def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None, opt_rank=False,
-                 eval_backend='host'):
+                 eval_backend='host', rank_backend='landscape', rank_max_nodes=None):
         """Evaluation loop (BS_brain.py:986-1162): greedy policy of the trained network vs the random-action baseline
         and, with opt_flag, the brute-force optimum over all C^N joint actions (the reference hard-codes 4^4,
         :1071-1078; here any N with C^N <= 65536, or C^N <= 2^36 with opt_backend='device': the search on the GPU,
@@ -1127,6 +1169,11 @@ class Agent(object):
         action), `ra_better` / `ra_equal` (the random one), `total` (C^N) and `uniform_mean_reward` (the mean reward over
         all joint actions: the exact expectation of the random scheme).  The returned tuple, the RNG draws and every
         recorded array are those of opt_rank=False.
+        rank_backend='bound' (up to 32 links, weights >= 0: 20 x 4 and beyond) ranks by counting branch and bound
+        (rank_of(..., backend='bound')) with rank_max_nodes nodes per step (None: DEFAULT_RANK_MAX_NODES of rl/optimum.py).
+        `rank_book` then also holds `exact` / `ra_exact` (the budget sufficed: better / equal are the landscape's numbers) and
+        `better_max` / `ra_better_max` (the upper end of the bracket, equal to the count where exact); `total` and the maxima
+        are Python ints, and `uniform_mean_reward` stays zero: nothing enumerates the landscape.
         eval_backend='device' (a DeviceBatchedEnviron with streams='device' and E = 1, a brain on the gfx950 engine, one
         receiver per link, no data parallelism; anything else is a ValueError before any draw or reset): an episode is one
         evaluate_steps call -- the draws of its T steps are taken first, in this loop's order --, one stacked optimum search
@@ -1155,17 +1202,17 @@ class Agent(object):
         if opt_flag:
             optimum = self._optimum_search(opt_backend, opt_restarts)
         if opt_rank:
-            ranker = self._rank_search()
-            shape = (num_episodes, num_test_step)
-            self.rank_book = {k: np.zeros(shape, np.int64) for k in ('better', 'equal', 'ra_better', 'ra_equal', 'total')}
-            self.rank_book['uniform_mean_reward'] = np.zeros(shape)
+            rank_budget = self._check_rank_backend(rank_backend, rank_max_nodes)
+            ranker = self._rank_search(rank_backend, rank_budget)
+            self.rank_book = self._new_rank_book((num_episodes, num_test_step), rank_backend)
         T = num_test_step
         for ep in range(num_episodes):
             self.env.new_random_game(self.num_D2D)
             if eval_backend == 'device' and T > 0 and self._device_episode_possible():
                 baseline = self._draw_test_run_ahead(T)
                 got = self._device_episode(np.zeros(T, np.uint8), np.zeros((T, n), int), baseline,
-                                           optimum=(opt_backend, opt_restarts) if opt_flag else None, rank=opt_rank)
+                                           optimum=(opt_backend, opt_restarts) if opt_flag else None,
+                                           rank=(rank_backend, rank_budget) if opt_rank else False)
                 r = got['res']
                 for st in range(T):
                     record(ra, ep, st, r.v2v_rate[1, st, 0][:, None], r.v2i_rate[1, st, 0], r.interference[1, st, 0])
@@ -1174,11 +1221,7 @@ class Agent(object):
                         if reward[st] > 0:
                             record(opt, ep, st, v2v[st][:, None], v2i[st], intf[st])
                     if opt_rank:
-                        rk, b = got['rank'], self.rank_book
-                        b['ra_better'][ep, st], b['better'][ep, st] = rk['better'][st]
-                        b['ra_equal'][ep, st], b['equal'][ep, st] = rk['equal'][st]
-                        b['total'][ep, st] = rk['total']
-                        b['uniform_mean_reward'][ep, st] = rk['mean_reward'][st]
+                        self._book_rank(ep, st, got['rank'], st)
                     record(rl, ep, st, r.v2v_rate[0, st, 0][:, None], r.v2i_rate[0, st, 0], r.interference[0, st, 0])
                 continue
             self.eval_stats['host_episodes'] += 1
@@ -1193,12 +1236,7 @@ class Agent(object):
                 q = self._predict(d2d_state[None], adj[None])[:, 0, :]
                 action = np.argmax(q, axis=1).reshape(n, self.num_Neighbor).astype(int)
                 if opt_rank:                                                              # the state both actions were chosen in
-                    rk = ranker(np.stack([np.asarray(ra_action).reshape(n), action.reshape(n)])[None])
-                    b = self.rank_book
-                    b['ra_better'][ep, st], b['better'][ep, st] = rk['better'][0]
-                    b['ra_equal'][ep, st], b['equal'][ep, st] = rk['equal'][0]
-                    b['total'][ep, st] = rk['total']
-                    b['uniform_mean_reward'][ep, st] = rk['mean_reward'][0]
+                    self._book_rank(ep, st, ranker(np.stack([np.asarray(ra_action).reshape(n), action.reshape(n)])[None]), 0)
                 record(rl, ep, st, *self.act(action))
         return tuple(rl + ra + opt) if opt_flag else tuple(rl + ra)
 

@@ -28,6 +28,12 @@ Where an allocation stands among ALL C^N joint actions of its state (C^N <= 2^36
 a histogram of every reward over given edges and the rewards' sum, reduced on the device (v2x_opt_landscape), and from it
 the number of joint actions strictly better than / exactly equal to given ones, and the exact mean of the landscape -- the
 expectation of the random-action scheme.
+
+At 20 links and beyond the landscape cannot be walked, but the same two numbers can still be had for a GOOD allocation:
+`count_better` counts the joint actions above / exactly at given thresholds by branch and bound (v2x_opt_count_bound: the
+tree of `search_bound` with the threshold in the incumbent's place, so only the neighbourhood of the better actions is
+visited), and `rank_of(..., backend='bound')` ranks given actions with it.  A node budget ends in a certified bracket
+[count, count + open], never in a refusal.
 """
 import ctypes as C
 
@@ -48,6 +54,17 @@ DEVICE_S_PER_ACTION = 2e-10          # search kernel time per joint action at 16
 # after about three minutes: a safety stop, not a tuning knob.
 DEFAULT_MAX_NODES = 1 << 32
 
+
+# Node budget of one rank_of(..., backend='bound') call and of a ranked step of the evaluation drivers.  Measured at 20 links
+# x 4 channels (profiles/opt_count_bound_timing.json): an allocation at 97 % of the optimum has 2.7e4 .. 2.4e6
+# strictly better joint actions and is counted exactly in 1.8e6 .. 1.5e7 nodes (4.5 .. 66 per better action), while a random
+# action has more than 7e7 better ones and no budget ranks it.  2^26 = 6.7e7 nodes rank an allocation with a few million
+# better ones exactly and bound the time spent on one that cannot be ranked to 2 .. 3.4 s; its rank comes back as a bracket.
+DEFAULT_RANK_MAX_NODES = 1 << 26
+MAX_THRESHOLDS = 31                 # thresholds per state of one count_better call (v2x_opt_count_bound)
+MAX_COUNT_ROOTS = 1 << 18           # states x thresholds of one call: its root items fill the search's queue at most
+MAX_COUNT_SLOTS = 318               # rb * (n + 1): the LDS slots of a lane (64 lanes x 8 bytes each within 159 KiB)
+RANK_BACKENDS = ('landscape', 'bound')
 
 MAX_LOCAL_LINKS = 128               # v2x_opt_search_local / v2x_opt_rewards_actions
 MAX_LOCAL_RESTARTS = 65536
@@ -154,6 +171,39 @@ def rank_from_counts(counts, edges, rewards):
                 equal[e, a] = c[e, s]
                 better[e, a] = above[s + 1]
     return better, equal
+
+
+def open_leaves(depth_counts, n, rb):
+    """depth_counts [n + 1] (entry k: open subtrees rooted at depth k, i.e. with k links assigned) -> the number of leaves
+    below them, sum_k depth_counts[k] * rb^(n - k), as a Python int: the arithmetic behind `open` of count_better (the
+    library does it in two 64-bit words: v2x_opt_count_open_leaves)."""
+    c = [int(v) for v in (depth_counts.tolist() if hasattr(depth_counts, 'tolist') else depth_counts)]    # (no float on the way)
+    if len(c) != n + 1 or min(c) < 0:
+        raise ValueError("%d non-negative per-depth counts expected, got %r" % (n + 1, c))
+    return sum(v * int(rb) ** (n - k) for k, v in enumerate(c))
+
+
+def join128(hi, lo):
+    """two arrays of 64-bit words (signed or unsigned storage) -> object array of Python ints hi * 2^64 + lo"""
+    hi, lo = np.asarray(hi), np.asarray(lo)
+    out = np.empty(hi.shape, object)
+    for i in np.ndindex(*hi.shape):
+        out[i] = ((int(hi[i]) & _MASK64) << 64) | (int(lo[i]) & _MASK64)
+    return out
+
+
+def check_thresholds(thresholds, E):
+    """The argument checks of count_better (ValueError): thresholds [A] (for every state) or [E, A] floats, 1 <= A <= 31,
+    none of them NaN -> float64 [E, A]."""
+    th = np.asarray(thresholds, np.float64)
+    if th.ndim not in (1, 2) or (th.ndim == 2 and th.shape[0] not in (1, E)):
+        raise ValueError("thresholds of shape [A] or [%d, A] expected, got %s" % (E, list(th.shape)))
+    th = np.atleast_2d(th)
+    if not 1 <= th.shape[1] <= MAX_THRESHOLDS:
+        raise ValueError("1..%d thresholds per state can be counted in one call, got %d" % (MAX_THRESHOLDS, th.shape[1]))
+    if np.isnan(th).any():
+        raise ValueError("a threshold is NaN (not a number): nothing can be counted against it")
+    return np.array(np.broadcast_to(th, (E, th.shape[1])), np.float64, order='C')
 
 
 class BoundBudgetExceeded(RuntimeError):
@@ -266,6 +316,25 @@ class OptimalAllocation(object):
             raise ValueError("max_nodes must be an integer >= 1, got %r" % (max_nodes,))
 
     @staticmethod
+    def check_count(n, rb, v2v_weight=0.0, v2i_weight=0.0, max_nodes=DEFAULT_MAX_NODES, n_thr=1, E=1):
+        """The argument checks of count_better (ValueError), before any device work: the sizes of search_bound without
+        its cap on rb^n (no joint action is named by an index), within the LDS of a lane."""
+        OptimalAllocation.check_size(n, rb, 1 << 128)
+        if rb * (n + 1) > MAX_COUNT_SLOTS:
+            raise ValueError("the counting search keeps rb * (n + 1) = %d values per lane in LDS, %d at most (%d x %d)"
+                             % (rb * (n + 1), MAX_COUNT_SLOTS, n, rb))
+        if not (float(v2v_weight) >= 0.0 and float(v2i_weight) >= 0.0):
+            raise ValueError("the counting search needs weights >= 0 (its bound assumes interference can only lower the "
+                             "reward), got %r / %r" % (v2v_weight, v2i_weight))
+        if int(max_nodes) != max_nodes or int(max_nodes) < 1:
+            raise ValueError("max_nodes must be an integer >= 1, got %r" % (max_nodes,))
+        if not 1 <= int(n_thr) <= MAX_THRESHOLDS:
+            raise ValueError("1..%d thresholds per state can be counted in one call, got %d" % (MAX_THRESHOLDS, n_thr))
+        if int(E) * int(n_thr) > MAX_COUNT_ROOTS:
+            raise ValueError("%d states x %d thresholds exceed the %d (state, threshold) pairs of one call"
+                             % (E, n_thr, MAX_COUNT_ROOTS))
+
+    @staticmethod
     def check_local(n, rb, restarts=DEFAULT_LOCAL_RESTARTS, max_sweeps=DEFAULT_MAX_SWEEPS):
         """The argument checks of search_local / rewards_of (ValueError), before any device work."""
         if not 1 <= n <= MAX_LOCAL_LINKS or not 2 <= rb <= 16:
@@ -287,9 +356,9 @@ class OptimalAllocation(object):
             raise ValueError("channel outside [0, %d) in the joint actions" % rb)
         return np.ascontiguousarray(a.reshape(E, -1, n), np.int32), a.ndim == 3
 
-    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None, n_edges=None):
-        """max_nodes not None: the problem of search_bound (its checks, its workspace); local = (restarts, max_sweeps): of
-        search_local / rewards_of; n_edges: of landscape."""
+    def _setup(self, env, v2v_weight, v2i_weight, limit, max_nodes=None, local=None, n_edges=None, n_thr=None):
+        """max_nodes not None: the problem of search_bound (its checks, its workspace), with n_thr of count_better;
+        local = (restarts, max_sweeps): of search_local / rewards_of; n_edges: of landscape."""
         on_device = hasattr(env, 'problem_tensors')       # DeviceChannels / DeviceBatchedEnviron (rl/device_sim.py): no upload
         if on_device:
             E, (n, rb) = env.E, _sizes(env)
@@ -298,6 +367,8 @@ class OptimalAllocation(object):
             E, n, rb = v2v.shape[0], v2v.shape[1], v2v.shape[3]
         if local is not None:
             self.check_local(n, rb, *local)
+        elif n_thr is not None:
+            self.check_count(n, rb, v2v_weight, v2i_weight, max_nodes, n_thr, E)
         elif max_nodes is None:
             self.check_size(n, rb, limit)
         else:
@@ -313,6 +384,8 @@ class OptimalAllocation(object):
                           w_v2i=float(v2i_weight), **const)
         if local is not None:
             need = int(self._lib.v2x_opt_local_workspace_bytes(C.byref(prob), int(local[0])))
+        elif n_thr is not None:
+            need = int(self._lib.v2x_opt_count_bound_workspace_bytes(C.byref(prob), int(n_thr), int(max_nodes)))
         elif n_edges is not None:
             need = int(self._lib.v2x_opt_landscape_workspace_bytes(C.byref(prob), int(n_edges)))
         elif max_nodes is None:
@@ -514,23 +587,89 @@ class OptimalAllocation(object):
         counts, sums = self.landscape_device(env, v2v_weight, v2i_weight, edges)
         return counts.cpu().numpy(), sums.cpu().numpy()
 
-    def rank_of(self, env, v2v_weight, v2i_weight, actions):
+    def count_better_device(self, env, v2v_weight, v2i_weight, thresholds, max_nodes=DEFAULT_MAX_NODES):
+        """count_better() with the results left on the device: dict of torch tensors `better` / `equal` (int64 [E, A]),
+        `open_hi` / `open_lo` (int64 [E, A] holding the two unsigned 64-bit words of `open`) and `exact` (bool [E, A]), and
+        `nodes_visited` (int).  thresholds: a host array (checked) or a float64 torch tensor [E, A] on the device (a NaN in
+        it is refused by the library: V2XInvalidArgument, a ValueError)."""
+        n, rb = _sizes(env)
+        E = env.E if hasattr(env, 'E') else 1
+        if hasattr(thresholds, 'data_ptr'):                             # a torch tensor
+            if thresholds.dim() != 2 or thresholds.shape[0] != E:
+                raise ValueError("thresholds of shape [%d, A] expected, got %s" % (E, list(thresholds.shape)))
+            A, host = int(thresholds.shape[1]), None
+        else:
+            host = check_thresholds(thresholds, E)
+            A = host.shape[1]
+        self.check_count(n, rb, v2v_weight, v2i_weight, max_nodes, A, E)
+        prob, E, n, rb = self._setup(env, v2v_weight, v2i_weight, MAX_INDEX, max_nodes, n_thr=A)
+        t = self.torch
+        dev = (t.from_numpy(host).to(self.device) if host is not None
+               else thresholds.to(device=self.device, dtype=t.float64).contiguous())
+        out = {k: t.empty((E, A), dtype=t.int64, device=self.device) for k in ('better', 'equal', 'open_hi', 'open_lo')}
+        nodes = C.c_int64(0)
+        rc = self._lib.v2x_opt_count_bound(C.byref(prob), self._ws.data_ptr(), dev.data_ptr(), A, int(max_nodes),
+                                           out['better'].data_ptr(), out['equal'].data_ptr(), out['open_hi'].data_ptr(),
+                                           out['open_lo'].data_ptr(), C.byref(nodes), self._stream())
+        self._keep = self._keep + [dev]
+        self.nodes_visited = int(nodes.value)
+        if rc != V2X_EBUDGET:                                           # a spent budget is a result: the bracket
+            check(self._lib, rc)
+        out['exact'] = (out['open_hi'] == 0) & (out['open_lo'] == 0)
+        out['nodes_visited'] = self.nodes_visited
+        return out
+
+    def count_better(self, env, v2v_weight, v2i_weight, thresholds, max_nodes=DEFAULT_MAX_NODES):
+        """How many joint actions of every state score above / exactly at given thresholds, by branch and bound
+        (v2x_opt_count_bound) -- no cap on rb^n: 1..32 links, 2..16 channels with rb * (n + 1) <= 318, weights >= 0.
+        thresholds [A] (for every state) or [E, A], 1 <= A <= 31, no NaN.  -> dict: `better` / `equal` (int64 [E, A]: joint
+        actions with a reward > / == the threshold, each reward with the bits rewards() returns: what rank_from_counts
+        yields from a landscape), `open` (object [E, A] of Python ints: leaves the search did not examine), `exact` (bool
+        [E, A]: open == 0) and `nodes_visited`.  max_nodes: search-tree nodes the call may visit over all states and
+        thresholds.  A spent budget does not raise: better / equal are then certified lower bounds and the true counts lie
+        in [better, better + open] and [equal, equal + open].  The counts of an exact entry are the same in every run."""
+        out = self.count_better_device(env, v2v_weight, v2i_weight, thresholds, max_nodes)
+        better, equal = out['better'].cpu().numpy(), out['equal'].cpu().numpy()
+        opened = join128(out['open_hi'].cpu().numpy(), out['open_lo'].cpu().numpy())
+        return dict(better=better, equal=equal, open=opened, exact=np.array(opened == 0, bool),
+                    nodes_visited=out['nodes_visited'])
+
+    def rank_of(self, env, v2v_weight, v2i_weight, actions, backend='landscape', max_nodes=DEFAULT_RANK_MAX_NODES):
         """Where given joint actions stand among all rb^n of their state: actions [E, A, n] (A <= 31) or [E, n], channel
         numbers -> dict of `better` / `equal` (int64: joint actions with a strictly larger / an exactly equal reward, the
         action itself included in `equal`), `reward` (rewards_of(actions)), each [E, A] or [E]; `total` (rb^n) and
         `mean_reward` (float64 [E]: the mean over all joint actions).  better == 0: an optimum; better / total: the share
-        of joint actions strictly better than the given one.  One rewards_of and one landscape call."""
+        of joint actions strictly better than the given one.
+        backend='landscape' (the default; rb^n <= 2^36): one rewards_of and one landscape call.
+        backend='bound' (1..32 links, no cap on rb^n; weights >= 0): one rewards_of call and one count_better call with
+        those rewards as thresholds and `max_nodes` as its budget.  The dict then also holds `exact` (bool), `better_max` /
+        `equal_max` (object arrays of Python ints: count + open).  Where `exact`, better / equal are the landscape's numbers;
+        elsewhere the budget ran out and the true counts lie in [better, better_max] and [equal, equal_max].  `mean_reward`
+        is None with 'bound': nothing enumerates the landscape."""
+        if backend not in RANK_BACKENDS:
+            raise ValueError("backend must be one of %s, got %r" % (RANK_BACKENDS, backend))
         n, rb = _sizes(env)
-        self.check_size(n, rb)
+        if backend == 'bound':
+            self.check_count(n, rb, v2v_weight, v2i_weight, max_nodes)
+        else:
+            self.check_size(n, rb)
         E = env.E if hasattr(env, 'E') else 1
         host, had_k = self._check_actions(actions, E, n, rb)
         if host.shape[1] > MAX_RANKED:
             raise ValueError("1..%d joint actions per state can be ranked in one call, got %d" % (MAX_RANKED, host.shape[1]))
         reward = self.rewards_of(env, v2v_weight, v2i_weight, host)
+        total = rb ** n
+        if backend == 'bound':
+            got = self.count_better(env, v2v_weight, v2i_weight, reward, max_nodes)
+            out = dict(better=got['better'], equal=got['equal'], reward=reward, exact=got['exact'],
+                       better_max=got['better'].astype(object) + got['open'], equal_max=got['equal'].astype(object) + got['open'])
+            if not had_k:
+                out = {k: v[:, 0] for k, v in out.items()}
+            out.update(total=total, mean_reward=None, nodes_visited=got['nodes_visited'])
+            return out
         edges = rank_edges(reward)
         counts, sums = self.landscape(env, v2v_weight, v2i_weight, edges)
         better, equal = rank_from_counts(counts, edges, reward)
-        total = rb ** n
         if not had_k:
             better, equal, reward = better[:, 0], equal[:, 0], reward[:, 0]
         return dict(better=better, equal=equal, total=total, mean_reward=sums / float(total), reward=reward)

@@ -4,7 +4,8 @@
 
     python -m v2xgnn.rl.train --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
-                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] [--opt-rank] \\
+                              --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] \\
+                              [--opt-rank [--opt-rank-backend bound [--opt-rank-max-nodes N]]] \\
                               [--sim-backend device --sim-streams device --eval-backend device]
 """
 import argparse
@@ -58,13 +59,16 @@ def evaluation_env(ap, args):
     return start_env(args.links)
 
 
-def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False, eval_backend='host'):
+def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False, eval_backend='host', rank_backend='landscape',
+             rank_max_nodes=None):
     """RL_Run_main.py:151-: -> dict of the test_run outputs plus the mean rewards per scheme.  opt_backend: where the
     optimum is searched ('host': numpy over every joint action; 'device' / 'bound': the GPU searches of rl/optimum.py;
     'local': its local search with opt_restarts restarts -- a lower bound on the optimum, not the optimum).  opt_rank: also
-    rank every step's greedy and random action among all C^N joint actions of its state (agent.rank_book; rank_summary)."""
+    rank every step's greedy and random action among all C^N joint actions of its state (agent.rank_book; rank_summary);
+    rank_backend / rank_max_nodes: how ('landscape': C^N <= 2^36; 'bound': counting branch and bound, up to 32 links)."""
     out = agent.test_run(cfg.Num_Run_Episodes, cfg.Num_Test_Steps, cfg.Opt_Flag, opt_backend=opt_backend,
-                         opt_restarts=opt_restarts, opt_rank=opt_rank, eval_backend=eval_backend)
+                         opt_restarts=opt_restarts, opt_rank=opt_rank, eval_backend=eval_backend, rank_backend=rank_backend,
+                         rank_max_nodes=rank_max_nodes)
     names = ['Expect_Return', 'Reward', 'Per_V2V_Rate', 'Per_V2I_Rate', 'Per_V2B_Interference']
     res = {}
     for prefix, chunk in zip(('', 'RA_', 'Opt_'), (out[0:5], out[5:10], out[10:15])):
@@ -76,6 +80,18 @@ def run_test(cfg, agent, opt_backend='host', opt_restarts=None, opt_rank=False, 
 def rank_summary(book):
     """The --opt-rank entries of the JSON summary from Agent.rank_book."""
     total = book['total'].astype(np.float64)
+    if 'exact' in book:                               # --opt-rank-backend bound: exact where the node budget sufficed, else a bracket
+        out = {}
+        for name, pre in (('gnn', ''), ('random', 'ra_')):
+            exact = book[pre + 'exact']
+            share = book[pre + 'better'][exact] / total[exact]
+            upper = book[pre + 'better_max'][~exact].astype(np.float64) / total[~exact]
+            out["share_states_%s_ranked_exactly" % name] = float(np.mean(exact))
+            if name == 'gnn':
+                out["share_exact_states_gnn_optimal"] = float(np.mean(book['better'][exact] == 0)) if exact.any() else None
+            out["median_share_better_%s_exact_states" % name] = float(np.median(share)) if exact.any() else None
+            out["median_upper_share_better_%s_bracketed_states" % name] = float(np.median(upper)) if (~exact).any() else None
+        return out
     return {"share_states_gnn_optimal": float(np.mean(book['better'] == 0)),
             "median_share_better_gnn": float(np.median(book['better'] / total)),
             "median_share_better_random": float(np.median(book['ra_better'] / total)),
@@ -101,6 +117,11 @@ def main(argv=None):
     ap.add_argument("--opt-rank", action="store_true",
                     help="rank every step's greedy and random action among ALL C^N joint actions of its state on the GPU "
                          "(C^N <= 2^36; with or without --opt, any --opt-backend) and add the shares to the summary")
+    ap.add_argument("--opt-rank-backend", choices=("landscape", "bound"), default="landscape",
+                    help="how --opt-rank counts: the whole reward landscape (C^N <= 2^36) or counting branch and bound (bound: up "
+                         "to 32 links, e.g. 20 x 4; exact for a good allocation, a certified bracket where the budget runs out)")
+    ap.add_argument("--opt-rank-max-nodes", type=int, default=None,
+                    help="node budget per ranked step of --opt-rank-backend bound (default: rl/optimum.py DEFAULT_RANK_MAX_NODES)")
     ap.add_argument("--seed", type=int, default=11)
     add_sim_arguments(ap)
     args = ap.parse_args(argv)
@@ -117,7 +138,7 @@ def main(argv=None):
     env = evaluation_env(ap, args)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed)
     res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank,
-                   eval_backend=args.eval_backend)
+                   eval_backend=args.eval_backend, rank_backend=args.opt_rank_backend, rank_max_nodes=args.opt_rank_max_nodes)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,
                "mean_reward_gnn": float(res['Reward'].mean()), "mean_reward_random": float(res['RA_Reward'].mean())}
     if args.opt:

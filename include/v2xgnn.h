@@ -67,6 +67,7 @@ extern "C" {
 #define V2X_ESTATE       -4   /* call order violated (e.g. backward before forward) */
 #define V2X_ECOMM        -5   /* a collective of a v2x_comm table returned non-zero   */
 #define V2X_EBUDGET      -6   /* v2x_opt_search_bound spent its node budget: the result is a lower bound, not proven */
+                              /* (v2x_opt_count_bound: the counts are lower bounds, `open` brackets them)             */
 
 #define V2X_XE_WIDTH     16   /* packed [x|e|pad] row width */
 
@@ -379,6 +380,28 @@ int  v2x_opt_search_bound(const v2x_opt_problem* p, void* workspace, int64_t max
  * Workspace: v2x_opt_bound_workspace_bytes. */
 int  v2x_opt_search_bound_seeded(const v2x_opt_problem* p, void* workspace, int64_t max_nodes, const int32_t* start_actions,
                                  int64_t* best_index, double* best_reward, int64_t* nodes_visited, void* stream);
+/* Counting branch and bound: how many joint actions of state e score strictly above / exactly at thresholds[e][a] -- the
+ * pair a landscape with the edges { v, nextafter(v) } yields, each reward with the bits v2x_opt_rewards returns for its index --
+ * without walking rb^n joint actions: v2x_opt_search_bound's tree with the fixed threshold in the incumbent's place.  A
+ * subtree is dropped only when its upper bound lies strictly below the threshold by the search's rounding margin, so no
+ * better and no equal action is lost, and every leaf reached is compared with the threshold exactly.  Limits: 1..32 links,
+ * 2..16 channels (no cap on rb^n: no index is returned; rb * (n + 1) <= 318, the lanes' LDS), both weights >= 0,
+ * 1 <= n_thr <= 31, E * n_thr <= 262144, no NaN threshold, max_nodes >= 1: V2X_EINVAL otherwise.
+ * thresholds [dev] [E][n_thr]; better, equal [dev] [E][n_thr] int64: exact integers, the same from run to run and whatever
+ * states are stacked around a state.  max_nodes: nodes the call may visit over all (state, threshold) pairs, checked between
+ * launches; when it is spent the call returns V2X_EBUDGET, better / equal hold what has been counted (certified lower
+ * bounds) and open_hi : open_lo [dev] [E][n_thr] the 128-bit number of leaves not examined, so that
+ * better <= true better <= better + open, and the same for equal; nothing is dropped silently.  On V2X_OK open is 0.
+ * nodes_visited: [host], may be NULL; varies from run to run.  Synchronises `stream` once for the threshold check and once
+ * per round of launches (not capturable); allocates nothing.  v2x_opt_count_bound_workspace_bytes:
+ * v2x_opt_bound_workspace_bytes + E * n_thr * (n + 1) * 8 rounded up to 256; < 0 on a bad argument. */
+int64_t v2x_opt_count_bound_workspace_bytes(const v2x_opt_problem* p, int32_t n_thr, int64_t max_nodes);
+int  v2x_opt_count_bound(const v2x_opt_problem* p, void* workspace, const double* thresholds, int32_t n_thr, int64_t max_nodes,
+                         int64_t* better, int64_t* equal, uint64_t* open_hi, uint64_t* open_lo, int64_t* nodes_visited,
+                         void* stream);
+/* The arithmetic behind `open`, on the host (no device is touched): depth_counts [host] [n + 1], entry k the open subtrees
+ * rooted at depth k -> open_hi : open_lo = sum_k depth_counts[k] * rb^(n - k) modulo 2^128. */
+int  v2x_opt_count_open_leaves(const uint64_t* depth_counts, int32_t n, int32_t rb, uint64_t* open_hi, uint64_t* open_lo);
 /* A near-optimal allocation where the exact searches cannot go: multi-start best-response local search, one wave per
  * (state, restart) -- a LOWER BOUND on the optimum, not the optimum.  1 <= n <= 128 links, 2 <= rb <= 16, E <= 65535; a joint
  * action is an array of n channel numbers, never an index.  Restart 0 starts from a[l] = l mod rb, restart r from

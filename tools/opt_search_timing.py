@@ -23,6 +23,13 @@ the seeded states of --bound, beside search() on the same states, the four taken
 time per state and the ratio of the landscape's kernel time to the search's.
 
     python tools/opt_search_timing.py --landscape [--out profiles/opt_landscape_timing.json] [--states 10] [--reps 5]
+
+With --count: the counting branch and bound (count_better, v2x_opt_count_bound) on the seeded states of --bound at 12, 16 and
+20 links x 4 RBs, one (state, threshold) per call: the state's optimum (from search_bound), 0.97 x it and the reward of one
+seeded random action as thresholds -- better, equal, open, nodes, wall and kernel time --, beside search_bound on the same state
+in the same run and, at 12 and 16 links, the landscape (whose counts the exact results must equal).
+
+    python tools/opt_search_timing.py --count [--out profiles/opt_count_bound_timing.json] [--states 10] [--count-max-nodes N]
 """
 import argparse
 import json
@@ -397,6 +404,99 @@ def main_landscape(args):
     return 0
 
 
+COUNT_THRESHOLDS = ("optimum", "0.97 x optimum", "random action")
+
+
+def count_rows(opt, n, states, max_nodes):
+    """count_better on `states` seeded states of n links x 4 RBs, one threshold per call (so every threshold has its own nodes
+    and times): wall of the Python call (upload, launches, the per-round counter read-backs, download) and the time between HIP
+    events around v2x_opt_count_bound alone.  search_bound on the same state first (its optimum is the first threshold); the
+    landscape with the three thresholds' edges at n <= 12, and for 3 states at 16 links."""
+    import ctypes
+    import torch
+    from v2xgnn.rl.optimum import MAX_INDEX, rank_edges, rank_from_counts
+    w_v2v, w_v2i = 1.0, 0.1
+    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
+    per_state = []
+    for seed in range(states):
+        env = _state(n, seed)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        _, best = opt.search_bound(env, w_v2v, w_v2i)
+        row = {"seed": seed, "search_bound": {"wall_ms": round((time.perf_counter() - t0) * 1e3, 3), "nodes": opt.nodes_visited,
+                                              "reward": float(best[0])}}
+        rnd = np.random.default_rng(seed).integers(0, 4, size=(1, n))
+        th = np.array([[best[0], 0.97 * best[0], opt.rewards_of(env, w_v2v, w_v2i, rnd)[0]]])
+        truth = None
+        if n <= 12 or (n <= 16 and seed < 3):
+            edges = rank_edges(th)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            counts, _ = opt.landscape(env, w_v2v, w_v2i, edges)
+            row["landscape_wall_ms"] = round((time.perf_counter() - t0) * 1e3, 3)
+            truth = rank_from_counts(counts, edges, th)
+        for k, name in enumerate(COUNT_THRESHOLDS):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            got = opt.count_better(env, w_v2v, w_v2i, th[:, k], max_nodes)
+            wall = (time.perf_counter() - t0) * 1e3
+            prob, _, _, _ = opt._setup(env, w_v2v, w_v2i, MAX_INDEX, max_nodes, n_thr=1)
+            dev = torch.from_numpy(np.ascontiguousarray(th[:, k:k + 1])).to(opt.device)
+            outs = [torch.empty((1, 1), dtype=torch.int64, device=opt.device) for _ in range(4)]
+            cnt = ctypes.c_int64(0)
+            ev[0].record()
+            opt._lib.v2x_opt_count_bound(ctypes.byref(prob), opt._ws.data_ptr(), dev.data_ptr(), 1, int(max_nodes),
+                                         *[o.data_ptr() for o in outs], ctypes.byref(cnt), opt._stream())
+            ev[1].record()
+            torch.cuda.synchronize()
+            better, opened = int(got['better'][0, 0]), int(got['open'][0, 0])
+            if truth is not None:
+                assert better <= int(truth[0][0, k]) <= better + opened and int(got['equal'][0, 0]) <= int(truth[1][0, k]), (n, seed, name)
+                assert not got['exact'][0, 0] or better == int(truth[0][0, k]), (n, seed, name)
+            row[name] = {"threshold": float(th[0, k]), "better": better, "equal": int(got['equal'][0, 0]), "open": opened,
+                         "exact": bool(got['exact'][0, 0]), "nodes": got['nodes_visited'], "wall_ms": round(wall, 3),
+                         "kernel_ms": round(ev[0].elapsed_time(ev[1]), 3),
+                         "nodes_per_better": round(got['nodes_visited'] / better, 2) if better else None}
+        print(json.dumps({"n": n, **row}), flush=True)
+        per_state.append(row)
+    out = {"case": "count %d links" % n, "n": n, "rb": 4, "states": states, "joint_actions_per_state": 4 ** n,
+           "max_nodes": int(max_nodes), "search_bound_wall_ms": _mmm([r["search_bound"]["wall_ms"] for r in per_state]),
+           "search_bound_nodes": _mmm([r["search_bound"]["nodes"] for r in per_state])}
+    for name in COUNT_THRESHOLDS:
+        rows = [r[name] for r in per_state]
+        exact = [r for r in rows if r["exact"]]
+        out[name] = {"states_exact": len(exact), "nodes": _mmm([r["nodes"] for r in rows]), "wall_ms": _mmm([r["wall_ms"] for r in rows]),
+                     "kernel_ms": _mmm([r["kernel_ms"] for r in rows]),
+                     "nodes_per_s_kernel_median": float("%.4g" % np.median([r["nodes"] / (r["kernel_ms"] * 1e-3) for r in rows]))}
+        if exact:
+            out[name]["better_where_exact"] = _mmm([r["better"] for r in exact])
+            ratios = [r["nodes_per_better"] for r in exact if r["nodes_per_better"]]
+            if ratios:
+                out[name]["nodes_per_better_where_exact"] = _mmm(ratios)
+        if len(exact) < len(rows):
+            out[name]["open_share_where_bracketed"] = _mmm([r["open"] / 4.0 ** n for r in rows if not r["exact"]])
+    out["per_state"] = per_state
+    return out
+
+
+def main_count(args):
+    import torch
+    from v2xgnn.rl import OptimalAllocation
+    opt = OptimalAllocation()
+    opt.search_bound(_state(8), 1.0, 0.1)                              # warm-up: code objects, workspace
+    opt.count_better(_state(8), 1.0, 0.1, [1.0])
+    rows = []
+    for n in (12, 16, 20):
+        rows.append(count_rows(opt, n, args.states, args.count_max_nodes))
+        print(json.dumps({k: v for k, v in rows[-1].items() if k != "per_state"}), flush=True)
+    out = {"device": torch.cuda.get_device_name(0), "rows": rows}
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(out, f, indent=1)
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=None)
@@ -404,7 +504,10 @@ def main(argv=None):
     ap.add_argument("--bound", action="store_true", help="measure the branch-and-bound search instead")
     ap.add_argument("--local", action="store_true", help="measure the multi-start local search instead")
     ap.add_argument("--landscape", action="store_true", help="measure the reward landscape beside search() instead")
-    ap.add_argument("--states", type=int, default=10, help="--bound / --local / --landscape: seeded states per size")
+    ap.add_argument("--count", action="store_true", help="measure the counting branch and bound beside search_bound instead")
+    ap.add_argument("--count-max-nodes", type=int, default=1 << 26,
+                    help="--count: node budget of one (state, threshold) call (default: DEFAULT_RANK_MAX_NODES of rl/optimum.py)")
+    ap.add_argument("--states", type=int, default=10, help="--bound / --local / --landscape / --count: seeded states per size")
     ap.add_argument("--links", type=int, nargs="+", default=[12, 16, 20, 24], help="--bound / --local: sizes against the exact optimum")
     args = ap.parse_args(argv)
     import torch
@@ -416,6 +519,8 @@ def main(argv=None):
         return main_local(args)
     if args.landscape:
         return main_landscape(args)
+    if args.count:
+        return main_count(args)
     from v2xgnn.rl import OptimalAllocation
     opt = OptimalAllocation()
     rows = []
