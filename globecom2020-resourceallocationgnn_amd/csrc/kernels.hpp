@@ -1662,6 +1662,18 @@ __global__ __launch_bounds__(256) void k_gather_rows_multi(GatherJobs jobs, cons
   }
 }
 
+// np.amax of a row of C values: the largest entry, NaN as soon as one entry is NaN (fmaxf would drop it; the target rule and the
+// Q statistics of BS_brain.py:690 / :746 are numpy's).  Finite rows give what fmaxf gave.  The one rule of k_q_stats, k_dqn_tq
+// and k_dqn_targets.
+__device__ inline float amax_row(const float* __restrict__ r, int C) {
+  float mx = r[0];
+  for (int c = 1; c < C; ++c) {
+    const float v = r[c];
+    if (mx == mx && (v > mx || v != v)) mx = v;
+  }
+  return mx;
+}
+
 // Q statistics of a minibatch of fitted targets y[B][N][C] (BS_brain.py:743-746: per link the mean of all entries and the mean of
 // the per-sample maxima), as float64 SUMS per link: out[0][k] = sum_b sum_c y, out[1][k] = sum_b max_c y.  QS_PARTS workgroups
 // per link, each a fixed range of the samples (every thread a fixed subset, combined through LDS in a fixed order); the last
@@ -1676,11 +1688,10 @@ __global__ __launch_bounds__(256) void k_q_stats(const float* y, int B, int N, i
   double a = 0.0, m = 0.0;
   for (int b = b0 + threadIdx.x; b < b1; b += 256) {
     const float* row = y + ((int64_t)b * N + k) * C;
-    float mx = row[0];
     double s = (double)row[0];
-    for (int c = 1; c < C; ++c) { s += (double)row[c]; mx = fmaxf(mx, row[c]); }
+    for (int c = 1; c < C; ++c) s += (double)row[c];
     a += s;
-    m += (double)mx;
+    m += (double)amax_row(row, C);
   }
   s_all[threadIdx.x] = a; s_max[threadIdx.x] = m;
   __syncthreads();
@@ -1712,8 +1723,7 @@ __global__ __launch_bounds__(256) void k_dqn_tq(const float* qn, const int32_t* 
                                                 int n_nodes, int C, float* tq) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= n_rows) return;
-  float mx = qn[(int64_t)row * C];
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, qn[(int64_t)row * C + c]);
+  const float mx = amax_row(qn + (int64_t)row * C, C);
   const float t = (float)(reward[row / n_nodes] + gamma * (double)mx);
   *reinterpret_cast<float4*>(tq + (int64_t)row * 4) = make_float4(t, __int_as_float(action[row]), 0.f, 0.f);
 }
@@ -1724,8 +1734,7 @@ __global__ __launch_bounds__(256) void k_dqn_targets(const float* q, const float
                                                      int C, float* y) {
   const int row = blockIdx.x * 256 + threadIdx.x;
   if (row >= n_rows) return;
-  float mx = qn[(int64_t)row * C];
-  for (int c = 1; c < C; ++c) mx = fmaxf(mx, qn[(int64_t)row * C + c]);
+  const float mx = amax_row(qn + (int64_t)row * C, C);
   // `r + GAMMA * np.amax(p_)` (BS_brain.py:690) scalar by scalar with p_ float32: under the reference's numpy-1.x
   // stack the product is float64 (python float x np.float32), rounded to fp32 once when stored.  (numpy >= 2 / NEP 50
   // rounds the product to fp32 first; the fixtures captured under numpy 2.2.6 differ from this by <= 1 ulp.)
