@@ -27,6 +27,7 @@ NATIVE_SAMPLER_MIN = 16384         # stored transitions from which Memory.sample
 OPT_BACKENDS = ('host', 'device', 'bound', 'local')
 ROLLOUT_BACKENDS = ('host', 'device', 'trajectory')
 EVAL_BACKENDS = ('host', 'device')
+TRAJECTORY_WALKS = ('serial', 'wide')
 
 
 def _check_opt_backend(opt_backend):
@@ -77,7 +78,7 @@ class Memory(object):
 
 class Agent(object):
     def __init__(self, num_d2d, num_ch, num_neighbor, num_d2d_feedback, environment, curr_rl_config, brain=None,
-                 device_replay='auto', rollouts='replicated', rollout_backend='host', **brain_kwargs):
+                 device_replay='auto', rollouts='replicated', rollout_backend='host', trajectory_walk='serial', **brain_kwargs):
         """rollout_backend: 'host' (the default: _packed_iteration -- the observation comes down, is scored, the actions go up,
         the transitions go up again) or 'device': a whole rollout iteration is ONE call on the resident state (v2x_rollout_step:
         score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
@@ -87,6 +88,12 @@ class Agent(object):
         (v2x_rollout_steps: one kernel walks every simulator through its steps, one forward scores all observations, one
         kernel picks, pays and stores) -- the policy draws of the whole rollout are taken first, in the order 'device' takes
         them; bit for bit 'device' (tests/test_gpu_rollout_trajectory.py).
+
+        trajectory_walk: how the trajectory calls of rollout_backend='trajectory' and of eval_backend='device' (test_run,
+        test_run_fixed_positions) walk a simulator's T steps: 'serial' (the default: one workgroup per simulator, step after
+        step) or 'wide' (v2x_rollout_steps_wide / v2x_eval_steps_wide: only the streams and the shadowing recursion step by
+        step, everything else of all T steps at once) -- the same bits (tests/test_gpu_trajectory_wide.py), opt-in because it
+        does not win at every size.  'wide' where neither backend can ever run is a ValueError here.
 
         device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
         visiting the host; 'auto' = whenever the brain runs on the gfx950 engine.
@@ -145,6 +152,8 @@ class Agent(object):
             self.device_replay = DeviceReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device)
         self._check_rollout_backend(rollout_backend, on_gpu)
         self.rollout_backend = rollout_backend
+        self._check_trajectory_walk(trajectory_walk)
+        self.trajectory_walk = trajectory_walk
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
@@ -168,6 +177,17 @@ class Agent(object):
             why = "a single GPU (no data parallelism)"
         if why is not None:
             raise ValueError("rollout_backend=%r needs %s" % (rollout_backend, why))
+
+    def _check_trajectory_walk(self, trajectory_walk):
+        if trajectory_walk not in TRAJECTORY_WALKS:
+            raise ValueError("trajectory_walk must be one of %s, got %r" % (TRAJECTORY_WALKS, trajectory_walk))
+        if trajectory_walk == 'serial' or self.rollout_backend == 'trajectory':
+            return
+        try:                                           # no trajectory rollouts: an evaluation on the resident state is what is left
+            self._check_eval_backend('device')
+        except ValueError as exc:
+            raise ValueError("trajectory_walk=%r needs rollout_backend='trajectory' or an agent that eval_backend='device' "
+                             "can run on: rollout_backend is %r, and %s" % (trajectory_walk, self.rollout_backend, exc))
 
     def _trainer(self):
         return getattr(getattr(self.brain, 'model', None), 'trainer', None)
@@ -466,8 +486,9 @@ class Agent(object):
         else:                                          # one iteration: no leading axis
             call, explore, actions = env.rollout_step, explore[0], drawn[0][0]
         head = rep.reserve(K)
+        walk = dict(walk=self.trajectory_walk) if whole else {}
         result = call(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
-                      engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None)
+                      engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None, **walk)
         rep.commit(K, result)
         self.num_step += K
         samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
@@ -1132,7 +1153,8 @@ class Agent(object):
         explore = np.asarray(explore, np.uint8)
         engine = None if explore.all() else self.brain.model.engine
         res = self.env.evaluate_steps(explore.reshape(T, 1), np.asarray(policy_random).reshape(T, 1, n),
-                                      np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine)
+                                      np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine,
+                                      walk=self.trajectory_walk)
         out = {'res': res.resolve()}
         if optimum is not None or rank:
             states = self.env.trajectory_states(T)

@@ -42,6 +42,9 @@ rates instead of a reward alone), and the T snapshots it leaves are one stacked 
     states = dc.trajectory_states(T)            # E' = T E states; valid until the next trajectory call of that T
     index, reward = OptimalAllocation().search(states, 1.0, 0.1); states.rates(actions)
 
+Both trajectory calls take walk='serial' (the default: one workgroup per simulator walks its T steps) or walk='wide'
+(v2x_rollout_steps_wide / v2x_eval_steps_wide: the steps spread over the chip, the same bits); dc.walk_calls counts them.
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -85,6 +88,29 @@ def trajectory_workspace_layout(E, n, rb, T):
         offs.append(o)
         o += _align(b, 256)
     return dict(zip(('traj_xe', 'traj_col', 'traj_mask', 'traj_regular', 'traj_v2v_ff', 'traj_v2i_ff', 'traj_v2i_abs'), offs)), o
+
+
+def wide_workspace_layout(E, n, rb, T):
+    """-> (the byte offsets of u_all, xy_all, pl, gs, ob_state, ob_interf in the workspace of the wide walk, its size): the
+    formula of include/v2xgnn.h (v2x_traj_wide_workspace_bytes), every array rounded up to 256 bytes"""
+    n_u, n_el = uniforms_per_step(n, rb), n + n * n
+    parts = (8 * T * E * n_u, 16 * T * E * n, 8 * T * E * n_el, 8 * T * E * n_el, 8 * (T - 1) * E * n * (3 * rb + 1),
+             8 * (T - 1) * E * n * rb)
+    offs, o = [], 0
+    for b in parts:
+        offs.append(o)
+        o += _align(b, 256)
+    return dict(zip(('u_all', 'xy_all', 'pl', 'gs', 'ob_state', 'ob_interf'), offs)), o
+
+
+WALKS = ('serial', 'wide')                               # how a trajectory call walks a state's T steps (v2x_*_steps / v2x_*_steps_wide)
+
+
+def check_walk(who, walk):
+    """ValueError unless walk names a form of the trajectory"""
+    if walk not in WALKS:
+        raise ValueError("%s: walk must be one of %s, got %r" % (who, ", ".join(repr(w) for w in WALKS), walk))
+    return walk
 
 
 def eval_result_layout(E, n, rb, T, schemes):
@@ -254,6 +280,7 @@ class DeviceChannels(object):
         self._grid_sent = False
         self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
         self._roll = {}                                  # _rollout_io(): None (rollout_step) or T (rollout_steps) -> its buffers
+        self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
 
     # ------------------------------------------------------------------ shapes and checks
     def shapes(self):
@@ -684,6 +711,21 @@ class DeviceChannels(object):
                 io['col'] = ws[offs['traj_col']:offs['traj_col'] + 4 * K * n * (n - 2)].view(t.int32)
         return io
 
+    def _wide_workspace(self, T):
+        """the workspace of the wide walk for blocks of T, made at the first wide call of that T and kept in _rollout_io(T) next
+        to the trajectory workspace; the device never sends it anywhere: no traffic"""
+        io = self._rollout_io(T)
+        ws = io.get('wide_workspace')
+        if ws is None:
+            E, n, rb = self.E, self.n, self.rb
+            _, size = wide_workspace_layout(E, n, rb, T)
+            need = self._lib.v2x_traj_wide_workspace_bytes(E, n, rb, T)
+            if need != size:
+                raise ValueError("the library sizes the wide-walk workspace of E = %d, n = %d, rb = %d, T = %d at %d bytes, the "
+                                 "documented layout at %d" % (E, n, rb, T, need, size))
+            ws = io['wide_workspace'] = self.torch.zeros(max(size, 256), dtype=self.torch.uint8, device=self.device)
+        return ws
+
     def rollout_buffers(self):
         """the device buffers of rollout_step(): policy_dev (random_actions [E, n] int32 | explore [E] bytes), result_dev (reward [E]
         float64 | regular [2, E] bytes), q [E n, rb] float32"""
@@ -767,8 +809,10 @@ class DeviceChannels(object):
         ev.record(t.cuda.current_stream(self.device))
         return RolloutResult(free, ev, pinned, self.E, T)
 
-    def _rollout(self, who, T, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power):
+    def _rollout(self, who, T, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power,
+                 walk='serial'):
         """rollout_step() (T None) / rollout_steps(): check, upload the policy, the one library call, start the download"""
+        check_walk(who, walk)
         ex, ra = self._check_rollout(who, T, explore, random_actions, storage, head, capacity)
         if engine is not None and row_ptr is None:
             raise ValueError("%s: scoring needs the CSR row pointer of the %s batch" % (who, "resident" if T is None else "trajectory's"))
@@ -779,10 +823,21 @@ class DeviceChannels(object):
         self._upload_policy(io, ra, ex)
         r = self._rollout_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power)
         self._keep_actions = self._t['actions']
-        call = self._lib.v2x_rollout_step if T is None else self._lib.v2x_rollout_steps
-        check(self._lib, call(C.byref(r), self._stream()))
+        if T is None:
+            check(self._lib, self._lib.v2x_rollout_step(C.byref(r), self._stream()))
+        else:
+            self._trajectory_call(self._lib.v2x_rollout_steps, self._lib.v2x_rollout_steps_wide, r, T, walk)
         self._obs_ready = True
         return self._download_result(io, T)
+
+    def _trajectory_call(self, serial, wide, r, T, walk):
+        """the library call of a trajectory struct r in the form `walk` names, counted in walk_calls"""
+        if walk == 'wide':
+            ws = self._wide_workspace(T)
+            check(self._lib, wide(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+        else:
+            check(self._lib, serial(C.byref(r), self._stream()))
+        self.walk_calls[walk] += 1
 
     def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                      power=None):
@@ -797,15 +852,17 @@ class DeviceChannels(object):
                              row_ptr, power)
 
     def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                      power=None):
+                      power=None, walk='serial'):
         """T DQN rollout iterations in ONE call (v2x_rollout_steps) on the resident state: every simulator walks its T steps in
         one kernel, one forward scores all T E observations (engine: a GnnEngine, with row_ptr the constant CSR pointer of
         T E n rows; None: nobody is greedy anywhere in the block, no forward), and one kernel picks (explore [T, E] flags,
         random_actions [T, E, n]: the host's draws, one upload), pays and stores the T E transitions into slots
         (head + t E + e) % capacity of `storage`.  Bit for bit T calls of rollout_step().  -> a RolloutResult whose download
-        (one) is in flight.  Afterwards as after the last rollout_step: fetch_rates(), fetch_observation()."""
+        (one) is in flight.  Afterwards as after the last rollout_step: fetch_rates(), fetch_observation().
+        walk: 'serial' (one workgroup per simulator walks its T steps) or 'wide' (v2x_rollout_steps_wide: the steps spread over
+        the chip, four launches, the same bits); walk_calls counts which ran."""
         return self._rollout("rollout_steps", _block_length(explore), explore, random_actions, storage, head, capacity, v2v_weight,
-                             v2i_weight, engine, row_ptr, power)
+                             v2i_weight, engine, row_ptr, power, walk)
 
     # ------------------------------------------------------------------ an evaluation episode on the resident state
     def eval_steps_policy_bytes(self, T, baseline=True):
@@ -881,14 +938,17 @@ class DeviceChannels(object):
             r.batch = _batch_struct(self._rollout_batch(io, K, io['xe'], io['col'], row_ptr))
         return r
 
-    def eval_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None):
+    def eval_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None,
+                   walk='serial'):
         """The T steps of an evaluation episode in ONE call (v2x_eval_steps) on the resident state: every simulator walks its T
         steps in one kernel, one forward scores all T E observations (engine: a GnnEngine; row_ptr: the constant CSR pointer of
         T E n rows, made here when None; engine None: nobody is greedy, no forward), and one kernel pays two schemes per state --
         the policy (explore [T, E] flags, policy_random [T, E, n]) and the baseline (baseline_actions [T, E, n]; None: no
         baseline scheme) -- on the step's snapshot.  No replay memory is touched.  One upload (the draws), one download (the
         result block) -> an EvalResult whose download is in flight.  Afterwards the resident state is what T advance() calls
-        under the policy's actions leave, and trajectory_states(T) holds the T snapshots."""
+        under the policy's actions leave, and trajectory_states(T) holds the T snapshots.  walk: as for rollout_steps()
+        (v2x_eval_steps_wide)."""
+        check_walk("eval_steps", walk)
         T, ex, ra, ba = self.check_eval_steps(explore, policy_random, baseline_actions)
         self._init_device()
         if not self._obs_ready:
@@ -911,7 +971,7 @@ class DeviceChannels(object):
         io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
         r = self.eval_steps_struct(T, v2v_weight, v2i_weight, engine, row_ptr, power, ba is not None)
         self._keep_actions = self._t['actions']
-        check(self._lib, self._lib.v2x_eval_steps(C.byref(r), self._stream()))
+        self._trajectory_call(self._lib.v2x_eval_steps, self._lib.v2x_eval_steps_wide, r, T, walk)
         self._obs_ready = True
         S = 2 if ba is not None else 1
         size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
@@ -1253,16 +1313,21 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
 
-    def _resident_rollout(self, steps, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr):
+    def _resident_rollout(self, steps, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr,
+                          walk='serial'):
         """rollout_step() / rollout_steps() (steps): DeviceChannels' call of that name with act()'s bookkeeping around it -- the
         device holds the newer streams and channel arrays, the observable interference is on the device, no host copy of the
         observation exists; V2I_Interference / V2V_Interference download the rates when they are next read"""
         def check_args(dc):
+            check_walk('rollout_steps' if steps else 'rollout_step', walk)
             (dc.check_rollout_steps if steps else dc.check_rollout)(explore, random_actions, storage, head, capacity)
 
         def call(dc):
-            return (dc.rollout_steps if steps else dc.rollout_step)(explore, random_actions, storage, head, capacity, v2v_weight,
-                                                                    v2i_weight, engine=engine, row_ptr=row_ptr)
+            if steps:
+                return dc.rollout_steps(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
+                                        row_ptr=row_ptr, walk=walk)
+            return dc.rollout_step(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
+                                   row_ptr=row_ptr)
 
         return self._resident_call('rollout_steps' if steps else 'rollout_step', check_args, call)
 
@@ -1298,19 +1363,28 @@ class DeviceBatchedEnviron(BatchedEnviron):
         return self._resident_rollout(False, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
                                       row_ptr)
 
-    def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None):
+    def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
+                      walk='serial'):
         """T iterations of rollout_step() in one call (explore [T, E], random_actions [T, E, n]; DeviceChannels.rollout_steps):
-        the same bookkeeping, once.  -> the RolloutResult of the block, its download in flight."""
+        the same bookkeeping, once.  walk: 'serial' or 'wide', the form of the trajectory (the same bits).  -> the RolloutResult
+        of the block, its download in flight."""
         return self._resident_rollout(True, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
-                                      row_ptr)
+                                      row_ptr, walk)
 
-    def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None):
+    def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
+                       walk='serial'):
         """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
         bookkeeping of rollout_steps() around it: explore [T, E], policy_random [T, E, n], baseline_actions [T, E, n] or None.
+        walk: 'serial' or 'wide', the form of the trajectory (the same bits).
         -> the EvalResult, its download in flight.  trajectory_states(T) then holds the T snapshots."""
+        def check_args(dc):
+            check_walk('evaluate_steps', walk)
+            dc.check_eval_steps(explore, policy_random, baseline_actions)
+
         return self._resident_call(
-            'evaluate_steps', lambda dc: dc.check_eval_steps(explore, policy_random, baseline_actions),
-            lambda dc: dc.eval_steps(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr))
+            'evaluate_steps', check_args,
+            lambda dc: dc.eval_steps(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr,
+                                     walk=walk))
 
     def trajectory_states(self, T):
         """the T snapshots of the last evaluate_steps() / rollout_steps() of block length T as one stacked search problem

@@ -107,6 +107,10 @@ def build_parser():
                          "step, reward, store) as one call on the state resident in HBM, 'trajectory' all iterations of a "
                          "rollout as one call (one kernel walks the simulators, one forward scores every observation, one kernel "
                          "picks, pays and stores); 'host' (the default) scores and stores through the host")
+    ap.add_argument("--trajectory-walk", choices=["serial", "wide"], default="serial",
+                    help="with --rollout trajectory: how a simulator's steps are walked -- 'serial' (the default: one workgroup "
+                         "per simulator, step after step) or 'wide' (the steps spread over the chip in four launches; the same "
+                         "bits; DESIGN.md section 6 says at which sizes it wins)")
     return ap
 
 
@@ -117,6 +121,8 @@ def main(argv=None):
         ap.error("--sim-streams device needs --sim-backend device")
     if args.rollout != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
         ap.error("--rollout %s needs --sim-backend device --sim-streams device" % args.rollout)
+    if args.trajectory_walk != "serial" and args.rollout != "trajectory":
+        ap.error("--trajectory-walk %s needs --rollout trajectory" % args.trajectory_walk)
     if args.sim_backend == "device" and args.envs < 1:
         ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:
@@ -161,7 +167,7 @@ def main(argv=None):
         agent, (loss, reward_step, reward_ep, q_mean, q_max, _, _) = run_train(
             env, cfg, save_dir=args.save_dir if rank == 0 else None, verbose=rank == 0,
             device=local, seed=args.seed, use_graph=args.use_graph, data_parallel=world > 1 or force_dp,
-            rollouts=args.rollouts, rollout_backend=args.rollout)
+            rollouts=args.rollouts, rollout_backend=args.rollout, trajectory_walk=args.trajectory_walk)
     dt = time.perf_counter() - t0
     if rank == 0:
         n_fit = args.episodes * args.train_steps

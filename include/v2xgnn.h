@@ -656,6 +656,38 @@ typedef struct v2x_eval {
 int64_t v2x_eval_steps_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
 int  v2x_eval_steps(const v2x_eval* r, void* stream);
 
+/* The wide walk: v2x_rollout_steps and v2x_eval_steps with the trajectory spread over the chip.  k_sim_trajectory walks a
+ * state's T steps one after the other in one workgroup; of a step only mobility with the MT19937 stream position and the
+ * shadowing recursion depend on the step before.  The wide forms replace that one launch by four, in this order on the one
+ * stream, no parallel branches, no allocation, no synchronisation; the forward and the finish launch are the serial forms':
+ *   k_traj_stream   grid (E), 256 threads, the key array in LDS: entry 0 and snapshot 0 as k_sim_trajectory copies them, then
+ *                   T times the walk and the draws of v2x_sim_stream -- the uniforms of every step into u_all, the moved
+ *                   positions into xy_all;
+ *   k_traj_terms    one thread per (t, e, element), elements as in v2x_sim_channels: the path loss, the shadowing Gaussian
+ *                   times its standard deviation, and the rb terms 20 log10 |h| of the fast fading, written where step t's
+ *                   fast fading lives (snapshot t + 1, or the resident v2v_ff / v2i_ff for t = T - 1);
+ *   k_traj_scan     one thread per (e, element): the shadowing recursion over t from the resident shadowing, path loss +
+ *                   shadowing into traj_v2i_abs, the fast fading in place over its terms;
+ *   k_traj_observe  one wave per (t, e), entries 1..T: the observation of v2x_sim_observe on step t's fast fading, straight
+ *                   into trajectory entry t.
+ * Every expression is a piece of the serial walk's, cut where that one rounds to a double: the trajectory, the results, the
+ * replay slots and the resident state are the serial call's bit for bit, and the two forms (and v2x_rollout_step /
+ * v2x_sim_advance) mix freely on one state.  Resident arrays written: keys, mtpos, xy, dirs, u (the uniforms of step T - 1),
+ * v2i_shadow, v2v_shadow, v2v_abs, v2i_abs, v2v_ff, v2i_ff, interf_db, state, xe, mask, col, regular, and what the finish
+ * launch leaves (actions, rates, interference) -- those of T calls of v2x_sim_advance.
+ * wide_ws [dev]: the call's own workspace, contents undefined afterwards.  Six arrays back to back, each rounded up to a
+ * multiple of 256 bytes, with n_u = n + n^2 + 2 n rb + 2 n^2 rb the uniforms of a step and n_el = n + n^2 its elements:
+ *   u_all [T][E][n_u], xy_all [T][E][n][2], path loss [T][E][n_el], Gaussian term [T][E][n_el] (doubles), and what the
+ *   observations of entries 1..T-1 leave beside the trajectory: state [T-1][E][n][3 rb + 1], interf_db [T-1][E][n][rb]:
+ *   A(8 T E n_u) + A(16 T E n) + A(8 T E n_el) + A(8 T E n_el) + A(8 (T-1) E n (3 rb + 1)) + A(8 (T-1) E n rb),
+ *   A(x) = ceil(x / 256) * 256.  v2x_traj_wide_workspace_bytes: that sum, or a negative V2X_E* code on sizes outside the limits
+ *   of v2x_rollout_steps_workspace_bytes.
+ * Checks: every check of v2x_rollout_steps / v2x_eval_steps, then wide_ws non-NULL and wide_ws_bytes >= the need, all before
+ * the first launch (V2X_EINVAL, text in v2x_last_error(NULL)).                                                               */
+int64_t v2x_traj_wide_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
+int  v2x_rollout_steps_wide(const v2x_rollout_traj* r, void* wide_ws, int64_t wide_ws_bytes, void* stream);
+int  v2x_eval_steps_wide(const v2x_eval* r, void* wide_ws, int64_t wide_ws_bytes, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

@@ -276,7 +276,7 @@ ROLLOUT_SETTINGS = {"host_lookahead": (dict(backend="host"), "host"),
                     "device_streams_device_rollout": (dict(backend="device", streams="device"), "device")}
 
 
-def _rollout_agent(E, kw, rollout, batch=4096):
+def _rollout_agent(E, kw, rollout, batch=4096, walk="serial"):
     import random
     from v2xgnn.rl import Agent, RL_Config
     from v2xgnn.rl.train import start_env_batched
@@ -286,7 +286,8 @@ def _rollout_agent(E, kw, rollout, batch=4096):
     cfg.set_train_value(64, 0.5, batch, 1, 0.1)
     cfg.Num_Episodes, cfg.Num_Train_Steps = 1, 20
     env = start_env_batched(LINKS, E, 1001, **kw)
-    return Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True, rollout_backend=rollout)
+    return Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True, rollout_backend=rollout,
+                 trajectory_walk=walk)
 
 
 def rollout_legs(E, reps, warmup):
@@ -377,8 +378,36 @@ def loop_in_process_rollout(reps):
 
 
 TRAJECTORY_SETTINGS = {"trajectory": (dict(backend="device", streams="device"), "trajectory"),
+                       "trajectory_wide": (dict(backend="device", streams="device"), "trajectory", 4096, "wide"),
                        "device": (dict(backend="device", streams="device"), "device"),
                        "host_native_rollout": (dict(backend="host"), "host")}            # (E = 1 only: the single-call v2xsim_rollout)
+
+
+WALK_KERNELS = {"serial": ("k_sim_trajectory",), "wide": ("k_traj_stream", "k_traj_terms", "k_traj_scan", "k_traj_observe")}
+
+
+def kernel_times(call, names, reps):
+    """median duration in ms of every kernel whose name holds one of `names`, over `reps` calls of call() under torch's
+    profiler (the device's own kernel timestamps: a launch inside a library call cannot be bracketed by events from outside)
+    -> {name: ms}, or {"error": text} when the profiler gives no kernel records"""
+    import torch
+    from torch.profiler import ProfilerActivity, profile
+    try:
+        torch.cuda.synchronize()
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for _ in range(reps):
+                call()
+            torch.cuda.synchronize()
+        seen = {k: [] for k in names}
+        for ev in prof.events():
+            for k in names:
+                if k in ev.name:
+                    seen[k].append(float(getattr(ev, "device_time", None) or getattr(ev, "cuda_time", 0.0)))
+        if not all(seen.values()):
+            return {"error": "no kernel records for %s" % [k for k, v in seen.items() if not v]}
+        return {k: round(float(np.median(v)) * 1e-3, 4) for k, v in seen.items()}
+    except Exception as exc:                                           # written down, not hidden
+        return {"error": "%s: %s" % (type(exc).__name__, exc)}
 
 
 def trajectory_legs(E, reps, warmup, loop_reps):
@@ -410,26 +439,35 @@ def trajectory_legs(E, reps, warmup, loop_reps):
                 after = ag.env.device_channels.traffic
                 for key in ("bytes_up", "bytes_down"):
                     row["%s_%s_per_rollout" % (name, key)] = (after[key] - traffic[name][key]) // reps
-        # the call alone between HIP events (policy already on the device), and what the host spends enqueueing it
+        # the call alone between HIP events (policy already on the device), and what the host spends enqueueing it: the serial
+        # and the wide form on the same agent's state, taken in turn; then the trajectory's own kernels, one by one
         ag = agents["trajectory"]
         dc, rep, T = ag.env.device_channels, ag.device_replay, -(-50 // E)
         engine, rp = ag.brain.model.engine, rep.row_ptr(T * E)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         head = rep.reserve(T * E)
         r = dc.rollout_steps_struct(T, rep.storage(), head, rep.capacity, 1.0, 0.1, engine=engine, row_ptr=rp)
-        gpu, host = [], []
+        ws = dc._wide_workspace(T)
+        stream = lambda: torch.cuda.current_stream().cuda_stream           # noqa: E731
+        calls = {"serial": lambda: check(dc._lib, dc._lib.v2x_rollout_steps(ctypes.byref(r), stream())),
+                 "wide": lambda: check(dc._lib, dc._lib.v2x_rollout_steps_wide(ctypes.byref(r), ws.data_ptr(), ws.numel(), stream()))}
+        gpu, host = {w: [] for w in calls}, {w: [] for w in calls}
         for k in range(warmup + reps):
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-            ev[0].record()
-            check(dc._lib, dc._lib.v2x_rollout_steps(ctypes.byref(r), torch.cuda.current_stream().cuda_stream))
-            ev[1].record()
-            t1 = time.perf_counter()
-            torch.cuda.synchronize()
-            if k >= warmup:
-                gpu.append(ev[0].elapsed_time(ev[1]) * 1e-3)
-                host.append(t1 - t0)
-        row["call_gpu_ms"], row["call_enqueue_ms"] = _median_ms(gpu), _median_ms(host)
+            for w, call in calls.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                ev[0].record()
+                call()
+                ev[1].record()
+                t1 = time.perf_counter()
+                torch.cuda.synchronize()
+                if k >= warmup:
+                    gpu[w].append(ev[0].elapsed_time(ev[1]) * 1e-3)
+                    host[w].append(t1 - t0)
+        row["call_gpu_ms"], row["call_enqueue_ms"] = _median_ms(gpu["serial"]), _median_ms(host["serial"])
+        row["call_wide_gpu_ms"], row["call_wide_enqueue_ms"] = _median_ms(gpu["wide"]), _median_ms(host["wide"])
+        for w, call in calls.items():
+            row["kernels_%s_ms" % w] = kernel_times(call, WALK_KERNELS[w], min(reps, 20))
         # the loop: Agent.train(1, 20), the agents taken in turn
         loop = {k: [] for k in names}
         for ag in agents.values():
@@ -450,11 +488,11 @@ def trajectory_legs(E, reps, warmup, loop_reps):
 
 EVALUATE_CONFIGS = (("no_optimum", 20, False, "host"), ("optimum_bound", 20, True, "bound"), ("optimum_device", 12, True, "device"))
 # name -> (simulator backend, streams, eval_backend)
-EVALUATE_SETTINGS = {"device_eval": ("device", "device", "device"), "host_eval_device_streams": ("device", "device", "host"),
-                     "host_eval_host_simulator": ("host", "host", "host")}
+EVALUATE_SETTINGS = {"device_eval": ("device", "device", "device"), "device_eval_wide": ("device", "device", "device", "wide"),
+                     "host_eval_device_streams": ("device", "device", "host"), "host_eval_host_simulator": ("host", "host", "host")}
 
 
-def _evaluate_agent(links, backend, streams):
+def _evaluate_agent(links, backend, streams, walk="serial"):
     import random
     from v2xgnn.rl import Agent, RL_Config
     from v2xgnn.rl.train import start_env_batched
@@ -463,7 +501,7 @@ def _evaluate_agent(links, backend, streams):
     env = start_env_batched(links, 1, 7, lookahead=False, backend=backend, streams=streams)
     cfg = RL_Config()
     cfg.set_train_value(64, 0.5, 4096, 1, 0.1)
-    return Agent(links, env.n_RB, env.n_Neighbor, 64, env, cfg, seed=7, device_replay=False)
+    return Agent(links, env.n_RB, env.n_Neighbor, 64, env, cfg, seed=7, device_replay=False, trajectory_walk=walk)
 
 
 def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
@@ -471,7 +509,7 @@ def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
     import torch
     row = {"config": name, "links": links, "rb": RB, "episodes": episodes, "steps": 50, "opt_backend": opt_backend if opt_flag else None,
            "reps": reps, "warmup": warmup}
-    agents = {k: _evaluate_agent(links, v[0], v[1]) for k, v in EVALUATE_SETTINGS.items()}
+    agents = {k: _evaluate_agent(links, v[0], v[1], *v[3:]) for k, v in EVALUATE_SETTINGS.items()}
     walls, traffic = {k: [] for k in agents}, {}
     for k in range(warmup + reps):
         if k == warmup:
@@ -490,6 +528,8 @@ def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
             for key in ("bytes_up", "bytes_down"):
                 row["%s_%s_per_episode" % (n, key)] = (after[key] - traffic[n][key]) // (reps * episodes)
         row["%s_stats" % n] = dict(ag.eval_stats)
+        if n in traffic:
+            row["%s_walk_calls" % n] = dict(ag.env.device_channels.walk_calls)
         ag.brain.close()
     return row
 
@@ -499,6 +539,8 @@ def main_evaluate(args):
     from v2xgnn.rl.batched_env import _usable_cpus
     result = {"device": torch.cuda.get_device_name(0), "usable_cpus": _usable_cpus(), "runs": []}
     for name, links, opt_flag, opt_backend in EVALUATE_CONFIGS:
+        if args.eval_configs and name not in args.eval_configs:
+            continue
         reps, warmup = (max(3, args.loop_reps), 1) if opt_flag else (min(args.reps, 20), min(args.warmup, 3))
         result["runs"].append(evaluate_legs(name, links, opt_flag, opt_backend, args.episodes, reps, warmup))
         print(json.dumps(result["runs"][-1]), flush=True)
@@ -546,6 +588,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--mode", choices=["channels", "streams", "rollout", "trajectory", "evaluate"], default="channels")
     ap.add_argument("--episodes", type=int, default=1, help="--mode evaluate: episodes per timed test_run")
+    ap.add_argument("--eval-configs", nargs="+", default=None, choices=[c[0] for c in EVALUATE_CONFIGS],
+                    help="--mode evaluate: only these configurations (default: all)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--reps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
