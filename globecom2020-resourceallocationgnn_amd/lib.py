@@ -196,6 +196,9 @@ SYMBOLS = [
     ("v2x_traj_wide_workspace_bytes", _L, [_I, _I, _I, _I]),
     ("v2x_rollout_steps_wide", C.c_int, [C.POINTER(RolloutTraj), _P, _L, _P]),
     ("v2x_eval_steps_wide", C.c_int, [C.POINTER(Eval), _P, _L, _P]),
+    ("v2x_traj_split_workspace_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_rollout_steps_split", C.c_int, [C.POINTER(RolloutTraj), _P, _L, _P, _L, _P]),
+    ("v2x_eval_steps_split", C.c_int, [C.POINTER(Eval), _P, _L, _P, _L, _P]),
 ]
 
 

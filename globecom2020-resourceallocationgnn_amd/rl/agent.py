@@ -28,6 +28,7 @@ OPT_BACKENDS = ('host', 'device', 'bound', 'local')
 ROLLOUT_BACKENDS = ('host', 'device', 'trajectory')
 EVAL_BACKENDS = ('host', 'device')
 TRAJECTORY_WALKS = ('serial', 'wide')
+TRAJECTORY_STREAMS = ('chain', 'split')
 
 
 def _check_opt_backend(opt_backend):
@@ -78,7 +79,8 @@ class Memory(object):
 
 class Agent(object):
     def __init__(self, num_d2d, num_ch, num_neighbor, num_d2d_feedback, environment, curr_rl_config, brain=None,
-                 device_replay='auto', rollouts='replicated', rollout_backend='host', trajectory_walk='serial', **brain_kwargs):
+                 device_replay='auto', rollouts='replicated', rollout_backend='host', trajectory_walk='serial', trajectory_streams='chain',
+                 **brain_kwargs):
         """rollout_backend: 'host' (the default: _packed_iteration -- the observation comes down, is scored, the actions go up,
         the transitions go up again) or 'device': a whole rollout iteration is ONE call on the resident state (v2x_rollout_step:
         score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
@@ -94,6 +96,11 @@ class Agent(object):
         step) or 'wide' (v2x_rollout_steps_wide / v2x_eval_steps_wide: only the streams and the shadowing recursion step by
         step, everything else of all T steps at once) -- the same bits (tests/test_gpu_trajectory_wide.py), opt-in because it
         does not win at every size.  'wide' where neither backend can ever run is a ValueError here.
+
+        trajectory_streams: the stream phase of trajectory_walk='wide': 'chain' (the default: one launch draws the MT19937
+        streams of all T steps, refill by refill) or 'split' (v2x_rollout_steps_split / v2x_eval_steps_split: the raw words,
+        the offset walk and the conversion as three launches) -- the same bits (tests/test_gpu_trajectory_split.py).  'split'
+        needs trajectory_walk='wide'; anything else is a ValueError here.
 
         device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
         visiting the host; 'auto' = whenever the brain runs on the gfx950 engine.
@@ -154,6 +161,8 @@ class Agent(object):
         self.rollout_backend = rollout_backend
         self._check_trajectory_walk(trajectory_walk)
         self.trajectory_walk = trajectory_walk
+        self._check_trajectory_streams(trajectory_streams)
+        self.trajectory_streams = trajectory_streams
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
@@ -188,6 +197,13 @@ class Agent(object):
         except ValueError as exc:
             raise ValueError("trajectory_walk=%r needs rollout_backend='trajectory' or an agent that eval_backend='device' "
                              "can run on: rollout_backend is %r, and %s" % (trajectory_walk, self.rollout_backend, exc))
+
+    def _check_trajectory_streams(self, trajectory_streams):
+        if trajectory_streams not in TRAJECTORY_STREAMS:
+            raise ValueError("trajectory_streams must be one of %s, got %r" % (TRAJECTORY_STREAMS, trajectory_streams))
+        if trajectory_streams == 'split' and self.trajectory_walk != 'wide':
+            raise ValueError("trajectory_streams='split' needs trajectory_walk='wide' (it is a form of the wide walk's stream phase): "
+                             "trajectory_walk is %r" % (self.trajectory_walk,))
 
     def _trainer(self):
         return getattr(getattr(self.brain, 'model', None), 'trainer', None)
@@ -486,7 +502,7 @@ class Agent(object):
         else:                                          # one iteration: no leading axis
             call, explore, actions = env.rollout_step, explore[0], drawn[0][0]
         head = rep.reserve(K)
-        walk = dict(walk=self.trajectory_walk) if whole else {}
+        walk = dict(walk=self.trajectory_walk, stream_phase=self.trajectory_streams) if whole else {}
         result = call(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
                       engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None, **walk)
         rep.commit(K, result)
@@ -1154,7 +1170,7 @@ class Agent(object):
         engine = None if explore.all() else self.brain.model.engine
         res = self.env.evaluate_steps(explore.reshape(T, 1), np.asarray(policy_random).reshape(T, 1, n),
                                       np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine,
-                                      walk=self.trajectory_walk)
+                                      walk=self.trajectory_walk, stream_phase=self.trajectory_streams)
         out = {'res': res.resolve()}
         if optimum is not None or rank:
             states = self.env.trajectory_states(T)

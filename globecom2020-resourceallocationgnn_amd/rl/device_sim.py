@@ -44,6 +44,11 @@ rates instead of a reward alone), and the T snapshots it leaves are one stacked 
 
 Both trajectory calls take walk='serial' (the default: one workgroup per simulator walks its T steps) or walk='wide'
 (v2x_rollout_steps_wide / v2x_eval_steps_wide: the steps spread over the chip, the same bits); dc.walk_calls counts them.
+With walk='wide' they also take stream_phase='chain' (the default: one launch draws the streams of all T steps) or
+stream_phase='split' (v2x_rollout_steps_split / v2x_eval_steps_split: raw words, offset walk and conversion in three launches,
+the same bits); dc.stream_phase_calls counts the wide calls by the form that ran.  At one simulator of 20 links and T = 50
+the split form takes the rollout from 1.54 to 0.88 ms (the host library's native rollout: 1.06 ms); at 50 simulators and T = 1
+the forms are level (profiles/trajectory_split_timing.json).
 
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
@@ -111,6 +116,36 @@ def check_walk(who, walk):
     if walk not in WALKS:
         raise ValueError("%s: walk must be one of %s, got %r" % (who, ", ".join(repr(w) for w in WALKS), walk))
     return walk
+
+
+STREAM_PHASES = ('chain', 'split')                       # the stream phase of a wide walk: k_traj_stream, or words / walk / uniforms
+
+
+def check_stream_phase(who, stream_phase, walk='wide'):
+    """ValueError unless stream_phase names a form of the wide walk's stream phase, and 'split' comes with walk='wide'"""
+    if stream_phase not in STREAM_PHASES:
+        raise ValueError("%s: stream_phase must be one of %s, got %r" % (who, ", ".join(repr(w) for w in STREAM_PHASES), stream_phase))
+    if stream_phase == 'split' and walk != 'wide':
+        raise ValueError("%s: stream_phase='split' needs walk='wide' (it is a form of the wide walk's stream phase), got walk=%r"
+                         % (who, walk))
+    return stream_phase
+
+
+def split_stream_blocks(n, rb, T, n_lanes):
+    """NB of include/v2xgnn.h: the blocks of 624 words that bound what T steps of a state consume -- a step draws 2 n_u words
+    and at most one double per pair of a vehicle and a lane of its two tables, the entry position is at most 624"""
+    return 1 + -(-T * (2 * uniforms_per_step(n, rb) + 4 * n * n_lanes) // MT_WORDS)
+
+
+def split_workspace_layout(E, n, rb, T, n_lanes):
+    """-> (the byte offsets of words [E][NB][624] uint32 and off [T + 1][E] int64 in the workspace of the split stream phase, its
+    size): the formula of include/v2xgnn.h (v2x_traj_split_workspace_bytes), both arrays rounded up to 256 bytes"""
+    parts = (4 * E * split_stream_blocks(n, rb, T, n_lanes) * MT_WORDS, 8 * (T + 1) * E)
+    offs, o = [], 0
+    for b in parts:
+        offs.append(o)
+        o += _align(b, 256)
+    return dict(zip(('words', 'off'), offs)), o
 
 
 def eval_result_layout(E, n, rb, T, schemes):
@@ -281,6 +316,7 @@ class DeviceChannels(object):
         self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
         self._roll = {}                                  # _rollout_io(): None (rollout_step) or T (rollout_steps) -> its buffers
         self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
+        self.stream_phase_calls = {p: 0 for p in STREAM_PHASES}     # the wide ones among them, by the form of the stream phase
 
     # ------------------------------------------------------------------ shapes and checks
     def shapes(self):
@@ -726,6 +762,23 @@ class DeviceChannels(object):
             ws = io['wide_workspace'] = self.torch.zeros(max(size, 256), dtype=self.torch.uint8, device=self.device)
         return ws
 
+    def _split_workspace(self, T):
+        """the second workspace of a wide walk whose stream phase is split, for blocks of T on the current lane grid: made at the
+        first split call of that T (again when set_grid() changes the number of lanes) and kept in _rollout_io(T) under its own
+        key; like the wide workspace it never crosses the bus"""
+        io = self._rollout_io(T)
+        E, n, rb, n_lanes = self.E, self.n, self.rb, self._grid[0].shape[1]
+        ws = io.get('split_workspace')
+        if ws is None or io.get('split_lanes') != n_lanes:
+            _, size = split_workspace_layout(E, n, rb, T, n_lanes)
+            need = self._lib.v2x_traj_split_workspace_bytes(E, n, rb, T, n_lanes)
+            if need != size:
+                raise ValueError("the library sizes the split-stream workspace of E = %d, n = %d, rb = %d, T = %d, n_lanes = %d at %d "
+                                 "bytes, the documented layout at %d" % (E, n, rb, T, n_lanes, need, size))
+            ws = io['split_workspace'] = self.torch.zeros(size, dtype=self.torch.uint8, device=self.device)
+            io['split_lanes'] = n_lanes
+        return ws
+
     def rollout_buffers(self):
         """the device buffers of rollout_step(): policy_dev (random_actions [E, n] int32 | explore [E] bytes), result_dev (reward [E]
         float64 | regular [2, E] bytes), q [E n, rb] float32"""
@@ -810,9 +863,10 @@ class DeviceChannels(object):
         return RolloutResult(free, ev, pinned, self.E, T)
 
     def _rollout(self, who, T, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power,
-                 walk='serial'):
+                 walk='serial', stream_phase='chain'):
         """rollout_step() (T None) / rollout_steps(): check, upload the policy, the one library call, start the download"""
         check_walk(who, walk)
+        check_stream_phase(who, stream_phase, walk)
         ex, ra = self._check_rollout(who, T, explore, random_actions, storage, head, capacity)
         if engine is not None and row_ptr is None:
             raise ValueError("%s: scoring needs the CSR row pointer of the %s batch" % (who, "resident" if T is None else "trajectory's"))
@@ -826,15 +880,22 @@ class DeviceChannels(object):
         if T is None:
             check(self._lib, self._lib.v2x_rollout_step(C.byref(r), self._stream()))
         else:
-            self._trajectory_call(self._lib.v2x_rollout_steps, self._lib.v2x_rollout_steps_wide, r, T, walk)
+            self._trajectory_call(self._lib.v2x_rollout_steps, self._lib.v2x_rollout_steps_wide, self._lib.v2x_rollout_steps_split, r,
+                                  T, walk, stream_phase)
         self._obs_ready = True
         return self._download_result(io, T)
 
-    def _trajectory_call(self, serial, wide, r, T, walk):
-        """the library call of a trajectory struct r in the form `walk` names, counted in walk_calls"""
+    def _trajectory_call(self, serial, wide, split, r, T, walk, stream_phase):
+        """the library call of a trajectory struct r in the form `walk` and `stream_phase` name, counted in walk_calls (a split
+        call is a wide one there) and, the wide ones, in stream_phase_calls"""
         if walk == 'wide':
             ws = self._wide_workspace(T)
-            check(self._lib, wide(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+            if stream_phase == 'split':
+                ss = self._split_workspace(T)
+                check(self._lib, split(C.byref(r), ws.data_ptr(), ws.numel(), ss.data_ptr(), ss.numel(), self._stream()))
+            else:
+                check(self._lib, wide(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+            self.stream_phase_calls[stream_phase] += 1
         else:
             check(self._lib, serial(C.byref(r), self._stream()))
         self.walk_calls[walk] += 1
@@ -852,7 +913,7 @@ class DeviceChannels(object):
                              row_ptr, power)
 
     def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                      power=None, walk='serial'):
+                      power=None, walk='serial', stream_phase='chain'):
         """T DQN rollout iterations in ONE call (v2x_rollout_steps) on the resident state: every simulator walks its T steps in
         one kernel, one forward scores all T E observations (engine: a GnnEngine, with row_ptr the constant CSR pointer of
         T E n rows; None: nobody is greedy anywhere in the block, no forward), and one kernel picks (explore [T, E] flags,
@@ -860,9 +921,12 @@ class DeviceChannels(object):
         (head + t E + e) % capacity of `storage`.  Bit for bit T calls of rollout_step().  -> a RolloutResult whose download
         (one) is in flight.  Afterwards as after the last rollout_step: fetch_rates(), fetch_observation().
         walk: 'serial' (one workgroup per simulator walks its T steps) or 'wide' (v2x_rollout_steps_wide: the steps spread over
-        the chip, four launches, the same bits); walk_calls counts which ran."""
+        the chip, four launches, the same bits); walk_calls counts which ran.
+        stream_phase (walk='wide' only): 'chain' (the first of the four launches draws the streams of all T steps) or 'split'
+        (v2x_rollout_steps_split: raw words, offset walk and conversion as three launches, the same bits); stream_phase_calls
+        counts the wide calls by it."""
         return self._rollout("rollout_steps", _block_length(explore), explore, random_actions, storage, head, capacity, v2v_weight,
-                             v2i_weight, engine, row_ptr, power, walk)
+                             v2i_weight, engine, row_ptr, power, walk, stream_phase)
 
     # ------------------------------------------------------------------ an evaluation episode on the resident state
     def eval_steps_policy_bytes(self, T, baseline=True):
@@ -939,16 +1003,17 @@ class DeviceChannels(object):
         return r
 
     def eval_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None,
-                   walk='serial'):
+                   walk='serial', stream_phase='chain'):
         """The T steps of an evaluation episode in ONE call (v2x_eval_steps) on the resident state: every simulator walks its T
         steps in one kernel, one forward scores all T E observations (engine: a GnnEngine; row_ptr: the constant CSR pointer of
         T E n rows, made here when None; engine None: nobody is greedy, no forward), and one kernel pays two schemes per state --
         the policy (explore [T, E] flags, policy_random [T, E, n]) and the baseline (baseline_actions [T, E, n]; None: no
         baseline scheme) -- on the step's snapshot.  No replay memory is touched.  One upload (the draws), one download (the
         result block) -> an EvalResult whose download is in flight.  Afterwards the resident state is what T advance() calls
-        under the policy's actions leave, and trajectory_states(T) holds the T snapshots.  walk: as for rollout_steps()
-        (v2x_eval_steps_wide)."""
+        under the policy's actions leave, and trajectory_states(T) holds the T snapshots.  walk, stream_phase: as for
+        rollout_steps() (v2x_eval_steps_wide, v2x_eval_steps_split)."""
         check_walk("eval_steps", walk)
+        check_stream_phase("eval_steps", stream_phase, walk)
         T, ex, ra, ba = self.check_eval_steps(explore, policy_random, baseline_actions)
         self._init_device()
         if not self._obs_ready:
@@ -971,7 +1036,8 @@ class DeviceChannels(object):
         io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
         r = self.eval_steps_struct(T, v2v_weight, v2i_weight, engine, row_ptr, power, ba is not None)
         self._keep_actions = self._t['actions']
-        self._trajectory_call(self._lib.v2x_eval_steps, self._lib.v2x_eval_steps_wide, r, T, walk)
+        self._trajectory_call(self._lib.v2x_eval_steps, self._lib.v2x_eval_steps_wide, self._lib.v2x_eval_steps_split, r, T, walk,
+                              stream_phase)
         self._obs_ready = True
         S = 2 if ba is not None else 1
         size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
@@ -1314,18 +1380,19 @@ class DeviceBatchedEnviron(BatchedEnviron):
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
 
     def _resident_rollout(self, steps, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr,
-                          walk='serial'):
+                          walk='serial', stream_phase='chain'):
         """rollout_step() / rollout_steps() (steps): DeviceChannels' call of that name with act()'s bookkeeping around it -- the
         device holds the newer streams and channel arrays, the observable interference is on the device, no host copy of the
         observation exists; V2I_Interference / V2V_Interference download the rates when they are next read"""
         def check_args(dc):
             check_walk('rollout_steps' if steps else 'rollout_step', walk)
+            check_stream_phase('rollout_steps' if steps else 'rollout_step', stream_phase, walk)
             (dc.check_rollout_steps if steps else dc.check_rollout)(explore, random_actions, storage, head, capacity)
 
         def call(dc):
             if steps:
                 return dc.rollout_steps(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
-                                        row_ptr=row_ptr, walk=walk)
+                                        row_ptr=row_ptr, walk=walk, stream_phase=stream_phase)
             return dc.rollout_step(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=engine,
                                    row_ptr=row_ptr)
 
@@ -1364,27 +1431,29 @@ class DeviceBatchedEnviron(BatchedEnviron):
                                       row_ptr)
 
     def rollout_steps(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                      walk='serial'):
+                      walk='serial', stream_phase='chain'):
         """T iterations of rollout_step() in one call (explore [T, E], random_actions [T, E, n]; DeviceChannels.rollout_steps):
-        the same bookkeeping, once.  walk: 'serial' or 'wide', the form of the trajectory (the same bits).  -> the RolloutResult
-        of the block, its download in flight."""
+        the same bookkeeping, once.  walk: 'serial' or 'wide', the form of the trajectory; stream_phase: 'chain' or 'split', the
+        form of a wide walk's stream phase (the same bits all).  -> the RolloutResult of the block, its download in flight."""
         return self._resident_rollout(True, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
-                                      row_ptr, walk)
+                                      row_ptr, walk, stream_phase)
 
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                       walk='serial'):
+                       walk='serial', stream_phase='chain'):
         """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
         bookkeeping of rollout_steps() around it: explore [T, E], policy_random [T, E, n], baseline_actions [T, E, n] or None.
-        walk: 'serial' or 'wide', the form of the trajectory (the same bits).
+        walk: 'serial' or 'wide', the form of the trajectory; stream_phase: 'chain' or 'split', the form of a wide walk's stream
+        phase (the same bits all).
         -> the EvalResult, its download in flight.  trajectory_states(T) then holds the T snapshots."""
         def check_args(dc):
             check_walk('evaluate_steps', walk)
+            check_stream_phase('evaluate_steps', stream_phase, walk)
             dc.check_eval_steps(explore, policy_random, baseline_actions)
 
         return self._resident_call(
             'evaluate_steps', check_args,
             lambda dc: dc.eval_steps(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr,
-                                     walk=walk))
+                                     walk=walk, stream_phase=stream_phase))
 
     def trajectory_states(self, T):
         """the T snapshots of the last evaluate_steps() / rollout_steps() of block length T as one stacked search problem

@@ -45,7 +45,7 @@ def main(argv=None):
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
     env = evaluation_env(ap, args)
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False,
-                  trajectory_walk=args.trajectory_walk)
+                  trajectory_walk=args.trajectory_walk, trajectory_streams=args.trajectory_streams)
     out = agent.evaluate_training_diff_trials(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials,
                                               model_dir=args.save_dir, num_train_steps=args.train_steps,
                                               opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,

@@ -6,7 +6,8 @@
     python -m v2xgnn.rl.run   --links 4 --episodes 5 --train-steps 20 --batch 512 --save-dir runs/a \\
                               --test-episodes 10 --test-steps 50 --opt [--opt-backend device | bound | local] \\
                               [--opt-rank [--opt-rank-backend bound [--opt-rank-max-nodes N]]] \\
-                              [--sim-backend device --sim-streams device --eval-backend device [--trajectory-walk wide]]
+                              [--sim-backend device --sim-streams device --eval-backend device
+                               [--trajectory-walk wide [--trajectory-streams split]]]
 """
 import argparse
 import json
@@ -36,7 +37,7 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
 
 
 def add_sim_arguments(ap):
-    """--sim-backend / --sim-streams / --eval-backend / --trajectory-walk of the two evaluation drivers"""
+    """--sim-backend / --sim-streams / --eval-backend / --trajectory-walk / --trajectory-streams of the two evaluation drivers"""
     ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
                     help="where the simulator's channel update, observation and rates run: the single host simulator (the "
                          "default) or ONE batched simulator on the GPU (rl/device_sim.py)")
@@ -48,6 +49,9 @@ def add_sim_arguments(ap):
     ap.add_argument("--trajectory-walk", choices=["serial", "wide"], default="serial",
                     help="with --eval-backend device: how the episode's steps are walked -- 'serial' (the default: one workgroup, "
                          "step after step) or 'wide' (the steps spread over the chip in four launches; the same bits)")
+    ap.add_argument("--trajectory-streams", choices=["chain", "split"], default="chain",
+                    help="with --trajectory-walk wide: the stream phase of the wide walk -- 'chain' (the default: one launch draws "
+                         "the streams of all steps) or 'split' (raw words, offset walk and conversion in three launches; the same bits)")
 
 
 def evaluation_env(ap, args):
@@ -59,6 +63,8 @@ def evaluation_env(ap, args):
         ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
     if args.trajectory_walk != "serial" and args.eval_backend != "device":
         ap.error("--trajectory-walk %s needs --eval-backend device" % args.trajectory_walk)
+    if args.trajectory_streams != "chain" and args.trajectory_walk != "wide":
+        ap.error("--trajectory-streams %s needs --trajectory-walk wide" % args.trajectory_streams)
     if args.sim_backend == "device":
         return start_env_batched(args.links, 1, args.seed, backend="device", streams=args.sim_streams)
     return start_env(args.links)
@@ -141,7 +147,8 @@ def main(argv=None):
     cfg.Num_Episodes, cfg.Num_Train_Steps = args.episodes, args.train_steps
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = evaluation_env(ap, args)
-    agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed, trajectory_walk=args.trajectory_walk)
+    agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed, trajectory_walk=args.trajectory_walk,
+                               trajectory_streams=args.trajectory_streams)
     res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank,
                    eval_backend=args.eval_backend, rank_backend=args.opt_rank_backend, rank_max_nodes=args.opt_rank_max_nodes)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,

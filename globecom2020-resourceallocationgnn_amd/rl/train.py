@@ -111,6 +111,9 @@ def build_parser():
                     help="with --rollout trajectory: how a simulator's steps are walked -- 'serial' (the default: one workgroup "
                          "per simulator, step after step) or 'wide' (the steps spread over the chip in four launches; the same "
                          "bits; DESIGN.md section 6 says at which sizes it wins)")
+    ap.add_argument("--trajectory-streams", choices=["chain", "split"], default="chain",
+                    help="with --trajectory-walk wide: the stream phase of the wide walk -- 'chain' (the default: one launch draws "
+                         "the streams of all steps) or 'split' (raw words, offset walk and conversion in three launches; the same bits)")
     return ap
 
 
@@ -123,6 +126,8 @@ def main(argv=None):
         ap.error("--rollout %s needs --sim-backend device --sim-streams device" % args.rollout)
     if args.trajectory_walk != "serial" and args.rollout != "trajectory":
         ap.error("--trajectory-walk %s needs --rollout trajectory" % args.trajectory_walk)
+    if args.trajectory_streams != "chain" and args.trajectory_walk != "wide":
+        ap.error("--trajectory-streams %s needs --trajectory-walk wide" % args.trajectory_streams)
     if args.sim_backend == "device" and args.envs < 1:
         ap.error("--sim-backend device steps batched simulators: give --envs")
     if args.links < 4 or args.links % 4:
@@ -167,7 +172,8 @@ def main(argv=None):
         agent, (loss, reward_step, reward_ep, q_mean, q_max, _, _) = run_train(
             env, cfg, save_dir=args.save_dir if rank == 0 else None, verbose=rank == 0,
             device=local, seed=args.seed, use_graph=args.use_graph, data_parallel=world > 1 or force_dp,
-            rollouts=args.rollouts, rollout_backend=args.rollout, trajectory_walk=args.trajectory_walk)
+            rollouts=args.rollouts, rollout_backend=args.rollout, trajectory_walk=args.trajectory_walk,
+            trajectory_streams=args.trajectory_streams)
     dt = time.perf_counter() - t0
     if rank == 0:
         n_fit = args.episodes * args.train_steps

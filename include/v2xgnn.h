@@ -688,6 +688,36 @@ int64_t v2x_traj_wide_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t 
 int  v2x_rollout_steps_wide(const v2x_rollout_traj* r, void* wide_ws, int64_t wide_ws_bytes, void* stream);
 int  v2x_eval_steps_wide(const v2x_eval* r, void* wide_ws, int64_t wide_ws_bytes, void* stream);
 
+/* The split stream phase: the wide forms with k_traj_stream, their one serial launch, as three.  Of that launch only the
+ * MT19937 recurrence, mobility (how many words a vehicle draws depends on the values drawn) and the stream position where a
+ * step's uniforms begin are serial; tempering, the conversion to doubles and the stores of u_all are not.  In k_traj_stream's
+ * place, in this order on the one stream (no parallel branches, no allocation, no synchronisation):
+ *   k_traj_words    grid (E), 256 threads: the raw word stream of state e -- block 0 the key array at entry, word i + 624 from
+ *                   words i, i + 1 and i + 397 -- 227 words per barrier through a ring in LDS, every word also stored to the
+ *                   workspace; entry 0 and snapshot 0 as k_traj_stream copies them;
+ *   k_traj_walk     grid (E), one wave, lane v = vehicle v: the walk of v2x_sim_stream for all T steps on those words, the
+ *                   moved positions into xy_all, the offset of every step's uniforms, and keys / mtpos / xy / dirs at the end;
+ *   k_traj_uniforms one thread per (t, e, i < n_u): uniform i of step t into u_all (step T - 1 also into the resident u).
+ * k_traj_terms, k_traj_scan, k_traj_observe, the forward and the finish launch are the wide forms': six launches in
+ * k_sim_trajectory's place.  Integer and exactly rounded arithmetic only: every byte the call leaves is the wide form's, and
+ * the three forms (and v2x_rollout_step / v2x_sim_advance) mix freely on one state.
+ * wide_ws [dev]: the wide forms' workspace, same size and layout.
+ * split_ws [dev]: the call's own second workspace, contents undefined afterwards.  Two arrays back to back, each rounded up
+ * to a multiple of 256 bytes: the words [E][NB][624] (uint32) and the offsets [T + 1][E] (int64), where
+ *   NB = 1 + ceil(T (2 n_u + 4 n n_lanes) / 624)
+ * blocks bound what a state can consume: a step draws 2 n_u words for its uniforms and at most one double (two words) per
+ * pair of a vehicle and a lane of its two tables, and the entry position is at most 624:
+ *   A(4 E NB 624) + A(8 (T + 1) E),  A(x) = ceil(x / 256) * 256.
+ * v2x_traj_split_workspace_bytes: that sum, or a negative V2X_E* code on sizes outside the limits of
+ * v2x_rollout_steps_workspace_bytes or n_lanes outside 1..64.  The call sizes its need by the step's own n_lanes.
+ * Checks: every check of the _wide form, then split_ws non-NULL and split_ws_bytes >= the need, all before the first launch
+ * (V2X_EINVAL, text in v2x_last_error(NULL)).                                                                                */
+int64_t v2x_traj_split_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t n_lanes);
+int  v2x_rollout_steps_split(const v2x_rollout_traj* r, void* wide_ws, int64_t wide_ws_bytes, void* split_ws,
+                             int64_t split_ws_bytes, void* stream);
+int  v2x_eval_steps_split(const v2x_eval* r, void* wide_ws, int64_t wide_ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                          void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */

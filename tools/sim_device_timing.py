@@ -35,15 +35,18 @@ a graph the tool captures itself (the agent issues it eagerly: head moves with e
 
 --mode trajectory measures the whole-rollout call (Agent(rollout_backend='trajectory'): v2x_rollout_steps) with the same recipe at
 E = 1, 5, 10, 25 and 50 simulators: a 50-transition rollout (Agent.generate_d2d_transition(50), epsilon held near 0.4) for
-'trajectory', for 'device' (one v2x_rollout_step per iteration) and, at E = 1, for the host simulator's single-call native
-rollout; the bytes each moves per rollout; the one call alone between HIP events and its host enqueue time; and the DQN loop
-Agent.train(1, 20) per train step for the same backends, all agents of one E alive in one process and taken in turn.
+'trajectory' in its three forms (the serial walk, the wide walk, the wide walk with the split stream phase), for 'device' (one
+v2x_rollout_step per iteration) and, at E = 1, for the host simulator's single-call native rollout; the bytes each moves per
+rollout; the one call alone between HIP events and its host enqueue time, the three forms on one agent's state taken in turn,
+and their kernels one by one (WALK_KERNELS); and the DQN loop Agent.train(1, 20) per train step for the same backends, all
+agents of one E alive in one process and taken in turn.
 
     python tools/sim_device_timing.py --mode trajectory [--out profiles/rollout_trajectory_timing.json]
+    python tools/sim_device_timing.py --mode trajectory --out profiles/trajectory_split_timing.json     (the run with the split form)
 
---mode evaluate measures an evaluation run, Agent.test_run(--episodes episodes, 50 steps), with eval_backend 'host' and 'device' on
-the same kind of device-streams environment (E = 1) and with the host loop on the host BatchedEnviron (E = 1), the three agents
-alive in one process and taken in turn, medians after warm-up: without the optimum at 20 links, with --opt-backend bound at 20
+--mode evaluate measures an evaluation run, Agent.test_run(--episodes episodes, 50 steps), with eval_backend 'host' and 'device'
+(the serial walk, the wide walk, the wide walk with the split stream phase) on the same kind of device-streams environment
+(E = 1) and with the host loop on the host BatchedEnviron (E = 1), the agents alive in one process and taken in turn, medians after warm-up: without the optimum at 20 links, with --opt-backend bound at 20
 links and with --opt-backend device at 12 links (--loop-reps timed runs each for the two with an optimum); and the bytes each
 device environment moves per episode (DeviceChannels.traffic).
 
@@ -276,7 +279,7 @@ ROLLOUT_SETTINGS = {"host_lookahead": (dict(backend="host"), "host"),
                     "device_streams_device_rollout": (dict(backend="device", streams="device"), "device")}
 
 
-def _rollout_agent(E, kw, rollout, batch=4096, walk="serial"):
+def _rollout_agent(E, kw, rollout, batch=4096, walk="serial", streams="chain"):
     import random
     from v2xgnn.rl import Agent, RL_Config
     from v2xgnn.rl.train import start_env_batched
@@ -287,7 +290,7 @@ def _rollout_agent(E, kw, rollout, batch=4096, walk="serial"):
     cfg.Num_Episodes, cfg.Num_Train_Steps = 1, 20
     env = start_env_batched(LINKS, E, 1001, **kw)
     return Agent(env.n_Veh, env.n_RB, env.n_Neighbor, 64, env, cfg, device=0, seed=1001, use_graph=True, rollout_backend=rollout,
-                 trajectory_walk=walk)
+                 trajectory_walk=walk, trajectory_streams=streams)
 
 
 def rollout_legs(E, reps, warmup):
@@ -379,11 +382,13 @@ def loop_in_process_rollout(reps):
 
 TRAJECTORY_SETTINGS = {"trajectory": (dict(backend="device", streams="device"), "trajectory"),
                        "trajectory_wide": (dict(backend="device", streams="device"), "trajectory", 4096, "wide"),
+                       "trajectory_split": (dict(backend="device", streams="device"), "trajectory", 4096, "wide", "split"),
                        "device": (dict(backend="device", streams="device"), "device"),
                        "host_native_rollout": (dict(backend="host"), "host")}            # (E = 1 only: the single-call v2xsim_rollout)
 
 
-WALK_KERNELS = {"serial": ("k_sim_trajectory",), "wide": ("k_traj_stream", "k_traj_terms", "k_traj_scan", "k_traj_observe")}
+WALK_KERNELS = {"serial": ("k_sim_trajectory",), "wide": ("k_traj_stream", "k_traj_terms", "k_traj_scan", "k_traj_observe"),
+                "split": ("k_traj_words", "k_traj_walk", "k_traj_uniforms", "k_traj_terms", "k_traj_scan", "k_traj_observe")}
 
 
 def kernel_times(call, names, reps):
@@ -440,17 +445,20 @@ def trajectory_legs(E, reps, warmup, loop_reps):
                 for key in ("bytes_up", "bytes_down"):
                     row["%s_%s_per_rollout" % (name, key)] = (after[key] - traffic[name][key]) // reps
         # the call alone between HIP events (policy already on the device), and what the host spends enqueueing it: the serial
-        # and the wide form on the same agent's state, taken in turn; then the trajectory's own kernels, one by one
+        # form, the wide form and the wide form with the split stream phase on the same agent's state, taken in turn; then the
+        # trajectory's own kernels, one by one
         ag = agents["trajectory"]
         dc, rep, T = ag.env.device_channels, ag.device_replay, -(-50 // E)
         engine, rp = ag.brain.model.engine, rep.row_ptr(T * E)
         ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
         head = rep.reserve(T * E)
         r = dc.rollout_steps_struct(T, rep.storage(), head, rep.capacity, 1.0, 0.1, engine=engine, row_ptr=rp)
-        ws = dc._wide_workspace(T)
+        ws, ss = dc._wide_workspace(T), dc._split_workspace(T)
         stream = lambda: torch.cuda.current_stream().cuda_stream           # noqa: E731
         calls = {"serial": lambda: check(dc._lib, dc._lib.v2x_rollout_steps(ctypes.byref(r), stream())),
-                 "wide": lambda: check(dc._lib, dc._lib.v2x_rollout_steps_wide(ctypes.byref(r), ws.data_ptr(), ws.numel(), stream()))}
+                 "wide": lambda: check(dc._lib, dc._lib.v2x_rollout_steps_wide(ctypes.byref(r), ws.data_ptr(), ws.numel(), stream())),
+                 "split": lambda: check(dc._lib, dc._lib.v2x_rollout_steps_split(ctypes.byref(r), ws.data_ptr(), ws.numel(), ss.data_ptr(),
+                                                                                 ss.numel(), stream()))}
         gpu, host = {w: [] for w in calls}, {w: [] for w in calls}
         for k in range(warmup + reps):
             for w, call in calls.items():
@@ -466,6 +474,7 @@ def trajectory_legs(E, reps, warmup, loop_reps):
                     host[w].append(t1 - t0)
         row["call_gpu_ms"], row["call_enqueue_ms"] = _median_ms(gpu["serial"]), _median_ms(host["serial"])
         row["call_wide_gpu_ms"], row["call_wide_enqueue_ms"] = _median_ms(gpu["wide"]), _median_ms(host["wide"])
+        row["call_split_gpu_ms"], row["call_split_enqueue_ms"] = _median_ms(gpu["split"]), _median_ms(host["split"])
         for w, call in calls.items():
             row["kernels_%s_ms" % w] = kernel_times(call, WALK_KERNELS[w], min(reps, 20))
         # the loop: Agent.train(1, 20), the agents taken in turn
@@ -489,10 +498,11 @@ def trajectory_legs(E, reps, warmup, loop_reps):
 EVALUATE_CONFIGS = (("no_optimum", 20, False, "host"), ("optimum_bound", 20, True, "bound"), ("optimum_device", 12, True, "device"))
 # name -> (simulator backend, streams, eval_backend)
 EVALUATE_SETTINGS = {"device_eval": ("device", "device", "device"), "device_eval_wide": ("device", "device", "device", "wide"),
+                     "device_eval_split": ("device", "device", "device", "wide", "split"),
                      "host_eval_device_streams": ("device", "device", "host"), "host_eval_host_simulator": ("host", "host", "host")}
 
 
-def _evaluate_agent(links, backend, streams, walk="serial"):
+def _evaluate_agent(links, backend, streams, walk="serial", stream_phase="chain"):
     import random
     from v2xgnn.rl import Agent, RL_Config
     from v2xgnn.rl.train import start_env_batched
@@ -501,7 +511,8 @@ def _evaluate_agent(links, backend, streams, walk="serial"):
     env = start_env_batched(links, 1, 7, lookahead=False, backend=backend, streams=streams)
     cfg = RL_Config()
     cfg.set_train_value(64, 0.5, 4096, 1, 0.1)
-    return Agent(links, env.n_RB, env.n_Neighbor, 64, env, cfg, seed=7, device_replay=False, trajectory_walk=walk)
+    return Agent(links, env.n_RB, env.n_Neighbor, 64, env, cfg, seed=7, device_replay=False, trajectory_walk=walk,
+                 trajectory_streams=stream_phase)
 
 
 def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
@@ -530,6 +541,7 @@ def evaluate_legs(name, links, opt_flag, opt_backend, episodes, reps, warmup):
         row["%s_stats" % n] = dict(ag.eval_stats)
         if n in traffic:
             row["%s_walk_calls" % n] = dict(ag.env.device_channels.walk_calls)
+            row["%s_stream_phase_calls" % n] = dict(ag.env.device_channels.stream_phase_calls)
         ag.brain.close()
     return row
 
