@@ -271,6 +271,8 @@ int v2x_dqn_step_dp(v2x_model* online, v2x_model* target, const v2x_batch* s, co
                     const v2x_comm* comm, float* y_out, float* loss_out, int loss_on_device, void* stream) {
   v2x_model* m = online;
   if (!m) FAIL(m, V2X_EINVAL, "dqn_step_dp: null argument");
+  if (m->cfg.variable_graphs || (target && target->cfg.variable_graphs))
+    FAIL(m, V2X_EINVAL, "dqn_step_dp: variable_graphs models are not supported (the ragged replay step runs on one GPU: v2x_dqn_step)");
   if (n_graphs_global <= 0)
     FAIL(m, V2X_EINVAL, "dqn_step_dp: n_graphs_global must be the global batch (> 0, got %d)", (int)n_graphs_global);
   CHK(dp_check_comm(m, comm, V2X_DP_ALLREDUCE, "dqn_step_dp"));

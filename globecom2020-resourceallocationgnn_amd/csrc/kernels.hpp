@@ -1743,6 +1743,87 @@ __global__ __launch_bounds__(256) void k_dqn_targets(const float* q, const float
   for (int c = 0; c < C; ++c) y[(int64_t)row * C + c] = c == a ? t : q[(int64_t)row * C + c];
 }
 
+// The target rule on RAGGED batches (variable_graphs models: one reward per graph, graphs of different sizes): a row takes the
+// reward of the graph that graph_off puts it in -- one wave per graph (four graphs per workgroup) walks the graph's rows, so no
+// row searches the offsets.  The arithmetic per row is k_dqn_tq's / k_dqn_targets' own.  Offsets are clamped to [0, n_rows]:
+// a batch that breaks the layout contract computes nonsense, it does not store outside the buffers.
+constexpr int DQN_RAGGED_GRAPHS_PER_WG = 4;
+__global__ __launch_bounds__(256) void k_dqn_tq_ragged(const float* qn, const int32_t* action, const double* reward, double gamma,
+                                                       const int32_t* graph_off, int n_graphs, int n_rows, int C, float* tq) {
+  const int g = blockIdx.x * DQN_RAGGED_GRAPHS_PER_WG + (threadIdx.x >> 6);
+  if (g >= n_graphs) return;
+  const int r0 = max(graph_off[g], 0), r1 = min(graph_off[g + 1], n_rows);
+  const double rw = reward[g];
+  for (int row = r0 + (threadIdx.x & 63); row < r1; row += 64) {
+    const float mx = amax_row(qn + (int64_t)row * C, C);
+    const float t = (float)(rw + gamma * (double)mx);
+    *reinterpret_cast<float4*>(tq + (int64_t)row * 4) = make_float4(t, __int_as_float(action[row]), 0.f, 0.f);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_dqn_targets_ragged(const float* q, const float* qn, const int32_t* action,
+                                                            const double* reward, double gamma, const int32_t* graph_off,
+                                                            int n_graphs, int n_rows, int C, float* y) {
+  const int g = blockIdx.x * DQN_RAGGED_GRAPHS_PER_WG + (threadIdx.x >> 6);
+  if (g >= n_graphs) return;
+  const int r0 = max(graph_off[g], 0), r1 = min(graph_off[g + 1], n_rows);
+  const double rw = reward[g];
+  for (int row = r0 + (threadIdx.x & 63); row < r1; row += 64) {
+    const float mx = amax_row(qn + (int64_t)row * C, C);
+    const float t = (float)(rw + gamma * (double)mx);
+    const int a = action[row];
+    for (int c = 0; c < C; ++c) y[(int64_t)row * C + c] = c == a ? t : q[(int64_t)row * C + c];
+  }
+}
+
+// A replay minibatch of graphs of DIFFERENT sizes in one launch (v2x_replay_gather_mixed): up to MIXED_MAX_POOLS replay
+// storages (rl/replay.py layout, one link count each) contribute count_k graphs by their slot lists; pool 0's graphs come first
+// in its idx order, then pool 1's, ...  Every stored graph is regular (in-degree n - 2), so graph j of pool k starts at row
+// rbase_k + j n_k and at edge ebase_k + j n_k (n_k - 2) -- bases the host sums up -- and the ragged batch's graph_off and
+// row_ptr are closed-form.  One wave per graph: 64-byte xe rows as 16-byte copies, the CSR sources graph-local as stored.
+constexpr int MIXED_MAX_POOLS = 8;
+struct MixedPool {
+  const float *xe, *xe_next;             // [cap][n][16]
+  const int32_t *col, *action;           // [cap][n (n - 2)], [cap][n]
+  const double* reward;                  // [cap]
+  const int32_t* idx;                    // [count] slots
+  int n, gbase, rbase, ebase;            // links; first graph / row / edge of the pool in the batch
+};
+struct MixedArgs {
+  MixedPool p[MIXED_MAX_POOLS];
+  float *xe, *xe_next; int32_t* action; double* reward;
+  int32_t *graph_off, *row_ptr, *col_idx;
+  int n_pools, B, R, E;
+};
+__global__ __launch_bounds__(256) void k_replay_gather_mixed(MixedArgs a) {
+  // (the pool is picked at run time: read its entry through the kernarg segment, an indexed copy would live in scratch)
+  typedef const __attribute__((address_space(4))) MixedPool* CP;
+  CP tab = (CP)((const __attribute__((address_space(4))) char*)__builtin_amdgcn_kernarg_segment_ptr() + offsetof(MixedArgs, p));
+  const int g = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + (threadIdx.x >> 6));
+  if (g >= a.B) return;
+  int k = 0;
+  for (int j = 1; j < a.n_pools; ++j)
+    if (g >= tab[j].gbase) k = j;          // gbase ascends; an empty pool shares its base with the next one, which wins
+  const int lane = threadIdx.x & 63;
+  const int n = tab[k].n, j = g - tab[k].gbase, deg = n - 2, ne = n * deg;
+  const int r0 = tab[k].rbase + j * n, e0 = tab[k].ebase + j * ne;
+  const int64_t slot = tab[k].idx[j];
+  const uint4* sx = reinterpret_cast<const uint4*>(tab[k].xe) + slot * n * 4;
+  const uint4* sn = reinterpret_cast<const uint4*>(tab[k].xe_next) + slot * n * 4;
+  uint4* dx = reinterpret_cast<uint4*>(a.xe) + (int64_t)r0 * 4;
+  uint4* dn = reinterpret_cast<uint4*>(a.xe_next) + (int64_t)r0 * 4;
+  for (int i = lane; i < n * 4; i += 64) { dx[i] = sx[i]; dn[i] = sn[i]; }
+  const int32_t* sc = tab[k].col + slot * ne;
+  for (int i = lane; i < ne; i += 64) a.col_idx[e0 + i] = sc[i];
+  const int32_t* sa = tab[k].action + slot * n;
+  for (int i = lane; i < n; i += 64) { a.action[r0 + i] = sa[i]; a.row_ptr[r0 + i] = e0 + i * deg; }
+  if (lane == 0) {
+    a.reward[g] = tab[k].reward[slot];
+    a.graph_off[g] = r0;
+    if (g == a.B - 1) { a.graph_off[a.B] = a.R; a.row_ptr[a.R] = a.E; }
+  }
+}
+
 // Contract check of a device-resident batch (include/v2xgnn.h "Data layout"): every graph has 1..max_nodes rows and at
 // most max_edges edges, row_ptr is monotone, every source id lies inside its graph and the sources of a row are strictly
 // ascending (=> no duplicate edges: the backward pass de-duplicates through bit masks, the forward pass would not).

@@ -2366,9 +2366,14 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   v2x_model* m = online;
   if (!online || !target || !action || !reward) FAIL(m, V2X_EINVAL, "dqn_step: null argument");
   if (online == target) FAIL(m, V2X_EINVAL, "dqn_step: online and target must be different models");
-  if (online->cfg.variable_graphs || target->N != online->N || target->F != online->F || target->L != online->L ||
+  // ragged form: two variable_graphs models on batches of graphs of different sizes (one reward per graph, one action per row)
+  const bool ragged = online->cfg.variable_graphs != 0;
+  if (ragged != (target->cfg.variable_graphs != 0))
+    FAIL(m, V2X_EINVAL, "dqn_step: online and target must both be variable_graphs models or both fixed-size (online %s, target %s)",
+         ragged ? "variable" : "fixed", ragged ? "fixed" : "variable");
+  if (target->N != online->N || target->F != online->F || target->L != online->L ||
       target->S != online->S || target->cfg.device != online->cfg.device)
-    FAIL(m, V2X_EINVAL, "dqn_step: fixed-size graphs and two models of the same shape on the same device are required");
+    FAIL(m, V2X_EINVAL, "dqn_step: two models of the same shape on the same device are required");
   if (!s || !s_next || !s->on_device || !s_next->on_device) FAIL(m, V2X_EINVAL, "dqn_step takes device-resident batches");
   hipStream_t st = (hipStream_t)stream;
   HIPCHK(m, hipSetDevice(online->cfg.device));
@@ -2376,7 +2381,11 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   CHK(resolve_batch(online, s, &ds, st));
   if (int rc = resolve_batch(target, s_next, &dn, st)) { online->err = target->err; return rc; }
   if (dn.R != ds.R) FAIL(m, V2X_EINVAL, "dqn_step: s and s' have different sizes");
-  if (n_graphs_global <= 0) n_graphs_global = ds.B;
+  // a transition's s and s' are the same links: ONE offset array (the graph's key has a slot for one, and bakes it in)
+  if (ragged && dn.goff != ds.goff)
+    FAIL(m, V2X_EINVAL, "dqn_step: s_next->graph_off must be the same device pointer as s->graph_off (s and s' of a transition are the same links)");
+  if (ragged && dn.B != ds.B) FAIL(m, V2X_EINVAL, "dqn_step: s and s' have different numbers of graphs (%d, %d)", ds.B, dn.B);
+  if (n_graphs_global <= 0) n_graphs_global = ragged ? ds.R : ds.B;          // a variable_graphs model counts node rows
   const BatchPlan po = plan_batch(online, ds), pt = plan_batch(target, dn);
   CHK(presize(online, ds, po));
   if (int rc = presize(target, dn, pt)) { online->err = target->err; return rc; }
@@ -2396,6 +2405,7 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
   // network, and the target kernel's pass over q, are gone (38 us of a 520-us step at 20 links, batch 4096).
   // Knobs::dqn_fused_targets = 0: the three-launch form (forward, k_dqn_targets, training launch on y).
   const bool fuse_targets = online->knobs.dqn_fused_targets && po.mlp_wg && online->C == 4;
+  const dim3 ragged_grid((ds.B + DQN_RAGGED_GRAPHS_PER_WG - 1) / DQN_RAGGED_GRAPHS_PER_WG);      // ragged: one wave per graph
   CHK(run_maybe_graph(online, st, key, [&]() -> int {
     target->capturing = online->capturing;
     int rc = run_forward(target, st, dn, pt, true);
@@ -2403,13 +2413,20 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
     if (rc) { online->err = target->err; return rc; }
     if (!fuse_targets) {
       CHK(run_forward(online, st, ds, po, true));
-      hipLaunchKernelGGL(k_dqn_targets, dim3((ds.R + 255) / 256), dim3(256), 0, st, online->q, target->q, action, reward, gamma,
-                         ds.R, online->N, online->C, y);
+      if (ragged)
+        hipLaunchKernelGGL(k_dqn_targets_ragged, ragged_grid, dim3(256), 0, st, online->q, target->q, action, reward, gamma, ds.goff,
+                           ds.B, ds.R, online->C, y);
+      else
+        hipLaunchKernelGGL(k_dqn_targets, dim3((ds.R + 255) / 256), dim3(256), 0, st, online->q, target->q, action, reward, gamma,
+                           ds.R, online->N, online->C, y);
       return run_backward(online, st, ds, po, BwdCall{}, y, n_graphs_global);
     }
     CHK(run_forward(online, st, ds, po, false));                           // graph layers only
     float* tq = online->dq;                                                // (a workspace this path does not use otherwise: [R][4])
-    hipLaunchKernelGGL(k_dqn_tq, dim3((ds.R + 255) / 256), dim3(256), 0, st, target->q, action, reward, gamma, ds.R, online->N, online->C, tq);
+    if (ragged)
+      hipLaunchKernelGGL(k_dqn_tq_ragged, ragged_grid, dim3(256), 0, st, target->q, action, reward, gamma, ds.goff, ds.B, ds.R, online->C, tq);
+    else
+      hipLaunchKernelGGL(k_dqn_tq, dim3((ds.R + 255) / 256), dim3(256), 0, st, target->q, action, reward, gamma, ds.R, online->N, online->C, tq);
     BwdCall c;
     c.tq = tq; c.y_out = y;
     return run_backward(online, st, ds, po, c, y, n_graphs_global);
@@ -2645,6 +2662,57 @@ int v2x_dqn_targets(const float* q, const float* q_next, const int32_t* action, 
                      reward, gamma, n_rows, n_nodes, n_channels, y_out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) FAIL(nullm, V2X_EHIP, "dqn_targets launch failed: %s", hipGetErrorString(e));
+  return V2X_OK;
+}
+
+int v2x_dqn_targets_ragged(const float* q, const float* q_next, const int32_t* action, const double* reward, double gamma,
+                           const int32_t* graph_off, int32_t n_graphs, int32_t n_rows, int32_t n_channels, float* y_out, void* stream) {
+  v2x_model* nullm = nullptr;
+  if (!q || !q_next || !action || !reward || !graph_off || !y_out || n_graphs <= 0 || n_rows <= 0 || n_channels <= 0)
+    FAIL(nullm, V2X_EINVAL, "dqn_targets_ragged: bad argument");
+  hipLaunchKernelGGL(k_dqn_targets_ragged, dim3((n_graphs + DQN_RAGGED_GRAPHS_PER_WG - 1) / DQN_RAGGED_GRAPHS_PER_WG), dim3(256), 0,
+                     (hipStream_t)stream, q, q_next, action, reward, gamma, graph_off, n_graphs, n_rows, n_channels, y_out);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) FAIL(nullm, V2X_EHIP, "dqn_targets_ragged launch failed: %s", hipGetErrorString(e));
+  return V2X_OK;
+}
+
+int v2x_replay_gather_mixed(int32_t n_pools, const v2x_replay_pool* pools, const v2x_mixed_batch* out, void* stream) {
+  v2x_model* nullm = nullptr;
+  if (n_pools < 1 || n_pools > MIXED_MAX_POOLS || !pools || !out)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: 1..%d pools, non-null pool table and output struct", MIXED_MAX_POOLS);
+  if (!out->xe || !out->xe_next || !out->action || !out->reward || !out->graph_off || !out->row_ptr || !out->col_idx)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: a null output pointer");
+  if (((uintptr_t)out->xe & 15) || ((uintptr_t)out->xe_next & 15))
+    FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: out->xe / out->xe_next must be 16-byte aligned");
+  MixedArgs a;
+  memset(&a, 0, sizeof(a));
+  int64_t B = 0, R = 0, E = 0;
+  for (int k = 0; k < n_pools; ++k) {
+    const v2x_replay_pool& p = pools[k];
+    if (p.n_nodes < 3 || p.n_nodes > 31) FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: pool %d: n_nodes %d outside 3..31", k, p.n_nodes);
+    if (p.count < 0) FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: pool %d: negative count %d", k, p.count);
+    if (p.count > 0 && (!p.xe || !p.xe_next || !p.col || !p.action || !p.reward || !p.idx))
+      FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: pool %d contributes %d graphs but has a null pointer", k, p.count);
+    if (p.count > 0 && (((uintptr_t)p.xe & 15) || ((uintptr_t)p.xe_next & 15)))
+      FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: pool %d: xe / xe_next must be 16-byte aligned", k);
+    if (R > INT32_MAX || E > INT32_MAX) break;           // (reported below; the bases are ints)
+    MixedPool& q = a.p[k];
+    q.xe = p.xe; q.xe_next = p.xe_next; q.col = p.col; q.action = p.action; q.reward = p.reward; q.idx = p.idx;
+    q.n = p.n_nodes; q.gbase = (int)B; q.rbase = (int)R; q.ebase = (int)E;
+    B += p.count;
+    R += (int64_t)p.count * p.n_nodes;
+    E += (int64_t)p.count * p.n_nodes * (p.n_nodes - 2);
+  }
+  if (R >= INT32_MAX || E >= INT32_MAX)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: the batch's rows or edges do not fit int32");
+  if (B == 0) FAIL(nullm, V2X_EINVAL, "replay_gather_mixed: the pools' counts sum to 0");
+  a.xe = out->xe; a.xe_next = out->xe_next; a.action = out->action; a.reward = out->reward;
+  a.graph_off = out->graph_off; a.row_ptr = out->row_ptr; a.col_idx = out->col_idx;
+  a.n_pools = n_pools; a.B = (int)B; a.R = (int)R; a.E = (int)E;
+  hipLaunchKernelGGL(k_replay_gather_mixed, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) FAIL(nullm, V2X_EHIP, "replay_gather_mixed launch failed: %s", hipGetErrorString(e));
   return V2X_OK;
 }
 

@@ -280,7 +280,11 @@ class GnnEngine(object):
 
     def dqn_step(self, target, batch, batch_next, action, reward, gamma, y_out=None, n_global=None, want_loss=True):
         """One replay step on device-resident data (v2x_dqn_step): target forward on s', online forward on s, target
-        rule, backward + Adam on this (online) engine.  action [B, N] int32, reward [B] float64 (device tensors)."""
+        rule, backward + Adam on this (online) engine.  action [B, N] int32, reward [B] float64 (device tensors).
+        Ragged form -- this engine and `target` both variable_graphs models: the batches carry graph_off and share ONE
+        graph_off tensor (s and s' of a transition are the same links); action [R] int32, one per node row; reward [B]
+        float64, one per graph (a row takes the reward of its graph); the returned loss is [1], the Huber mean over
+        rows x C; n_global counts node rows (default: the batch's R); y_out [R, C]."""
         torch = _torch()
         if not isinstance(batch, DeviceBatch) or not isinstance(batch_next, DeviceBatch):
             raise ValueError("dqn_step takes device-resident batches")

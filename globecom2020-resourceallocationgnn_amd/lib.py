@@ -101,6 +101,19 @@ class Eval(C.Structure):
         [(k, C.c_void_p) for k in TRAJ_WORKSPACES + EVAL_RESULTS]
 
 
+class ReplayPool(C.Structure):
+    """v2x_replay_pool of include/v2xgnn.h"""
+    _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
+        [(k, C.c_void_p) for k in ("xe", "xe_next", "col", "action", "reward", "idx")]
+
+
+class MixedBatch(C.Structure):
+    """v2x_mixed_batch of include/v2xgnn.h"""
+    _fields_ = [(k, C.c_void_p) for k in ("xe", "xe_next", "action", "reward", "graph_off", "row_ptr", "col_idx")]
+
+
+MIXED_MAX_POOLS = 8
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -147,6 +160,8 @@ SYMBOLS = [
     ("v2x_gather_rows_multi", C.c_int, [_I, _P, _P, _P, _P, _L, _P]),
     ("v2x_q_stats", C.c_int, [_P, _I, _I, _I, _P, _P]),
     ("v2x_dqn_targets", C.c_int, [_P, _P, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    ("v2x_dqn_targets_ragged", C.c_int, [_P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _P, _P]),
+    ("v2x_replay_gather_mixed", C.c_int, [_I, C.POINTER(ReplayPool), C.POINTER(MixedBatch), _P]),
     ("v2x_dqn_step", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_int32, _P, _P, C.c_int, _P]),
     ("v2x_comm_rccl_unique_id", C.c_int, [_P]),
     ("v2x_comm_rccl_create", C.c_int, [_P, _I, _I, _I, C.POINTER(Comm)]),

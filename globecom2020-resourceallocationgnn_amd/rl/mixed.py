@@ -1,0 +1,324 @@
+"""Mixed-size DQN: ONE shared-weight Q-network trained on scenarios with different numbers of V2V links at once.
+
+A shared-weight GNN does not care how many links a graph has (GnnSpec(share_weights=True, variable_graphs=True)); the engine's
+ragged path scores and fits batches whose graphs differ in size.  This module is the DQN glue around it:
+
+  MixedReplay   one unmodified DeviceReplay per link count; a minibatch that draws from several of them is assembled into one
+                ragged batch by ONE launch (v2x_replay_gather_mixed): xe / xe' rows, actions, rewards, graph_off, row_ptr and
+                the graph-local CSR sources, pool after pool in ascending size.
+  MixedAgent    one BatchedEnviron per link count; a rollout iteration steps every simulator of every environment once, all
+                observations scored by ONE forward; replay() draws B E_k / sum E graphs from pool k and runs one
+                v2x_dqn_step in its ragged form (one reward per graph, one action per node row, a single Huber mean).
+
+Only regular graphs (in-degree n - 2 everywhere) are stored: a transition whose graph has a link that is its own receiver (two
+vehicles on one spot, rare) is counted in MixedReplay.dropped_irregular and left out -- the assembly is closed-form because
+every stored graph of a pool has the same shape.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import lib as _lib
+from ..engine import DeviceBatch, GnnEngine, current_stream_ptr
+from ..packing import PackedBatch
+from ..spec import GnnSpec
+from .agent import Memory, MEMORY_CAPACITY, UPDATE_TARGET_FREQUENCY, MAX_EPSILON, MIN_EPSILON
+from .replay import DeviceReplay
+
+MIN_LINKS, MAX_LINKS = 3, DeviceReplay.MAX_LINKS
+
+
+def _check_sizes(sizes, what):
+    sizes = [int(n) for n in sizes]
+    if not sizes or len(sizes) > _lib.MIXED_MAX_POOLS:
+        raise ValueError("%s: 1..%d link counts, got %d" % (what, _lib.MIXED_MAX_POOLS, len(sizes)))
+    if len(set(sizes)) != len(sizes):
+        raise ValueError("%s: the link counts must be distinct, got %s" % (what, sizes))
+    for n in sizes:
+        if not MIN_LINKS <= n <= MAX_LINKS:
+            raise ValueError("%s: %d links -- a pool holds %d..%d links" % (what, n, MIN_LINKS, MAX_LINKS))
+    return sorted(sizes)
+
+
+def mixed_quotas(batch, weights):
+    """`batch` graphs split in proportion to `weights` (simulators per size) by largest remainder: floor(B w_k / sum w) each,
+    the graphs left over one by one to the largest fractional parts (ties: the earlier entry).  A zero quota is allowed."""
+    w = [int(v) for v in weights]
+    batch = int(batch)
+    if batch < 0 or not w or min(w) < 0 or sum(w) == 0:
+        raise ValueError("mixed_quotas: a non-negative batch and non-negative weights that do not all vanish")
+    total = sum(w)
+    quota = [batch * v // total for v in w]
+    by_remainder = sorted(range(len(w)), key=lambda k: (-(batch * w[k] % total), k))
+    for k in by_remainder[:batch - sum(quota)]:
+        quota[k] += 1
+    return quota
+
+
+class MixedReplay(object):
+    def __init__(self, capacity, sizes, device=0):
+        """capacity: transitions PER link count; sizes: the distinct link counts (3..31, at most 8)"""
+        self.sizes = _check_sizes(sizes, "MixedReplay")
+        self.pools = {n: DeviceReplay(capacity, n, device=device) for n in self.sizes}
+        first = self.pools[self.sizes[0]]
+        self.torch, self.device, self._lib = first.torch, first.device, first._lib
+        self.dropped_irregular = {n: 0 for n in self.sizes}
+        self._out = {}
+
+    def __len__(self):
+        return sum(len(p) for p in self.pools.values())
+
+    def stored(self, n):
+        return len(self.pools[n])
+
+    def add_many_packed(self, n, xe, xe_next, col, mask, regular, action, reward):
+        """DeviceReplay.add_many_packed of the pool of n links for the REGULAR transitions of the block; the others are counted
+        in dropped_irregular[n].  -> transitions stored"""
+        if n not in self.pools:
+            raise ValueError("MixedReplay: no pool of %d links (pools: %s)" % (n, self.sizes))
+        pool = self.pools[n]
+        regular = np.asarray(regular, bool)
+        action = np.asarray(action, np.int32).reshape(len(regular), -1)
+        reward = np.asarray(reward, np.float64).reshape(-1)
+        if not regular.all():
+            self.dropped_irregular[n] += int((~regular).sum())
+            if not regular.any():
+                return 0
+            xe, xe_next, col, mask = (np.ascontiguousarray(a[regular]) for a in (xe, xe_next, col, mask))
+            action, reward, regular = action[regular], reward[regular], regular[regular]
+        pool.add_many_packed(xe, xe_next, col, mask, regular, action, reward)
+        return int(len(regular))
+
+    def _buffers(self, counts):
+        """output tensors and batch descriptors of a minibatch of counts[k] graphs from pool k: cached, so that the pointers
+        are stable and a captured replay step is replayed"""
+        out = self._out.get(counts)
+        if out is None:
+            torch, dev = self.torch, self.device
+            B = sum(counts)
+            R = sum(c * n for c, n in zip(counts, self.sizes))
+            E = sum(c * n * (n - 2) for c, n in zip(counts, self.sizes))
+            live = [n for c, n in zip(counts, self.sizes) if c > 0]
+            t = dict(xe=torch.empty((R, 16), dtype=torch.float32, device=dev), xe_next=torch.empty((R, 16), dtype=torch.float32, device=dev),
+                     action=torch.empty(R, dtype=torch.int32, device=dev), reward=torch.empty(B, dtype=torch.float64, device=dev),
+                     graph_off=torch.empty(B + 1, dtype=torch.int32, device=dev), row_ptr=torch.empty(R + 1, dtype=torch.int32, device=dev),
+                     col_idx=torch.empty(max(E, 1), dtype=torch.int32, device=dev))
+            n_max = max(live)
+            mk = lambda x: DeviceBatch.from_tensors(B, 0, x, t['row_ptr'], t['col_idx'], n_max * (n_max - 2), graph_off=t['graph_off'],
+                                                    max_nodes=n_max)
+            desc = _lib.MixedBatch(**{k: v.data_ptr() for k, v in t.items()})
+            out = self._out[counts] = (t, mk(t['xe']), mk(t['xe_next']), desc)
+        return out
+
+    def sample(self, indices):
+        """indices: {link count: logical indices into that pool's FIFO order (0 = oldest)}; sizes that are left out contribute
+        nothing.  -> (batch of s, batch of s', action [R] int32, reward [B] float64), all in HBM: the graphs of the smallest
+        size first, in the order of their indices.  s and s' share graph_off, row_ptr and col_idx."""
+        for n in indices:
+            if n not in self.pools:
+                raise ValueError("MixedReplay.sample: no pool of %d links (pools: %s)" % (n, self.sizes))
+        idx = [np.asarray(indices.get(n, ()), np.int64).reshape(-1) for n in self.sizes]
+        counts = tuple(len(i) for i in idx)
+        if sum(counts) == 0:
+            raise ValueError("MixedReplay.sample: an empty minibatch")
+        table = (_lib.ReplayPool * len(self.sizes))()
+        used = []
+        for k, n in enumerate(self.sizes):
+            pool = self.pools[n]
+            pool.flush()
+            table[k].n_nodes, table[k].count = n, counts[k]
+            if counts[k] == 0:
+                continue
+            if idx[k].min() < 0 or idx[k].max() >= pool.size:
+                raise IndexError("MixedReplay.sample: pool of %d links holds %d transitions, index %d asked for"
+                                 % (n, pool.size, int(idx[k].max() if idx[k].min() >= 0 else idx[k].min())))
+            slots = pool.upload_slots(pool.logical_to_slot(idx[k]))
+            used.append(pool)
+            for name in ("xe", "xe_next", "col", "action", "reward"):
+                setattr(table[k], name, getattr(pool, name).data_ptr())
+            table[k].idx = slots.data_ptr()
+        t, sb, sn, desc = self._buffers(counts)
+        rc = self._lib.v2x_replay_gather_mixed(len(self.sizes), table, C.byref(desc), current_stream_ptr(self.device.index))
+        _lib.check(self._lib, rc, None)
+        for pool in used:
+            pool.slots_consumed()
+        return sb, sn, t['action'], t['reward']
+
+
+class MixedAgent(object):
+    """DQN on several scenario sizes with one shared-weight network (module docstring).  The epsilon schedule, the reward
+    rule, the 50 transitions per train step and the 500-transition target sync are rl.agent.Agent's, counted over the
+    simulators of all environments (stored and dropped transitions alike)."""
+
+    def __init__(self, envs, cfg, feat_dim, n_mp_layers=2, use_graph=False, device=0, seed=None, capacity=MEMORY_CAPACITY):
+        envs = list(envs)
+        sizes = _check_sizes([getattr(e, 'n_Veh', 0) for e in envs], "MixedAgent")
+        for e in envs:
+            if not hasattr(e, 'observe_packed') or not hasattr(e, 'E'):
+                raise ValueError("MixedAgent steps BatchedEnviron simulators, got %s" % type(e).__name__)
+            if e.n_RB != 4 or not e.packed_ok(4):
+                raise ValueError("MixedAgent: the environment of %d links must have n_RB = 4 and packed observations "
+                                 "(libv2xsim.so), n_RB is %d" % (e.n_Veh, e.n_RB))
+        self.envs = sorted(envs, key=lambda e: e.n_Veh)           # ascending size everywhere
+        self.sizes = sizes
+        self.num_CH = 4
+        self.n_sims = sum(e.E for e in self.envs)
+        self.batch_size, self.gamma = int(cfg.Batch_Size), cfg.Gamma
+        self.v2v_weight, self.v2i_weight = cfg.v2v_weight, cfg.v2i_weight
+        self.spec = GnnSpec(n_nodes=1, n_channels=self.num_CH, feat_dim=int(feat_dim), n_mp_layers=int(n_mp_layers),
+                            share_weights=True, variable_graphs=True)
+        self.online = GnnEngine(self.spec, device=device, use_graph=use_graph)
+        self.target = GnnEngine(self.spec, device=device, use_graph=use_graph)
+        from ..bs_brain import _glorot_list
+        rng = np.random.default_rng(seed)
+        self.online.set_weights(_glorot_list(self.spec, rng))
+        self.target.set_weights(_glorot_list(self.spec, rng))
+        self.memory = MixedReplay(capacity, sizes, device=device)
+        self._draws = Memory(0)                        # (its sample_indices is the drawing rule; it stores nothing)
+        self.epsilon, self.num_step, self._sync_mark = MAX_EPSILON, 0, 0
+        self.num_Episodes, self.num_Train_Step = 1, 1
+        self.n_iter = -(-50 // self.n_sims)            # rollout iterations per train step
+        self.num_transition = self.n_iter * self.n_sims
+        self.last_minibatch = None
+        self._y, self._stats = {}, None
+
+    def close(self):
+        self.online.close()
+        self.target.close()
+
+    # ------------------------------------------------------------------ acting
+    def observe(self):
+        """[(xe [E, n, 16], mask [E, n], col [E, n (n - 2)], regular [E])] per environment, ascending size"""
+        return [e.observe_packed(self.num_CH) for e in self.envs]
+
+    def score(self, obs):
+        """Q-values of all environments' observations by ONE forward of one ragged batch -> [q [E, n, C]] per environment"""
+        xe, rp, ci, sizes, edges = [], [np.zeros(1, np.int64)], [], [], 0
+        for env, (x, mask, col, regular) in zip(self.envs, obs):
+            E, n = mask.shape
+            xe.append(x.reshape(E * n, 16))
+            sizes += [n] * E
+            if regular.all():                          # in-degree n - 2 everywhere: the CSR sources as observed
+                deg = np.full(E * n, n - 2, np.int64)
+                ci.append(col.reshape(-1))
+            else:                                      # a link that is its own receiver (rare): expand the source masks
+                bits = (mask[:, :, None] >> np.arange(n, dtype=np.int32)) & 1          # [E, q, p]
+                deg = bits.sum(axis=2).reshape(-1).astype(np.int64)
+                ci.append(np.nonzero(bits)[2].astype(np.int32))
+            rp.append(edges + np.cumsum(deg))
+            edges += int(deg.sum())
+        offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+        pb = PackedBatch(len(sizes), 0, np.ascontiguousarray(np.concatenate(xe)), np.concatenate(rp).astype(np.int32),
+                         np.concatenate(ci).astype(np.int32), graph_off=offs)
+        q = self.online.forward(pb)
+        out, r = [], 0
+        for env in self.envs:
+            rows = env.E * env.n_Veh
+            out.append(q[r:r + rows].reshape(env.E, env.n_Veh, -1))
+            r += rows
+        return out
+
+    def _iteration(self):
+        """every simulator of every environment steps once -> the rewards [E] per environment"""
+        C_ = self.num_CH
+        steps = self.num_Episodes * 0.8 * self.num_Train_Step * self.num_transition
+        per_step = (MAX_EPSILON - MIN_EPSILON) / steps
+        obs = self.observe()
+        actions, greedy, step_no = [], [], self.num_step
+        for env in self.envs:                          # the draws of rl.agent.Agent._packed_iteration, environment after environment
+            E, n = env.E, env.n_Veh
+            a, g = np.zeros((E, n, 1), int), []
+            for e in range(E):
+                self.epsilon = MAX_EPSILON - per_step * step_no if step_no < steps else MIN_EPSILON
+                step_no += 1
+                if np.random.random() < self.epsilon:
+                    a[e] = np.random.randint(0, C_, size=(n, 1))
+                else:
+                    g.append(e)
+            actions.append(a)
+            greedy.append(g)
+        if any(greedy):
+            for a, g, q in zip(actions, greedy, self.score(obs)):
+                if g:
+                    a[g] = np.argmax(q[g], axis=2)[:, :, None]
+        rewards = []
+        for env, a, (xe, mask, col, regular) in zip(self.envs, actions, obs):
+            v2v, v2i, _ = env.act(a)
+            reward = self.v2v_weight * v2v.sum(axis=(1, 2)) + self.v2i_weight * v2i.sum(axis=1)
+            xe_next = env.observe_packed(C_)[0]
+            self.memory.add_many_packed(env.n_Veh, xe, xe_next, col, mask, regular, a.reshape(env.E, env.n_Veh), reward)
+            rewards.append(reward)
+        self.num_step += self.n_sims
+        return rewards
+
+    def generate_transitions(self):
+        """the ceil(50 / sum E) rollout iterations of one train step -> {link count: rewards [iterations x E]}"""
+        out = {e.n_Veh: [] for e in self.envs}
+        for _ in range(self.n_iter):
+            for env, r in zip(self.envs, self._iteration()):
+                out[env.n_Veh].append(r)
+        return {n: np.concatenate(v) for n, v in out.items()}
+
+    # ------------------------------------------------------------------ learning
+    def quotas(self):
+        """graphs of a minibatch per pool: B E_k / sum E by largest remainder over the pools that hold transitions"""
+        w = [e.E if self.memory.stored(e.n_Veh) > 0 else 0 for e in self.envs]
+        return mixed_quotas(self.batch_size, w)
+
+    def replay(self, defer=False):
+        """One DQN update on a mixed minibatch -> (loss, Q mean, Q max mean) as floats, or with defer (loss [1], sums [2, 1]) as
+        device tensors (the sums of v2x_q_stats: all entries, per-row maxima)."""
+        torch = self.memory.torch
+        drawn = {}
+        for env, quota in zip(self.envs, self.quotas()):                  # Memory.sample_indices' rule, ascending size
+            if quota > 0:
+                drawn[env.n_Veh] = np.asarray(self._draws.sample_indices(quota, self.memory.stored(env.n_Veh)), np.int64)
+        self.last_minibatch = drawn
+        sb, sn, action, reward = self.memory.sample(drawn)
+        R, C_ = sb.n_rows, self.num_CH
+        y = self._y.get(R)
+        if y is None:
+            y = self._y[R] = torch.empty((R, C_), dtype=torch.float32, device=sb.device)
+        loss = self.online.dqn_step(self.target, sb, sn, action, reward, self.gamma, y_out=y)
+        if self._stats is None or self._stats[1] == self._stats[0].shape[0]:   # a row per call: a deferred caller reads them later
+            self._stats = [torch.empty((64, 2, 1), dtype=torch.float64, device=sb.device), 0]
+        st = self._stats[0][self._stats[1]]
+        self._stats[1] += 1
+        rc = self.online._lib.v2x_q_stats(y.data_ptr(), R, 1, C_, st.data_ptr(), current_stream_ptr(self.online.device))
+        _lib.check(self.online._lib, rc, None)
+        if defer:
+            return loss, st, R
+        s = st.cpu().numpy()
+        return float(loss.cpu().numpy()[0]), float(s[0, 0] / (R * C_)), float(s[1, 0] / R)
+
+    def train(self, num_episodes, num_train_steps, verbose=False):
+        """episodes x train steps x (ceil(50 / sum E) rollout iterations + 1 replay); target sync whenever another 500
+        transitions have been collected.  -> (loss [1, episodes, steps], {link count: rewards [episodes, steps, iterations x E]},
+        Q mean [episodes, steps], Q max mean [episodes, steps])"""
+        self.num_Episodes, self.num_Train_Step = int(num_episodes), int(num_train_steps)
+        self.num_step, self._sync_mark = 0, 0
+        loss = np.ones((1, num_episodes, num_train_steps))
+        q_mean, q_max = np.zeros((num_episodes, num_train_steps)), np.zeros((num_episodes, num_train_steps))
+        rewards = {e.n_Veh: np.zeros((num_episodes, num_train_steps, self.n_iter * e.E)) for e in self.envs}
+        torch = self.memory.torch
+        for ep in range(num_episodes):
+            for env in self.envs:
+                env.new_random_game(env.n_Veh)
+            pending = []
+            for it in range(num_train_steps):
+                for n, r in self.generate_transitions().items():
+                    rewards[n][ep, it] = r
+                pending.append(self.replay(defer=True))
+                mark = self.num_step // UPDATE_TARGET_FREQUENCY
+                if mark > self._sync_mark:
+                    self._sync_mark = mark
+                    self.target.copy_weights_from(self.online)
+            lo = torch.stack([p[0].double() for p in pending]).cpu().numpy()              # one read-back per episode
+            st = torch.stack([p[1] for p in pending]).cpu().numpy()
+            rows = np.array([p[2] for p in pending], np.float64)
+            loss[0, ep] = lo[:, 0]
+            q_mean[ep], q_max[ep] = st[:, 0, 0] / (rows * self.num_CH), st[:, 1, 0] / rows
+            if verbose:
+                print('episode', ep + 1, 'loss %.4f' % loss[0, ep].mean(),
+                      'reward', {n: round(float(v[ep].sum()), 3) for n, v in rewards.items()})
+        return loss, rewards, q_mean, q_max

@@ -349,6 +349,15 @@ class DeviceReplay(object):
             ev.record()
             use[0]["ev"][use[1]] = ev
 
+    def upload_slots(self, slots):
+        """Storage slots -> a buffer of this memory's pinned index ring that kernels can read (what sample() does with its own
+        draw), for a caller that gathers from storage() itself (rl/mixed.py); call slots_consumed() behind the last launch that
+        reads it."""
+        return self._upload_indices(np.ascontiguousarray(slots, np.int32))
+
+    def slots_consumed(self):
+        self._indices_consumed()
+
     def row_ptr(self, k):
         if k not in self._row_ptr:
             deg = self.n_edges // self.n

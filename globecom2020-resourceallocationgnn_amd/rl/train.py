@@ -114,12 +114,79 @@ def build_parser():
     ap.add_argument("--trajectory-streams", choices=["chain", "split"], default="chain",
                     help="with --trajectory-walk wide: the stream phase of the wide walk -- 'chain' (the default: one launch draws "
                          "the streams of all steps) or 'split' (raw words, offset walk and conversion in three launches; the same bits)")
+    ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
+                    help="train ONE shared-weight network on scenarios of these link counts at once (rl/mixed.py: MixedAgent), "
+                         "--envs simulators per size; distinct multiples of 4 up to 28, at most 8 of them.  Host simulators, host "
+                         "rollouts, one GPU; --links is ignored")
     return ap
+
+
+def parse_mixed_links(text):
+    """'8,12,20' -> [8, 12, 20]; ValueError with the reason for anything MixedAgent or the simulator cannot take"""
+    try:
+        sizes = [int(t) for t in text.split(",")]
+    except ValueError:
+        raise ValueError("--mixed-links takes link counts separated by commas, got %r" % (text,))
+    if not 1 <= len(sizes) <= 8:
+        raise ValueError("--mixed-links takes 1 to 8 link counts, got %d" % len(sizes))
+    if len(set(sizes)) != len(sizes):
+        raise ValueError("--mixed-links: the link counts must be distinct, got %s" % sizes)
+    for n in sizes:
+        # (groups of four vehicles, as for --links; the replay pools hold graphs of up to 31 links)
+        if n < 4 or n % 4 or n > 31:
+            raise ValueError("--mixed-links: every link count must be a multiple of 4 between 4 and 28 (got %d)" % n)
+    return sorted(sizes)
+
+
+def run_mixed(args):
+    """--mixed-links: one MixedAgent over one batched host simulator per link count"""
+    from .mixed import MixedAgent
+    sizes = parse_mixed_links(args.mixed_links)
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    cfg = RL_Config()
+    cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
+    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k) for k, n in enumerate(sizes)]
+    import contextlib
+    ctx = contextlib.nullcontext()
+    if args.use_graph:
+        import torch
+        ctx = torch.cuda.stream(torch.cuda.Stream())
+    t0 = time.perf_counter()
+    with ctx:
+        agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed)
+        loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True)
+    dt = time.perf_counter() - t0
+    n_fit = args.episodes * args.train_steps
+    print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,
+                      "episodes": args.episodes, "train_steps": args.train_steps, "env_steps": int(agent.num_step),
+                      "stored": {str(n): agent.memory.stored(n) for n in sizes},
+                      "dropped_irregular": {str(n): v for n, v in agent.memory.dropped_irregular.items()},
+                      "wall_s": round(dt, 3), "fit_steps_per_s": round(n_fit / dt, 2),
+                      "mean_loss_last_episode": round(float(loss[0, -1].mean()), 6),
+                      "reward_last_episode": {str(n): round(float(v[-1].sum()), 4) for n, v in rewards.items()}}))
+    agent.close()
+    return 0
 
 
 def main(argv=None):
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.mixed_links is not None:
+        # mixed-size training is single-size nowhere: the device simulator, the resident rollouts and data parallelism stay with --links
+        if args.sim_backend != "host" or args.sim_streams != "host":
+            ap.error("--mixed-links steps host simulators: --sim-backend / --sim-streams device hold one link count")
+        if args.rollout != "host":
+            ap.error("--mixed-links scores through the host: --rollout %s holds one link count" % args.rollout)
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("V2X_FORCE_DP") == "1" or args.rollouts != "replicated":
+            ap.error("--mixed-links runs on one GPU: the ragged replay step has no data-parallel form")
+        if args.envs < 1:
+            ap.error("--mixed-links steps batched simulators: give --envs (simulators per link count)")
+        try:
+            parse_mixed_links(args.mixed_links)
+        except ValueError as exc:
+            ap.error(str(exc))
+        return run_mixed(args)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
     if args.rollout != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):

@@ -267,12 +267,47 @@ int  v2x_q_stats(const float* y, int32_t n_graphs, int32_t n_nodes, int32_t n_ch
 int  v2x_dqn_targets(const float* q, const float* q_next, const int32_t* action, const double* reward,
                      double gamma, int32_t n_graphs, int32_t n_nodes, int32_t n_channels, float* y_out,
                      void* stream);
+/* The same rule on a RAGGED batch (graphs of different sizes, a variable_graphs model): row r takes the reward of the graph
+ * that graph_off [n_graphs + 1] puts it in.  q, q_next, y: [n_rows][n_channels]; action: [n_rows]; reward: [n_graphs] double.
+ * One launch on `stream`, no allocation, no synchronisation.                                                              */
+int  v2x_dqn_targets_ragged(const float* q, const float* q_next, const int32_t* action, const double* reward,
+                            double gamma, const int32_t* graph_off, int32_t n_graphs, int32_t n_rows,
+                            int32_t n_channels, float* y_out, void* stream);
+
+/* A replay minibatch of graphs of DIFFERENT sizes assembled in one launch.  Every pool is the storage of one link count in
+ * the layout of rl/replay.py; every stored graph is regular (in-degree n - 2).  The graphs of pool 0 come first, in its idx
+ * order, then pool 1's, ...: graph j of pool k starts at row rbase_k + j n_k and at edge ebase_k + j n_k (n_k - 2), the
+ * bases being the sums over the pools before it.  Written: xe / xe_next [R][16], action [R], reward [B], graph_off [B + 1],
+ * row_ptr [R + 1] and col_idx [E] (graph-local sources, as stored), with B = sum count, R = sum count n, E = sum count
+ * n (n - 2): the arrays of two ragged v2x_batch (s and s') that share graph_off / row_ptr / col_idx.  `pools` is a [host]
+ * array (the kernel takes the table by value), all pointers inside [dev]; `out` is a [host] struct of [dev] pointers, xe /
+ * xe_next 16-byte aligned.  One launch on `stream`, no allocation, no synchronisation, no environment variable read.
+ * V2X_EINVAL with the reason (v2x_last_error(NULL)): n_pools outside 1..8, counts that sum to 0 or a negative one, n_nodes
+ * outside 3..31, a null pointer in a pool with count > 0 or in `out`, R or E beyond int32.  Slots are not range-checked.   */
+typedef struct v2x_replay_pool {      /* one link count's replay storage (rl/replay.py layout) */
+  int32_t n_nodes, count;             /* 3..31 links; graphs this pool contributes (>= 0) */
+  const float *xe, *xe_next;          /* [cap][n][16] */
+  const int32_t *col, *action;        /* [cap][n (n-2)], [cap][n] */
+  const double* reward;               /* [cap] */
+  const int32_t* idx;                 /* [count] storage slots, device-addressable */
+} v2x_replay_pool;
+typedef struct v2x_mixed_batch {
+  float *xe, *xe_next; int32_t* action; double* reward;
+  int32_t *graph_off, *row_ptr, *col_idx;
+} v2x_mixed_batch;
+int  v2x_replay_gather_mixed(int32_t n_pools /*1..8*/, const v2x_replay_pool* pools /*[host]*/,
+                             const v2x_mixed_batch* out /*[dev] pointers*/, void* stream);
 
 /* One whole replay step (BS_brain.py:664-728: predict on s, predict(target) on s', target rule, train_dnn) as a
  * single call on device-resident batches: the graph layers of the online network run ONCE (their activations feed
  * the backward pass), where predict + fit would run them twice.  y_out: optional [dev] [n_rows][C] buffer that
  * receives the training targets (for the caller's Q statistics, BS_brain.py:730-746); loss_out: per-output Huber
- * means like v2x_train_step.                                                                                   */
+ * means like v2x_train_step.
+ * Ragged form: online and target are both variable_graphs models of the same F and L.  Both batches carry graph_off and
+ * s_next->graph_off is the SAME device pointer as s->graph_off (a transition's s and s' are the same links; n_graphs and
+ * n_rows are equal too); action is [n_rows], one per node row; reward is [n_graphs], one per graph -- row r takes the
+ * reward of its graph; loss_out is the single Huber mean over rows x C; n_graphs_global <= 0 defaults to the batch's node
+ * rows (variable_graphs models count rows).  Anything else is V2X_EINVAL with a text that names the problem.            */
 int  v2x_dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, const v2x_batch* s_next,
                   const int32_t* action, const double* reward, double gamma, int32_t n_graphs_global,
                   float* y_out, float* loss_out, int loss_on_device, void* stream);
