@@ -89,6 +89,12 @@ class RolloutTraj(C.Structure):
         [(k, C.c_void_p) for k in ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")]
 
 
+class RolloutMixed(C.Structure):
+    """v2x_rollout_mixed of include/v2xgnn.h"""
+    _fields_ = [("n_pools", C.c_int32), ("T", C.c_int32), ("pools", C.POINTER(RolloutTraj)), ("model", C.c_void_p)] + \
+        [(k, C.c_void_p) for k in ("xe", "graph_off", "row_ptr", "col_idx", "q")]
+
+
 TRAJ_WORKSPACES = ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")
 EVAL_RESULTS = ("result_actions", "result_v2v_rate", "result_v2i_rate", "result_interference", "result_reward", "result_regular")
 
@@ -206,6 +212,7 @@ SYMBOLS = [
     ("v2x_rollout_step", C.c_int, [C.POINTER(Rollout), _P]),
     ("v2x_rollout_steps_workspace_bytes", _L, [_I, _I, _I, _I]),
     ("v2x_rollout_steps", C.c_int, [C.POINTER(RolloutTraj), _P]),
+    ("v2x_rollout_steps_mixed", C.c_int, [C.POINTER(RolloutMixed), _P]),
     ("v2x_eval_steps_result_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_eval_steps", C.c_int, [C.POINTER(Eval), _P]),
     ("v2x_traj_wide_workspace_bytes", _L, [_I, _I, _I, _I]),

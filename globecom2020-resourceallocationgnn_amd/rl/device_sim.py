@@ -50,6 +50,14 @@ the same bits); dc.stream_phase_calls counts the wide calls by the form that ran
 the split form takes the rollout from 1.54 to 0.88 ms (the host library's native rollout: 1.06 ms); at 50 simulators and T = 1
 the forms are level (profiles/trajectory_split_timing.json).
 
+Several DeviceChannels of DIFFERENT link counts make their rollouts in one library call (v2x_rollout_steps_mixed: one walk
+launch, one assembly launch, one forward of a variable_graphs engine over all pools' observations, one finish launch), every
+pool with its own policy upload, replay storage and result download; resident_rollout_steps_mixed does the same for one
+DeviceBatchedEnviron per link count (rl/mixed.py, MixedAgent(rollout='trajectory')); the serial walk only:
+
+    rows = rollout_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [storage8, storage12], heads, capacities,
+                               w_v2v, w_v2i, engine)                                          # -> [RolloutResult] per pool
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -61,7 +69,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import Eval, OptProblem, Rollout, RolloutTraj, SimStep, check, load_library
+from ..lib import (Eval, MIXED_MAX_POOLS, OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -315,6 +323,7 @@ class DeviceChannels(object):
         self._grid_sent = False
         self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
         self._roll = {}                                  # _rollout_io(): None (rollout_step) or T (rollout_steps) -> its buffers
+        self._mixed = {}                                 # mixed_rollout_buffers(): ((E_k, n_k)..., T) of the pools this one leads
         self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
         self.stream_phase_calls = {p: 0 for p in STREAM_PHASES}     # the wide ones among them, by the form of the stream phase
 
@@ -1076,6 +1085,126 @@ class DeviceChannels(object):
         return [self._t[k] for k in ('v2v_ff', 'v2i_ff', 'v2i_abs', 'dest')], dict(self.constants)
 
 
+# ---------------------------------------------------------------------- rollouts of several link counts in one call
+def mixed_rollout_bases(pools, T):
+    """pools: [(E_k, n_k)] in ascending n; -> (gbase, rbase, ebase, (B, R, Ed)): the first graph / row / edge of every pool in the
+    ragged batch of v2x_rollout_steps_mixed (pool-major: T E_j graphs of n_j rows and n_j (n_j - 2) edges for every pool j
+    before k) and the batch's totals"""
+    gbase, rbase, ebase, B, R, Ed = [], [], [], 0, 0, 0
+    for E, n in pools:
+        gbase.append(B)
+        rbase.append(R)
+        ebase.append(Ed)
+        B, R, Ed = B + T * E, R + T * E * n, Ed + T * E * n * (n - 2)
+    return gbase, rbase, ebase, (B, R, Ed)
+
+
+def mixed_rollout_buffers(channels, T):
+    """the ragged batch a mixed rollout of these DeviceChannels with blocks of T scores -- xe [R, 16], graph_off [B + 1],
+    row_ptr [R + 1], col_idx [Ed], q [R, rb], written by the call -- made once per ((E_k, n_k)..., T) and owned by the FIRST
+    pool's DeviceChannels: stable pointers, released with that object, and two sets of simulators never share a buffer
+    (16 R and Ed are 32-bit sizes of a batch: ValueError beyond)"""
+    dc0 = channels[0]
+    dc0._init_device()
+    key = (tuple((dc.E, dc.n) for dc in channels), int(T))
+    buf = dc0._mixed.get(key)
+    if buf is None:
+        t = dc0.torch
+        _, _, _, (B, R, Ed) = mixed_rollout_bases(key[0], T)
+        if R * XE_WIDTH >= 2 ** 31 or Ed >= 2 ** 31:
+            raise ValueError("rollout_steps_mixed: %d rows and %d edges exceed the 32-bit sizes of a batch" % (R, Ed))
+        i32 = lambda k: t.zeros(k, dtype=t.int32, device=dc0.device)       # noqa: E731
+        buf = dc0._mixed[key] = {
+            'xe': t.zeros((R, XE_WIDTH), dtype=t.float32, device=dc0.device), 'graph_off': i32(B + 1), 'row_ptr': i32(R + 1),
+            'col_idx': i32(max(Ed, 1)), 'q': t.zeros((R, dc0.rb), dtype=t.float32, device=dc0.device), 'sizes': (B, R, Ed)}
+    return buf
+
+
+def _check_mixed_pools(who, channels, per_pool):
+    channels = list(channels)
+    if not 1 <= len(channels) <= MIXED_MAX_POOLS:
+        raise ValueError("%s: 1..%d pools, got %d" % (who, MIXED_MAX_POOLS, len(channels)))
+    for name, arg in per_pool.items():
+        if len(arg) != len(channels):
+            raise ValueError("%s: one %s per pool expected, got %d for %d pools" % (who, name, len(arg), len(channels)))
+    sizes = [dc.n for dc in channels]
+    if any(b <= a for a, b in zip(sizes, sizes[1:])):
+        raise ValueError("%s: the pools' link counts must ascend strictly, got %s" % (who, sizes))
+    if len(set(dc.rb for dc in channels)) != 1:
+        raise ValueError("%s: one channel count for all pools, got %s" % (who, [dc.rb for dc in channels]))
+    return channels
+
+
+def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None,
+                        power=None):
+    """DeviceChannels.rollout_steps for several link counts in ONE library call (v2x_rollout_steps_mixed): channels is one
+    DeviceChannels per link count in ascending size, and explore [T, E_k], random_actions [T, E_k, n_k], storages, heads and
+    capacities are lists with pool k's argument of rollout_steps in place k (the same T everywhere).  One launch walks every
+    simulator of every pool, one forward of a variable_graphs `engine` scores all their observations as one ragged batch
+    (None: nobody is greedy anywhere, no forward), one launch picks, pays and stores every transition into its own pool's
+    slots.  Per pool the bits of its own rollout_steps, given the same Q-values.  Every pool keeps its own policy upload and
+    result download.  -> [RolloutResult] per pool, the downloads in flight."""
+    who = "rollout_steps_mixed"
+    per_pool = dict(explore=explore, random_actions=random_actions, storages=storages, heads=heads, capacities=capacities)
+    channels = _check_mixed_pools(who, channels, per_pool)
+    T = _block_length(explore[0])
+    checked = []
+    for k, dc in enumerate(channels):
+        if _block_length(explore[k]) != T:
+            raise ValueError("%s: pool %d (%d links) has a block of %d iterations, pool 0 of %d"
+                             % (who, k, dc.n, _block_length(explore[k]), T))
+        checked.append(dc._check_rollout(who, T, explore[k], random_actions[k], storages[k], heads[k], capacities[k]))
+    if engine is not None and not (engine.spec.variable_graphs and engine.spec.n_channels == channels[0].rb):
+        raise ValueError("%s: scoring needs a variable_graphs engine of %d channels" % (who, channels[0].rb))
+    for dc in channels:
+        dc._init_device()
+        if dc.device != channels[0].device:
+            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
+        if not dc._obs_ready:
+            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    table = (RolloutTraj * len(channels))()
+    ios = []
+    for k, (dc, (ex, ra)) in enumerate(zip(channels, checked)):
+        io = dc._rollout_io(T)
+        dc._upload_policy(io, ra, ex)
+        table[k] = dc.rollout_steps_struct(T, storages[k], heads[k], capacities[k], v2v_weight, v2i_weight, engine=None, power=power)
+        ios.append(io)
+    m = RolloutMixed(n_pools=len(channels), T=T, pools=table, model=None)
+    if engine is not None:
+        buf = mixed_rollout_buffers(channels, T)
+        m.model = engine._h
+        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx', 'q'):
+            setattr(m, name, buf[name].data_ptr())
+    for dc in channels:
+        dc._keep_actions = dc._t['actions']
+    check(channels[0]._lib, channels[0]._lib.v2x_rollout_steps_mixed(C.byref(m), channels[0]._stream()))
+    out = []
+    for dc, io in zip(channels, ios):
+        dc._obs_ready = True
+        dc.walk_calls['serial'] += 1
+        out.append(dc._download_result(io, T))
+    return out
+
+
+def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None):
+    """rollout_steps_mixed() on the resident states of one DeviceBatchedEnviron (streams='device') per link count, ascending
+    size: the bookkeeping of DeviceBatchedEnviron.rollout_steps around every environment, the ONE library call in the middle.
+    -> [RolloutResult] per environment, the downloads in flight."""
+    who = "rollout_steps_mixed"
+    envs = list(envs)
+    per_pool = dict(explore=explore, random_actions=random_actions, storages=storages, heads=heads, capacities=capacities)
+    for name, arg in per_pool.items():
+        if len(arg) != len(envs):
+            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
+    channels = [env._resident_before(who, lambda dc, k=k: dc.check_rollout_steps(explore[k], random_actions[k], storages[k], heads[k],
+                                                                                 capacities[k]))
+                for k, env in enumerate(envs)]
+    results = rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=engine)
+    for env, result in zip(envs, results):
+        env._resident_after(result)
+    return results
+
+
 # attribute of BatchedEnviron -> (device tensor, host shape from (E, n, rb))
 _DEVICE_ARRAYS = {
     '_v2i_shadow': ('v2i_shadow', lambda E, n, rb: (E, n)),
@@ -1400,7 +1529,15 @@ class DeviceBatchedEnviron(BatchedEnviron):
 
     def _resident_call(self, who, check_args, call):
         """the bookkeeping every call that steps the resident state shares (rollout_step / rollout_steps / evaluate_steps):
-        check_args(dc) raises ValueError before any device work of the call, call(dc) makes it -> its result object"""
+        check_args(dc) raises ValueError before any device work of the call, call(dc) makes it -> its result object.  The two
+        halves around the call are methods of their own for a call that steps several environments at once
+        (resident_rollout_steps_mixed): every environment's first half, the one call, every environment's second half."""
+        dc = self._resident_before(who, check_args)
+        return self._resident_after(call(dc))
+
+    def _resident_before(self, who, check_args):
+        """_resident_call up to the library call: everything the device needs is on it, the arguments are checked, the
+        observation is resident -> the DeviceChannels"""
         if self.stream_backend != 'device':
             raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
         self.finish_step()
@@ -1413,7 +1550,10 @@ class DeviceBatchedEnviron(BatchedEnviron):
         if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
             dc.observe(self.dest)
         self._obs = None
-        result = call(dc)
+        return dc
+
+    def _resident_after(self, result):
+        """_resident_call after the library call: who holds the newer copy of what -> result"""
         self._streams_ahead = True
         self._channels_updated()
         self._on_device.add('V2V_Interference_all')

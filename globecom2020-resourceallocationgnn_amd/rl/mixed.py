@@ -9,6 +9,11 @@ ragged path scores and fits batches whose graphs differ in size.  This module is
   MixedAgent    one BatchedEnviron per link count; a rollout iteration steps every simulator of every environment once, all
                 observations scored by ONE forward; replay() draws B E_k / sum E graphs from pool k and runs one
                 v2x_dqn_step in its ragged form (one reward per graph, one action per node row, a single Huber mean).
+                rollout='trajectory': every environment is a DeviceBatchedEnviron with streams='device' and the ceil(50 / sum E)
+                iterations of a train step are ONE library call (v2x_rollout_steps_mixed: one walk launch, one assembly launch,
+                one ragged forward, one finish launch for all link counts); the epsilon-greedy draws are taken ahead in the
+                order the host rollout takes them, the transitions land in the pools' slots on the device, and the rewards
+                come back with the losses at the end of the episode.  The default stays 'host'.
 
 Only regular graphs (in-degree n - 2 everywhere) are stored: a transition whose graph has a link that is its own receiver (two
 vehicles on one spot, rare) is counted in MixedReplay.dropped_irregular and left out -- the assembly is closed-form because
@@ -26,6 +31,7 @@ from .agent import Memory, MEMORY_CAPACITY, UPDATE_TARGET_FREQUENCY, MAX_EPSILON
 from .replay import DeviceReplay
 
 MIN_LINKS, MAX_LINKS = 3, DeviceReplay.MAX_LINKS
+ROLLOUTS = ('host', 'trajectory')                     # how MixedAgent makes the iterations of a train step
 
 
 def _check_sizes(sizes, what):
@@ -89,6 +95,25 @@ class MixedReplay(object):
         pool.add_many_packed(xe, xe_next, col, mask, regular, action, reward)
         return int(len(regular))
 
+    # ------------------------------------------------------------------ transitions written by the device (v2x_rollout_steps_mixed)
+    def _pool(self, n, who):
+        if n not in self.pools:
+            raise ValueError("MixedReplay.%s: no pool of %d links (pools: %s)" % (who, n, self.sizes))
+        return self.pools[n]
+
+    def storage(self, n):
+        """DeviceReplay.storage() of the pool of n links"""
+        return self._pool(n, "storage").storage()
+
+    def reserve(self, n, K):
+        """DeviceReplay.reserve(K) of the pool of n links -> the first slot of the block the device is about to write"""
+        return self._pool(n, "reserve").reserve(K)
+
+    def commit(self, n, K, result):
+        """DeviceReplay.commit(K, result) of the pool of n links: its head and size advance at once, the flags of the block are
+        read from `result` when they are first needed"""
+        self._pool(n, "commit").commit(K, result)
+
     def _buffers(self, counts):
         """output tensors and batch descriptors of a minibatch of counts[k] graphs from pool k: cached, so that the pointers
         are stable and a captured replay step is replayed"""
@@ -150,8 +175,11 @@ class MixedAgent(object):
     rule, the 50 transitions per train step and the 500-transition target sync are rl.agent.Agent's, counted over the
     simulators of all environments (stored and dropped transitions alike)."""
 
-    def __init__(self, envs, cfg, feat_dim, n_mp_layers=2, use_graph=False, device=0, seed=None, capacity=MEMORY_CAPACITY):
+    def __init__(self, envs, cfg, feat_dim, n_mp_layers=2, use_graph=False, device=0, seed=None, capacity=MEMORY_CAPACITY,
+                 rollout='host'):
         envs = list(envs)
+        if rollout not in ROLLOUTS:
+            raise ValueError("MixedAgent: rollout must be one of %s, got %r" % (list(ROLLOUTS), rollout))
         sizes = _check_sizes([getattr(e, 'n_Veh', 0) for e in envs], "MixedAgent")
         for e in envs:
             if not hasattr(e, 'observe_packed') or not hasattr(e, 'E'):
@@ -159,6 +187,17 @@ class MixedAgent(object):
             if e.n_RB != 4 or not e.packed_ok(4):
                 raise ValueError("MixedAgent: the environment of %d links must have n_RB = 4 and packed observations "
                                  "(libv2xsim.so), n_RB is %d" % (e.n_Veh, e.n_RB))
+        if rollout == 'trajectory':
+            from .device_sim import DeviceBatchedEnviron
+            for e in envs:
+                if not isinstance(e, DeviceBatchedEnviron) or e.stream_backend != 'device':
+                    raise ValueError("MixedAgent: rollout='trajectory' steps every environment on the device: the environment of "
+                                     "%d links must be a DeviceBatchedEnviron with streams='device', got %s%s"
+                                     % (e.n_Veh, type(e).__name__,
+                                        " with streams=%r" % e.stream_backend if isinstance(e, DeviceBatchedEnviron) else ""))
+        self.rollout = rollout
+        self.rollout_stats = {'trajectory': 0, 'host': 0}         # rollouts (one per train step) by the path that made them
+        self._regular_look = None                                 # (the receivers last looked at, were all their graphs regular)
         self.envs = sorted(envs, key=lambda e: e.n_Veh)           # ascending size everywhere
         self.sizes = sizes
         self.num_CH = 4
@@ -218,13 +257,14 @@ class MixedAgent(object):
             r += rows
         return out
 
-    def _iteration(self):
-        """every simulator of every environment steps once -> the rewards [E] per environment"""
+    def _policy_draws(self, step_no):
+        """the epsilon-greedy draws of one iteration that starts at step `step_no`: environment after environment in ascending
+        size, per simulator one uniform draw and, if it explores, its randint right after; epsilon advances per simulator
+        -> ([actions [E, n, 1] int] per environment, [greedy simulators] per environment)"""
         C_ = self.num_CH
         steps = self.num_Episodes * 0.8 * self.num_Train_Step * self.num_transition
         per_step = (MAX_EPSILON - MIN_EPSILON) / steps
-        obs = self.observe()
-        actions, greedy, step_no = [], [], self.num_step
+        actions, greedy = [], []
         for env in self.envs:                          # the draws of rl.agent.Agent._packed_iteration, environment after environment
             E, n = env.E, env.n_Veh
             a, g = np.zeros((E, n, 1), int), []
@@ -237,6 +277,20 @@ class MixedAgent(object):
                     g.append(e)
             actions.append(a)
             greedy.append(g)
+        return actions, greedy
+
+    def _draw_rollout_ahead(self, n_iter):
+        """the draws of n_iter iterations, taken before the first of them runs: iteration, then environment in ascending size,
+        then simulator -- the order _iteration consumes them in; nothing else draws inside a rollout, so the process-wide numpy
+        stream and the final epsilon are those of the per-iteration path -> [_policy_draws] per iteration"""
+        return [self._policy_draws(self.num_step + it * self.n_sims) for it in range(n_iter)]
+
+    def _iteration(self, drawn=None):
+        """every simulator of every environment steps once -> the rewards [E] per environment.  drawn: the iteration's
+        _policy_draws when they were taken ahead (a device rollout that had to fall back)"""
+        C_ = self.num_CH
+        obs = self.observe()
+        actions, greedy = self._policy_draws(self.num_step) if drawn is None else drawn
         if any(greedy):
             for a, g, q in zip(actions, greedy, self.score(obs)):
                 if g:
@@ -251,11 +305,58 @@ class MixedAgent(object):
         self.num_step += self.n_sims
         return rewards
 
-    def generate_transitions(self):
-        """the ceil(50 / sum E) rollout iterations of one train step -> {link count: rewards [iterations x E]}"""
+    def _all_regular(self):
+        """every environment's resident graph is regular.  Receivers are fixed within an episode, so one look per set of
+        receivers suffices (after a reset: one small download per environment); no wait for a result row in between."""
+        key = tuple(np.asarray(e.dest).tobytes() for e in self.envs)
+        if self._regular_look is None or self._regular_look[0] != key:
+            self._regular_look = (key, all(bool(np.all(e.resident_regular(self.num_CH))) for e in self.envs))
+        return self._regular_look[1]
+
+    def _trajectory_rollout(self, drawn):
+        """The iterations `drawn` (_draw_rollout_ahead) as ONE library call on the resident states of all environments: per pool
+        one reserve and one commit of T E_k slots, the model passed only when somebody is greedy.  -> [RolloutResult] per
+        environment (the rewards [T, E_k] once they have arrived), or None when the host path has to run with these draws: an
+        environment's resident graph is not regular (it cannot be scored from the fixed-degree CSR, and the host path leaves
+        such transitions out), or a block does not fit a pool's ring."""
+        from .device_sim import resident_rollout_steps_mixed
+        T, mem = len(drawn), self.memory
+        if any(T * e.E > mem.pools[e.n_Veh].capacity for e in self.envs) or not self._all_regular():
+            return None
+        explore, actions = [], []
+        for k, env in enumerate(self.envs):
+            ex = np.ones((T, env.E), np.uint8)
+            for t, (_, greedy) in enumerate(drawn):
+                ex[t, greedy[k]] = 0
+            explore.append(ex)
+            actions.append(np.stack([a[k] for a, _ in drawn]).reshape(T, env.E, env.n_Veh))
+        anybody = any(g for _, greedy in drawn for g in greedy)
+        sizes = [e.n_Veh for e in self.envs]
+        heads = [mem.reserve(e.n_Veh, T * e.E) for e in self.envs]
+        results = resident_rollout_steps_mixed(self.envs, explore, actions, [mem.storage(n) for n in sizes], heads,
+                                               [mem.pools[n].capacity for n in sizes], self.v2v_weight, self.v2i_weight,
+                                               engine=self.online if anybody else None)
+        for env, result in zip(self.envs, results):
+            mem.commit(env.n_Veh, T * env.E, result)
+        self.num_step += T * self.n_sims
+        return results
+
+    def generate_transitions(self, defer=False):
+        """the ceil(50 / sum E) rollout iterations of one train step -> {link count: rewards [iterations x E]}.
+        rollout='trajectory': all of them in one call on the device (rollout_stats counts the rollouts by the path they took);
+        with defer the values are the RolloutResults whose downloads are in flight (.resolve().reward.reshape(-1): the same
+        array) -- nothing waits for the device."""
         out = {e.n_Veh: [] for e in self.envs}
-        for _ in range(self.n_iter):
-            for env, r in zip(self.envs, self._iteration()):
+        drawn = [None] * self.n_iter
+        if self.rollout == 'trajectory':
+            drawn = self._draw_rollout_ahead(self.n_iter)
+            results = self._trajectory_rollout(drawn)
+            if results is not None:
+                self.rollout_stats['trajectory'] += 1
+                return {e.n_Veh: (r if defer else r.resolve().reward.reshape(-1)) for e, r in zip(self.envs, results)}
+        self.rollout_stats['host'] += 1
+        for d in drawn:
+            for env, r in zip(self.envs, self._iteration(drawn=d)):
                 out[env.n_Veh].append(r)
         return {n: np.concatenate(v) for n, v in out.items()}
 
@@ -304,10 +405,13 @@ class MixedAgent(object):
         for ep in range(num_episodes):
             for env in self.envs:
                 env.new_random_game(env.n_Veh)
-            pending = []
+            pending, rows = [], []
             for it in range(num_train_steps):
-                for n, r in self.generate_transitions().items():
-                    rewards[n][ep, it] = r
+                for n, r in self.generate_transitions(defer=True).items():
+                    if isinstance(r, np.ndarray):
+                        rewards[n][ep, it] = r
+                    else:                              # a device rollout's result row: read with the losses, below
+                        rows.append((n, it, r))
                 pending.append(self.replay(defer=True))
                 mark = self.num_step // UPDATE_TARGET_FREQUENCY
                 if mark > self._sync_mark:
@@ -315,6 +419,10 @@ class MixedAgent(object):
                     self.target.copy_weights_from(self.online)
             lo = torch.stack([p[0].double() for p in pending]).cpu().numpy()              # one read-back per episode
             st = torch.stack([p[1] for p in pending]).cpu().numpy()
+            for n, it, r in rows:
+                rewards[n][ep, it] = r.resolve().reward.reshape(-1)
+            for pool in self.memory.pools.values():    # (the flags of the device blocks: their rows have arrived)
+                pool.regular_flags()
             rows = np.array([p[2] for p in pending], np.float64)
             loss[0, ep] = lo[:, 0]
             q_mean[ep], q_max[ep] = st[:, 0, 0] / (rows * self.num_CH), st[:, 1, 0] / rows

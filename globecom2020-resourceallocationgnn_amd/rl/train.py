@@ -117,7 +117,16 @@ def build_parser():
     ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
                     help="train ONE shared-weight network on scenarios of these link counts at once (rl/mixed.py: MixedAgent), "
                          "--envs simulators per size; distinct multiples of 4 up to 28, at most 8 of them.  Host simulators, host "
-                         "rollouts, one GPU; --links is ignored")
+                         "rollouts, one GPU unless the --mixed-* options below say otherwise; --links is ignored")
+    ap.add_argument("--mixed-sim-backend", choices=["host", "device"], default="host",
+                    help="with --mixed-links: --sim-backend for every link count's simulators (--sim-backend itself holds one link "
+                         "count and stays refused)")
+    ap.add_argument("--mixed-sim-streams", choices=["host", "device"], default="host",
+                    help="with --mixed-links --mixed-sim-backend device: --sim-streams for every link count's simulators")
+    ap.add_argument("--mixed-rollout", choices=["host", "trajectory"], default="host",
+                    help="with --mixed-links --mixed-sim-backend device --mixed-sim-streams device: 'trajectory' runs all iterations "
+                         "of a rollout for ALL link counts as one call on the resident states (one walk launch, one assembly launch, "
+                         "one ragged forward, one finish launch); 'host' (the default) scores and stores through the host")
     return ap
 
 
@@ -139,14 +148,16 @@ def parse_mixed_links(text):
 
 
 def run_mixed(args):
-    """--mixed-links: one MixedAgent over one batched host simulator per link count"""
+    """--mixed-links: one MixedAgent over one batched simulator per link count (--mixed-sim-backend / --mixed-sim-streams say
+    where they run, --mixed-rollout who makes the rollout)"""
     from .mixed import MixedAgent
     sizes = parse_mixed_links(args.mixed_links)
     random.seed(args.seed)
     np.random.seed(args.seed)
     cfg = RL_Config()
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
-    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k) for k, n in enumerate(sizes)]
+    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.mixed_sim_backend, streams=args.mixed_sim_streams)
+            for k, n in enumerate(sizes)]
     import contextlib
     ctx = contextlib.nullcontext()
     if args.use_graph:
@@ -154,12 +165,14 @@ def run_mixed(args):
         ctx = torch.cuda.stream(torch.cuda.Stream())
     t0 = time.perf_counter()
     with ctx:
-        agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed)
+        agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed, rollout=args.mixed_rollout)
         loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True)
     dt = time.perf_counter() - t0
     n_fit = args.episodes * args.train_steps
     print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,
                       "episodes": args.episodes, "train_steps": args.train_steps, "env_steps": int(agent.num_step),
+                      "sim_backend": args.mixed_sim_backend, "sim_streams": args.mixed_sim_streams, "rollout": args.mixed_rollout,
+                      "rollouts_by_path": dict(agent.rollout_stats),
                       "stored": {str(n): agent.memory.stored(n) for n in sizes},
                       "dropped_irregular": {str(n): v for n, v in agent.memory.dropped_irregular.items()},
                       "wall_s": round(dt, 3), "fit_steps_per_s": round(n_fit / dt, 2),
@@ -169,23 +182,44 @@ def run_mixed(args):
     return 0
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """the command line, parsed, with every check that concerns --mixed-links made (a refusal exits with its message)
+    -> (parser, arguments)"""
     ap = build_parser()
     args = ap.parse_args(argv)
     if args.mixed_links is not None:
-        # mixed-size training is single-size nowhere: the device simulator, the resident rollouts and data parallelism stay with --links
+        # the single-size options hold one link count and stay refused; the device simulators and the resident rollout of ALL
+        # link counts are asked for by --mixed-sim-backend / --mixed-sim-streams / --mixed-rollout
         if args.sim_backend != "host" or args.sim_streams != "host":
-            ap.error("--mixed-links steps host simulators: --sim-backend / --sim-streams device hold one link count")
+            ap.error("--mixed-links steps host simulators: --sim-backend / --sim-streams device hold one link count "
+                     "(--mixed-sim-backend / --mixed-sim-streams put every link count's simulators on the device)")
         if args.rollout != "host":
-            ap.error("--mixed-links scores through the host: --rollout %s holds one link count" % args.rollout)
+            ap.error("--mixed-links scores through the host: --rollout %s holds one link count (--mixed-rollout trajectory runs "
+                     "the rollouts of all link counts in one call)" % args.rollout)
+        if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
+            ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
+                     "link count")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("V2X_FORCE_DP") == "1" or args.rollouts != "replicated":
             ap.error("--mixed-links runs on one GPU: the ragged replay step has no data-parallel form")
         if args.envs < 1:
             ap.error("--mixed-links steps batched simulators: give --envs (simulators per link count)")
+        if args.mixed_sim_streams == "device" and args.mixed_sim_backend != "device":
+            ap.error("--mixed-sim-streams device needs --mixed-sim-backend device")
+        if args.mixed_rollout == "trajectory" and args.mixed_sim_streams != "device":
+            ap.error("--mixed-rollout trajectory needs --mixed-sim-backend device --mixed-sim-streams device (the simulators "
+                     "advance inside the call)")
         try:
             parse_mixed_links(args.mixed_links)
         except ValueError as exc:
             ap.error(str(exc))
+    elif args.mixed_sim_backend != "host" or args.mixed_sim_streams != "host" or args.mixed_rollout != "host":
+        ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-rollout need --mixed-links")
+    return ap, args
+
+
+def main(argv=None):
+    ap, args = parse_args(argv)
+    if args.mixed_links is not None:
         return run_mixed(args)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")

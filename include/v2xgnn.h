@@ -639,6 +639,41 @@ typedef struct v2x_rollout_traj {
 int64_t v2x_rollout_steps_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
 int  v2x_rollout_steps(const v2x_rollout_traj* r, void* stream);
 
+/* v2x_rollout_steps_mixed: v2x_rollout_steps for up to 8 pools of DIFFERENT link counts in one call, all scored by one forward
+ * of one ragged batch on a variable_graphs model (rl/mixed.py: one shared-weight network over several scenario sizes).  Pool k
+ * is the v2x_rollout_traj of its own resident state, trajectory workspace and replay storage (E_k states of n_k links), and
+ * every pool walks the same T steps.  With B = T S(E_k) graphs, R = T S(E_k n_k) rows and Ed = T S(E_k n_k (n_k - 2)) edges,
+ * the batch is pool-major and inside a pool in the trajectory's own order (t, e): pool k's graphs start at graph
+ * gbase_k = T S_{j<k}(E_j), at row rbase_k = T S_{j<k}(E_j n_j) and at edge ebase_k = T S_{j<k}(E_j n_j (n_j - 2)); transition
+ * (k, t, e) reads the Q rows rbase_k + (t E_k + e) n_k + i.  Enqueues, in this order on one stream with no parallel branches,
+ *   k_sim_trajectory_mixed  grid (S E_k), 256 threads: one workgroup per state, the body of k_sim_trajectory on its pool's
+ *                           arguments (the states of the largest n in the lowest block indices);
+ *   k_traj_assemble_mixed   grid (ceil(B / 4)), one wave per graph: xe [R][16] and col_idx [Ed] are entries 0..T-1 of every
+ *                           pool's traj_xe and traj_col one after the other (graph-local sources, as v2x_replay_gather_mixed
+ *                           leaves them), graph_off [B + 1] and row_ptr [R + 1] in closed form (n_k - 2 sources per row) --
+ *                           skipped without a model;
+ *   v2x_forward             of that batch on `model` into q [R][rb] -- skipped when model is NULL (nobody is greedy);
+ *   k_rollout_finish_mixed  grid (B), one wave per transition: the body of k_rollout_finish on its pool's arguments with
+ *                           q + rbase_k rb, into the pool's own replay slot (head_k + t E_k + e) % capacity_k, result row and
+ *                           resident arrays.
+ * The device functions are those of v2x_rollout_steps: per pool the bits of that call (given the same Q rows).  Same rules:
+ * all pointers [dev] except `pools` ([host]; the kernels take their tables by value), asynchronous, no allocation, no
+ * synchronisation, no environment variable read; every check of every pool and of the mixed part before the first launch.
+ * V2X_EINVAL with a text that names the pool (v2x_last_error(NULL)): n_pools outside 1..8, link counts not strictly ascending,
+ * a pool whose T is not the call's, a pool with a model of its own, anything v2x_rollout_steps refuses of a pool, pools that
+ * differ in rb, a model that is not variable_graphs or whose channel count is not rb, a null xe / graph_off / row_ptr /
+ * col_idx / q or a pool's null explore with a model (xe and every traj_xe 16-byte aligned), 16 R or Ed beyond INT32_MAX (the
+ * float count of xe and the edge count are 32-bit sizes of a batch).  Only the serial walk has a mixed form.                  */
+typedef struct v2x_rollout_mixed {
+  int32_t n_pools, T;               /* 1..8 pools; every pool walks the same T >= 1 steps */
+  const v2x_rollout_traj* pools;    /* [host][n_pools], strictly ascending step.problem.n; pools[k].T == T;
+                                       pools[k].r.model must be NULL; r.batch and r.q are not read */
+  v2x_model* model;                 /* a variable_graphs model with rb channels, or NULL: nobody is greedy */
+  float* xe; int32_t *graph_off, *row_ptr, *col_idx;   /* [dev] the ragged batch, written by the call (unused without a model) */
+  float* q;                         /* [dev] [R][rb] */
+} v2x_rollout_mixed;
+int  v2x_rollout_steps_mixed(const v2x_rollout_mixed* m, void* stream);
+
 /* v2x_eval_steps: the T steps of an EVALUATION episode in one call -- v2x_rollout_steps without a replay memory, paying up to
  * two schemes per state and returning their rates, not only a reward.  Enqueues, in this order on one stream with no parallel
  * branches,
