@@ -220,59 +220,72 @@ class GnnQModel(object):
         self.engine.set_weights(weights)
 
     def keras_layer_table(self):
-        """[(layer name, [weight names])] of the layers that own weights, in the order of get_weights() -- the names
-        Keras gives the reference model's layers (BS_brain.py:121-200).  Auto-named layers get their class's snake-case
-        name and a running index in CREATION order: the message-passing layers are created stage by stage, node by node
-        (:154-164: gnn_layer_1..N, then N+1..2N), the hidden Dense layers node by node (:176-200: dense_1/2/3 are node
-        1's 80/40/20, dense_4/5/6 node 2's, ...).  The running index is global to the Keras session, so the second
-        model BS builds (the target network, :106) continues where the first stopped: `model_index` offsets it."""
-        sp = self.spec
-        slots = list(range(1, sp.n_nodes + 1)) if not sp.share_weights else [None]
-        n_slots = len(slots)
-        gnn_base = self.model_index * sp.n_mp_layers * n_slots
-        dense_base = self.model_index * 3 * n_slots
-        table = []
-        for stage in range(sp.n_mp_layers + 1):
-            for i, k in enumerate(slots):
-                if stage == 0:
-                    name = 'D%d_GNN' % k if k else 'GNN'
-                else:
-                    name = 'gnn_layer_%d' % (gnn_base + (stage - 1) * n_slots + i + 1)
-                table.append((name, ['%s/%s:0' % (name, w) for w in ('W1', 'W2', 'W3', 'bias')]))
-        for layer in range(4):
-            for i, k in enumerate(slots):
-                if layer == 3:
-                    name = 'D%d_Decide_Output' % k if k else 'Decide_Output'
-                else:
-                    name = 'dense_%d' % (dense_base + 3 * i + layer + 1)
-                table.append((name, ['%s/kernel:0' % name, '%s/bias:0' % name]))
-        return table
+        """keras_layer_table(spec, model_index) of this model"""
+        return keras_layer_table(self.spec, self.model_index)
 
     def save_weights(self, filepath, overwrite=True):
-        """Weights only, like Keras `save_weights` (no optimizer state: BS_brain.py:853-870).  A '.h5' / '.hdf5' name
-        is written as a Keras-layout HDF5 file through libhdf5 (h5weights.py) when that library can be loaded;
-        otherwise (and for any other name) the container is NumPy's .npz under exactly the name the caller gives."""
-        from . import h5weights
-        weights = self.get_weights()
-        if str(filepath).lower().endswith(('.h5', '.hdf5', '.keras.h5')) and h5weights.available():
-            it = iter(weights)
-            layers = [(ln, [(wn, next(it)) for wn in wns]) for ln, wns in self.keras_layer_table()]
-            h5weights.save_keras_weights(filepath, layers)
-            return
-        arrays = {('w%03d' % i): w for i, w in enumerate(weights)}
-        with open(filepath, 'wb') as f:
-            np.savez(f, **arrays)
+        """Weights only, like Keras `save_weights` (no optimizer state: BS_brain.py:853-870): save_weight_file."""
+        save_weight_file(filepath, self.get_weights(), self.keras_layer_table())
 
     def load_weights(self, filepath):
-        """Keras-layout HDF5 (matched to the model by ORDER of the weighted layers, as Keras does) or the .npz
-        container written by save_weights; the format is detected from the file signature."""
-        from . import h5weights
-        if h5weights.is_hdf5(filepath):
-            layers = h5weights.load_keras_weights(filepath)
-            self.set_weights([arr for _, ws in layers for _, arr in ws])
-            return
-        with np.load(filepath) as z:
-            self.set_weights([z['w%03d' % i] for i in range(len(z.files))])
+        """load_weight_file into this model"""
+        self.set_weights(load_weight_file(filepath))
+
+
+def keras_layer_table(spec, model_index=0):
+    """[(layer name, [weight names])] of the layers that own weights, in the order of get_weights() -- the names
+    Keras gives the reference model's layers (BS_brain.py:121-200).  Auto-named layers get their class's snake-case
+    name and a running index in CREATION order: the message-passing layers are created stage by stage, node by node
+    (:154-164: gnn_layer_1..N, then N+1..2N), the hidden Dense layers node by node (:176-200: dense_1/2/3 are node
+    1's 80/40/20, dense_4/5/6 node 2's, ...).  The running index is global to the Keras session, so the second
+    model BS builds (the target network, :106) continues where the first stopped: `model_index` offsets it."""
+    sp = spec
+    slots = list(range(1, sp.n_nodes + 1)) if not sp.share_weights else [None]
+    n_slots = len(slots)
+    gnn_base = model_index * sp.n_mp_layers * n_slots
+    dense_base = model_index * 3 * n_slots
+    table = []
+    for stage in range(sp.n_mp_layers + 1):
+        for i, k in enumerate(slots):
+            if stage == 0:
+                name = 'D%d_GNN' % k if k else 'GNN'
+            else:
+                name = 'gnn_layer_%d' % (gnn_base + (stage - 1) * n_slots + i + 1)
+            table.append((name, ['%s/%s:0' % (name, w) for w in ('W1', 'W2', 'W3', 'bias')]))
+    for layer in range(4):
+        for i, k in enumerate(slots):
+            if layer == 3:
+                name = 'D%d_Decide_Output' % k if k else 'Decide_Output'
+            else:
+                name = 'dense_%d' % (dense_base + 3 * i + layer + 1)
+            table.append((name, ['%s/kernel:0' % name, '%s/bias:0' % name]))
+    return table
+
+
+def save_weight_file(filepath, weights, layer_table):
+    """The weight list of an engine (get_weights()) into one file.  A '.h5' / '.hdf5' name is written as a Keras-layout HDF5
+    file through libhdf5 (h5weights.py) with the names of layer_table (keras_layer_table) when that library can be loaded;
+    otherwise (and for any other name) the container is NumPy's .npz under exactly the name the caller gives."""
+    from . import h5weights
+    if str(filepath).lower().endswith(('.h5', '.hdf5', '.keras.h5')) and h5weights.available():
+        it = iter(weights)
+        layers = [(ln, [(wn, next(it)) for wn in wns]) for ln, wns in layer_table]
+        h5weights.save_keras_weights(filepath, layers)
+        return
+    arrays = {('w%03d' % i): w for i, w in enumerate(weights)}
+    with open(filepath, 'wb') as f:
+        np.savez(f, **arrays)
+
+
+def load_weight_file(filepath):
+    """-> the weight list of a file save_weight_file wrote: Keras-layout HDF5 (matched to the model by ORDER of the weighted
+    layers, as Keras does) or the .npz container; the format is detected from the file signature."""
+    from . import h5weights
+    if h5weights.is_hdf5(filepath):
+        layers = h5weights.load_keras_weights(filepath)
+        return [arr for _, ws in layers for _, arr in ws]
+    with np.load(filepath) as z:
+        return [z['w%03d' % i] for i in range(len(z.files))]
 
 
 class BS(object):

@@ -107,6 +107,12 @@ class Eval(C.Structure):
         [(k, C.c_void_p) for k in TRAJ_WORKSPACES + EVAL_RESULTS]
 
 
+class EvalMixed(C.Structure):
+    """v2x_eval_mixed of include/v2xgnn.h"""
+    _fields_ = [("n_pools", C.c_int32), ("T", C.c_int32), ("pools", C.POINTER(Eval)), ("model", C.c_void_p)] + \
+        [(k, C.c_void_p) for k in ("xe", "graph_off", "row_ptr", "col_idx", "q")]
+
+
 class ReplayPool(C.Structure):
     """v2x_replay_pool of include/v2xgnn.h"""
     _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
@@ -215,6 +221,7 @@ SYMBOLS = [
     ("v2x_rollout_steps_mixed", C.c_int, [C.POINTER(RolloutMixed), _P]),
     ("v2x_eval_steps_result_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_eval_steps", C.c_int, [C.POINTER(Eval), _P]),
+    ("v2x_eval_steps_mixed", C.c_int, [C.POINTER(EvalMixed), _P]),
     ("v2x_traj_wide_workspace_bytes", _L, [_I, _I, _I, _I]),
     ("v2x_rollout_steps_wide", C.c_int, [C.POINTER(RolloutTraj), _P, _L, _P]),
     ("v2x_eval_steps_wide", C.c_int, [C.POINTER(Eval), _P, _L, _P]),

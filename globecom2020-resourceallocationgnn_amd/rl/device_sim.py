@@ -58,6 +58,14 @@ DeviceBatchedEnviron per link count (rl/mixed.py, MixedAgent(rollout='trajectory
     rows = rollout_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [storage8, storage12], heads, capacities,
                                w_v2v, w_v2i, engine)                                          # -> [RolloutResult] per pool
 
+... and their evaluation episodes (v2x_eval_steps_mixed: the same walk, assembly and forward, one finish launch that pays both
+schemes of every pool), every pool with its own policy upload and result download; resident_evaluate_steps_mixed for one
+DeviceBatchedEnviron per link count (MixedAgent.test_run(eval_backend='device')); afterwards every pool's trajectory_states(T)
+holds its T snapshots:
+
+    rows = eval_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [baseline8, baseline12], w_v2v, w_v2i,
+                            engine)                                                           # -> [EvalResult] per pool
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -69,7 +77,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, MIXED_MAX_POOLS, OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, check, load_library)
+from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -989,6 +997,37 @@ class DeviceChannels(object):
             io['eval_free'] = []
         return io
 
+    def _eval_upload(self, io, T, ex, ra, ba):
+        """the host's draws of an evaluation block -> io['eval_policy_dev'] through the next of the four page-locked copies (its
+        event guards the reuse)"""
+        t, i = self.torch, io['eval_next']
+        io['eval_next'] = (i + 1) % 4
+        if io['eval_policy_ev'][i] is not None:
+            io['eval_policy_ev'][i].synchronize()
+        pin, K, n = io['eval_policy_pin'][i].numpy(), T * self.E, self.n
+        nb = self.eval_steps_policy_bytes(T, ba is not None)
+        pin[:4 * K * n].view(np.int32)[:] = ra.reshape(-1)
+        pin[4 * K * n:4 * K * n + K] = ex.reshape(-1)
+        if ba is not None:
+            pin[nb - 4 * K * n:nb].view(np.int32)[:] = ba.reshape(-1)
+        io['eval_policy_dev'][:nb].copy_(io['eval_policy_pin'][i][:nb], non_blocking=True)
+        self.traffic['bytes_up'] += nb
+        if io['eval_policy_ev'][i] is None:
+            io['eval_policy_ev'][i] = t.cuda.Event()
+        io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
+
+    def _eval_download(self, io, T, S):
+        """the result block of S schemes in io['eval_result_dev'] -> a page-locked copy (a returned one, or a new one); -> the
+        EvalResult, its download in flight"""
+        t = self.torch
+        size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
+        pinned = free.pop() if free else t.zeros(io['eval_result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
+        pinned[:size].copy_(io['eval_result_dev'][:size], non_blocking=True)
+        self.traffic['bytes_down'] += size
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return EvalResult(free, ev, pinned, self.E, self.n, self.rb, T, S)
+
     def eval_steps_struct(self, T, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None, baseline=True):
         """the v2x_eval of the resident tensors and the buffers of _eval_io(T) (what eval_steps() passes to the library)"""
         io = self._eval_io(T)
@@ -1028,34 +1067,13 @@ class DeviceChannels(object):
         if not self._obs_ready:
             raise RuntimeError("eval_steps: no observe() since the last step()")
         io = self._eval_io(T)
-        t, i = self.torch, io['eval_next']
-        io['eval_next'] = (i + 1) % 4
-        if io['eval_policy_ev'][i] is not None:
-            io['eval_policy_ev'][i].synchronize()
-        pin, K, n = io['eval_policy_pin'][i].numpy(), T * self.E, self.n
-        nb = self.eval_steps_policy_bytes(T, ba is not None)
-        pin[:4 * K * n].view(np.int32)[:] = ra.reshape(-1)
-        pin[4 * K * n:4 * K * n + K] = ex.reshape(-1)
-        if ba is not None:
-            pin[nb - 4 * K * n:nb].view(np.int32)[:] = ba.reshape(-1)
-        io['eval_policy_dev'][:nb].copy_(io['eval_policy_pin'][i][:nb], non_blocking=True)
-        self.traffic['bytes_up'] += nb
-        if io['eval_policy_ev'][i] is None:
-            io['eval_policy_ev'][i] = t.cuda.Event()
-        io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
+        self._eval_upload(io, T, ex, ra, ba)
         r = self.eval_steps_struct(T, v2v_weight, v2i_weight, engine, row_ptr, power, ba is not None)
         self._keep_actions = self._t['actions']
         self._trajectory_call(self._lib.v2x_eval_steps, self._lib.v2x_eval_steps_wide, self._lib.v2x_eval_steps_split, r, T, walk,
                               stream_phase)
         self._obs_ready = True
-        S = 2 if ba is not None else 1
-        size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
-        pinned = free.pop() if free else t.zeros(io['eval_result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
-        pinned[:size].copy_(io['eval_result_dev'][:size], non_blocking=True)
-        self.traffic['bytes_down'] += size
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return EvalResult(free, ev, pinned, self.E, n, self.rb, T, S)
+        return self._eval_download(io, T, 2 if ba is not None else 1)
 
     def trajectory_states(self, T):
         """-> TrajectoryStates: the T snapshots the last rollout_steps() / eval_steps() of block length T left in its workspace,
@@ -1203,6 +1221,108 @@ def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads,
     for env, result in zip(envs, results):
         env._resident_after(result)
     return results
+
+
+def _check_eval_mixed(who, channels, explore, policy_random, baseline_actions):
+    """what eval_steps_mixed refuses of its lists, before any device work -> (channels, T, [check_eval_steps] per pool)"""
+    channels = _check_mixed_pools(who, channels, dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions))
+    T = _block_length(explore[0])
+    checked = []
+    for k, dc in enumerate(channels):
+        if _block_length(explore[k]) != T:
+            raise ValueError("%s: pool %d (%d links) has a block of %d steps, pool 0 of %d" % (who, k, dc.n, _block_length(explore[k]), T))
+        if (baseline_actions[k] is None) != (baseline_actions[0] is None):
+            raise ValueError("%s: pool %d (%d links) has %s baseline_actions, pool 0 has %s: one number of schemes for all pools"
+                             % (who, k, dc.n, "no" if baseline_actions[k] is None else "", "none" if baseline_actions[0] is None else "them"))
+        try:
+            checked.append(dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
+        except ValueError as err:
+            raise ValueError("%s: pool %d (%d links): %s" % (who, k, dc.n, err))
+    return channels, T, checked
+
+
+def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, power=None):
+    """DeviceChannels.eval_steps for several link counts in ONE library call (v2x_eval_steps_mixed): channels is one
+    DeviceChannels per link count in ascending size, and explore [T, E_k], policy_random [T, E_k, n_k] and baseline_actions
+    [T, E_k, n_k] (None in every place: no baseline scheme) are lists with pool k's argument of eval_steps in place k (the
+    same T everywhere).  One launch walks every simulator of every pool, one forward of a variable_graphs `engine` scores all
+    their observations as one ragged batch (None: nobody is greedy anywhere, no forward), one launch pays both schemes of
+    every (pool, t, e).  Per pool the bits of its own eval_steps, given the same Q-values.  Every pool keeps its own policy
+    upload and result download.  Afterwards every pool's trajectory_states(T) holds its T snapshots.
+    -> [EvalResult] per pool, the downloads in flight."""
+    who = "eval_steps_mixed"
+    channels, T, checked = _check_eval_mixed(who, channels, explore, policy_random, baseline_actions)
+    if engine is not None and not (engine.spec.variable_graphs and engine.spec.n_channels == channels[0].rb):
+        raise ValueError("%s: scoring needs a variable_graphs engine of %d channels" % (who, channels[0].rb))
+    for dc in channels:
+        dc._init_device()
+        if dc.device != channels[0].device:
+            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
+        if not dc._obs_ready:
+            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    baseline = checked[0][3] is not None
+    table = (Eval * len(channels))()
+    ios = []
+    for k, (dc, (_, ex, ra, ba)) in enumerate(zip(channels, checked)):
+        io = dc._eval_io(T)
+        dc._eval_upload(io, T, ex, ra, ba)
+        table[k] = dc.eval_steps_struct(T, v2v_weight, v2i_weight, engine=None, power=power, baseline=baseline)
+        ios.append(io)
+    m = EvalMixed(n_pools=len(channels), T=T, pools=table, model=None)
+    if engine is not None:
+        buf = mixed_rollout_buffers(channels, T)
+        m.model = engine._h
+        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx', 'q'):
+            setattr(m, name, buf[name].data_ptr())
+    for dc in channels:
+        dc._keep_actions = dc._t['actions']
+    check(channels[0]._lib, channels[0]._lib.v2x_eval_steps_mixed(C.byref(m), channels[0]._stream()))
+    out = []
+    for dc, io in zip(channels, ios):
+        dc._obs_ready = True
+        dc.walk_calls['serial'] += 1
+        out.append(dc._eval_download(io, T, 2 if baseline else 1))
+    return out
+
+
+def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None):
+    """eval_steps_mixed() on the resident states of one DeviceBatchedEnviron (streams='device') per link count, ascending size:
+    the bookkeeping of DeviceBatchedEnviron.evaluate_steps around every environment, the ONE library call in the middle.
+    Afterwards env.trajectory_states(T) of every environment holds that pool's T snapshots.
+    -> [EvalResult] per environment, the downloads in flight."""
+    who = "eval_steps_mixed"
+    envs = list(envs)
+    for name, arg in dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions).items():
+        if len(arg) != len(envs):
+            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
+    for env in envs:
+        if getattr(env, 'stream_backend', None) != 'device':
+            raise ValueError("%s needs streams='device' in every environment (mobility and the MT19937 streams advance inside the "
+                             "call)" % who)
+    _check_eval_mixed(who, [_PoolShape(env) for env in envs], explore, policy_random, baseline_actions)   # before any device work
+    channels = [env._resident_before(who, lambda dc, k=k: dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
+                for k, env in enumerate(envs)]
+    results = eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine)
+    for env, result in zip(envs, results):
+        env._resident_after(result)
+    return results
+
+
+class _PoolShape(object):
+    """what the argument checks of a mixed call read of a DeviceChannels, taken from an environment whose device side may not
+    exist yet: the checks then run before the first environment's state is touched"""
+
+    def __init__(self, env):
+        self.E, self.n, self.rb = env.E, env.n_Veh, env.n_RB
+
+    def check_eval_steps(self, explore, policy_random, baseline_actions):
+        return DeviceChannels.check_eval_steps(self, explore, policy_random, baseline_actions)
+
+    def check_observe(self, n, C_, rb=None):
+        return DeviceChannels.check_observe(n, C_, rb)
+
+    def _check_mobility(self, who, mobility):
+        return None
 
 
 # attribute of BatchedEnviron -> (device tensor, host shape from (E, n, rb))

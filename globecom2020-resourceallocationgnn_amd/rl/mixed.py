@@ -14,12 +14,17 @@ ragged path scores and fits batches whose graphs differ in size.  This module is
                 one ragged forward, one finish launch for all link counts); the epsilon-greedy draws are taken ahead in the
                 order the host rollout takes them, the transitions land in the pools' slots on the device, and the rewards
                 come back with the losses at the end of the episode.  The default stays 'host'.
+                test_run() evaluates the network on ANY set of link counts (the training sizes or others) against the
+                random baseline and, on request, the optimum; eval_backend='device' runs an episode of all link counts as ONE
+                library call (v2x_eval_steps_mixed) and one stacked optimum search per link count.  save_weights() /
+                load_weights() keep the online and the target network in the files of rl.run.weight_file_names.
 
 Only regular graphs (in-degree n - 2 everywhere) are stored: a transition whose graph has a link that is its own receiver (two
 vehicles on one spot, rare) is counted in MixedReplay.dropped_irregular and left out -- the assembly is closed-form because
 every stored graph of a pool has the same shape.
 """
 import ctypes as C
+import os
 
 import numpy as np
 
@@ -27,11 +32,14 @@ from .. import lib as _lib
 from ..engine import DeviceBatch, GnnEngine, current_stream_ptr
 from ..packing import PackedBatch
 from ..spec import GnnSpec
-from .agent import Memory, MEMORY_CAPACITY, UPDATE_TARGET_FREQUENCY, MAX_EPSILON, MIN_EPSILON
+from .agent import Memory, MEMORY_CAPACITY, UPDATE_TARGET_FREQUENCY, MAX_EPSILON, MIN_EPSILON, _random_channels
 from .replay import DeviceReplay
 
 MIN_LINKS, MAX_LINKS = 3, DeviceReplay.MAX_LINKS
 ROLLOUTS = ('host', 'trajectory')                     # how MixedAgent makes the iterations of a train step
+EVAL_BACKENDS = ('host', 'device')                    # how MixedAgent.test_run makes the steps of an episode
+EVAL_OPT_BACKENDS = ('device', 'bound', 'local')      # where MixedAgent.test_run searches the optimum (rl/optimum.py)
+SCHEMES = ('gnn', 'random', 'optimal')                # the books of MixedAgent.test_run
 
 
 def _check_sizes(sizes, what):
@@ -59,6 +67,34 @@ def mixed_quotas(batch, weights):
     for k in by_remainder[:batch - sum(quota)]:
         quota[k] += 1
     return quota
+
+
+def draw_eval_step(envs, n_channels, fixed_epsilon):
+    """the host draws of ONE step of MixedAgent.test_run, on the process-wide numpy stream: environment after environment
+    (the caller's order: ascending size), simulator after simulator -- the random scheme's action, then np.random.random(),
+    and _random_channels right after it when that draw is below fixed_epsilon (the simulator explores)
+    -> ([baseline [E, n] int], [explore [E] uint8], [policy_random [E, n] int, zeros where greedy]) per environment"""
+    baseline, explore, rand = [], [], []
+    for env in envs:
+        E, n = env.E, env.n_Veh
+        b, x, r = np.zeros((E, n), int), np.zeros(E, np.uint8), np.zeros((E, n), int)
+        for e in range(E):
+            b[e] = _random_channels(n, 1, n_channels).reshape(n)
+            if np.random.random() < fixed_epsilon:
+                x[e] = 1
+                r[e] = _random_channels(n, 1, n_channels).reshape(n)
+        baseline.append(b)
+        explore.append(x)
+        rand.append(r)
+    return baseline, explore, rand
+
+
+def draw_eval_episode_ahead(envs, n_channels, fixed_epsilon, T):
+    """the draws of the T steps of an episode, taken before its first step runs: step after step draw_eval_step -- nothing else
+    draws inside an episode, so the numpy stream is the host loop's
+    -> ([baseline [T, E, n]], [explore [T, E] uint8], [policy_random [T, E, n]]) per environment"""
+    steps = [draw_eval_step(envs, n_channels, fixed_epsilon) for _ in range(T)]
+    return tuple([np.stack([step[part][k] for step in steps]) for k in range(len(envs))] for part in range(3))
 
 
 class MixedReplay(object):
@@ -197,6 +233,8 @@ class MixedAgent(object):
                                         " with streams=%r" % e.stream_backend if isinstance(e, DeviceBatchedEnviron) else ""))
         self.rollout = rollout
         self.rollout_stats = {'trajectory': 0, 'host': 0}         # rollouts (one per train step) by the path that made them
+        self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
+        self._eval_opt = None
         self._regular_look = None                                 # (the receivers last looked at, were all their graphs regular)
         self.envs = sorted(envs, key=lambda e: e.n_Veh)           # ascending size everywhere
         self.sizes = sizes
@@ -230,10 +268,12 @@ class MixedAgent(object):
         """[(xe [E, n, 16], mask [E, n], col [E, n (n - 2)], regular [E])] per environment, ascending size"""
         return [e.observe_packed(self.num_CH) for e in self.envs]
 
-    def score(self, obs):
-        """Q-values of all environments' observations by ONE forward of one ragged batch -> [q [E, n, C]] per environment"""
+    def score(self, obs, envs=None):
+        """Q-values of all environments' observations by ONE forward of one ragged batch -> [q [E, n, C]] per environment.
+        envs: the environments the observations are of (default: the agent's own)"""
+        envs = self.envs if envs is None else envs
         xe, rp, ci, sizes, edges = [], [np.zeros(1, np.int64)], [], [], 0
-        for env, (x, mask, col, regular) in zip(self.envs, obs):
+        for env, (x, mask, col, regular) in zip(envs, obs):
             E, n = mask.shape
             xe.append(x.reshape(E * n, 16))
             sizes += [n] * E
@@ -251,7 +291,7 @@ class MixedAgent(object):
                          np.concatenate(ci).astype(np.int32), graph_off=offs)
         q = self.online.forward(pb)
         out, r = [], 0
-        for env in self.envs:
+        for env in envs:
             rows = env.E * env.n_Veh
             out.append(q[r:r + rows].reshape(env.E, env.n_Veh, -1))
             r += rows
@@ -305,12 +345,14 @@ class MixedAgent(object):
         self.num_step += self.n_sims
         return rewards
 
-    def _all_regular(self):
-        """every environment's resident graph is regular.  Receivers are fixed within an episode, so one look per set of
-        receivers suffices (after a reset: one small download per environment); no wait for a result row in between."""
-        key = tuple(np.asarray(e.dest).tobytes() for e in self.envs)
+    def _all_regular(self, envs=None):
+        """every environment's resident graph is regular (envs: default the agent's own).  Receivers are fixed within an
+        episode, so one look per set of receivers suffices (after a reset: one small download per environment); no wait for a
+        result row in between."""
+        envs = self.envs if envs is None else envs
+        key = tuple(np.asarray(e.dest).tobytes() for e in envs)
         if self._regular_look is None or self._regular_look[0] != key:
-            self._regular_look = (key, all(bool(np.all(e.resident_regular(self.num_CH))) for e in self.envs))
+            self._regular_look = (key, all(bool(np.all(e.resident_regular(self.num_CH))) for e in envs))
         return self._regular_look[1]
 
     def _trajectory_rollout(self, drawn):
@@ -392,9 +434,10 @@ class MixedAgent(object):
         s = st.cpu().numpy()
         return float(loss.cpu().numpy()[0]), float(s[0, 0] / (R * C_)), float(s[1, 0] / R)
 
-    def train(self, num_episodes, num_train_steps, verbose=False):
+    def train(self, num_episodes, num_train_steps, verbose=False, save_dir=None):
         """episodes x train steps x (ceil(50 / sum E) rollout iterations + 1 replay); target sync whenever another 500
-        transitions have been collected.  -> (loss [1, episodes, steps], {link count: rewards [episodes, steps, iterations x E]},
+        transitions have been collected.  save_dir: save_weights(save_dir, num_episodes, num_train_steps) at the end.
+        -> (loss [1, episodes, steps], {link count: rewards [episodes, steps, iterations x E]},
         Q mean [episodes, steps], Q max mean [episodes, steps])"""
         self.num_Episodes, self.num_Train_Step = int(num_episodes), int(num_train_steps)
         self.num_step, self._sync_mark = 0, 0
@@ -429,4 +472,170 @@ class MixedAgent(object):
             if verbose:
                 print('episode', ep + 1, 'loss %.4f' % loss[0, ep].mean(),
                       'reward', {n: round(float(v[ep].sum()), 3) for n, v in rewards.items()})
+        if save_dir is not None:
+            self.save_weights(save_dir, num_episodes, num_train_steps)
         return loss, rewards, q_mean, q_max
+
+    # ------------------------------------------------------------------ weights
+    def _weight_paths(self, save_dir, num_episodes, num_train_steps):
+        from .run import weight_file_names
+        return [os.path.join(save_dir, name) for name in weight_file_names(int(num_episodes), int(num_train_steps), self.batch_size)]
+
+    def save_weights(self, save_dir, num_episodes, num_train_steps):
+        """the online and the target network into save_dir under the names of rl.run.weight_file_names(num_episodes,
+        num_train_steps, batch size), in the container of GnnQModel.save_weights -> the two paths"""
+        from ..bs_brain import keras_layer_table, save_weight_file
+        os.makedirs(save_dir, exist_ok=True)
+        paths = self._weight_paths(save_dir, num_episodes, num_train_steps)
+        for index, (engine, path) in enumerate(zip((self.online, self.target), paths)):
+            save_weight_file(path, engine.get_weights(), keras_layer_table(self.spec, index))
+        return paths
+
+    def load_weights(self, save_dir, num_episodes, num_train_steps):
+        """the online and the target network from the two files save_weights wrote -> the two paths"""
+        from ..bs_brain import load_weight_file
+        paths = self._weight_paths(save_dir, num_episodes, num_train_steps)
+        for engine, path in zip((self.online, self.target), paths):
+            engine.set_weights(load_weight_file(path))
+        return paths
+
+    # ------------------------------------------------------------------ evaluation
+    def _check_test_run(self, eval_envs, opt_backend, eval_backend, num_test_step):
+        """ValueError for anything test_run cannot take, before any draw or reset -> the environments in ascending size"""
+        if eval_backend not in EVAL_BACKENDS:
+            raise ValueError("MixedAgent.test_run: eval_backend must be one of %s, got %r" % (list(EVAL_BACKENDS), eval_backend))
+        if opt_backend not in EVAL_OPT_BACKENDS:
+            raise ValueError("MixedAgent.test_run: opt_backend must be one of %s (the searches of rl/optimum.py on the GPU), got %r"
+                             % (list(EVAL_OPT_BACKENDS), opt_backend))
+        envs = list(eval_envs)
+        _check_sizes([getattr(e, 'n_Veh', 0) for e in envs], "MixedAgent.test_run")
+        for e in envs:
+            if not hasattr(e, 'observe_packed') or not hasattr(e, 'E'):
+                raise ValueError("MixedAgent.test_run steps BatchedEnviron simulators, got %s" % type(e).__name__)
+            if e.n_RB != self.num_CH or not e.packed_ok(self.num_CH):
+                raise ValueError("MixedAgent.test_run: the environment of %d links must have n_RB = %d and packed observations "
+                                 "(libv2xsim.so), n_RB is %d" % (e.n_Veh, self.num_CH, e.n_RB))
+        if eval_backend == 'device':
+            from .device_sim import MAX_STATES, DeviceBatchedEnviron
+            for e in envs:
+                if not isinstance(e, DeviceBatchedEnviron) or e.stream_backend != 'device':
+                    raise ValueError("MixedAgent.test_run: eval_backend='device' steps every environment on the device: the "
+                                     "environment of %d links must be a DeviceBatchedEnviron with streams='device', got %s%s"
+                                     % (e.n_Veh, type(e).__name__,
+                                        " with streams=%r" % e.stream_backend if isinstance(e, DeviceBatchedEnviron) else ""))
+                if num_test_step * e.E > MAX_STATES:
+                    raise ValueError("MixedAgent.test_run: eval_backend='device' needs T E <= %d (the snapshots of an episode are "
+                                     "one stacked search problem), got T = %d, E = %d at %d links"
+                                     % (MAX_STATES, num_test_step, e.E, e.n_Veh))
+        return sorted(envs, key=lambda e: e.n_Veh)
+
+    def _optimum_actions(self, states, n_states, n, opt_backend, opt_restarts, calls):
+        """the joint actions [n_states, n] one search of rl/optimum.py finds for the stacked states (an environment's E
+        simulators, or the T E snapshots of an episode); calls: the single-state calls the search stands for -- 'bound' gets
+        their node budget"""
+        from .optimum import DEFAULT_LOCAL_RESTARTS, DEFAULT_MAX_NODES, OptimalAllocation, decode
+        if self._eval_opt is None:
+            self._eval_opt = OptimalAllocation(self.online.device)
+        opt, w_v2v, w_v2i = self._eval_opt, self.v2v_weight, self.v2i_weight
+        if opt_backend == 'local':
+            restarts = DEFAULT_LOCAL_RESTARTS if opt_restarts is None else opt_restarts
+            return np.asarray(opt.search_local(states, w_v2v, w_v2i, restarts=restarts)[0]).reshape(n_states, n)
+        if opt_backend == 'bound':
+            index, _ = opt.search_bound(states, w_v2v, w_v2i, max_nodes=calls * DEFAULT_MAX_NODES)
+        else:
+            index, _ = opt.search(states, w_v2v, w_v2i)
+        return decode(index, n, self.num_CH).reshape(n_states, n)
+
+    def test_run(self, eval_envs, num_episodes, num_test_step, opt_flag=False, opt_backend='device', opt_restarts=None,
+                 fixed_epsilon=0.0, eval_backend='host'):
+        """Agent.test_run for the shared-weight network on several link counts at once: the policy (greedy, or random with
+        probability fixed_epsilon per simulator and step) next to the random-action baseline and, with opt_flag, the optimum.
+        eval_envs: BatchedEnvirons of 1..8 distinct link counts -- not necessarily the training sizes; the E_k simulators of an
+        environment are parallel episodes.  -> {link count: {'gnn': books, 'random': books[, 'optimal': books]}}, books the five
+        arrays of Agent.test_run -- return [episodes, E_k], reward [episodes, E_k, steps], V2V rates [episodes, E_k, steps, n],
+        V2I rates and base-station interference [episodes, E_k, steps, C] -- filled with its numpy expressions.
+        A step of the 'host' loop: draw_eval_step (every environment in ascending size, every simulator: the random scheme's
+        action, np.random.random(), _random_channels if it is below fixed_epsilon); the baseline's rates
+        (compute_reward_with_channel_selection); with opt_flag one search of rl/optimum.py per environment over its E_k states
+        (opt_backend 'device': exhaustive, 'bound': branch and bound, 'local' with opt_restarts restarts: a lower bound on the
+        optimum, not the optimum; the host's brute force is refused) and the rates of what it found; ONE score() of all
+        observations when somebody is greedy; env.act under the policy's actions.
+        eval_backend='device' (every environment a DeviceBatchedEnviron with streams='device', T E_k <= 65535; anything else is
+        a ValueError before any draw or reset): the draws of an episode are taken ahead in the host loop's order
+        (draw_eval_episode_ahead), ONE resident_evaluate_steps_mixed call walks, scores and pays all link counts, and with
+        opt_flag one stacked search and one rates() call per link count run on trajectory_states(T) ('bound' with the node
+        budget of T E_k single calls).  Same books, numpy stream, num_step and simulator state as 'host'.  An episode in which
+        some environment's graph is not regular after the reset runs through the host loop; eval_stats counts both kinds."""
+        T, C_ = int(num_test_step), self.num_CH
+        envs = self._check_test_run(eval_envs, opt_backend, eval_backend, T)
+        n_sims = sum(e.E for e in envs)
+        w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
+        schemes = SCHEMES if opt_flag else SCHEMES[:2]
+
+        def book(E, n):
+            return [np.zeros((num_episodes, E)), np.zeros((num_episodes, E, T)), np.zeros((num_episodes, E, T, n)),
+                    np.zeros((num_episodes, E, T, C_)), np.zeros((num_episodes, E, T, C_))]
+
+        def record(b, ep, e, st, v2v, v2i, interference):
+            b[1][ep, e, st] = w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i)
+            b[0][ep, e] += b[1][ep, e, st]
+            b[2][ep, e, st, :] = np.sum(v2v, axis=1)
+            b[3][ep, e, st, :] = v2i
+            b[4][ep, e, st, :] = interference
+
+        def record_optimum(b, ep, e, st, v2v, v2i, interference):
+            if w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i) > 0:             # at least one feasible solution
+                record(b, ep, e, st, v2v, v2i, interference)
+
+        books = {env.n_Veh: {s: book(env.E, env.n_Veh) for s in schemes} for env in envs}
+        for ep in range(num_episodes):
+            for env in envs:
+                env.new_random_game(env.n_Veh)
+            if eval_backend == 'device' and T > 0 and self._all_regular(envs):
+                from .device_sim import resident_evaluate_steps_mixed
+                baseline, explore, rand = draw_eval_episode_ahead(envs, C_, fixed_epsilon, T)
+                anybody = not all(x.all() for x in explore)
+                results = resident_evaluate_steps_mixed(envs, explore, rand, baseline, w_v2v, w_v2i,
+                                                        engine=self.online if anybody else None)
+                for env, res in zip(envs, results):
+                    E, n, b = env.E, env.n_Veh, books[env.n_Veh]
+                    r = res.resolve()
+                    if opt_flag:
+                        states = env.trajectory_states(T)
+                        found = self._optimum_actions(states, T * E, n, opt_backend, opt_restarts, T * E)
+                        o_v2v, o_v2i, o_intf = (a.reshape((T, E) + a.shape[1:]) for a in states.rates(found))
+                    for st in range(T):
+                        for e in range(E):
+                            record(b['random'], ep, e, st, r.v2v_rate[1, st, e][:, None], r.v2i_rate[1, st, e], r.interference[1, st, e])
+                            if opt_flag:
+                                record_optimum(b['optimal'], ep, e, st, o_v2v[st, e][:, None], o_v2i[st, e], o_intf[st, e])
+                            record(b['gnn'], ep, e, st, r.v2v_rate[0, st, e][:, None], r.v2i_rate[0, st, e], r.interference[0, st, e])
+                self.num_step += T * n_sims
+                self.eval_stats['device_episodes'] += 1
+                continue
+            self.eval_stats['host_episodes'] += 1
+            for st in range(T):
+                baseline, explore, rand = draw_eval_step(envs, C_, fixed_epsilon)
+                for env, a in zip(envs, baseline):
+                    v2v, v2i, intf = env.compute_reward_with_channel_selection(a[:, :, None])
+                    for e in range(env.E):
+                        record(books[env.n_Veh]['random'], ep, e, st, v2v[e], v2i[e], intf[e])
+                if opt_flag:
+                    for env in envs:
+                        found = self._optimum_actions(env, env.E, env.n_Veh, opt_backend, opt_restarts, env.E)
+                        v2v, v2i, intf = env.compute_reward_with_channel_selection(found[:, :, None])
+                        for e in range(env.E):
+                            record_optimum(books[env.n_Veh]['optimal'], ep, e, st, v2v[e], v2i[e], intf[e])
+                actions = [r[:, :, None].copy() for r in rand]
+                if not all(x.all() for x in explore):
+                    obs = [env.observe_packed(C_) for env in envs]
+                    for a, x, q in zip(actions, explore, self.score(obs, envs)):
+                        g = np.nonzero(x == 0)[0]
+                        if len(g):
+                            a[g] = np.argmax(q[g], axis=2)[:, :, None]
+                for env, a in zip(envs, actions):
+                    v2v, v2i, intf = env.act(a)
+                    for e in range(env.E):
+                        record(books[env.n_Veh]['gnn'], ep, e, st, v2v[e], v2i[e], intf[e])
+                self.num_step += n_sims
+        return books

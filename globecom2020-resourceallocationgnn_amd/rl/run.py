@@ -8,6 +8,13 @@
                               [--opt-rank [--opt-rank-backend bound [--opt-rank-max-nodes N]]] \\
                               [--sim-backend device --sim-streams device --eval-backend device
                                [--trajectory-walk wide [--trajectory-streams split]]]
+
+A shared-weight network trained on several link counts at once (rl.train --mixed-links ... --save-dir D) is evaluated per link
+count, on the training sizes or on others, --envs parallel episodes per size (rl/mixed.py MixedAgent.test_run):
+
+    python -m v2xgnn.rl.run   --mixed-links 8,12,20 [--eval-links 8,16,28] [--envs 4] --feedback 64 --batch 4096 --train-steps 20 \\
+                              --save-dir D [--opt --opt-backend device | bound | local] \\
+                              [--sim-backend device --sim-streams device --eval-backend device]
 """
 import argparse
 import json
@@ -109,7 +116,7 @@ def rank_summary(book):
             "mean_reward_uniform_exact": float(book['uniform_mean_reward'].mean())}
 
 
-def main(argv=None):
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--links", type=int, default=4)
     ap.add_argument("--feedback", type=int, default=16)
@@ -121,8 +128,11 @@ def main(argv=None):
     ap.add_argument("--test-episodes", type=int, default=10)
     ap.add_argument("--test-steps", type=int, default=50)
     ap.add_argument("--opt", action="store_true", help="also run the brute-force optimum (C^N joint actions)")
-    ap.add_argument("--opt-backend", choices=("host", "device", "bound", "local"), default="host",
-                    help="where --opt searches: numpy on the host (C^N <= 65536) or the GPU, exhaustively (C^N <= 2^36)\n                         or by branch and bound (bound: up to 32 links, e.g. 20 x 4);\n                         local: NOT the optimum but a lower bound on it, the best of --opt-restarts local searches on the GPU\n                         (up to 128 links, e.g. 100 x 4)")
+    ap.add_argument("--opt-backend", choices=("host", "device", "bound", "local"), default=None,
+                    help="where --opt searches: numpy on the host (the default; C^N <= 65536) or the GPU, exhaustively (device: "
+                         "C^N <= 2^36; the default with --mixed-links) or by branch and bound (bound: up to 32 links, e.g. 20 x 4); "
+                         "local: NOT the optimum but a lower bound on it, the best of --opt-restarts local searches on the GPU "
+                         "(up to 128 links, e.g. 100 x 4)")
     ap.add_argument("--opt-restarts", type=int, default=None,
                     help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
     ap.add_argument("--opt-rank", action="store_true",
@@ -134,8 +144,92 @@ def main(argv=None):
     ap.add_argument("--opt-rank-max-nodes", type=int, default=None,
                     help="node budget per ranked step of --opt-rank-backend bound (default: rl/optimum.py DEFAULT_RANK_MAX_NODES)")
     ap.add_argument("--seed", type=int, default=11)
+    ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
+                    help="evaluate the shared-weight network rl.train --mixed-links N1,N2,... saved (rl/mixed.py): the training "
+                         "sizes, used only to find the files; --links is ignored")
+    ap.add_argument("--eval-links", default=None, metavar="M1,M2,...",
+                    help="with --mixed-links: the link counts to evaluate on (distinct multiples of 4 up to 28, at most 8; "
+                         "default: the training sizes)")
+    ap.add_argument("--envs", type=int, default=1,
+                    help="with --mixed-links: simulators per evaluated link count, each a parallel episode (default 1)")
     add_sim_arguments(ap)
+    return ap
+
+
+def parse_args(argv=None):
+    """the command line, parsed, with every check that concerns --mixed-links made (a refusal exits with its message)
+    -> (parser, arguments); arguments.mixed_links / eval_links are then sorted lists of link counts (or None)"""
+    from .train import parse_mixed_links
+    ap = build_parser()
     args = ap.parse_args(argv)
+    if args.mixed_links is None:
+        if args.eval_links is not None or args.envs != 1:
+            ap.error("--eval-links / --envs need --mixed-links")
+        if args.opt_backend is None:
+            args.opt_backend = "host"
+        return ap, args
+    # the mixed network is scored as one ragged batch of all link counts: what holds one link count stays refused
+    if args.opt_rank:
+        ap.error("--mixed-links has no ranks: --opt-rank ranks the actions of one link count (rl.run --links)")
+    if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
+        ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
+                 "link count")
+    if args.opt_backend == "host":
+        ap.error("--mixed-links searches the optimum on the GPU: --opt-backend host enumerates one link count on the host "
+                 "(--opt-backend device, bound or local)")
+    if args.opt_backend is None:
+        args.opt_backend = "device"
+    if args.envs < 1:
+        ap.error("--mixed-links steps batched simulators: --envs must be at least 1 (got %d)" % args.envs)
+    if args.sim_streams == "device" and args.sim_backend != "device":
+        ap.error("--sim-streams device needs --sim-backend device")
+    if args.eval_backend != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
+    try:
+        args.mixed_links = parse_mixed_links(args.mixed_links)
+    except ValueError as exc:
+        ap.error(str(exc))
+    if args.eval_links is None:
+        args.eval_links = list(args.mixed_links)
+    else:
+        try:
+            args.eval_links = parse_mixed_links(args.eval_links)
+        except ValueError as exc:
+            ap.error(str(exc).replace("--mixed-links", "--eval-links"))
+    return ap, args
+
+
+def run_mixed(args):
+    """--mixed-links: load the two networks rl.train --mixed-links saved and evaluate them on --eval-links, --envs parallel
+    episodes per link count (MixedAgent.test_run) -> the JSON summary, per link count the mean rewards per scheme"""
+    from .mixed import MixedAgent
+    random.seed(args.seed)
+    np.random.seed(args.seed)
+    cfg = RL_Config()
+    cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
+    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.sim_backend, streams=args.sim_streams)
+            for k, n in enumerate(args.eval_links)]
+    agent = MixedAgent(envs, cfg, args.feedback, seed=args.seed)
+    agent.load_weights(args.save_dir, args.episodes, args.train_steps)
+    books = agent.test_run(envs, args.test_episodes, args.test_steps, opt_flag=args.opt, opt_backend=args.opt_backend,
+                           opt_restarts=args.opt_restarts, eval_backend=args.eval_backend)
+    per_links = {}
+    for n in args.eval_links:
+        per_links[str(n)] = {"mean_reward_gnn": float(books[n]['gnn'][1].mean()),
+                             "mean_reward_random": float(books[n]['random'][1].mean())}
+        if args.opt:
+            per_links[str(n)]["mean_reward_optimal"] = float(books[n]['optimal'][1].mean())
+    print(json.dumps({"mixed_links": args.mixed_links, "eval_links": args.eval_links, "envs_per_size": args.envs,
+                      "test_episodes": args.test_episodes, "test_steps": args.test_steps, "eval_backend": args.eval_backend,
+                      "episodes_by_path": dict(agent.eval_stats), "per_links": per_links}))
+    agent.close()
+    return 0
+
+
+def main(argv=None):
+    ap, args = parse_args(argv)
+    if args.mixed_links is not None:
+        return run_mixed(args)
     if args.links < 4 or args.links % 4:
         # the simulator drops vehicles in groups of four, one per direction (Environment.py:217-231), and the
         # observation divides by links - 2 (BS_brain.py:405)

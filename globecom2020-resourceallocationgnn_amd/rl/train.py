@@ -149,7 +149,7 @@ def parse_mixed_links(text):
 
 def run_mixed(args):
     """--mixed-links: one MixedAgent over one batched simulator per link count (--mixed-sim-backend / --mixed-sim-streams say
-    where they run, --mixed-rollout who makes the rollout)"""
+    where they run, --mixed-rollout who makes the rollout); with --save-dir the two networks are saved at the end"""
     from .mixed import MixedAgent
     sizes = parse_mixed_links(args.mixed_links)
     random.seed(args.seed)
@@ -166,7 +166,7 @@ def run_mixed(args):
     t0 = time.perf_counter()
     with ctx:
         agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed, rollout=args.mixed_rollout)
-        loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True)
+        loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True, save_dir=args.save_dir)
     dt = time.perf_counter() - t0
     n_fit = args.episodes * args.train_steps
     print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,

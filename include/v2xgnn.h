@@ -726,6 +726,38 @@ typedef struct v2x_eval {
 int64_t v2x_eval_steps_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
 int  v2x_eval_steps(const v2x_eval* r, void* stream);
 
+/* v2x_eval_steps_mixed: v2x_eval_steps for up to 8 pools of DIFFERENT link counts in one call, all scored by one forward of one
+ * ragged batch on a variable_graphs model -- the evaluation sibling of v2x_rollout_steps_mixed (rl/mixed.py MixedAgent.test_run:
+ * an episode of every link count at once).  Pool k is the v2x_eval of its own resident state, trajectory workspace and result
+ * block (E_k states of n_k links); every pool walks the same T steps and pays the same S schemes (S = 2 when the pools have
+ * baseline_actions, else 1).  The ragged batch, gbase_k, rbase_k and ebase_k are those of v2x_rollout_steps_mixed.  Enqueues,
+ * in this order on one stream with no parallel branches,
+ *   k_sim_trajectory_mixed  as in v2x_rollout_steps_mixed, unchanged;
+ *   k_traj_assemble_mixed   as in v2x_rollout_steps_mixed, unchanged -- skipped without a model;
+ *   v2x_forward             of that batch on `model` into q [R][rb] -- skipped when model is NULL (nobody is greedy);
+ *   k_eval_finish_mixed     grid (S T S(E_k)), one wave per (pool, scheme, t, e): the body of k_eval_finish on its pool's arguments
+ *                           with q + rbase_k rb.  Pool-major: pool k owns blocks S gbase_k .. S gbase_k + S T E_k - 1, and inside
+ *                           a pool the order is k_eval_finish's (scheme, t, e): every pool's result block has exactly the layout
+ *                           of v2x_eval_steps (v2x_eval_steps_result_bytes(E_k, n_k, rb, T, S)), and the policy scheme at
+ *                           t = T - 1 leaves the pool's resident arrays as v2x_eval_steps does.
+ * The device functions are those of v2x_eval_steps: per pool the bits of that call (given the same Q rows).  Same rules: all
+ * pointers [dev] except `pools` ([host]; the kernels take their tables by value), asynchronous, no allocation, no
+ * synchronisation, no environment variable read; every check of every pool and of the mixed part before the first launch.
+ * V2X_EINVAL with a text that names the pool (v2x_last_error(NULL)): n_pools outside 1..8 or a null table, link counts not
+ * strictly ascending, a pool whose T is not the call's, a pool with a model of its own, anything v2x_eval_steps refuses of a
+ * pool (T E_k <= 65535 among it), pools that differ in rb or in having baseline_actions, a model that is not variable_graphs
+ * or whose channel count is not rb, a null xe / graph_off / row_ptr / col_idx / q or a pool's null explore with a model (xe and
+ * every traj_xe 16-byte aligned), 16 R or Ed beyond INT32_MAX.  Only the serial walk has a mixed form.                        */
+typedef struct v2x_eval_mixed {
+  int32_t n_pools, T;               /* 1..8 pools; every pool walks the same T >= 1 steps */
+  const v2x_eval* pools;            /* [host][n_pools], strictly ascending step.problem.n; pools[k].T == T;
+                                       pools[k].model must be NULL; batch and q of a pool are not read */
+  v2x_model* model;                 /* a variable_graphs model with rb channels, or NULL: nobody is greedy */
+  float* xe; int32_t *graph_off, *row_ptr, *col_idx;   /* [dev] the ragged batch, written by the call (unused without a model) */
+  float* q;                         /* [dev] [R][rb] */
+} v2x_eval_mixed;
+int  v2x_eval_steps_mixed(const v2x_eval_mixed* m, void* stream);
+
 /* The wide walk: v2x_rollout_steps and v2x_eval_steps with the trajectory spread over the chip.  k_sim_trajectory walks a
  * state's T steps one after the other in one workgroup; of a step only mobility with the MT19937 stream position and the
  * shadowing recursion depend on the step before.  The wide forms replace that one launch by four, in this order on the one
