@@ -113,6 +113,11 @@ class EvalMixed(C.Structure):
         [(k, C.c_void_p) for k in ("xe", "graph_off", "row_ptr", "col_idx", "q")]
 
 
+class TrajWs(C.Structure):
+    """v2x_traj_ws of include/v2xgnn.h"""
+    _fields_ = [("wide_ws", C.c_void_p), ("wide_ws_bytes", C.c_int64), ("split_ws", C.c_void_p), ("split_ws_bytes", C.c_int64)]
+
+
 class ReplayPool(C.Structure):
     """v2x_replay_pool of include/v2xgnn.h"""
     _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
@@ -228,6 +233,8 @@ SYMBOLS = [
     ("v2x_traj_split_workspace_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_rollout_steps_split", C.c_int, [C.POINTER(RolloutTraj), _P, _L, _P, _L, _P]),
     ("v2x_eval_steps_split", C.c_int, [C.POINTER(Eval), _P, _L, _P, _L, _P]),
+    ("v2x_rollout_steps_mixed_wide", C.c_int, [C.POINTER(RolloutMixed), C.POINTER(TrajWs), _P]),
+    ("v2x_eval_steps_mixed_wide", C.c_int, [C.POINTER(EvalMixed), C.POINTER(TrajWs), _P]),
 ]
 
 

@@ -53,15 +53,17 @@ the forms are level (profiles/trajectory_split_timing.jso
 Several DeviceChannels of DIFFERENT link counts make their rollouts in one library call (v2x_rollout_steps_mixed: one walk
 launch, one assembly launch, one forward of a variable_graphs engine over all pools' observations, one finish launch), every
 pool with its own policy upload, replay storage and result download; resident_rollout_steps_mixed does the same for one
-DeviceBatchedEnviron per link count (rl/mixed.py, MixedAgent(rollout='trajectory')); the serial walk only:
+DeviceBatchedEnviron per link count (rl/mixed.py, MixedAgent(rollout='trajectory')).  walk='wide' spreads every pool's steps
+over the chip (v2x_rollout_steps_mixed_wide: six launches in the walk's place, the wide walk with the split stream phase on
+every pool's own cached workspaces, the same bits; each pool's walk_calls['wide'] and stream_phase_calls['split'] count it):
 
     rows = rollout_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [storage8, storage12], heads, capacities,
                                w_v2v, w_v2i, engine)                                          # -> [RolloutResult] per pool
 
 ... and their evaluation episodes (v2x_eval_steps_mixed: the same walk, assembly and forward, one finish launch that pays both
 schemes of every pool), every pool with its own policy upload and result download; resident_evaluate_steps_mixed for one
-DeviceBatchedEnviron per link count (MixedAgent.test_run(eval_backend='device')); afterwards every pool's trajectory_states(T)
-holds its T snapshots:
+DeviceBatchedEnviron per link count (MixedAgent.test_run(eval_backend='device')), walk='wide' as above
+(v2x_eval_steps_mixed_wide); afterwards every pool's trajectory_states(T) holds its T snapshots:
 
     rows = eval_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [baseline8, baseline12], w_v2v, w_v2i,
                             engine)                                                           # -> [EvalResult] per pool
@@ -77,7 +79,8 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, check, load_library)
+from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, TrajWs, check,
+                   load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -1153,16 +1156,37 @@ def _check_mixed_pools(who, channels, per_pool):
     return channels
 
 
+def _mixed_trajectory_call(serial, wide, m, channels, T, walk):
+    """the library call of a mixed trajectory struct m in the form `walk` names: with 'wide' every pool supplies the wide and
+    split workspaces its own single-size calls use (v2x_traj_ws per pool).  Counted per pool as _trajectory_call counts: the
+    mixed wide walk is a wide call whose stream phase is split."""
+    dc0 = channels[0]
+    if walk == 'wide':
+        table = (TrajWs * len(channels))()
+        for k, dc in enumerate(channels):
+            ws, ss = dc._wide_workspace(T), dc._split_workspace(T)       # (cached in the pool's _rollout_io(T): they outlive the call)
+            table[k] = TrajWs(ws.data_ptr(), ws.numel(), ss.data_ptr(), ss.numel())
+        check(dc0._lib, wide(C.byref(m), table, dc0._stream()))
+    else:
+        check(dc0._lib, serial(C.byref(m), dc0._stream()))
+    for dc in channels:
+        dc.walk_calls[walk] += 1
+        if walk == 'wide':
+            dc.stream_phase_calls['split'] += 1
+
+
 def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None,
-                        power=None):
+                        power=None, walk='serial'):
     """DeviceChannels.rollout_steps for several link counts in ONE library call (v2x_rollout_steps_mixed): channels is one
     DeviceChannels per link count in ascending size, and explore [T, E_k], random_actions [T, E_k, n_k], storages, heads and
     capacities are lists with pool k's argument of rollout_steps in place k (the same T everywhere).  One launch walks every
     simulator of every pool, one forward of a variable_graphs `engine` scores all their observations as one ragged batch
     (None: nobody is greedy anywhere, no forward), one launch picks, pays and stores every transition into its own pool's
     slots.  Per pool the bits of its own rollout_steps, given the same Q-values.  Every pool keeps its own policy upload and
-    result download.  -> [RolloutResult] per pool, the downloads in flight."""
+    result download.  walk='wide': six launches over all pools' steps in the walk launch's place (v2x_rollout_steps_mixed_wide,
+    the same bits).  -> [RolloutResult] per pool, the downloads in flight."""
     who = "rollout_steps_mixed"
+    check_walk(who, walk)
     per_pool = dict(explore=explore, random_actions=random_actions, storages=storages, heads=heads, capacities=capacities)
     channels = _check_mixed_pools(who, channels, per_pool)
     T = _block_length(explore[0])
@@ -1195,20 +1219,22 @@ def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capa
             setattr(m, name, buf[name].data_ptr())
     for dc in channels:
         dc._keep_actions = dc._t['actions']
-    check(channels[0]._lib, channels[0]._lib.v2x_rollout_steps_mixed(C.byref(m), channels[0]._stream()))
+    lib = channels[0]._lib
+    _mixed_trajectory_call(lib.v2x_rollout_steps_mixed, lib.v2x_rollout_steps_mixed_wide, m, channels, T, walk)
     out = []
     for dc, io in zip(channels, ios):
         dc._obs_ready = True
-        dc.walk_calls['serial'] += 1
         out.append(dc._download_result(io, T))
     return out
 
 
-def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None):
+def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None,
+                                 walk='serial'):
     """rollout_steps_mixed() on the resident states of one DeviceBatchedEnviron (streams='device') per link count, ascending
     size: the bookkeeping of DeviceBatchedEnviron.rollout_steps around every environment, the ONE library call in the middle.
     -> [RolloutResult] per environment, the downloads in flight."""
     who = "rollout_steps_mixed"
+    check_walk(who, walk)
     envs = list(envs)
     per_pool = dict(explore=explore, random_actions=random_actions, storages=storages, heads=heads, capacities=capacities)
     for name, arg in per_pool.items():
@@ -1217,7 +1243,8 @@ def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads,
     channels = [env._resident_before(who, lambda dc, k=k: dc.check_rollout_steps(explore[k], random_actions[k], storages[k], heads[k],
                                                                                  capacities[k]))
                 for k, env in enumerate(envs)]
-    results = rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=engine)
+    results = rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=engine,
+                                  walk=walk)
     for env, result in zip(envs, results):
         env._resident_after(result)
     return results
@@ -1241,16 +1268,19 @@ def _check_eval_mixed(who, channels, explore, policy_random, baseline_actions):
     return channels, T, checked
 
 
-def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, power=None):
+def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, power=None,
+                     walk='serial'):
     """DeviceChannels.eval_steps for several link counts in ONE library call (v2x_eval_steps_mixed): channels is one
     DeviceChannels per link count in ascending size, and explore [T, E_k], policy_random [T, E_k, n_k] and baseline_actions
     [T, E_k, n_k] (None in every place: no baseline scheme) are lists with pool k's argument of eval_steps in place k (the
     same T everywhere).  One launch walks every simulator of every pool, one forward of a variable_graphs `engine` scores all
     their observations as one ragged batch (None: nobody is greedy anywhere, no forward), one launch pays both schemes of
     every (pool, t, e).  Per pool the bits of its own eval_steps, given the same Q-values.  Every pool keeps its own policy
-    upload and result download.  Afterwards every pool's trajectory_states(T) holds its T snapshots.
+    upload and result download.  walk='wide': six launches over all pools' steps in the walk launch's place
+    (v2x_eval_steps_mixed_wide, the same bits).  Afterwards every pool's trajectory_states(T) holds its T snapshots.
     -> [EvalResult] per pool, the downloads in flight."""
     who = "eval_steps_mixed"
+    check_walk(who, walk)
     channels, T, checked = _check_eval_mixed(who, channels, explore, policy_random, baseline_actions)
     if engine is not None and not (engine.spec.variable_graphs and engine.spec.n_channels == channels[0].rb):
         raise ValueError("%s: scoring needs a variable_graphs engine of %d channels" % (who, channels[0].rb))
@@ -1276,21 +1306,23 @@ def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
             setattr(m, name, buf[name].data_ptr())
     for dc in channels:
         dc._keep_actions = dc._t['actions']
-    check(channels[0]._lib, channels[0]._lib.v2x_eval_steps_mixed(C.byref(m), channels[0]._stream()))
+    lib = channels[0]._lib
+    _mixed_trajectory_call(lib.v2x_eval_steps_mixed, lib.v2x_eval_steps_mixed_wide, m, channels, T, walk)
     out = []
     for dc, io in zip(channels, ios):
         dc._obs_ready = True
-        dc.walk_calls['serial'] += 1
         out.append(dc._eval_download(io, T, 2 if baseline else 1))
     return out
 
 
-def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None):
+def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None,
+                                  walk='serial'):
     """eval_steps_mixed() on the resident states of one DeviceBatchedEnviron (streams='device') per link count, ascending size:
     the bookkeeping of DeviceBatchedEnviron.evaluate_steps around every environment, the ONE library call in the middle.
     Afterwards env.trajectory_states(T) of every environment holds that pool's T snapshots.
     -> [EvalResult] per environment, the downloads in flight."""
     who = "eval_steps_mixed"
+    check_walk(who, walk)
     envs = list(envs)
     for name, arg in dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions).items():
         if len(arg) != len(envs):
@@ -1302,7 +1334,7 @@ def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions
     _check_eval_mixed(who, [_PoolShape(env) for env in envs], explore, policy_random, baseline_actions)   # before any device work
     channels = [env._resident_before(who, lambda dc, k=k: dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
                 for k, env in enumerate(envs)]
-    results = eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine)
+    results = eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, walk=walk)
     for env, result in zip(envs, results):
         env._resident_after(result)
     return results

@@ -14,6 +14,9 @@ ragged path scores and fits batches whose graphs differ in size.  This module is
                 one ragged forward, one finish launch for all link counts); the epsilon-greedy draws are taken ahead in the
                 order the host rollout takes them, the transitions land in the pools' slots on the device, and the rewards
                 come back with the losses at the end of the episode.  The default stays 'host'.
+                trajectory_walk='wide': that call and test_run's device episodes spread every pool's steps over the chip
+                (v2x_rollout_steps_mixed_wide / v2x_eval_steps_mixed_wide: six launches in the walk's place, the same bits);
+                with rollout='host' it applies to evaluation alone.  The default stays 'serial'.
                 test_run() evaluates the network on ANY set of link counts (the training sizes or others) against the
                 random baseline and, on request, the optimum; eval_backend='device' runs an episode of all link counts as ONE
                 library call (v2x_eval_steps_mixed) and one stacked optimum search per link count.  save_weights() /
@@ -212,10 +215,12 @@ class MixedAgent(object):
     simulators of all environments (stored and dropped transitions alike)."""
 
     def __init__(self, envs, cfg, feat_dim, n_mp_layers=2, use_graph=False, device=0, seed=None, capacity=MEMORY_CAPACITY,
-                 rollout='host'):
+                 rollout='host', trajectory_walk='serial'):
+        from .device_sim import check_walk
         envs = list(envs)
         if rollout not in ROLLOUTS:
             raise ValueError("MixedAgent: rollout must be one of %s, got %r" % (list(ROLLOUTS), rollout))
+        check_walk("MixedAgent: trajectory_walk", trajectory_walk)
         sizes = _check_sizes([getattr(e, 'n_Veh', 0) for e in envs], "MixedAgent")
         for e in envs:
             if not hasattr(e, 'observe_packed') or not hasattr(e, 'E'):
@@ -232,6 +237,7 @@ class MixedAgent(object):
                                      % (e.n_Veh, type(e).__name__,
                                         " with streams=%r" % e.stream_backend if isinstance(e, DeviceBatchedEnviron) else ""))
         self.rollout = rollout
+        self.trajectory_walk = trajectory_walk                    # the walk of the mixed trajectory calls (rollout and evaluation)
         self.rollout_stats = {'trajectory': 0, 'host': 0}         # rollouts (one per train step) by the path that made them
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
         self._eval_opt = None
@@ -377,7 +383,7 @@ class MixedAgent(object):
         heads = [mem.reserve(e.n_Veh, T * e.E) for e in self.envs]
         results = resident_rollout_steps_mixed(self.envs, explore, actions, [mem.storage(n) for n in sizes], heads,
                                                [mem.pools[n].capacity for n in sizes], self.v2v_weight, self.v2i_weight,
-                                               engine=self.online if anybody else None)
+                                               engine=self.online if anybody else None, walk=self.trajectory_walk)
         for env, result in zip(self.envs, results):
             mem.commit(env.n_Veh, T * env.E, result)
         self.num_step += T * self.n_sims
@@ -596,7 +602,7 @@ class MixedAgent(object):
                 baseline, explore, rand = draw_eval_episode_ahead(envs, C_, fixed_epsilon, T)
                 anybody = not all(x.all() for x in explore)
                 results = resident_evaluate_steps_mixed(envs, explore, rand, baseline, w_v2v, w_v2i,
-                                                        engine=self.online if anybody else None)
+                                                        engine=self.online if anybody else None, walk=self.trajectory_walk)
                 for env, res in zip(envs, results):
                     E, n, b = env.E, env.n_Veh, books[env.n_Veh]
                     r = res.resolve()

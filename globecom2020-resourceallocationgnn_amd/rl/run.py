@@ -14,7 +14,7 @@ count, on the training sizes or on others, --envs parallel episodes per size (rl
 
     python -m v2xgnn.rl.run   --mixed-links 8,12,20 [--eval-links 8,16,28] [--envs 4] --feedback 64 --batch 4096 --train-steps 20 \\
                               --save-dir D [--opt --opt-backend device | bound | local] \\
-                              [--sim-backend device --sim-streams device --eval-backend device]
+                              [--sim-backend device --sim-streams device --eval-backend device [--mixed-trajectory-walk wide]]
 """
 import argparse
 import json
@@ -152,6 +152,10 @@ def build_parser():
                          "default: the training sizes)")
     ap.add_argument("--envs", type=int, default=1,
                     help="with --mixed-links: simulators per evaluated link count, each a parallel episode (default 1)")
+    ap.add_argument("--mixed-trajectory-walk", choices=["serial", "wide"], default="serial",
+                    help="with --mixed-links --eval-backend device: how an episode's steps are walked -- 'serial' (the default: one "
+                         "workgroup per simulator, step after step) or 'wide' (the steps of all link counts spread over the chip, "
+                         "six launches in the walk's place; the same bits)")
     add_sim_arguments(ap)
     return ap
 
@@ -165,6 +169,8 @@ def parse_args(argv=None):
     if args.mixed_links is None:
         if args.eval_links is not None or args.envs != 1:
             ap.error("--eval-links / --envs need --mixed-links")
+        if args.mixed_trajectory_walk != "serial":
+            ap.error("--mixed-trajectory-walk %s needs --mixed-links" % args.mixed_trajectory_walk)
         if args.opt_backend is None:
             args.opt_backend = "host"
         return ap, args
@@ -173,7 +179,7 @@ def parse_args(argv=None):
         ap.error("--mixed-links has no ranks: --opt-rank ranks the actions of one link count (rl.run --links)")
     if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
         ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
-                 "link count")
+                 "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
     if args.opt_backend == "host":
         ap.error("--mixed-links searches the optimum on the GPU: --opt-backend host enumerates one link count on the host "
                  "(--opt-backend device, bound or local)")
@@ -185,6 +191,8 @@ def parse_args(argv=None):
         ap.error("--sim-streams device needs --sim-backend device")
     if args.eval_backend != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
         ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
+    if args.mixed_trajectory_walk != "serial" and args.eval_backend != "device":
+        ap.error("--mixed-trajectory-walk %s needs --eval-backend device" % args.mixed_trajectory_walk)
     try:
         args.mixed_links = parse_mixed_links(args.mixed_links)
     except ValueError as exc:
@@ -209,7 +217,7 @@ def run_mixed(args):
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
     envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.sim_backend, streams=args.sim_streams)
             for k, n in enumerate(args.eval_links)]
-    agent = MixedAgent(envs, cfg, args.feedback, seed=args.seed)
+    agent = MixedAgent(envs, cfg, args.feedback, seed=args.seed, trajectory_walk=args.mixed_trajectory_walk)
     agent.load_weights(args.save_dir, args.episodes, args.train_steps)
     books = agent.test_run(envs, args.test_episodes, args.test_steps, opt_flag=args.opt, opt_backend=args.opt_backend,
                            opt_restarts=args.opt_restarts, eval_backend=args.eval_backend)
@@ -221,7 +229,7 @@ def run_mixed(args):
             per_links[str(n)]["mean_reward_optimal"] = float(books[n]['optimal'][1].mean())
     print(json.dumps({"mixed_links": args.mixed_links, "eval_links": args.eval_links, "envs_per_size": args.envs,
                       "test_episodes": args.test_episodes, "test_steps": args.test_steps, "eval_backend": args.eval_backend,
-                      "episodes_by_path": dict(agent.eval_stats), "per_links": per_links}))
+                      "trajectory_walk": args.mixed_trajectory_walk, "episodes_by_path": dict(agent.eval_stats), "per_links": per_links}))
     agent.close()
     return 0
 

@@ -127,6 +127,10 @@ def build_parser():
                     help="with --mixed-links --mixed-sim-backend device --mixed-sim-streams device: 'trajectory' runs all iterations "
                          "of a rollout for ALL link counts as one call on the resident states (one walk launch, one assembly launch, "
                          "one ragged forward, one finish launch); 'host' (the default) scores and stores through the host")
+    ap.add_argument("--mixed-trajectory-walk", choices=["serial", "wide"], default="serial",
+                    help="with --mixed-links --mixed-rollout trajectory: how that call walks the simulators' steps -- 'serial' (the "
+                         "default: one workgroup per simulator, step after step) or 'wide' (the steps of all link counts spread "
+                         "over the chip, six launches in the walk's place; the same bits; DESIGN.md section 3.8 says where it wins)")
     return ap
 
 
@@ -149,7 +153,7 @@ def parse_mixed_links(text):
 
 def run_mixed(args):
     """--mixed-links: one MixedAgent over one batched simulator per link count (--mixed-sim-backend / --mixed-sim-streams say
-    where they run, --mixed-rollout who makes the rollout); with --save-dir the two networks are saved at the end"""
+    where they run, --mixed-rollout who makes the rollout, --mixed-trajectory-walk how its steps are walked); with --save-dir the two networks are saved at the end"""
     from .mixed import MixedAgent
     sizes = parse_mixed_links(args.mixed_links)
     random.seed(args.seed)
@@ -165,13 +169,15 @@ def run_mixed(args):
         ctx = torch.cuda.stream(torch.cuda.Stream())
     t0 = time.perf_counter()
     with ctx:
-        agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed, rollout=args.mixed_rollout)
+        agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed, rollout=args.mixed_rollout,
+                           trajectory_walk=args.mixed_trajectory_walk)
         loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True, save_dir=args.save_dir)
     dt = time.perf_counter() - t0
     n_fit = args.episodes * args.train_steps
     print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,
                       "episodes": args.episodes, "train_steps": args.train_steps, "env_steps": int(agent.num_step),
                       "sim_backend": args.mixed_sim_backend, "sim_streams": args.mixed_sim_streams, "rollout": args.mixed_rollout,
+                      "trajectory_walk": args.mixed_trajectory_walk,
                       "rollouts_by_path": dict(agent.rollout_stats),
                       "stored": {str(n): agent.memory.stored(n) for n in sizes},
                       "dropped_irregular": {str(n): v for n, v in agent.memory.dropped_irregular.items()},
@@ -198,7 +204,7 @@ def parse_args(argv=None):
                      "the rollouts of all link counts in one call)" % args.rollout)
         if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
             ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
-                     "link count")
+                     "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
         if int(os.environ.get("WORLD_SIZE", "1")) > 1 or os.environ.get("V2X_FORCE_DP") == "1" or args.rollouts != "replicated":
             ap.error("--mixed-links runs on one GPU: the ragged replay step has no data-parallel form")
         if args.envs < 1:
@@ -208,12 +214,15 @@ def parse_args(argv=None):
         if args.mixed_rollout == "trajectory" and args.mixed_sim_streams != "device":
             ap.error("--mixed-rollout trajectory needs --mixed-sim-backend device --mixed-sim-streams device (the simulators "
                      "advance inside the call)")
+        if args.mixed_trajectory_walk != "serial" and args.mixed_rollout != "trajectory":
+            ap.error("--mixed-trajectory-walk %s needs --mixed-rollout trajectory" % args.mixed_trajectory_walk)
         try:
             parse_mixed_links(args.mixed_links)
         except ValueError as exc:
             ap.error(str(exc))
-    elif args.mixed_sim_backend != "host" or args.mixed_sim_streams != "host" or args.mixed_rollout != "host":
-        ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-rollout need --mixed-links")
+    elif (args.mixed_sim_backend != "host" or args.mixed_sim_streams != "host" or args.mixed_rollout != "host" or
+          args.mixed_trajectory_walk != "serial"):
+        ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-rollout / --mixed-trajectory-walk need --mixed-links")
     return ap, args
 
 

@@ -663,7 +663,8 @@ int  v2x_rollout_steps(const v2x_rollout_traj* r, void* stream);
  * a pool whose T is not the call's, a pool with a model of its own, anything v2x_rollout_steps refuses of a pool, pools that
  * differ in rb, a model that is not variable_graphs or whose channel count is not rb, a null xe / graph_off / row_ptr /
  * col_idx / q or a pool's null explore with a model (xe and every traj_xe 16-byte aligned), 16 R or Ed beyond INT32_MAX (the
- * float count of xe and the edge count are 32-bit sizes of a batch).  Only the serial walk has a mixed form.                  */
+ * float count of xe and the edge count are 32-bit sizes of a batch).  v2x_rollout_steps_mixed_wide (below, after the split
+ * stream phase) is this call with the wide walk in k_sim_trajectory_mixed's place.                                            */
 typedef struct v2x_rollout_mixed {
   int32_t n_pools, T;               /* 1..8 pools; every pool walks the same T >= 1 steps */
   const v2x_rollout_traj* pools;    /* [host][n_pools], strictly ascending step.problem.n; pools[k].T == T;
@@ -747,7 +748,8 @@ int  v2x_eval_steps(const v2x_eval* r, void* stream);
  * strictly ascending, a pool whose T is not the call's, a pool with a model of its own, anything v2x_eval_steps refuses of a
  * pool (T E_k <= 65535 among it), pools that differ in rb or in having baseline_actions, a model that is not variable_graphs
  * or whose channel count is not rb, a null xe / graph_off / row_ptr / col_idx / q or a pool's null explore with a model (xe and
- * every traj_xe 16-byte aligned), 16 R or Ed beyond INT32_MAX.  Only the serial walk has a mixed form.                        */
+ * every traj_xe 16-byte aligned), 16 R or Ed beyond INT32_MAX.  v2x_eval_steps_mixed_wide (below, after the split stream
+ * phase) is this call with the wide walk in k_sim_trajectory_mixed's place.                                                   */
 typedef struct v2x_eval_mixed {
   int32_t n_pools, T;               /* 1..8 pools; every pool walks the same T >= 1 steps */
   const v2x_eval* pools;            /* [host][n_pools], strictly ascending step.problem.n; pools[k].T == T;
@@ -819,6 +821,33 @@ int  v2x_rollout_steps_split(const v2x_rollout_traj* r, void* wide_ws, int64_t w
                              int64_t split_ws_bytes, void* stream);
 int  v2x_eval_steps_split(const v2x_eval* r, void* wide_ws, int64_t wide_ws_bytes, void* split_ws, int64_t split_ws_bytes,
                           void* stream);
+
+/* The mixed wide walk: v2x_rollout_steps_mixed and v2x_eval_steps_mixed with every pool's trajectory spread over the chip --
+ * the wide walk with the split stream phase, for all link counts at once.  Both calls enqueue, on the one stream with no
+ * parallel branches, exactly what their serial siblings enqueue, with six launches in k_sim_trajectory_mixed's place; each is
+ * the body of its single-size kernel on the arguments of the block's pool (one table of the pools' arguments by value, the
+ * pool found from the block index alone, the largest pool's blocks in the lowest indices):
+ *   k_traj_words_mixed     grid (S E_k), 256 threads: the body of k_traj_words for state e of its pool;
+ *   k_traj_walk_mixed      grid (S E_k), one wave: the body of k_traj_walk;
+ *   k_traj_uniforms_mixed  grid (S_k ceil(T E_k n_u,k / 256)), 256 threads: the body of k_traj_uniforms, one thread per
+ *                          (t, e, i < n_u,k) of its pool -- a pool's padded last block touches nothing of the next pool;
+ *   k_traj_terms_mixed     grid (S_k ceil(T E_k n_el,k / 256)): the body of k_traj_terms, n_el,k = n_k + n_k^2;
+ *   k_traj_scan_mixed      grid (S_k ceil(E_k n_el,k / 256)): the body of k_traj_scan;
+ *   k_traj_observe_mixed   grid (T S E_k), one wave: the body of k_traj_observe for entry (t, e) of its pool.
+ * k_traj_assemble_mixed, v2x_forward and k_rollout_finish_mixed / k_eval_finish_mixed follow unchanged.  Per pool every byte
+ * the call leaves -- resident state, trajectory, replay slots or results, and the pool's two workspaces -- is that of the
+ * serial mixed call and of the pool's own v2x_rollout_steps_split / v2x_eval_steps_split; the forms mix freely on one state.
+ * There is no mixed form of the chained k_traj_stream.
+ * ws [host][n_pools]: per pool its own wide and split workspaces [dev], sized by the pool's own E_k, n_k, rb, T and n_lanes
+ * (v2x_traj_wide_workspace_bytes, v2x_traj_split_workspace_bytes), contents undefined afterwards.
+ * Checks: every check of the serial mixed call, then ws non-NULL and per pool the checks of the _wide and _split forms, all
+ * before the first launch (V2X_EINVAL, the text names the pool: "pool k (n links): ..."); a refused call writes nothing.     */
+typedef struct v2x_traj_ws {
+  void* wide_ws;  int64_t wide_ws_bytes;     /* v2x_traj_wide_workspace_bytes(E_k, n_k, rb, T)            */
+  void* split_ws; int64_t split_ws_bytes;    /* v2x_traj_split_workspace_bytes(E_k, n_k, rb, T, n_lanes_k) */
+} v2x_traj_ws;
+int  v2x_rollout_steps_mixed_wide(const v2x_rollout_mixed* m, const v2x_traj_ws* ws /*[host][n_pools]*/, void* stream);
+int  v2x_eval_steps_mixed_wide(const v2x_eval_mixed* m, const v2x_traj_ws* ws /*[host][n_pools]*/, void* stream);
 
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream

@@ -15,7 +15,14 @@ in one process, warmed up and taken in turn:
 
 Medians of --reps episodes after --warmup, with their min-max; no ratio is promised, the file says who won.
 
+--walk-leg measures something else and nothing of the above: the serial mixed call against the mixed wide walk
+(v2x_eval_steps_mixed_wide) on the same pools, both alive in one process and taken in turn -- the call between HIP events and
+its host enqueue (draws and reset outside), the wall time of an episode through mixed_call and through test_run_device with
+either walk, and the kernels' own durations through torch's profiler; the call also at T = 1.  Written under "eval" into
+profiles/mixed_wide_timing.json (tools/mixed_rollout_timing.py --walk-leg writes "rollout" beside it).
+
     python tools/mixed_eval_timing.py [--out profiles/mixed_eval_timing.json] [--reps 20] [--warmup 3]
+    python tools/mixed_eval_timing.py --walk-leg [--walk-out profiles/mixed_wide_timing.json]
 """
 import argparse
 import json
@@ -37,14 +44,92 @@ def _envs(backend, streams):
     return [start_env_batched(n, E, 1001 + 15485863 * k, backend=backend, streams=streams) for k, n in enumerate(SIZES)]
 
 
+def walk_leg(args, torch):
+    from mixed_rollout_timing import SERIAL_KERNELS, WIDE_KERNELS, merge_walk_leg, walks_in_turn
+    from sim_device_timing import kernel_times
+    from v2xgnn.rl.device_sim import resident_evaluate_steps_mixed
+    from v2xgnn.rl.mixed import MixedAgent, draw_eval_episode_ahead
+    from v2xgnn.rl.sim_config import RL_Config
+    cfg = RL_Config()
+    cfg.set_train_value(FEAT, 0.5, 4096, 1, 0.1)
+    np.random.seed(1001)
+    envs = _envs("device", "device")
+    agent = MixedAgent(envs, cfg, FEAT, seed=1001)
+    shared = ("k_traj_assemble_mixed", "k_eval_finish_mixed")
+    res = {"sizes": list(SIZES), "simulators_per_size": E, "feat_dim": FEAT, "n_mp_layers": 2, "fixed_epsilon": 0.0, "optimum": False,
+           "reps": args.reps, "warmup": args.warmup, "call": [],
+           "baseline": "the serial mixed call of the same build, alive in the same process and taken in turn with the wide one "
+                       "(its kernels and its host path are the parent commit's, unchanged)"}
+
+    def reset_and_draw(steps):
+        for env in envs:
+            env.new_random_game(env.n_Veh)
+        return draw_eval_episode_ahead(envs, 4, 0.0, steps)
+
+    # (1) the call alone, on one set of draws: between HIP events, the host enqueue, the kernels
+    for steps in (T, 1):
+        baseline, explore, rand = reset_and_draw(steps)
+        calls = {w: (lambda w=w: resident_evaluate_steps_mixed(envs, explore, rand, baseline, 1.0, 0.1, engine=agent.online, walk=w))
+                 for w in ("serial", "wide")}
+        out = walks_in_turn(calls, args.reps, args.warmup, torch)
+        out["kernels_ms"] = {"serial": kernel_times(calls["serial"], SERIAL_KERNELS + shared, 10),
+                             "wide": kernel_times(calls["wide"], WIDE_KERNELS + shared, 10)}
+        out["steps"] = steps
+        res["call"].append(out)
+        print("walk call", json.dumps(out), flush=True)
+
+    # (2) an episode: reset, draws, the call, the downloads -- and through test_run, which also fills the books
+    def mixed_call(walk):
+        baseline, explore, rand = reset_and_draw(T)
+        for r in resident_evaluate_steps_mixed(envs, explore, rand, baseline, 1.0, 0.1, engine=agent.online, walk=walk):
+            r.resolve()
+
+    def test_run(walk):
+        agent.trajectory_walk = walk
+        agent.test_run(envs, 1, T, eval_backend='device')
+
+    forms = {"mixed_call_serial": lambda: mixed_call("serial"), "mixed_call_wide": lambda: mixed_call("wide"),
+             "test_run_device_serial": lambda: test_run("serial"), "test_run_device_wide": lambda: test_run("wide")}
+    for _ in range(args.warmup):
+        for fn in forms.values():
+            fn()
+    torch.cuda.synchronize()
+    ms = {name: [] for name in forms}
+    for _ in range(args.reps):
+        for name, fn in forms.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ms[name].append((time.perf_counter() - t0) * 1e3)
+    res["steps"] = T
+    for name, v in ms.items():
+        res[name] = {"wall_ms_per_episode": float(np.median(v)), "min_max": [min(v), max(v)]}
+    for form in ("mixed_call", "test_run_device"):
+        s, w = res[form + "_serial"], res[form + "_wide"]
+        spread = max(s["min_max"][1] - s["min_max"][0], w["min_max"][1] - w["min_max"][0])
+        diff = s["wall_ms_per_episode"] - w["wall_ms_per_episode"]
+        res[form + "_winner"] = "wide" if diff > spread else "serial" if -diff > spread else "level"
+        res[form + "_serial_over_wide"] = round(s["wall_ms_per_episode"] / w["wall_ms_per_episode"], 3)
+    res["walk_calls"] = [dict(e.device_channels.walk_calls) for e in envs]
+    print("walk episode", json.dumps({k: v for k, v in res.items() if k != "call"}), flush=True)
+    merge_walk_leg(args.walk_out, "eval", res)
+    agent.close()
+    return 0
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
+    ap.add_argument("--walk-leg", action="store_true", help="measure the serial against the wide mixed walk, and nothing else")
+    ap.add_argument("--walk-out", default=os.path.join(ROOT, "profiles", "mixed_wide_timing.json"))
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "mixed_eval_timing.json"))
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     args = ap.parse_args(argv)
     import torch
     assert torch.cuda.is_available(), "a measurement needs the GPU"
+    if args.walk_leg:
+        return walk_leg(args, torch)
     from v2xgnn import GnnEngine, GnnSpec
     from v2xgnn.bs_brain import _glorot_list
     from v2xgnn.rl.device_sim import resident_evaluate_steps_mixed
