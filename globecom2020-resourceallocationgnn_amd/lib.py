@@ -74,6 +74,11 @@ class SimStep(C.Structure):
                                    "v2i_interf", "v2v_interf", "actions")]
 
 
+class SimReset(C.Structure):
+    """v2x_sim_reset_args of include/v2xgnn.h"""
+    _fields_ = [("step", SimStep), ("vel", C.c_void_p), ("dest", C.c_void_p), ("status", C.c_void_p)]
+
+
 class Rollout(C.Structure):
     """v2x_rollout of include/v2xgnn.h"""
     _fields_ = [("model", C.c_void_p), ("batch", Batch)] + \
@@ -218,6 +223,8 @@ SYMBOLS = [
     ("v2x_sim_rates", C.c_int, [C.POINTER(OptProblem), _P, _P, _P, _P, _P, _P, _P]),
     ("v2x_sim_stream", C.c_int, [_I, _I, _P, _P, _P, _P, _P, C.c_double, _I, _P, C.c_double, C.c_double, _P, _I, _P]),
     ("v2x_sim_advance", C.c_int, [C.POINTER(SimStep), _P]),
+    ("v2x_sim_reset", C.c_int, [C.POINTER(SimReset), _P]),
+    ("v2x_sim_reset_draw", C.c_int, [C.POINTER(SimReset), _P]),
     ("v2x_rollout_pick", C.c_int, [_I, _I, _I] + [_P] * 11 + [_L, _L, _P, _P]),
     ("v2x_rollout_store", C.c_int, [_I, _I, _I, _P, _P, C.c_double, C.c_double] + [_P] * 6 + [_L, _L, _P, _P, _P]),
     ("v2x_rollout_step", C.c_int, [C.POINTER(Rollout), _P]),

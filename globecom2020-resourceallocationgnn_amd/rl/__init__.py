@@ -5,5 +5,5 @@ from .sim_config import RL_Config                              # noqa: F401
 from .agent import Agent, Memory                               # noqa: F401
 from .batched_env import BatchedEnviron                        # noqa: F401
 from .optimum import OptimalAllocation, BoundBudgetExceeded     # noqa: F401
-from .device_sim import DeviceChannels, DeviceBatchedEnviron    # noqa: F401
+from .device_sim import DeviceChannels, DeviceBatchedEnviron, reset_tie_flags    # noqa: F401
 from .mixed import MixedReplay, MixedAgent                      # noqa: F401

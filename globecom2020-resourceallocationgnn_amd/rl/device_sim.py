@@ -24,6 +24,12 @@ from the host but the actions (v2x_sim_advance: rates, stream, channels, observa
     dc.advance(actions)                         # or all of a step at once
     dc.traffic                                  # {'bytes_up': ..., 'bytes_down': ...}: every byte this object sent over the bus
 
+The episode reset (new_random_game) runs on the resident state too (v2x_sim_reset: the draws, the channel update and the
+observation in three launches; reset_draw() is the first launch alone):
+
+    dc.reset()                                  # new vehicles, initial shadowing, channels, receivers, observation
+    vel, dest, regular, status = dc.fetch_reset()      # one small download; status bit 0: reset_tie_flags(pos, dest)
+
 A DQN rollout runs on the resident state as well, one iteration per call (v2x_rollout_step) or T of them in one call
 (v2x_rollout_steps).  The two calls are ONE host path -- one argument check, one set of buffers per T (T = None: the single
 iteration), one policy upload through a ring of page-locked copies, one struct builder, one result download -- that ends in
@@ -79,7 +85,7 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimStep, TrajWs, check,
+from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimReset, SimStep, TrajWs, check,
                    load_library)
 from .batched_env import BatchedEnviron
 
@@ -96,6 +102,39 @@ _CHANNEL_TENSORS = ('v2i_shadow', 'v2v_shadow', 'v2v_abs', 'v2i_abs', 'v2v_ff', 
 def uniforms_per_step(n, rb):
     """uniforms one channel update of a state consumes: n + n^2 shadowing draws, 2 n rb + 2 n^2 rb Rayleigh draws (even)"""
     return n + n * n + 2 * n * rb + 2 * n * n * rb
+
+
+RESET_MAX_LINKS = 28                                     # v2x_sim_reset: groups of four vehicles, one thread per link in a wave
+RESET_TIE, RESET_NO_DRAW = 1, 2                          # the bits of its status flags
+RESETS = ('host', 'device')                              # who runs new_random_game of a DeviceBatchedEnviron
+
+
+def check_reset_grid(who, lanes, width, height):
+    """ValueError unless the squared distances of a device reset are exact: every lane coordinate a multiple of 2^-10 in
+    [0, 2^15), width and height integers there (vehicles stand on a lane and on an integer along it), so dx dx + dy dy is a sum
+    of two 50-bit integers over 2^20 and the ranking by it is the ranking by the host's np.abs"""
+    tab = np.asarray(lanes, np.float64)
+    if not (np.all(tab >= 0) and np.all(tab < 32768.0) and np.all(tab * 1024.0 == np.floor(tab * 1024.0))):
+        raise ValueError("%s: the device reset ranks neighbours by exact squared distances: lane coordinates must be multiples of "
+                         "2^-10 in [0, 2^15)" % who)
+    for name, v in (('width', width), ('height', height)):
+        if not (0 <= v < 32768.0 and v == np.floor(v)):
+            raise ValueError("%s: the device reset draws positions as integers in [0, %s]: an integer in [0, 2^15) needed, got %r"
+                             % (who, name, v))
+
+
+def reset_tie_flags(pos, dest):
+    """Bit 0 of v2x_sim_reset's status from host arrays: pos [E, n, 2], dest [E, n] -> [E] uint8, 1 where for some link another
+    vehicle (the link itself included) has exactly the squared distance dx dx + dy dy of the link's receiver.  These are the
+    resets whose receivers depend on the order a sort leaves among equal keys: numpy's argsort leaves whatever its build and
+    the CPU give, the device ranks by (squared distance, index)."""
+    pos, dest = np.asarray(pos, np.float64), np.asarray(dest, np.int64)
+    dx = pos[:, :, None, 0] - pos[:, None, :, 0]
+    dy = pos[:, :, None, 1] - pos[:, None, :, 1]
+    d2 = dx * dx + dy * dy                                                   # [e, link, vehicle]
+    same = d2 == np.take_along_axis(d2, dest[:, :, None], axis=2)
+    np.put_along_axis(same, dest[:, :, None], False, axis=2)                 # (the receiver itself)
+    return same.any(axis=(1, 2)).astype(np.uint8)
 
 
 def _align(x, a=64):
@@ -345,7 +384,7 @@ class DeviceChannels(object):
                 'v2v_abs': (E, n, n), 'v2i_abs': (E, n), 'v2v_ff': (E, n, n, rb), 'v2i_ff': (E, n, rb), 'dest': (E, n),
                 'actions': (E, n), 'interf_db': (E, n, rb), 'state': (E, n, 3 * rb + 1), 'xe': (E, n, XE_WIDTH), 'mask': (E, n),
                 'col': (E, n * max(n - 2, 0)), 'regular': (E,), 'v2v_rate': (E, n), 'v2i_rate': (E, m), 'interference': (E, rb),
-                'v2i_interf': (E, rb), 'v2v_interf': (E, n), 'keys': (E, MT_WORDS), 'mtpos': (E,), 'dirs': (E, n)}
+                'v2i_interf': (E, rb), 'v2v_interf': (E, n), 'keys': (E, MT_WORDS), 'mtpos': (E,), 'dirs': (E, n), 'status': (E,)}
 
     @staticmethod
     def check_observe(n, C, rb=None):
@@ -420,6 +459,8 @@ class DeviceChannels(object):
         self._t['keys'] = t.zeros(sh['keys'], dtype=t.int32, device=self.device)
         self._t['mtpos'] = t.full(sh['mtpos'], MT_WORDS, dtype=t.int32, device=self.device)
         self._t['dirs'] = t.zeros(sh['dirs'], dtype=t.int8, device=self.device)
+        self._t['status'] = t.zeros(sh['status'], dtype=t.uint8, device=self.device)
+        self._reset_io = None                            # fetch_reset(): the packed copy of vel | dest | regular | status
         if self._grid is not None:
             self._send_grid()
         # the small results, each group one device buffer and one page-locked copy (one download per group)
@@ -672,6 +713,66 @@ class DeviceChannels(object):
                        **{k: T[k].data_ptr() for k in ('keys', 'mtpos', 'dirs', 'vel', 'lanes', 'u') + _CHANNEL_TENSORS + (
                            'interf_db', 'state', 'xe', 'mask', 'col', 'regular', 'v2v_rate', 'v2i_rate', 'interference',
                            'v2i_interf', 'v2v_interf')})
+
+    # ------------------------------------------------------------------ the episode reset on the resident state
+    def check_reset(self, who="reset"):
+        """ValueError unless an episode reset can run on this object: the limits of v2x_sim_reset and the lane grid"""
+        if self.n % 4 or not 4 <= self.n <= RESET_MAX_LINKS:
+            raise ValueError("%s: a reset places groups of four vehicles: a multiple of 4 in 4..%d links supported, got %d"
+                             % (who, RESET_MAX_LINKS, self.n))
+        self.check_observe(self.n, self.rb)
+        self._check_mobility(who, True)
+        check_reset_grid(who, self._grid[0], self._grid[1], self._grid[2])
+
+    def _sim_reset(self, power=None):
+        T = self._t
+        return SimReset(step=self._sim_step(None, power), vel=T['vel'].data_ptr(), dest=T['dest'].data_ptr(),
+                        status=T['status'].data_ptr())
+
+    def _reset_call(self, who, power):
+        """v2x_sim_<who> on the resident state, after the checks"""
+        self.check_reset(who)
+        self._init_device()
+        self._send_grid()
+        r = self._sim_reset(power)
+        check(self._lib, getattr(self._lib, "v2x_sim_" + who)(C.byref(r), self._stream()))
+
+    def reset_draw(self):
+        """The draws of an episode reset on the resident streams (v2x_sim_reset_draw, one launch): new vehicles into pos / dirs /
+        vel, the initial shadowing, the channel update's uniforms into tensor('u'), the receivers into tensor('dest'), the flags
+        into tensor('status') (bit 0: a receiver tied in distance, reset_tie_flags; bit 1: a draw found no value).  Bit for bit
+        native_sim.reset_vehicles, two native_sim.mt_uniforms calls and native_sim.sample_dest on the ranked neighbours, except
+        the receivers of flagged states."""
+        self._reset_call("reset_draw", None)
+        self._obs_ready = False
+
+    def reset(self, power=None):
+        """new_random_game of every resident state in one call (v2x_sim_reset: reset_draw, the channel update on the new
+        vehicles, the observation of the new receivers -- three launches).  fetch_reset() brings the small results down."""
+        self._reset_call("reset", power)
+        self._obs_ready = True
+
+    def fetch_reset(self):
+        """-> (vel [E, n] float64, dest [E, n] int64, regular [E] bool, status [E] uint8) as the last reset() left them: packed on
+        the device, one download, fresh host arrays"""
+        self._init_device()
+        t, E, n = self.torch, self.E, self.n
+        if self._reset_io is None:
+            nbytes = _align(16 * E * n + 2 * E)
+            self._reset_io = (t.zeros(nbytes, dtype=t.uint8, device=self.device), t.zeros(nbytes, dtype=t.uint8, pin_memory=self._pin))
+        dev, host = self._reset_io
+        o = 0
+        for k, width in (('vel', 8), ('dest', 8), ('regular', 1), ('status', 1)):
+            src = self._t[k]
+            dev[o:o + width * src.numel()].view(src.dtype).view(src.shape).copy_(src)
+            o += width * src.numel()
+        host.copy_(dev, non_blocking=True)
+        self.traffic['bytes_down'] += host.numel()
+        self._sync()
+        raw = host.numpy()
+        vel = raw[:8 * E * n].view(np.float64).reshape(E, n).copy()
+        dest = raw[8 * E * n:16 * E * n].view(np.int64).reshape(E, n).copy()
+        return vel, dest, raw[16 * E * n:16 * E * n + E].astype(bool), raw[16 * E * n + E:16 * E * n + 2 * E].copy()
 
     # ------------------------------------------------------------------ DQN rollouts on the resident state
     # One host path with two entry points: rollout_step() makes one iteration (v2x_rollout_step), rollout_steps() T of them
@@ -1357,6 +1458,14 @@ class _PoolShape(object):
         return None
 
 
+class _ResetRow(object):
+    """what a device reset knows of the observation it left resident: the regularity flags (the part of a RolloutResult that
+    DeviceBatchedEnviron.resident_regular reads)"""
+
+    def __init__(self, regular):
+        self.resident_regular = regular
+
+
 # attribute of BatchedEnviron -> (device tensor, host shape from (E, n, rb))
 _DEVICE_ARRAYS = {
     '_v2i_shadow': ('v2i_shadow', lambda E, n, rb: (E, n)),
@@ -1433,6 +1542,15 @@ class DeviceBatchedEnviron(BatchedEnviron):
     before the next device call.  The host draws of a reset (reset_vehicles, mt_uniforms, sample_dest, anything through an
     MTStream) therefore cost one pull and one push; a step costs none.  Trajectories are those of streams='host' bit for bit.
 
+    reset='device' (needs streams='device' and a lane grid on multiples of 2^-10 below 2^15; the default is 'host'):
+    new_random_game is ONE enqueue on the resident state (DeviceChannels.reset) and one small download of velocities,
+    receivers, regularity and status flags -- no pull of the streams, no push of the reset's arrays.  Everything is the host
+    reset's bit for bit (the initial shadowing to the rounding of the two math libraries) except the receivers of a state where
+    a receiver is tied in squared distance with another vehicle: there numpy's argsort leaves an order that depends on its
+    build, the device ranks by (squared distance, index); `reset_ties` counts such states (reset_tie_flags).  `reset_stats`
+    counts the resets by who ran them: the host runs the reset when the link count changes in that call or a stream holds a
+    cached Gaussian.
+
     Who holds the newer copy of the stream state (keys, positions in the stream, vehicle positions, directions), with
     streams='device' (with streams='host' the host always does and the flags below stay False):
 
@@ -1453,12 +1571,23 @@ class DeviceBatchedEnviron(BatchedEnviron):
       MTStream draw (on_touch)                -> F   -> T    the same
       _flush() before a device call           F      -> F    upload if dirty (not during a reset)
       act(), device channel update            -> T   F       none: the device advances its own copy
-      new_random_game()                       -> F   -> T    download if ahead; the upload waits for the next device call"""
+      new_random_game()                       -> F   -> T    download if ahead; the upload waits for the next device call
+      new_random_game(), reset='device'       -> T   -> F    upload if dirty, then the device resets its own copy"""
 
     def __init__(self, down_lane, up_lane, left_lane, right_lane, width, height, n_envs=1, seeds=None, workers=None,
-                 native=None, lookahead=False, device=0, streams='host'):
+                 native=None, lookahead=False, device=0, streams='host', reset='host'):
         if streams not in ('host', 'device'):
             raise ValueError("streams must be 'host' or 'device', got %r" % (streams,))
+        if reset not in RESETS:
+            raise ValueError("reset must be 'host' or 'device', got %r" % (reset,))
+        if reset == 'device':
+            if streams != 'device':
+                raise ValueError("reset='device' needs streams='device' (the reset draws from the streams where they live)")
+            check_reset_grid("reset='device'", np.concatenate([np.asarray(t, np.float64).ravel() for t in
+                                                               (up_lane, down_lane, left_lane, right_lane)]), width, height)
+        self.reset_backend = reset
+        self.reset_stats = {'device': 0, 'host': 0, 'host_cached_gauss': 0, 'host_links_changed': 0}   # resets, by who ran them and why
+        self.reset_ties = 0                                    # states a device reset flagged (status bit 0, reset_tie_flags)
         if lookahead:
             raise ValueError("DeviceBatchedEnviron has no look-ahead step (the channel update runs on the GPU); lookahead=True "
                              "is refused")
@@ -1532,7 +1661,8 @@ class DeviceBatchedEnviron(BatchedEnviron):
             self._move_pending = False
             BatchedEnviron.renew_positions(self)
 
-    def _flush(self, settle=True):
+    def _flush(self, settle=True, before_reset=False):
+        """before_reset: a device reset follows, which writes velocities and receivers itself (only the lane grid goes up)"""
         E, n, rb = self.E, self.n_Veh, self.n_RB
         if settle and self._move_pending:
             self._settle_streams()
@@ -1549,8 +1679,9 @@ class DeviceBatchedEnviron(BatchedEnviron):
             if self._static_dirty:
                 p = self._proto
                 dc.set_grid((p.up_lanes, p.down_lanes, p.left_lanes, p.right_lanes), p.width, p.height, p.timestep)
-                dc.upload('vel', self.vel)
-                dc.upload('dest', self.dest)
+                if not before_reset:
+                    dc.upload('vel', self.vel)
+                    dc.upload('dest', self.dest)
                 dc._obs_ready = False                          # (new receivers: the resident observation is of the old ones)
                 self._static_dirty = False
             if self._streams_dirty and not self._streams_ahead:
@@ -1572,7 +1703,20 @@ class DeviceBatchedEnviron(BatchedEnviron):
 
     # ------------------------------------------------------------------ the overridden steps
     def new_random_game(self, n_Veh=0):
+        """reset='device': the whole reset is one call on the resident state (DeviceChannels.reset) and one small download;
+        the host reset runs instead (counted in reset_stats) when the link count changes in this call or a stream holds a
+        cached Gaussian, which only the host's generator objects can hand out"""
         self._check_sizes(n_Veh if n_Veh > 0 else self.n_Veh)
+        if self.reset_backend == 'device':
+            if n_Veh > 0 and n_Veh != self.n_Veh:
+                self.reset_stats['host_links_changed'] += 1
+            elif any(s.gauss_next is not None for s in self.streams):
+                self.reset_stats['host_cached_gauss'] += 1
+            else:
+                self.reset_stats['device'] += 1
+                return self._device_reset()
+        else:
+            self.reset_stats['host'] += 1
         self._dev_obs = None
         self._resident_row = None
         self._settle_streams()                                 # the reset draws on the host: its copy of the streams first
@@ -1585,6 +1729,33 @@ class DeviceBatchedEnviron(BatchedEnviron):
             self._in_reset = False
         self._static_dirty = True                              # new velocities and receivers
         self._dev_obs = None                                   # new receivers
+
+    def _device_reset(self):
+        """new_random_game on the resident state: what the host holds newer goes up (a re-seeded stream included), the reset is
+        enqueued, the device then holds the newer streams, positions, directions, channels and observation, and velocities,
+        receivers, regularity and status flags come down in one download"""
+        E, n = self.E, self.n_Veh
+        self._drop_lookahead()
+        self._obs = None
+        self._dev_obs = None
+        self._resident_row = None
+        if self._stream_host.get('pos') is None or self._stream_host['pos'].shape != (E, n, 2):
+            self.pos = np.zeros((E, n, 2))                     # (the host copies a later read downloads into)
+            self.dirs = np.zeros((E, n), np.int8)
+        dc = self._flush(before_reset=True)
+        dc.reset()
+        self._streams_ahead = True
+        self._static_dirty = False                             # velocities and receivers are the device's own
+        self._channels_updated()
+        self._on_device.add('V2V_Interference_all')
+        vel, dest, regular, status = dc.fetch_reset()
+        if np.any(status & RESET_NO_DRAW):
+            raise RuntimeError("device reset: a draw of environment(s) %s found no value within 64 words of its stream (the "
+                               "generator state is broken)" % np.nonzero(status & RESET_NO_DRAW)[0].tolist())
+        self.reset_ties += int(np.count_nonzero(status & RESET_TIE))
+        self.vel, self.dest = vel, dest
+        self.activate_links = np.ones((E, n, 1), dtype=bool)
+        self._resident_row = _ResetRow(regular)
 
     def renew_positions(self):
         if self.stream_backend != 'device':

@@ -44,12 +44,16 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
 
 
 def add_sim_arguments(ap):
-    """--sim-backend / --sim-streams / --eval-backend / --trajectory-walk / --trajectory-streams of the two evaluation drivers"""
+    """--sim-backend / --sim-streams / --sim-reset / --eval-backend / --trajectory-walk / --trajectory-streams of the two
+    evaluation drivers"""
     ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
                     help="where the simulator's channel update, observation and rates run: the single host simulator (the "
                          "default) or ONE batched simulator on the GPU (rl/device_sim.py)")
     ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
                     help="with --sim-backend device: where mobility and the simulator's MT19937 stream advance")
+    ap.add_argument("--sim-reset", choices=["host", "device"], default="host",
+                    help="with --sim-backend device --sim-streams device: who resets the simulator at the start of an episode -- "
+                         "the host library (the default) or the GPU, one call on the state resident in HBM (v2x_sim_reset)")
     ap.add_argument("--eval-backend", choices=["host", "device"], default="host",
                     help="with --sim-backend device --sim-streams device: 'device' runs an evaluation episode as one call for "
                          "its steps and both schemes, one stacked optimum search and one rates call (Agent.test_run)")
@@ -66,6 +70,8 @@ def evaluation_env(ap, args):
     the argument errors are those of rl/train.py"""
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
+    if args.sim_reset == "device" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--sim-reset device needs --sim-backend device --sim-streams device")
     if args.eval_backend != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
         ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
     if args.trajectory_walk != "serial" and args.eval_backend != "device":
@@ -73,7 +79,7 @@ def evaluation_env(ap, args):
     if args.trajectory_streams != "chain" and args.trajectory_walk != "wide":
         ap.error("--trajectory-streams %s needs --trajectory-walk wide" % args.trajectory_streams)
     if args.sim_backend == "device":
-        return start_env_batched(args.links, 1, args.seed, backend="device", streams=args.sim_streams)
+        return start_env_batched(args.links, 1, args.seed, backend="device", streams=args.sim_streams, reset=args.sim_reset)
     return start_env(args.links)
 
 
@@ -189,6 +195,8 @@ def parse_args(argv=None):
         ap.error("--mixed-links steps batched simulators: --envs must be at least 1 (got %d)" % args.envs)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
+    if args.sim_reset == "device" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--sim-reset device needs --sim-backend device --sim-streams device")
     if args.eval_backend != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
         ap.error("--eval-backend %s needs --sim-backend device --sim-streams device" % args.eval_backend)
     if args.mixed_trajectory_walk != "serial" and args.eval_backend != "device":
@@ -215,7 +223,8 @@ def run_mixed(args):
     np.random.seed(args.seed)
     cfg = RL_Config()
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
-    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.sim_backend, streams=args.sim_streams)
+    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.sim_backend, streams=args.sim_streams,
+                              reset=args.sim_reset)
             for k, n in enumerate(args.eval_links)]
     agent = MixedAgent(envs, cfg, args.feedback, seed=args.seed, trajectory_walk=args.mixed_trajectory_walk)
     agent.load_weights(args.save_dir, args.episodes, args.train_steps)

@@ -38,14 +38,15 @@ def start_env(n_links=None):
     return env
 
 
-def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", device=0, streams="host"):
+def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", device=0, streams="host", reset="host"):
     """E environments on the same lane grid, environment e seeded with seed + 104729 e (rl/batched_env.py).
     lookahead: compute every next simulator step on the library's worker thread while the agent scores and replays (same
     trajectories, see BatchedEnviron); default on, V2X_SIM_LOOKAHEAD=0 switches it off.
     backend: "host" (the default: BatchedEnviron) or "device" (rl/device_sim.py: channel update, observation and rates on the
     GPU `device`; it has no look-ahead).
     streams: with backend="device", where mobility and the MT19937 streams advance: "host" (libv2xsim.so, the default) or
-    "device" (a step is then one enqueue that takes only the actions from the host)."""
+    "device" (a step is then one enqueue that takes only the actions from the host).
+    reset: with streams="device", who runs new_random_game: "host" (the default) or "device" (one call on the resident state)."""
     import os
     if lookahead is None:
         lookahead = os.environ.get("V2X_SIM_LOOKAHEAD", "1") != "0"
@@ -60,10 +61,15 @@ def start_env_batched(n_links, n_envs, seed, lookahead=None, backend="host", dev
         raise ValueError("streams must be 'host' or 'device', got %r" % (streams,))
     if streams == "device" and backend != "device":
         raise ValueError("streams='device' needs backend='device' (the host simulator's streams live in libv2xsim.so)")
+    if reset not in ("host", "device"):
+        raise ValueError("reset must be 'host' or 'device', got %r" % (reset,))
+    if reset == "device" and streams != "device":
+        raise ValueError("reset='device' needs backend='device' and streams='device' (the reset draws from the streams where they live)")
     if backend == "device":
         from .device_sim import DeviceBatchedEnviron
         env = DeviceBatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
-                                   seeds=[seed + 104729 * e for e in range(n_envs)], device=device, streams=streams)
+                                   seeds=[seed + 104729 * e for e in range(n_envs)], device=device, streams=streams,
+                                   reset=reset)
         env.new_random_game(n_links)
         return env
     env = BatchedEnviron(down_lanes, up_lanes, left_lanes, right_lanes, 750, 1299, n_envs=n_envs,
@@ -102,6 +108,9 @@ def build_parser():
     ap.add_argument("--sim-streams", choices=["host", "device"], default="host",
                     help="with --sim-backend device: where mobility and the simulators' MT19937 streams advance -- libv2xsim.so "
                          "(the default) or the GPU, where a step is one enqueue that takes only the actions from the host")
+    ap.add_argument("--sim-reset", choices=["host", "device"], default="host",
+                    help="with --sim-backend device --sim-streams device: who resets the simulators at the start of an episode -- "
+                         "the host library (the default) or the GPU, one call on the state resident in HBM (v2x_sim_reset)")
     ap.add_argument("--rollout", choices=["host", "device", "trajectory"], default="host",
                     help="with --sim-backend device --sim-streams device: 'device' runs a whole rollout iteration (score, pick, "
                          "step, reward, store) as one call on the state resident in HBM, 'trajectory' all iterations of a "
@@ -123,6 +132,9 @@ def build_parser():
                          "count and stays refused)")
     ap.add_argument("--mixed-sim-streams", choices=["host", "device"], default="host",
                     help="with --mixed-links --mixed-sim-backend device: --sim-streams for every link count's simulators")
+    ap.add_argument("--mixed-sim-reset", choices=["host", "device"], default="host",
+                    help="with --mixed-links --mixed-sim-backend device --mixed-sim-streams device: --sim-reset for every link "
+                         "count's simulators")
     ap.add_argument("--mixed-rollout", choices=["host", "trajectory"], default="host",
                     help="with --mixed-links --mixed-sim-backend device --mixed-sim-streams device: 'trajectory' runs all iterations "
                          "of a rollout for ALL link counts as one call on the resident states (one walk launch, one assembly launch, "
@@ -160,7 +172,8 @@ def run_mixed(args):
     np.random.seed(args.seed)
     cfg = RL_Config()
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
-    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.mixed_sim_backend, streams=args.mixed_sim_streams)
+    envs = [start_env_batched(n, args.envs, args.seed + 15485863 * k, backend=args.mixed_sim_backend, streams=args.mixed_sim_streams,
+                              reset=args.mixed_sim_reset)
             for k, n in enumerate(sizes)]
     import contextlib
     ctx = contextlib.nullcontext()
@@ -176,7 +189,8 @@ def run_mixed(args):
     n_fit = args.episodes * args.train_steps
     print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,
                       "episodes": args.episodes, "train_steps": args.train_steps, "env_steps": int(agent.num_step),
-                      "sim_backend": args.mixed_sim_backend, "sim_streams": args.mixed_sim_streams, "rollout": args.mixed_rollout,
+                      "sim_backend": args.mixed_sim_backend, "sim_streams": args.mixed_sim_streams, "sim_reset": args.mixed_sim_reset,
+                      "rollout": args.mixed_rollout,
                       "trajectory_walk": args.mixed_trajectory_walk,
                       "rollouts_by_path": dict(agent.rollout_stats),
                       "stored": {str(n): agent.memory.stored(n) for n in sizes},
@@ -196,7 +210,7 @@ def parse_args(argv=None):
     if args.mixed_links is not None:
         # the single-size options hold one link count and stay refused; the device simulators and the resident rollout of ALL
         # link counts are asked for by --mixed-sim-backend / --mixed-sim-streams / --mixed-rollout
-        if args.sim_backend != "host" or args.sim_streams != "host":
+        if args.sim_backend != "host" or args.sim_streams != "host" or args.sim_reset != "host":
             ap.error("--mixed-links steps host simulators: --sim-backend / --sim-streams device hold one link count "
                      "(--mixed-sim-backend / --mixed-sim-streams put every link count's simulators on the device)")
         if args.rollout != "host":
@@ -211,6 +225,8 @@ def parse_args(argv=None):
             ap.error("--mixed-links steps batched simulators: give --envs (simulators per link count)")
         if args.mixed_sim_streams == "device" and args.mixed_sim_backend != "device":
             ap.error("--mixed-sim-streams device needs --mixed-sim-backend device")
+        if args.mixed_sim_reset == "device" and args.mixed_sim_streams != "device":
+            ap.error("--mixed-sim-reset device needs --mixed-sim-backend device --mixed-sim-streams device")
         if args.mixed_rollout == "trajectory" and args.mixed_sim_streams != "device":
             ap.error("--mixed-rollout trajectory needs --mixed-sim-backend device --mixed-sim-streams device (the simulators "
                      "advance inside the call)")
@@ -221,8 +237,9 @@ def parse_args(argv=None):
         except ValueError as exc:
             ap.error(str(exc))
     elif (args.mixed_sim_backend != "host" or args.mixed_sim_streams != "host" or args.mixed_rollout != "host" or
-          args.mixed_trajectory_walk != "serial"):
-        ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-rollout / --mixed-trajectory-walk need --mixed-links")
+          args.mixed_trajectory_walk != "serial" or args.mixed_sim_reset != "host"):
+        ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-sim-reset / --mixed-rollout / --mixed-trajectory-walk need "
+                 "--mixed-links")
     return ap, args
 
 
@@ -232,6 +249,8 @@ def main(argv=None):
         return run_mixed(args)
     if args.sim_streams == "device" and args.sim_backend != "device":
         ap.error("--sim-streams device needs --sim-backend device")
+    if args.sim_reset == "device" and (args.sim_backend != "device" or args.sim_streams != "device"):
+        ap.error("--sim-reset device needs --sim-backend device --sim-streams device")
     if args.rollout != "host" and (args.sim_backend != "device" or args.sim_streams != "device"):
         ap.error("--rollout %s needs --sim-backend device --sim-streams device" % args.rollout)
     if args.trajectory_walk != "serial" and args.rollout != "trajectory":
@@ -266,7 +285,7 @@ def main(argv=None):
     cfg.Num_Episodes, cfg.Num_Train_Steps = args.episodes, args.train_steps
     if args.sim_backend == "device":
         env = start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0), backend="device", device=local,
-                                streams=args.sim_streams)
+                                streams=args.sim_streams, reset=args.sim_reset)
     else:
         env = (start_env_batched(args.links, args.envs, args.seed + (7919 * rank if sharded else 0)) if args.envs > 0
                else start_env(args.links))

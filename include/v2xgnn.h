@@ -546,6 +546,42 @@ typedef struct v2x_sim_step {
 } v2x_sim_step;
 int  v2x_sim_advance(const v2x_sim_step* s, void* stream);
 
+/* v2x_sim_reset: the episode reset (new_random_game, Environment.py:495-506) of E resident states -- the device counterpart of
+ * v2xsim_reset_vehicles, the initial shadowing out of v2xsim_mt_uniforms, the reset's channel update and v2xsim_sample_dest on
+ * the ranked neighbours.  Enqueues, in this order, k_sim_reset_draw (grid E, 256 threads, one state per workgroup, the key
+ * array in LDS throughout), v2x_sim_channels and v2x_sim_observe with C = rb: three launches on one stream.
+ * v2x_sim_reset_draw enqueues the first launch alone.  Same rules as v2x_sim_advance: all pointers [dev], no allocation, no
+ * synchronisation, no environment variable read; every check comes before the first launch; a refusal is V2X_EINVAL with
+ * text in v2x_last_error(NULL).  step: a v2x_sim_step whose actions is NULL (timestep is not read).  vel must be the step's
+ * vel, dest the problem's dest: both are WRITTEN here and read by the two launches that follow.
+ * Limits: n a multiple of 4 in 4..28; rb <= n and 3 rb + 1 <= 16; 1 <= n_lanes <= 64; width and height integral in [0, 2^31);
+ * n_u == n + n^2 + 2 n rb + 2 n^2 rb.
+ * k_sim_reset_draw consumes every state's stream in the host library's order:
+ *   1. vehicles: per group of four, below(n_lanes); for down and for up below(height + 1), then 10 + below(6); for left and
+ *      for right below(width + 1), then 10 + below(6).  below(m) takes the top bit_length(m) bits of successive tempered
+ *      words until the value is < m.  lanes[4][n_lanes] is the step's table (up, down, left, right), the direction codes are
+ *      v2x_sim_stream's.  Written: xy, dirs, vel.
+ *   2. initial shadowing: the next 2 (n^2 + n) doubles go through the state's u; Gaussians n^2 + n .. 2 (n^2 + n) - 1 of them
+ *      (v2x_sim_channels' pairing) give v2v_shadow = g * 3 (row-major) and v2i_shadow = g * 8; the first n^2 + n are consumed
+ *      and dropped (the reference's unused V2V_Shadowing / V2I_Shadowing).
+ *   3. the channel update's uniforms: the next n_u doubles into u, as v2x_sim_stream writes them.
+ *   4. receivers: vehicles are ranked per link i by (d2, index) ascending, d2 = dx dx + dy dy to vehicle i in fp64 without
+ *      contraction; then, in link order, j = below(n - 3) and dest[i] = the vehicle of rank 1 + j.
+ *   5. keys and mtpos are written back with v2x_sim_stream's lazy block rule.
+ * status[e], written: bit 0 -- for some link another vehicle (the link itself included) has exactly the chosen receiver's d2:
+ * the host's answer then depends on the order its argsort leaves among equal keys, the device's rule is ascending index;
+ * bit 1 -- a draw was not accepted within 64 words (probability below 1e-27 per draw with a working generator): the state's
+ * work ended there with its stream state written back, its other outputs are unspecified.  On a lane grid whose coordinates
+ * are multiples of 2^-10 below 2^15, d2 is exact and the order by d2 is the order by the host's np.abs.                    */
+typedef struct v2x_sim_reset_args {
+  v2x_sim_step step;
+  double* vel;             /* [E][n], == step.vel          */
+  int64_t* dest;           /* [E][n], == step.problem.dest */
+  uint8_t* status;         /* [E] */
+} v2x_sim_reset_args;
+int  v2x_sim_reset(const v2x_sim_reset_args* r, void* stream);
+int  v2x_sim_reset_draw(const v2x_sim_reset_args* r, void* stream);
+
 /* ---- one DQN rollout iteration on the resident state (csrc/v2xsimdev.hip) --------------------------------------------
  * Agent._packed_iteration (BS_brain.py:308-352 inside :409-553) for E simulator states whose observation, simulator arrays and
  * replay memory all live in HBM: score, pick the actions, step the simulators, compute the reward, write the transitions into
