@@ -1975,6 +1975,11 @@ void set_global_error(const char* text) { g_err = text; }
 void model_dims(const v2x_model* m, int* n_nodes, int* n_channels, int* variable_graphs) {
   *n_nodes = m->N; *n_channels = m->C; *variable_graphs = m->cfg.variable_graphs;
 }
+// feature width, message-passing layers and weight sharing: with model_dims what v2x_eval_sweep_mixed (v2xsimdev.hip) compares
+// between the networks of a sweep
+void model_shape(const v2x_model* m, int* feat_dim, int* n_mp_layers, int* share_weights) {
+  *feat_dim = m->cfg.feat_dim; *n_mp_layers = m->cfg.n_mp_layers; *share_weights = m->cfg.share_weights;
+}
 }
 
 // ======================================================================================= C ABI

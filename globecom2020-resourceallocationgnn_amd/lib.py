@@ -123,6 +123,14 @@ class TrajWs(C.Structure):
     _fields_ = [("wide_ws", C.c_void_p), ("wide_ws_bytes", C.c_int64), ("split_ws", C.c_void_p), ("split_ws_bytes", C.c_int64)]
 
 
+class EvalSweep(C.Structure):
+    """v2x_eval_sweep of include/v2xgnn.h"""
+    _fields_ = [("base", EvalMixed), ("K", C.c_int32), ("pad_", C.c_int32), ("models", C.POINTER(C.c_void_p)), ("q", C.c_void_p)]
+
+
+SWEEP_MAX_MODELS = 64
+
+
 class ReplayPool(C.Structure):
     """v2x_replay_pool of include/v2xgnn.h"""
     _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
@@ -242,6 +250,8 @@ SYMBOLS = [
     ("v2x_eval_steps_split", C.c_int, [C.POINTER(Eval), _P, _L, _P, _L, _P]),
     ("v2x_rollout_steps_mixed_wide", C.c_int, [C.POINTER(RolloutMixed), C.POINTER(TrajWs), _P]),
     ("v2x_eval_steps_mixed_wide", C.c_int, [C.POINTER(EvalMixed), C.POINTER(TrajWs), _P]),
+    ("v2x_eval_sweep_result_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_eval_sweep_mixed", C.c_int, [C.POINTER(EvalSweep), C.POINTER(TrajWs), _P]),
 ]
 
 

@@ -74,6 +74,13 @@ DeviceBatchedEnviron per link count (MixedAgent.test_run(eval_backend='device'))
     rows = eval_steps_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [baseline8, baseline12], w_v2v, w_v2i,
                             engine)                                                           # -> [EvalResult] per pool
 
+... and K networks on those same steps (v2x_eval_sweep_mixed: ONE walk, one assembly, K forwards of the one batch, one finish
+launch that pays every network's policy on the shared draws and the baseline); resident_evaluate_sweep_mixed for one
+DeviceBatchedEnviron per link count (MixedAgent.evaluate_training(eval_backend='device')):
+
+    rows = eval_sweep_mixed([dc8, dc12], [explore8, explore12], [random8, random12], [baseline8, baseline12], w_v2v, w_v2i,
+                            [engine_a, engine_b, engine_c])                    # -> [EvalResult] per pool, 3 + 1 schemes
+
 `DeviceBatchedEnviron` is a `BatchedEnviron` whose heavy arrays never leave HBM: the channel update, the observable
 interference, the observation and the rates run on the device; mobility and the MT19937 streams stay on the host
 (libv2xsim.so) by default and move to the device with streams='device'.
@@ -85,8 +92,8 @@ import ctypes as C
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, MIXED_MAX_POOLS,OptProblem, Rollout, RolloutMixed, RolloutTraj, SimReset, SimStep, TrajWs, check,
-                   load_library)
+from ..lib import (Eval, EvalMixed, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutTraj,
+                   SimReset, SimStep, TrajWs, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -1132,6 +1139,27 @@ class DeviceChannels(object):
         ev.record(t.cuda.current_stream(self.device))
         return EvalResult(free, ev, pinned, self.E, self.n, self.rb, T, S)
 
+    def _sweep_io(self, T, S):
+        """-> (_eval_io(T), the result block of a sweep of S schemes (eval_sweep_mixed): its device block 'dev' and the
+        page-locked copies that came back 'free', made at the first use of (T, S))"""
+        io = self._eval_io(T)
+        sw = io.setdefault('sweep', {}).get(S)
+        if sw is None:
+            t = self.torch
+            sw = io['sweep'][S] = {'dev': t.zeros(self.eval_steps_result_bytes(T, S), dtype=t.uint8, device=self.device), 'free': []}
+        return io, sw
+
+    def _sweep_download(self, sw, T, S):
+        """_eval_download for the result block of a sweep"""
+        t = self.torch
+        size, free = sw['dev'].numel(), sw['free']
+        pinned = free.pop() if free else t.zeros(size, dtype=t.uint8, pin_memory=self._pin)
+        pinned.copy_(sw['dev'], non_blocking=True)
+        self.traffic['bytes_down'] += size
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return EvalResult(free, ev, pinned, self.E, self.n, self.rb, T, S)
+
     def eval_steps_struct(self, T, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None, baseline=True):
         """the v2x_eval of the resident tensors and the buffers of _eval_io(T) (what eval_steps() passes to the library)"""
         io = self._eval_io(T)
@@ -1436,6 +1464,124 @@ def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions
     channels = [env._resident_before(who, lambda dc, k=k: dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
                 for k, env in enumerate(envs)]
     results = eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, walk=walk)
+    for env, result in zip(envs, results):
+        env._resident_after(result)
+    return results
+
+
+def mixed_sweep_q(channels, T, K):
+    """the Q workspace [K, R, rb] of a sweep of K networks over the ragged batch of mixed_rollout_buffers(channels, T), made once
+    per (K, T) and kept with that batch"""
+    buf = mixed_rollout_buffers(channels, T)
+    q = buf.setdefault('sweep_q', {}).get(K)
+    if q is None:
+        dc0 = channels[0]
+        q = buf['sweep_q'][K] = dc0.torch.zeros((K, buf['sizes'][1], dc0.rb), dtype=dc0.torch.float32, device=dc0.device)
+    return q
+
+
+def _check_sweep_engines(who, engines, K, rb):
+    """what a sweep refuses of its networks, before any device work -> K"""
+    if engines is None:
+        K = 1 if K is None else int(K)
+    else:
+        engines = list(engines)
+        if K is not None and int(K) != len(engines):
+            raise ValueError("%s: K = %d, but %d engines" % (who, K, len(engines)))
+        K = len(engines)
+    if not 1 <= K <= SWEEP_MAX_MODELS:
+        raise ValueError("%s: 1..%d networks, got %d" % (who, SWEEP_MAX_MODELS, K))
+    for k, engine in enumerate(engines or ()):
+        if engine is None or not (engine.spec.variable_graphs and engine.spec.n_channels == rb):
+            raise ValueError("%s: scoring needs variable_graphs engines of %d channels (engine %d)" % (who, rb, k))
+        if engine.spec != engines[0].spec:
+            raise ValueError("%s: engine %d has another spec than engine 0: the networks of a sweep are checkpoints of one network"
+                             % (who, k))
+    return K
+
+
+def eval_sweep_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None, power=None,
+                     walk='serial'):
+    """eval_steps_mixed for K networks on the SAME steps in ONE library call (v2x_eval_sweep_mixed): the arguments of
+    eval_steps_mixed with a list of K variable_graphs `engines` of one spec in the engine's place (None: nobody is greedy
+    anywhere, no forward; K then says how many identical policy schemes the result holds, default 1).  One walk (walk='wide':
+    the six launches of the mixed wide walk), one assembly, K forwards of the one ragged batch into the Q workspace of
+    mixed_sweep_q, one finish launch: scheme k < K is engine k's policy on the shared explore flags and random actions, scheme
+    K the baseline (when given).  The resident state afterwards is the one engine K - 1's own eval_steps_mixed leaves.
+    -> [EvalResult] per pool with K (+ 1) schemes, the downloads in flight."""
+    who = "eval_sweep_mixed"
+    check_walk(who, walk)
+    channels, T, checked = _check_eval_mixed(who, channels, explore, policy_random, baseline_actions)
+    K = _check_sweep_engines(who, engines, K, channels[0].rb)
+    for dc in channels:
+        dc._init_device()
+        if dc.device != channels[0].device:
+            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
+        if not dc._obs_ready:
+            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    baseline = checked[0][3] is not None
+    S = K + (1 if baseline else 0)
+    table = (Eval * len(channels))()
+    blocks = []
+    for k, (dc, (_, ex, ra, ba)) in enumerate(zip(channels, checked)):
+        io, sw = dc._sweep_io(T, S)
+        dc._eval_upload(io, T, ex, ra, ba)
+        table[k] = dc.eval_steps_struct(T, v2v_weight, v2i_weight, engine=None, power=power, baseline=baseline)
+        offs, _ = eval_result_layout(dc.E, dc.n, dc.rb, T, S)
+        for name, o in offs.items():                     # the sweep's own result block, S schemes
+            setattr(table[k], 'result_' + name, sw['dev'].data_ptr() + o)
+        blocks.append(sw)
+    m = EvalSweep(base=EvalMixed(n_pools=len(channels), T=T, pools=table, model=None), K=K, pad_=0, models=None, q=None)
+    if engines is not None:
+        buf = mixed_rollout_buffers(channels, T)
+        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx'):
+            setattr(m.base, name, buf[name].data_ptr())
+        handles = (C.c_void_p * K)(*[engine._h for engine in engines])
+        m.models = handles
+        m.q = mixed_sweep_q(channels, T, K).data_ptr()
+    for dc in channels:
+        dc._keep_actions = dc._t['actions']
+    dc0 = channels[0]
+    ws = None
+    if walk == 'wide':
+        ws = (TrajWs * len(channels))()
+        for k, dc in enumerate(channels):
+            wide, split = dc._wide_workspace(T), dc._split_workspace(T)
+            ws[k] = TrajWs(wide.data_ptr(), wide.numel(), split.data_ptr(), split.numel())
+    check(dc0._lib, dc0._lib.v2x_eval_sweep_mixed(C.byref(m), ws, dc0._stream()))
+    out = []
+    for dc, sw in zip(channels, blocks):
+        dc.walk_calls[walk] += 1
+        if walk == 'wide':
+            dc.stream_phase_calls['split'] += 1
+        dc._obs_ready = True
+        out.append(dc._sweep_download(sw, T, S))
+    return out
+
+
+def resident_evaluate_sweep_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None,
+                                  walk='serial'):
+    """eval_sweep_mixed() on the resident states of one DeviceBatchedEnviron (streams='device') per link count, ascending size:
+    the bookkeeping of resident_evaluate_steps_mixed around every environment, the ONE library call in the middle.  Afterwards
+    env.trajectory_states(T) of every environment holds that pool's T snapshots.
+    -> [EvalResult] per environment with K (+ 1) schemes, the downloads in flight."""
+    who = "eval_sweep_mixed"
+    check_walk(who, walk)
+    envs = list(envs)
+    for name, arg in dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions).items():
+        if len(arg) != len(envs):
+            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
+    for env in envs:
+        if getattr(env, 'stream_backend', None) != 'device':
+            raise ValueError("%s needs streams='device' in every environment (mobility and the MT19937 streams advance inside the "
+                             "call)" % who)
+    _check_eval_mixed(who, [_PoolShape(env) for env in envs], explore, policy_random, baseline_actions)   # before any device work
+    if envs:
+        _check_sweep_engines(who, engines, K, envs[0].n_RB)
+    channels = [env._resident_before(who, lambda dc, k=k: dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
+                for k, env in enumerate(envs)]
+    results = eval_sweep_mixed(channels, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=engines, K=K,
+                               walk=walk)
     for env, result in zip(envs, results):
         env._resident_after(result)
     return results

@@ -20,7 +20,11 @@ ragged path scores and fits batches whose graphs differ in size.  This module is
                 test_run() evaluates the network on ANY set of link counts (the training sizes or others) against the
                 random baseline and, on request, the optimum; eval_backend='device' runs an episode of all link counts as ONE
                 library call (v2x_eval_steps_mixed) and one stacked optimum search per link count.  save_weights() /
-                load_weights() keep the online and the target network in the files of rl.run.weight_file_names.
+                load_weights() keep the online and the target network in the files of rl.run.weight_file_names;
+                train(save_interval=k) saves them every k episodes, and evaluate_training() scores those checkpoints -- K
+                networks on ONE re-seeded episode per trial (the walk, the baseline and the optimum do not depend on the
+                network: with eval_backend='device' one v2x_eval_sweep_mixed call and one stacked search per link count
+                serve all K).
 
 Only regular graphs (in-degree n - 2 everywhere) are stored: a transition whose graph has a link that is its own receiver (two
 vehicles on one spot, rare) is counted in MixedReplay.dropped_irregular and left out -- the assembly is closed-form because
@@ -274,9 +278,10 @@ class MixedAgent(object):
         """[(xe [E, n, 16], mask [E, n], col [E, n (n - 2)], regular [E])] per environment, ascending size"""
         return [e.observe_packed(self.num_CH) for e in self.envs]
 
-    def score(self, obs, envs=None):
+    def score(self, obs, envs=None, engine=None):
         """Q-values of all environments' observations by ONE forward of one ragged batch -> [q [E, n, C]] per environment.
-        envs: the environments the observations are of (default: the agent's own)"""
+        envs: the environments the observations are of (default: the agent's own); engine: the network that scores (default:
+        the online network)"""
         envs = self.envs if envs is None else envs
         xe, rp, ci, sizes, edges = [], [np.zeros(1, np.int64)], [], [], 0
         for env, (x, mask, col, regular) in zip(envs, obs):
@@ -295,7 +300,7 @@ class MixedAgent(object):
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
         pb = PackedBatch(len(sizes), 0, np.ascontiguousarray(np.concatenate(xe)), np.concatenate(rp).astype(np.int32),
                          np.concatenate(ci).astype(np.int32), graph_off=offs)
-        q = self.online.forward(pb)
+        q = (self.online if engine is None else engine).forward(pb)
         out, r = [], 0
         for env in envs:
             rows = env.E * env.n_Veh
@@ -440,11 +445,15 @@ class MixedAgent(object):
         s = st.cpu().numpy()
         return float(loss.cpu().numpy()[0]), float(s[0, 0] / (R * C_)), float(s[1, 0] / R)
 
-    def train(self, num_episodes, num_train_steps, verbose=False, save_dir=None):
+    def train(self, num_episodes, num_train_steps, verbose=False, save_dir=None, save_interval=None):
         """episodes x train steps x (ceil(50 / sum E) rollout iterations + 1 replay); target sync whenever another 500
-        transitions have been collected.  save_dir: save_weights(save_dir, num_episodes, num_train_steps) at the end.
+        transitions have been collected.  save_dir: save_weights(save_dir, num_episodes, num_train_steps) at the end; with an
+        integer save_interval also save_weights(save_dir, episode, num_train_steps) after every save_interval-th episode (the
+        reference saves every 5: the checkpoints evaluate_training loads).
         -> (loss [1, episodes, steps], {link count: rewards [episodes, steps, iterations x E]},
         Q mean [episodes, steps], Q max mean [episodes, steps])"""
+        if save_interval is not None and (int(save_interval) != save_interval or save_interval < 1):
+            raise ValueError("MixedAgent.train: save_interval must be a positive integer or None, got %r" % (save_interval,))
         self.num_Episodes, self.num_Train_Step = int(num_episodes), int(num_train_steps)
         self.num_step, self._sync_mark = 0, 0
         loss = np.ones((1, num_episodes, num_train_steps))
@@ -478,6 +487,8 @@ class MixedAgent(object):
             if verbose:
                 print('episode', ep + 1, 'loss %.4f' % loss[0, ep].mean(),
                       'reward', {n: round(float(v[ep].sum()), 3) for n, v in rewards.items()})
+            if save_dir is not None and save_interval is not None and (ep + 1) % save_interval == 0:
+                self.save_weights(save_dir, ep + 1, num_train_steps)
         if save_dir is not None:
             self.save_weights(save_dir, num_episodes, num_train_steps)
         return loss, rewards, q_mean, q_max
@@ -506,6 +517,25 @@ class MixedAgent(object):
         return paths
 
     # ------------------------------------------------------------------ evaluation
+    def _check_evaluate_training(self, eval_envs, checkpoints, engines, save_dir, num_trials, opt_backend, eval_backend, T):
+        """ValueError for anything evaluate_training cannot take, before any draw, reset or load -> (the environments in
+        ascending size, K)"""
+        try:
+            envs = MixedAgent._check_test_run(self, eval_envs, opt_backend, eval_backend, T)
+        except ValueError as err:
+            raise ValueError(str(err).replace("MixedAgent.test_run", "MixedAgent.evaluate_training"))
+        if (engines is None) == (checkpoints is None):
+            raise ValueError("MixedAgent.evaluate_training: give the checkpoints' episode tags (with save_dir) or their loaded "
+                             "engines, one of the two")
+        if engines is None and save_dir is None:
+            raise ValueError("MixedAgent.evaluate_training: checkpoints are loaded from save_dir")
+        K = len(list(checkpoints if engines is None else engines))
+        if not 1 <= K <= _lib.SWEEP_MAX_MODELS:
+            raise ValueError("MixedAgent.evaluate_training: 1..%d checkpoints, got %d" % (_lib.SWEEP_MAX_MODELS, K))
+        if T < 1 or int(num_trials) < 1:
+            raise ValueError("MixedAgent.evaluate_training: at least one step and one trial, got %d and %d" % (T, num_trials))
+        return envs, K
+
     def _check_test_run(self, eval_envs, opt_backend, eval_backend, num_test_step):
         """ValueError for anything test_run cannot take, before any draw or reset -> the environments in ascending size"""
         if eval_backend not in EVAL_BACKENDS:
@@ -644,4 +674,132 @@ class MixedAgent(object):
                     for e in range(env.E):
                         record(books[env.n_Veh]['gnn'], ep, e, st, v2v[e], v2i[e], intf[e])
                 self.num_step += n_sims
+        return books
+
+    def evaluate_training(self, eval_envs, checkpoints, num_test_step, num_trials, fixed_epsilon, opt_flag=False,
+                          opt_backend='device', opt_restarts=None, eval_backend='host', save_dir=None, engines=None,
+                          num_train_steps=None):
+        """Evaluation of the TRAINING PROCESS for the shared-weight network (Agent.evaluate_training_diff_trials; the reference's
+        RL_Evaluated_main_Epsilon_DiffTrails.py): K saved networks under a FIXED epsilon-greedy policy over re-seeded trials,
+        next to the random scheme and, with opt_flag, the optimum -- on any link counts (eval_envs as for test_run).
+        checkpoints: the episode tags train(save_interval=...) saved under (save_weights(save_dir, tag, num_train_steps);
+        num_train_steps defaults to the agent's last train()); or engines: K loaded GnnEngines of the agent's spec.
+        The reference re-seeds before every (trial, checkpoint), so all checkpoints of a trial face the same episode and the
+        same epsilon draws and differ in the network alone.  Here that holds by construction -- trial t:
+        random.seed(t + 1), np.random.seed(t + 1); every environment is reset once; the episode's draws are taken once
+        (draw_eval_episode_ahead: ascending size, simulator); all K checkpoints are scored on that ONE walked episode, and the
+        simulators step under the LAST checkpoint's actions.
+        -> {link count: {'gnn': books, 'random': books[, 'optimal': books]}}, books the five arrays of test_run -- return,
+        reward, V2V rates, V2I rates, base-station interference -- filled with its numpy expressions, with the leading axes
+        [trials, K, E_k] for 'gnn' (reward [trials, K, E_k, steps]) and [trials, E_k] for the two others.
+        eval_backend='host' is the definition.  Per step: the baseline's rates; with opt_flag one search per environment;
+        for k = 0 .. K - 1 one score() by network k (when somebody is greedy) and the rates of its actions, computed without
+        stepping (compute_reward_with_channel_selection); then one env.act under network K - 1's actions.
+        eval_backend='device' (what test_run(eval_backend='device') needs of the environments, refused before any draw or
+        reset): ONE resident_evaluate_sweep_mixed call per trial (trajectory_walk='wide': on the pools' wide workspaces) and,
+        with opt_flag, one stacked search and one rates() call per link count on trajectory_states(T).  Same books, generator
+        states, num_step and simulator state as 'host'.  A trial in which some environment's graph is not regular after the
+        reset runs the host loop; eval_stats counts both kinds."""
+        import random
+        T, C_ = int(num_test_step), self.num_CH
+        envs, K = self._check_evaluate_training(eval_envs, checkpoints, engines, save_dir, num_trials, opt_backend, eval_backend, T)
+        num_trials = int(num_trials)
+        n_sims = sum(e.E for e in envs)
+        w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
+
+        def book(lead, n):
+            return [np.zeros(lead), np.zeros(lead + (T,)), np.zeros(lead + (T, n)), np.zeros(lead + (T, C_)), np.zeros(lead + (T, C_))]
+
+        def record(b, at, st, v2v, v2i, interference):                  # (test_run's record, `at` = the book's leading index)
+            b[1][at + (st,)] = w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i)
+            b[0][at] += b[1][at + (st,)]
+            b[2][at + (st,)] = np.sum(v2v, axis=1)
+            b[3][at + (st,)] = v2i
+            b[4][at + (st,)] = interference
+
+        def record_optimum(b, at, st, v2v, v2i, interference):
+            if w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i) > 0:             # at least one feasible solution
+                record(b, at, st, v2v, v2i, interference)
+
+        books = {}
+        for env in envs:
+            b = books[env.n_Veh] = {'gnn': book((num_trials, K, env.E), env.n_Veh), 'random': book((num_trials, env.E), env.n_Veh)}
+            if opt_flag:
+                b['optimal'] = book((num_trials, env.E), env.n_Veh)
+        loaded = []
+        if engines is None:
+            from ..bs_brain import load_weight_file
+            steps = self.num_Train_Step if num_train_steps is None else num_train_steps
+            for tag in checkpoints:
+                path = self._weight_paths(save_dir, tag, steps)[0]
+                if not os.path.exists(path):
+                    raise ValueError("MixedAgent.evaluate_training: no checkpoint %s" % path)
+            for tag in checkpoints:
+                engine = GnnEngine(self.spec, device=self.online.device)
+                loaded.append(engine)
+                engine.set_weights(load_weight_file(self._weight_paths(save_dir, tag, steps)[0]))
+            engines = loaded
+        engines = list(engines)
+        try:
+            for tr in range(num_trials):
+                random.seed(tr + 1)
+                np.random.seed(tr + 1)
+                for env in envs:
+                    env.new_random_game(env.n_Veh)
+                baseline, explore, rand = draw_eval_episode_ahead(envs, C_, fixed_epsilon, T)
+                if eval_backend == 'device' and self._all_regular(envs):
+                    from .device_sim import resident_evaluate_sweep_mixed
+                    anybody = not all(x.all() for x in explore)
+                    results = resident_evaluate_sweep_mixed(envs, explore, rand, baseline, w_v2v, w_v2i,
+                                                            engines=engines if anybody else None, K=K, walk=self.trajectory_walk)
+                    for env, res in zip(envs, results):
+                        E, n, b = env.E, env.n_Veh, books[env.n_Veh]
+                        r = res.resolve()
+                        if opt_flag:
+                            states = env.trajectory_states(T)
+                            found = self._optimum_actions(states, T * E, n, opt_backend, opt_restarts, T * E)
+                            o_v2v, o_v2i, o_intf = (a.reshape((T, E) + a.shape[1:]) for a in states.rates(found))
+                        for st in range(T):
+                            for e in range(E):
+                                record(b['random'], (tr, e), st, r.v2v_rate[K, st, e][:, None], r.v2i_rate[K, st, e],
+                                       r.interference[K, st, e])
+                                if opt_flag:
+                                    record_optimum(b['optimal'], (tr, e), st, o_v2v[st, e][:, None], o_v2i[st, e], o_intf[st, e])
+                                for k in range(K):
+                                    record(b['gnn'], (tr, k, e), st, r.v2v_rate[k, st, e][:, None], r.v2i_rate[k, st, e],
+                                           r.interference[k, st, e])
+                    self.num_step += T * n_sims
+                    self.eval_stats['device_episodes'] += 1
+                    continue
+                self.eval_stats['host_episodes'] += 1
+                for st in range(T):
+                    for env, a in zip(envs, baseline):
+                        v2v, v2i, intf = env.compute_reward_with_channel_selection(a[st][:, :, None])
+                        for e in range(env.E):
+                            record(books[env.n_Veh]['random'], (tr, e), st, v2v[e], v2i[e], intf[e])
+                    if opt_flag:
+                        for env in envs:
+                            found = self._optimum_actions(env, env.E, env.n_Veh, opt_backend, opt_restarts, env.E)
+                            v2v, v2i, intf = env.compute_reward_with_channel_selection(found[:, :, None])
+                            for e in range(env.E):
+                                record_optimum(books[env.n_Veh]['optimal'], (tr, e), st, v2v[e], v2i[e], intf[e])
+                    greedy = not all(x[st].all() for x in explore)
+                    obs = [env.observe_packed(C_) for env in envs] if greedy else None
+                    for k, engine in enumerate(engines):
+                        actions = [r[st][:, :, None].copy() for r in rand]
+                        if greedy:
+                            for a, x, q in zip(actions, explore, self.score(obs, envs, engine=engine)):
+                                g = np.nonzero(x[st] == 0)[0]
+                                if len(g):
+                                    a[g] = np.argmax(q[g], axis=2)[:, :, None]
+                        for env, a in zip(envs, actions):
+                            v2v, v2i, intf = env.compute_reward_with_channel_selection(a)
+                            for e in range(env.E):
+                                record(books[env.n_Veh]['gnn'], (tr, k, e), st, v2v[e], v2i[e], intf[e])
+                    for env, a in zip(envs, actions):                     # the simulators step under the last checkpoint's actions
+                        env.act(a)
+                    self.num_step += n_sims
+        finally:
+            for engine in loaded:
+                engine.close()
         return books

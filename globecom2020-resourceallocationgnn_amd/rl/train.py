@@ -143,6 +143,9 @@ def build_parser():
                     help="with --mixed-links --mixed-rollout trajectory: how that call walks the simulators' steps -- 'serial' (the "
                          "default: one workgroup per simulator, step after step) or 'wide' (the steps of all link counts spread "
                          "over the chip, six launches in the walk's place; the same bits; DESIGN.md section 3.8 says where it wins)")
+    ap.add_argument("--save-interval", type=int, default=None, metavar="K",
+                    help="with --mixed-links --save-dir: also save the two networks after every K-th episode (the reference saves "
+                         "every 5): the checkpoints rl.evaluate --mixed-links scores")
     return ap
 
 
@@ -165,7 +168,8 @@ def parse_mixed_links(text):
 
 def run_mixed(args):
     """--mixed-links: one MixedAgent over one batched simulator per link count (--mixed-sim-backend / --mixed-sim-streams say
-    where they run, --mixed-rollout who makes the rollout, --mixed-trajectory-walk how its steps are walked); with --save-dir the two networks are saved at the end"""
+    where they run, --mixed-rollout who makes the rollout, --mixed-trajectory-walk how its steps are walked); with --save-dir the two networks are saved at the end, with
+    --save-interval K also after every K-th episode"""
     from .mixed import MixedAgent
     sizes = parse_mixed_links(args.mixed_links)
     random.seed(args.seed)
@@ -184,7 +188,8 @@ def run_mixed(args):
     with ctx:
         agent = MixedAgent(envs, cfg, args.feedback, use_graph=args.use_graph, seed=args.seed, rollout=args.mixed_rollout,
                            trajectory_walk=args.mixed_trajectory_walk)
-        loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True, save_dir=args.save_dir)
+        loss, rewards, q_mean, q_max = agent.train(args.episodes, args.train_steps, verbose=True, save_dir=args.save_dir,
+                                                   save_interval=args.save_interval)
     dt = time.perf_counter() - t0
     n_fit = args.episodes * args.train_steps
     print(json.dumps({"mixed_links": sizes, "envs_per_size": args.envs, "feat_dim": args.feedback, "batch": args.batch,
@@ -232,10 +237,14 @@ def parse_args(argv=None):
                      "advance inside the call)")
         if args.mixed_trajectory_walk != "serial" and args.mixed_rollout != "trajectory":
             ap.error("--mixed-trajectory-walk %s needs --mixed-rollout trajectory" % args.mixed_trajectory_walk)
+        if args.save_interval is not None and (args.save_interval < 1 or args.save_dir is None):
+            ap.error("--save-interval must be at least 1 and needs --save-dir")
         try:
             parse_mixed_links(args.mixed_links)
         except ValueError as exc:
             ap.error(str(exc))
+    elif args.save_interval is not None:
+        ap.error("--save-interval needs --mixed-links (a single-size run saves every 5 episodes)")
     elif (args.mixed_sim_backend != "host" or args.mixed_sim_streams != "host" or args.mixed_rollout != "host" or
           args.mixed_trajectory_walk != "serial" or args.mixed_sim_reset != "host"):
         ap.error("--mixed-sim-backend / --mixed-sim-streams / --mixed-sim-reset / --mixed-rollout / --mixed-trajectory-walk need "

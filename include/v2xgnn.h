@@ -885,6 +885,40 @@ typedef struct v2x_traj_ws {
 int  v2x_rollout_steps_mixed_wide(const v2x_rollout_mixed* m, const v2x_traj_ws* ws /*[host][n_pools]*/, void* stream);
 int  v2x_eval_steps_mixed_wide(const v2x_eval_mixed* m, const v2x_traj_ws* ws /*[host][n_pools]*/, void* stream);
 
+/* v2x_eval_sweep_mixed: K networks scored on the SAME T steps of up to 8 pools of different link counts -- the checkpoints of a
+ * training run on one walked episode (rl/mixed.py MixedAgent.evaluate_training).  Nothing in a simulator step depends on the
+ * actions except the rates paid for them, so the walk, the ragged batch and the baseline are those of ONE v2x_eval_steps_mixed
+ * call; only the forward and the policy's pick differ between the networks.  Enqueues, in this order on one stream with no
+ * parallel branches,
+ *   the walk                    k_sim_trajectory_mixed (ws NULL), or the six launches of the mixed wide walk on `ws`, unchanged;
+ *   k_traj_assemble_mixed       unchanged, once -- skipped without models;
+ *   v2x_forward                 K times, of that one batch: models[k] into q + k R rb -- skipped without models;
+ *   k_eval_finish_sweep_mixed   grid (S T S(E_j)), S = K + 1 with baseline_actions, else K; one wave per (pool, scheme, t, e): the
+ *                               body of k_eval_finish on its pool's arguments.  Scheme k < K is the policy of network k: link i
+ *                               takes random_actions[t][e][i] when explore[t][e], else np.argmax of its row of models[k]'s Q --
+ *                               explore and random_actions are shared by all K.  Scheme K is the baseline.  Scheme K - 1 at
+ *                               t = T - 1 leaves the pool's resident actions, rates and interference, as scheme 0 of
+ *                               v2x_eval_steps_mixed does: the resident state afterwards is that of K calls of
+ *                               v2x_eval_steps_mixed with models[0..K-1], each started from the state before the first.
+ *                               Pool-major: pool j owns blocks S gbase_j .. S gbase_j + S T E_j - 1, inside a pool (scheme, t, e).
+ * Results: pool j's result pointers hold S schemes, scheme major, [S][T][E_j][..] -- the layout of v2x_eval_steps with S in the
+ * place of its 1 or 2; v2x_eval_sweep_result_bytes(E, n, rb, T, S) is the formula of v2x_eval_steps_result_bytes for
+ * 1 <= S <= 65.  Scheme k of the sweep holds the bits of scheme 0 of v2x_eval_steps_mixed with models[k], scheme K those of its
+ * scheme 1.
+ * Same rules as v2x_eval_steps_mixed: all pointers [dev] except `base.pools` and `models` ([host]), asynchronous, no allocation,
+ * no synchronisation, no environment variable read; every check of every part before the first launch.  V2X_EINVAL (text in
+ * v2x_last_error(NULL)): K outside 1..64, a NULL entry of models, models that are not variable_graphs or differ in channels,
+ * feature width, depth or weight sharing, a null q with models, and everything v2x_eval_steps_mixed (with ws: and
+ * v2x_eval_steps_mixed_wide) refuses of base, its pools and the ragged batch.                                               */
+typedef struct v2x_eval_sweep {
+  v2x_eval_mixed base;              /* as for v2x_eval_steps_mixed; base.model and base.q are ignored */
+  int32_t K, pad_;                  /* 1..64 networks */
+  v2x_model* const* models;         /* [host][K] variable_graphs models of one spec with rb channels, or NULL: everybody explores */
+  float* q;                         /* [dev] [K][R][rb] Q workspace, R the rows of the ragged batch (required with models) */
+} v2x_eval_sweep;
+int64_t v2x_eval_sweep_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
+int  v2x_eval_sweep_mixed(const v2x_eval_sweep* s, const v2x_traj_ws* ws /*[host][n_pools] or NULL*/, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */
