@@ -1824,6 +1824,77 @@ __global__ __launch_bounds__(256) void k_replay_gather_mixed(MixedArgs a) {
   }
 }
 
+// A replay minibatch of 3..128-link graphs from a storage that keeps a transition's adjacency as its RECEIVERS
+// (v2x_replay_gather_recv; rl/replay.py ReceiverReplay): recv[q] is the one vehicle that does not send to link q besides q
+// itself (Adj[p, q] = 1 unless p == q or p == recv[q], BS_brain.py:441-445), or q when there is none (two vehicles on one
+// spot: in-degree n - 1).  The CSR of graph g is then closed-form: row q starts at base_g + q (n - 2) + #{q' < q own
+// receiver} and holds every p except q and recv[q], ascending -- packing.adj_to_csr's order -- so regular and own-receiver
+// graphs come out of the same launch and nothing but n int32 per transition is stored for the topology.
+// A workgroup takes RECV_ROWS_PER_WG rows of one graph (a graph per workgroup leaves the chip idle at small K): it reads the
+// graph's n receivers into LDS, every wave ballots the own-receiver flags into two 64-bit masks (the row offsets are
+// popcounts, no prefix pass), the first two waves copy the rows' xe / xe' as 16-byte words, and each wave then writes whole
+// rows with its lanes along the sources (4-byte stores, contiguous over the wave and from row to row).  recv is only ever
+// compared, never used as an index; no store goes below 0, at or beyond edge_base[g + 1] or beyond (g + 1) n (n - 1).
+constexpr int RECV_MAX_LINKS = 128;
+constexpr int RECV_ROWS_PER_WG = 16;
+struct RecvArgs {
+  const float *xe, *xe_next;             // [cap][n][16]
+  const int32_t *recv, *action;          // [cap][n]
+  const double* reward;                  // [cap]
+  const int32_t *idx, *edge_base;        // [K] slots; [K + 1] first edges or null (every graph regular)
+  float *oxe, *oxe_next; int32_t* oaction; double* oreward;
+  int32_t *row_ptr, *col_idx;
+  int n, K, parts;                       // links; graphs; workgroups per graph
+};
+// #{q' < q : link q' is its own receiver} from the two ballot masks (links 0..63, 64..127); q in [0, 128]
+__device__ inline int recv_own_before(int q, uint64_t m0, uint64_t m1) {
+  const uint64_t lo = q >= 64 ? ~0ull : ((1ull << q) - 1ull);
+  const uint64_t hi = q >= 128 ? ~0ull : (q > 64 ? ((1ull << (q - 64)) - 1ull) : 0ull);
+  return __popcll(m0 & lo) + __popcll(m1 & hi);
+}
+__global__ __launch_bounds__(256) void k_replay_gather_recv(RecvArgs a) {
+  __shared__ int32_t s_recv[RECV_MAX_LINKS];
+  const int g = blockIdx.x / a.parts, part = blockIdx.x - g * a.parts;
+  const int n = a.n, deg = n - 2, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int64_t slot = a.idx[g];
+  if (t < RECV_MAX_LINKS) s_recv[t] = t < n ? a.recv[slot * n + t] : -1;
+  __syncthreads();
+  const uint64_t m0 = __ballot(s_recv[lane] == lane), m1 = __ballot(s_recv[lane + 64] == lane + 64);
+  const int q0 = part * RECV_ROWS_PER_WG, q1 = min(q0 + RECV_ROWS_PER_WG, n);
+  const int base = a.edge_base ? a.edge_base[g] : g * n * deg;
+  const int most = (g + 1) * n * (n - 1);                                  // (fits int32: the entry point checked K n (n - 1))
+  const int limit = a.edge_base ? min(a.edge_base[g + 1], most) : base + n * deg;
+  if (t < 128) {                                                           // the rows' xe (wave 0) and xe' (wave 1), 16 bytes a lane
+    if (lane < (q1 - q0) * 4) {
+      const uint4* s = reinterpret_cast<const uint4*>(w ? a.xe_next : a.xe) + (slot * n + q0) * 4;
+      uint4* d = reinterpret_cast<uint4*>(w ? a.oxe_next : a.oxe) + ((int64_t)g * n + q0) * 4;
+      d[lane] = s[lane];
+    }
+  } else if (w == 2) {                                                     // actions and row pointers of the rows
+    const int q = q0 + lane;
+    if (q < q1) {
+      a.oaction[(int64_t)g * n + q] = a.action[slot * n + q];
+      a.row_ptr[(int64_t)g * n + q] = base + q * deg + recv_own_before(q, m0, m1);
+    }
+  } else if (lane == 0 && part == 0) {
+    a.oreward[g] = a.reward[slot];
+  } else if (lane == 1 && g == a.K - 1 && part == a.parts - 1) {
+    a.row_ptr[(int64_t)a.K * n] = base + n * deg + recv_own_before(n, m0, m1);
+  }
+  for (int q = q0 + w; q < q1; q += 4) {                                   // a wave per row, lanes along its sources
+    const int r = s_recv[q];
+    const bool own = r == q;
+    const int lo = min(q, r), hi = max(q, r), dq = deg + (own ? 1 : 0);
+    const int e0 = base + q * deg + recv_own_before(q, m0, m1);
+    for (int o = lane; o < dq; o += 64) {
+      int p = o + (o >= lo ? 1 : 0);
+      if (!own) p += p >= hi ? 1 : 0;
+      const int e = e0 + o;
+      if (e >= 0 && e < limit) a.col_idx[e] = p;
+    }
+  }
+}
+
 // Contract check of a device-resident batch (include/v2xgnn.h "Data layout"): every graph has 1..max_nodes rows and at
 // most max_edges edges, row_ptr is monotone, every source id lies inside its graph and the sources of a row are strictly
 // ascending (=> no duplicate edges: the backward pass de-duplicates through bit masks, the forward pass would not).

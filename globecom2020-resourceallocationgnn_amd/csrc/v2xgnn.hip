@@ -2721,6 +2721,34 @@ int v2x_replay_gather_mixed(int32_t n_pools, const v2x_replay_pool* pools, const
   return V2X_OK;
 }
 
+int v2x_replay_gather_recv(const v2x_replay_recv* src, const v2x_mixed_batch* out, void* stream) {
+  v2x_model* nullm = nullptr;
+  if (!src || !out) FAIL(nullm, V2X_EINVAL, "replay_gather_recv: null source or output struct");
+  if (src->n_nodes < 3 || src->n_nodes > RECV_MAX_LINKS)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_recv: n_nodes %d outside 3..%d", src->n_nodes, RECV_MAX_LINKS);
+  if (src->count < 1) FAIL(nullm, V2X_EINVAL, "replay_gather_recv: count %d, at least 1 sampled transition", src->count);
+  if (!src->xe || !src->xe_next || !src->recv || !src->action || !src->reward || !src->idx)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_recv: a null source pointer (only edge_base may be null)");
+  if (!out->xe || !out->xe_next || !out->action || !out->reward || !out->row_ptr || !out->col_idx)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_recv: a null output pointer (only graph_off may be null)");
+  if (((uintptr_t)src->xe & 15) || ((uintptr_t)src->xe_next & 15) || ((uintptr_t)out->xe & 15) || ((uintptr_t)out->xe_next & 15))
+    FAIL(nullm, V2X_EINVAL, "replay_gather_recv: xe / xe_next of the source and of the output must be 16-byte aligned");
+  const int64_t n = src->n_nodes, K = src->count;
+  if (K * n > INT32_MAX || K * n * (n - 1) > INT32_MAX)
+    FAIL(nullm, V2X_EINVAL, "replay_gather_recv: the batch's rows (%lld) or edges (up to %lld) do not fit int32", (long long)(K * n),
+         (long long)(K * n * (n - 1)));
+  RecvArgs a;
+  a.xe = src->xe; a.xe_next = src->xe_next; a.recv = src->recv; a.action = src->action; a.reward = src->reward;
+  a.idx = src->idx; a.edge_base = src->edge_base;
+  a.oxe = out->xe; a.oxe_next = out->xe_next; a.oaction = out->action; a.oreward = out->reward;
+  a.row_ptr = out->row_ptr; a.col_idx = out->col_idx;
+  a.n = (int)n; a.K = (int)K; a.parts = (int)((n + RECV_ROWS_PER_WG - 1) / RECV_ROWS_PER_WG);
+  hipLaunchKernelGGL(k_replay_gather_recv, dim3((unsigned)(K * a.parts)), dim3(256), 0, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) FAIL(nullm, V2X_EHIP, "replay_gather_recv launch failed: %s", hipGetErrorString(e));
+  return V2X_OK;
+}
+
 // ---------------------------------------------------------------------------- dict payload -> packed host batch
 int v2x_pack_feed(const v2x_feed* f, int check_kron, float* xe_out, int32_t* row_ptr_out, int32_t* col_idx_out,
                   float* nbr_out, int32_t* info_out) {

@@ -144,6 +144,15 @@ class MixedBatch(C.Structure):
 
 MIXED_MAX_POOLS = 8
 
+
+class ReplayRecv(C.Structure):
+    """v2x_replay_recv of include/v2xgnn.h"""
+    _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
+        [(k, C.c_void_p) for k in ("xe", "xe_next", "recv", "action", "reward", "idx", "edge_base")]
+
+
+RECV_MAX_LINKS = 128
+
 # int (*)(float* buf, int64_t n, void* stream, void* ctx): an entry of v2x_comm
 COLLECTIVE = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p)
 
@@ -192,6 +201,7 @@ SYMBOLS = [
     ("v2x_dqn_targets", C.c_int, [_P, _P, _P, _P, C.c_double, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     ("v2x_dqn_targets_ragged", C.c_int, [_P, _P, _P, _P, C.c_double, _P, _I, _I, _I, _P, _P]),
     ("v2x_replay_gather_mixed", C.c_int, [_I, C.POINTER(ReplayPool), C.POINTER(MixedBatch), _P]),
+    ("v2x_replay_gather_recv", C.c_int, [C.POINTER(ReplayRecv), C.POINTER(MixedBatch), _P]),
     ("v2x_dqn_step", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_double, C.c_int32, _P, _P, C.c_int, _P]),
     ("v2x_comm_rccl_unique_id", C.c_int, [_P]),
     ("v2x_comm_rccl_create", C.c_int, [_P, _I, _I, _I, C.POINTER(Comm)]),

@@ -103,7 +103,9 @@ class Agent(object):
         needs trajectory_walk='wide'; anything else is a ValueError here.
 
         device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
-        visiting the host; 'auto' = whenever the brain runs on the gfx950 engine.
+        visiting the host; 'auto' = whenever the brain runs on the gfx950 engine and the scenario has at most 31 links.
+        'receivers' (opt-in): the HBM memory that stores a transition's adjacency as its receivers (ReceiverReplay), 3..128
+        links, one v2x_replay_gather_recv launch per minibatch; rollout_backend='host' only, the rollouts take the array path.
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
           'replicated'  every rank steps the SAME seeded simulator and draws the same minibatch, of which it fits its
@@ -157,6 +159,17 @@ class Agent(object):
             if not on_gpu:
                 raise ValueError("device_replay needs a brain on the gfx950 engine")
             self.device_replay = DeviceReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device)
+        elif isinstance(device_replay, str) and device_replay == 'receivers':
+            # opt-in: the adjacency stored as the links' receivers (rl/replay.py ReceiverReplay), 3..128 links
+            from .replay import ReceiverReplay
+            if not on_gpu:
+                raise ValueError("device_replay needs a brain on the gfx950 engine")
+            if not 3 <= self.num_D2D <= ReceiverReplay.MAX_LINKS:
+                raise ValueError("device_replay='receivers': 3..%d links (got %d)" % (ReceiverReplay.MAX_LINKS, self.num_D2D))
+            if rollout_backend != 'host':
+                raise ValueError("device_replay='receivers' takes rollout_backend='host' (got %r): the resident rollouts hold "
+                                 "3..31 links and write DeviceReplay's layout" % (rollout_backend,))
+            self.device_replay = ReceiverReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device)
         self._check_rollout_backend(rollout_backend, on_gpu)
         self.rollout_backend = rollout_backend
         self._check_trajectory_walk(trajectory_walk)
@@ -681,6 +694,8 @@ class Agent(object):
     def _packed_rollouts(self):
         """the batched rollout takes observations in the engine's packed layout (see _generate_batched)"""
         C = self.num_CH
+        if getattr(self.device_replay, 'RECEIVERS', False):      # (stores receivers, takes the array path's add / add_many)
+            return False
         return (self.device_replay is not None and self.num_Neighbor == 1 and hasattr(self.env, 'observe_packed')
                 and self.env.packed_ok(C) and self._compact()
                 and self.brain.num_One_Node_Input + self.brain.num_One_Edge_Input == 3 * C + 1

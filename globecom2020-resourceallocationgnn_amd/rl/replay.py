@@ -14,6 +14,9 @@ rows as is.  The simulator can, rarely, make a link its own receiver (two vehicl
 of Environment.py:365-375 then puts the other one first); such transitions have in-degree n-1 and a minibatch that
 contains one is expanded from the masks instead (torch ops, variable edge count).  New transitions are staged on the host and flushed in one copy per tensor before
 the next sample (the reference stores 50 transitions between replays, BS_brain.py:758).
+
+ReceiverReplay (below) is the same memory for 3..128 links: it stores the receivers instead of the masks and the columns,
+and one launch (`v2x_replay_gather_recv`) gathers a minibatch and emits its CSR, regular or not.
 """
 import ctypes as C
 import os
@@ -423,3 +426,261 @@ class DeviceReplay(object):
                                        current_stream_ptr(self.device.index))
         _lib.check(self._lib, rc, None)
         return y
+
+
+def receivers_from_adjacency(adj):
+    """adj [K, n, n] (Adj[p, q] != 0: p sends to q) -> (recv [K, n] int32, own [K] int32).  With one receiver per link the
+    reference's adjacency (Agent.adjacency, BS_brain.py:441-445) is all ones except the diagonal and Adj[receiver of q, q]:
+    recv[k, q] is the one p != q with adj[k, p, q] == 0, or q itself when there is none (link q is its own receiver: the
+    distance sort put the other vehicle of the same spot first); own[k] counts such links.  A matrix that is not of that
+    form -- a nonzero diagonal entry, two or more zero off-diagonal entries in a column -- is a ValueError naming the link."""
+    adj = np.asarray(adj)
+    if adj.ndim != 3 or adj.shape[1] != adj.shape[2]:
+        raise ValueError("receivers_from_adjacency: adjacency of shape %s, expected [K, n, n]" % (adj.shape,))
+    K, n = adj.shape[0], adj.shape[1]
+    zero = adj == 0
+    q = np.arange(n)
+    diag = zero[:, q, q]
+    if not diag.all():
+        k_, q_ = np.argwhere(~diag)[0]
+        raise ValueError("adjacency of transition %d: link %d sends to itself (nonzero diagonal entry): not a one-receiver "
+                         "topology" % (k_, q_))
+    zero[:, q, q] = False                                   # (zero is a fresh array: adj is not touched)
+    cnt = zero.sum(axis=1)                                  # [K, q]: sources besides q that do not send to q
+    if (cnt > 1).any():
+        k_, q_ = np.argwhere(cnt > 1)[0]
+        raise ValueError("adjacency of transition %d: link %d has %d vehicles besides itself that do not send to it, a "
+                         "one-receiver topology has at most one" % (k_, q_, cnt[k_, q_]))
+    recv = np.where(cnt == 1, zero.argmax(axis=1), q[None, :]).astype(np.int32)
+    return recv, (cnt == 0).sum(axis=1).astype(np.int32)
+
+
+def receivers_to_adjacency(recv):
+    """the inverse of receivers_from_adjacency: recv [K, n] -> adj [K, n, n] float64 of ones and zeros"""
+    recv = np.asarray(recv)
+    K, n = recv.shape
+    adj = np.ones((K, n, n))
+    q = np.arange(n)
+    adj[:, q, q] = 0.0
+    adj[np.arange(K)[:, None], recv, q[None, :]] = 0.0
+    return adj
+
+
+def edge_base_of(n, own):
+    """first edge of every graph of a minibatch and their total, int32 [K + 1]: the cumulative sum of n (n - 2) + own[g]"""
+    eb = np.zeros(len(own) + 1, np.int64)
+    np.cumsum(n * (n - 2) + np.asarray(own, np.int64), out=eb[1:])
+    if eb[-1] > np.iinfo(np.int32).max:
+        raise ValueError("the minibatch's %d edges do not fit int32" % eb[-1])
+    return eb.astype(np.int32)
+
+
+class ReceiverReplay(DeviceReplay):
+    """DeviceReplay for 3..128 links: a transition's adjacency is stored as its receivers (recv[n] int32; recv[q] == q: link q
+    is its own receiver) instead of a 32-bit source mask per link plus the ready-made CSR columns.  With one receiver per
+    link the adjacency is a function of the receivers alone, so a sampled minibatch's CSR is closed-form and ONE launch
+    (v2x_replay_gather_recv, csrc/kernels.hpp k_replay_gather_recv) gathers the rows and emits row_ptr / col_idx of regular
+    and own-receiver graphs alike.  A 100-link transition is 13.6 KB (52 KB with the columns).  Same ring, growth rule,
+    staging and sampling interface as DeviceReplay; the methods that let a DEVICE call write transitions (the resident
+    rollouts hold 3..31 links) raise."""
+    MAX_LINKS = _lib.RECV_MAX_LINKS
+    RECEIVERS = True
+
+    def __init__(self, capacity, n_nodes, device=0):
+        if not 3 <= int(n_nodes) <= self.MAX_LINKS:
+            raise ValueError("ReceiverReplay holds 3..%d links, got %d" % (self.MAX_LINKS, n_nodes))
+        super(ReceiverReplay, self).__init__(capacity, n_nodes, device=device)
+        self.n_edges = self.n * (self.n - 2)
+        self._own = np.zeros(0, np.int32)          # host-side: own-receiver links of the graph in the slot (0: regular)
+        self._eb_in_use = None
+
+    # ------------------------------------------------------------------ storage
+    def _grow(self, need):
+        if need <= self._alloc:
+            return
+        torch, n = self.torch, self.n
+        new = min(self.capacity, max(need, 2 * self._alloc, 65536))
+        def grow(old, shape, dtype):
+            t = torch.zeros((new,) + shape, dtype=dtype, device=self.device)
+            if old is not None:
+                t[:old.shape[0]] = old
+            return t
+        first = self._alloc == 0
+        self.xe = grow(None if first else self.xe, (n, 16), torch.float32)
+        self.xe_next = grow(None if first else self.xe_next, (n, 16), torch.float32)
+        self.recv = grow(None if first else self.recv, (n,), torch.int32)
+        self.action = grow(None if first else self.action, (n,), torch.int32)
+        self.reward = grow(None if first else self.reward, (), torch.float64)
+        own = np.zeros(new, np.int32)
+        own[:self._alloc] = self._own[:self._alloc]
+        self._own = own
+        self._alloc = new
+
+    def add(self, x, e, adj, action, reward, x_next, e_next):
+        """x, x_next [n, Dn]; e, e_next [n, De]; adj [n, n] (Adj[p, q] = 1: p sends to q); action [n]; reward scalar."""
+        self.add_many(np.asarray(x)[None], np.asarray(e)[None], np.asarray(adj)[None], np.asarray(action).reshape(1, -1),
+                      [float(reward)], np.asarray(x_next)[None], np.asarray(e_next)[None])
+
+    def add_many(self, x, e, adj, action, reward, x_next, e_next):
+        """K transitions at once, the arguments of DeviceReplay.add_many; ValueError for an adjacency that is not a
+        one-receiver topology (receivers_from_adjacency)."""
+        adj = np.asarray(adj)
+        K, n = adj.shape[0], self.n
+        if adj.shape[1:] != (n, n):
+            raise ValueError("add_many: adjacency of shape %s, this memory holds %d links" % (adj.shape, n))
+        recv, own = receivers_from_adjacency(adj)
+        x, e = np.asarray(x, np.float32), np.asarray(e, np.float32)
+        xn, en = np.asarray(x_next, np.float32), np.asarray(e_next, np.float32)
+        xe = pack_xe(x.reshape(K * n, -1), e.reshape(K * n, -1)).reshape(K, n, -1)
+        xe_next = pack_xe(xn.reshape(K * n, -1), en.reshape(K * n, -1)).reshape(K, n, -1)
+        self._stage.append((xe, xe_next, recv, np.asarray(action, np.int32).reshape(K, n),
+                            np.asarray(reward, np.float64).reshape(K), own))
+        self._n_staged += K
+
+    def _resident_only(self, what):
+        raise NotImplementedError("ReceiverReplay.%s: transitions written by a device call (the resident rollouts, the packed "
+                                  "observation) hold 3..31 links in DeviceReplay's layout; this memory takes add / add_many" % what)
+
+    def add_many_packed(self, *args, **kwargs):
+        self._resident_only("add_many_packed")
+
+    def stage_early(self, *args, **kwargs):
+        self._resident_only("stage_early")
+
+    def storage(self):
+        self._resident_only("storage")
+
+    def reserve(self, K):
+        self._resident_only("reserve")
+
+    def commit(self, K, row):
+        self._resident_only("commit")
+
+    def prefetch_indices(self, idx, K):
+        self._resident_only("prefetch_indices")
+
+    def row_ptr(self, k):
+        self._resident_only("row_ptr")
+
+    def regular_flags(self):
+        """[allocated slots] bool: the slot holds a graph with in-degree n - 2 everywhere"""
+        return self._own == 0
+
+    def flush(self):
+        """Staged transitions -> HBM (one copy per tensor; ring wrap handled by splitting at the end of the storage)."""
+        if not self._stage:
+            return
+        torch = self.torch
+        k = self._n_staged
+        self._grow(min(self.capacity, self.size + k))
+        one = len(self._stage) == 1
+        cols = [self._stage[0][i] if one else np.concatenate([s[i] for s in self._stage]) for i in range(6)]
+        dst = (self.xe, self.xe_next, self.recv, self.action, self.reward)
+        pos, done = self.head, 0
+        while done < k:
+            m = min(k - done, self._alloc - pos)
+            for t, a, name in zip(dst, cols, ("xe", "xe_next", "recv", "action", "reward")):
+                if self.device.type == "cuda" and m <= 4096:
+                    self._to_device(t[pos:pos + m], a[done:done + m], name)
+                else:
+                    t[pos:pos + m].copy_(torch.from_numpy(np.ascontiguousarray(a[done:done + m])))
+            self._own[pos:pos + m] = cols[5][done:done + m]
+            pos, done = pos + m, done + m
+            if pos == self.capacity:                   # full ring: overwrite the oldest transitions
+                pos = 0
+        self.head = pos
+        self.size = min(self.capacity, self.size + k)
+        self._stage = []
+        self._n_staged = 0
+
+    # ------------------------------------------------------------------ sampling
+    def _upload_edge_base(self, eb):
+        """edge_base [k + 1] where the kernel can read it: a ring of four pinned buffers of its own, like _upload_indices'"""
+        torch, m = self.torch, len(eb)
+        key = ("edge_base", m)
+        ring = self._idx_ring.get(key)
+        if ring is None:
+            ring = self._idx_ring[key] = {"pin": [torch.empty(m, dtype=torch.int32).pin_memory() for _ in range(4)],
+                                          "ev": [None] * 4, "next": 0, "dev": None}
+            zero_copy = os.environ.get("V2X_RL_ZERO_COPY", "1") != "0" and all(
+                self._lib.v2x_device_addressable(t.data_ptr()) == 1 for t in ring["pin"])
+            if not zero_copy:
+                ring["dev"] = [torch.empty(m, dtype=torch.int32, device=self.device) for _ in range(4)]
+        i = ring["next"]
+        ring["next"] = (i + 1) % 4
+        if ring["ev"][i] is not None:
+            ring["ev"][i].synchronize()
+            ring["ev"][i] = None
+        ring["pin"][i].numpy()[:] = eb
+        self._eb_in_use = (ring, i)
+        if ring["dev"] is not None:
+            ring["dev"][i].copy_(ring["pin"][i], non_blocking=True)
+            return ring["dev"][i]
+        return ring["pin"][i]
+
+    def _indices_consumed(self):
+        super(ReceiverReplay, self)._indices_consumed()
+        use, self._eb_in_use = self._eb_in_use, None
+        if use is not None:
+            ev = self.torch.cuda.Event()
+            ev.record()
+            use[0]["ev"][use[1]] = ev
+
+    def _sample_buffers(self, k):
+        """the output tensors of a k-transition minibatch, allocated once: stable pointers let cached batch descriptors and
+        hipGraph replays of the step keep working (col_any, the own-receiver case's n (n - 1) columns per graph, on demand)"""
+        b = self._bufs.get(("recv", k))
+        if b is None:
+            torch, n, dev = self.torch, self.n, self.device
+            b = self._bufs[("recv", k)] = {
+                "xe": torch.empty((k * n, 16), dtype=torch.float32, device=dev),
+                "xe_next": torch.empty((k * n, 16), dtype=torch.float32, device=dev),
+                "action": torch.empty((k, n), dtype=torch.int32, device=dev),
+                "reward": torch.empty(k, dtype=torch.float64, device=dev),
+                "row_ptr": torch.empty(k * n + 1, dtype=torch.int32, device=dev),
+                "col": torch.empty(k * n * (n - 2), dtype=torch.int32, device=dev), "col_any": None, "desc": {}}
+        return b
+
+    def sample(self, idx, pre=None):
+        """-> (batch of s, batch of s', action [k, n] int32, reward [k] float64), all in HBM: the slots go up through the
+        pinned index ring (and, only when a sampled graph has an own-receiver link, the graphs' first edges through a ring
+        of the same kind), then ONE v2x_replay_gather_recv launch fills the reused buffers."""
+        if pre is not None:
+            self._resident_only("sample(pre=...)")
+        self.flush()
+        torch, n, k = self.torch, self.n, len(idx)
+        slots = self.logical_to_slot(idx)
+        own = self._own[slots]
+        regular = not own.any()
+        b = self._sample_buffers(k)
+        if regular:
+            col, eb_dev, n_edges, max_edges = b["col"], None, k * n * (n - 2), n * (n - 2)
+        else:
+            if b["col_any"] is None:
+                b["col_any"] = torch.empty(k * n * (n - 1), dtype=torch.int32, device=self.device)
+            eb = edge_base_of(n, own)
+            col, n_edges, max_edges = b["col_any"], int(eb[-1]), n * (n - 1)
+            eb_dev = self._upload_edge_base(eb)
+        idx_dev = self._upload_indices(slots)
+        key = (self.xe.data_ptr(), col.data_ptr(), idx_dev.data_ptr(), None if eb_dev is None else eb_dev.data_ptr())
+        desc = b["desc"].get(key)
+        if desc is None:
+            if len(b["desc"]) > 64:                        # (storage re-allocated by _grow: the old tables are dead)
+                b["desc"].clear()
+            src = _lib.ReplayRecv(n, k, self.xe.data_ptr(), self.xe_next.data_ptr(), self.recv.data_ptr(), self.action.data_ptr(),
+                                  self.reward.data_ptr(), idx_dev.data_ptr(), None if eb_dev is None else eb_dev.data_ptr())
+            out = _lib.MixedBatch(b["xe"].data_ptr(), b["xe_next"].data_ptr(), b["action"].data_ptr(), b["reward"].data_ptr(),
+                                  None, b["row_ptr"].data_ptr(), col.data_ptr())
+            desc = b["desc"][key] = (src, out)
+        rc = self._lib.v2x_replay_gather_recv(C.byref(desc[0]), C.byref(desc[1]), current_stream_ptr(self.device.index))
+        _lib.check(self._lib, rc, None)
+        self._indices_consumed()
+        if regular:
+            dbs = self._db_cache.get(k)                    # the buffers are reused: so are the batch descriptors
+            if dbs is None:
+                dbs = self._db_cache[k] = tuple(DeviceBatch.from_tensors(k, n, b[t], b["row_ptr"], col, max_edges)
+                                                for t in ("xe", "xe_next"))
+            return dbs[0], dbs[1], b["action"], b["reward"]
+        cols = col[:n_edges]
+        mk = lambda t: DeviceBatch.from_tensors(k, n, t, b["row_ptr"], cols, max_edges)
+        return mk(b["xe"]), mk(b["xe_next"]), b["action"], b["reward"]

@@ -123,6 +123,10 @@ def build_parser():
     ap.add_argument("--trajectory-streams", choices=["chain", "split"], default="chain",
                     help="with --trajectory-walk wide: the stream phase of the wide walk -- 'chain' (the default: one launch draws "
                          "the streams of all steps) or 'split' (raw words, offset walk and conversion in three launches; the same bits)")
+    ap.add_argument("--replay", choices=["auto", "receivers"], default="auto",
+                    help="the replay memory: 'auto' (the default: in HBM up to 31 links, the reference's host memory beyond) or "
+                         "'receivers' (rl/replay.py ReceiverReplay: in HBM for 3..128 links, the adjacency stored as the links' "
+                         "receivers, one gather launch and one replay-step call per train step; --rollout host, one GPU)")
     ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
                     help="train ONE shared-weight network on scenarios of these link counts at once (rl/mixed.py: MixedAgent), "
                          "--envs simulators per size; distinct multiples of 4 up to 28, at most 8 of them.  Host simulators, host "
@@ -212,6 +216,12 @@ def parse_args(argv=None):
     -> (parser, arguments)"""
     ap = build_parser()
     args = ap.parse_args(argv)
+    if args.replay == "receivers":
+        if args.mixed_links is not None:
+            ap.error("--replay receivers holds one link count: --mixed-links keeps one DeviceReplay per link count (4..28 links)")
+        if args.rollout != "host":
+            ap.error("--replay receivers needs --rollout host: the resident rollouts (--rollout %s) hold 3..31 links and write "
+                     "the other memory's layout" % args.rollout)
     if args.mixed_links is not None:
         # the single-size options hold one link count and stay refused; the device simulators and the resident rollout of ALL
         # link counts are asked for by --mixed-sim-backend / --mixed-sim-streams / --mixed-rollout
@@ -311,7 +321,7 @@ def main(argv=None):
             env, cfg, save_dir=args.save_dir if rank == 0 else None, verbose=rank == 0,
             device=local, seed=args.seed, use_graph=args.use_graph, data_parallel=world > 1 or force_dp,
             rollouts=args.rollouts, rollout_backend=args.rollout, trajectory_walk=args.trajectory_walk,
-            trajectory_streams=args.trajectory_streams)
+            trajectory_streams=args.trajectory_streams, device_replay=args.replay)
     dt = time.perf_counter() - t0
     if rank == 0:
         n_fit = args.episodes * args.train_steps

@@ -298,6 +298,31 @@ typedef struct v2x_mixed_batch {
 int  v2x_replay_gather_mixed(int32_t n_pools /*1..8*/, const v2x_replay_pool* pools /*[host]*/,
                              const v2x_mixed_batch* out /*[dev] pointers*/, void* stream);
 
+/* A replay minibatch of 3..128-link graphs from a storage that keeps the adjacency of a transition as its RECEIVERS
+ * (rl/replay.py ReceiverReplay): with one receiver per link, Adj[p, q] = 1 unless p == q or p is the receiver of link q
+ * (BS_brain.py:441-445), so recv[n] stands for the whole matrix; recv[q] == q marks a link that is its own receiver (two
+ * vehicles on one spot: in-degree n - 1 instead of n - 2).  For graph g with slot s = idx[g] the call writes xe / xe_next
+ * rows [g n, (g + 1) n) (16-byte copies), action [g][n], reward [g], and the CSR in packing.adj_to_csr's order:
+ *   row_ptr[g n + q] = base_g + q (n - 2) + #{q' < q : recv[q'] == q'},  base_g = edge_base ? edge_base[g] : g n (n - 2),
+ *   row q: every p in [0, n) except q and recv[q], ascending (graph-local sources),
+ * and the last graph writes row_ptr[K n].  edge_base [K + 1] (first edge of every graph; needed as soon as one sampled graph
+ * has an own-receiver link) is the caller's cumulative sum of n (n - 2) + own(slot); no store goes at or beyond
+ * edge_base[g + 1] nor beyond (g + 1) n (n - 1), so col_idx of K n (n - 1) entries is always enough.  recv is only compared,
+ * never used as an index; slots are not range-checked.  `src` is a [host] struct of [dev] pointers (idx and edge_base
+ * device-addressable), `out` a [host] struct of [dev] pointers whose graph_off is not used and may be NULL; xe / xe_next of
+ * both 16-byte aligned.  One launch on `stream`, no allocation, no synchronisation, no environment variable read.
+ * V2X_EINVAL with the reason (v2x_last_error(NULL)): n_nodes outside 3..128, count < 1, a null pointer other than edge_base
+ * and out->graph_off, a misaligned xe, K n or K n (n - 1) beyond int32.                                                       */
+typedef struct v2x_replay_recv {
+  int32_t n_nodes, count;             /* 3..128 links; K >= 1 sampled transitions */
+  const float *xe, *xe_next;          /* [cap][n][16] */
+  const int32_t *recv, *action;       /* [cap][n]: recv[q] = receiver of link q; recv[q] == q: link q is its own receiver */
+  const double* reward;               /* [cap] */
+  const int32_t* idx;                 /* [K] storage slots, device-addressable */
+  const int32_t* edge_base;           /* [K + 1] first edge of every graph, device-addressable; NULL: every graph regular */
+} v2x_replay_recv;
+int  v2x_replay_gather_recv(const v2x_replay_recv* src /*[host]*/, const v2x_mixed_batch* out /*[dev] pointers*/, void* stream);
+
 /* One whole replay step (BS_brain.py:664-728: predict on s, predict(target) on s', target rule, train_dnn) as a
  * single call on device-resident batches: the graph layers of the online network run ONCE (their activations feed
  * the backward pass), where predict + fit would run them twice.  y_out: optional [dev] [n_rows][C] buffer that
