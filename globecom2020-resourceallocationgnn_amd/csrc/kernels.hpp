@@ -1852,6 +1852,25 @@ __device__ inline int recv_own_before(int q, uint64_t m0, uint64_t m1) {
   const uint64_t hi = q >= 128 ? ~0ull : (q > 64 ? ((1ull << (q - 64)) - 1ull) : 0ull);
   return __popcll(m0 & lo) + __popcll(m1 & hi);
 }
+// The column writer of both receiver kernels: rows [q0, q1) of one graph, wave w of four a row at a time with its lanes along
+// the sources -- row q holds every p in [0, n) except q and recv[q], ascending (all but q when recv[q] == q), from edge
+// base + q (n - 2) + #{q' < q own receiver}.  No store below 0 or at or beyond `limit`; recv is compared, never an index.
+__device__ inline void recv_write_cols(const int32_t* s_recv, uint64_t m0, uint64_t m1, int q0, int q1, int w, int lane, int n,
+                                       int base, int limit, int32_t* col_idx) {
+  const int deg = n - 2;
+  for (int q = q0 + w; q < q1; q += 4) {                                   // a wave per row, lanes along its sources
+    const int r = s_recv[q];
+    const bool own = r == q;
+    const int lo = min(q, r), hi = max(q, r), dq = deg + (own ? 1 : 0);
+    const int e0 = base + q * deg + recv_own_before(q, m0, m1);
+    for (int o = lane; o < dq; o += 64) {
+      int p = o + (o >= lo ? 1 : 0);
+      if (!own) p += p >= hi ? 1 : 0;
+      const int e = e0 + o;
+      if (e >= 0 && e < limit) col_idx[e] = p;
+    }
+  }
+}
 __global__ __launch_bounds__(256) void k_replay_gather_recv(RecvArgs a) {
   __shared__ int32_t s_recv[RECV_MAX_LINKS];
   const int g = blockIdx.x / a.parts, part = blockIdx.x - g * a.parts;
@@ -1881,18 +1900,37 @@ __global__ __launch_bounds__(256) void k_replay_gather_recv(RecvArgs a) {
   } else if (lane == 1 && g == a.K - 1 && part == a.parts - 1) {
     a.row_ptr[(int64_t)a.K * n] = base + n * deg + recv_own_before(n, m0, m1);
   }
-  for (int q = q0 + w; q < q1; q += 4) {                                   // a wave per row, lanes along its sources
-    const int r = s_recv[q];
-    const bool own = r == q;
-    const int lo = min(q, r), hi = max(q, r), dq = deg + (own ? 1 : 0);
-    const int e0 = base + q * deg + recv_own_before(q, m0, m1);
-    for (int o = lane; o < dq; o += 64) {
-      int p = o + (o >= lo ? 1 : 0);
-      if (!own) p += p >= hi ? 1 : 0;
-      const int e = e0 + o;
-      if (e >= 0 && e < limit) a.col_idx[e] = p;
-    }
+  recv_write_cols(s_recv, m0, m1, q0, q1, w, lane, n, base, limit, a.col_idx);
+}
+
+// The CSR alone, for graphs that are RESIDENT (v2x_csr_from_recv; the forward's batch of v2x_rollout_steps_recv): graph g of G
+// takes the receivers of state g % E of recv[E][n] -- the trajectory's T E observations share their states' receivers, which
+// do not change inside a rollout.  Same closed form, order, workgroup shape (RECV_ROWS_PER_WG rows of one graph) and bounds
+// as k_replay_gather_recv, through the same column writer: wave 2 the row pointers, then a wave per row.
+struct CsrRecvArgs {
+  const int32_t *recv, *edge_base;       // [E][n]; [G + 1] first edges or null (every graph regular)
+  int32_t *row_ptr, *col_idx;            // [G n + 1]; [edge_base[G]] or [G n (n - 2)], never beyond G n (n - 1)
+  int n, G, E, parts;                    // links; graphs; states; workgroups per graph
+};
+__global__ __launch_bounds__(256) void k_csr_from_recv(CsrRecvArgs a) {
+  __shared__ int32_t s_recv[RECV_MAX_LINKS];
+  const int g = blockIdx.x / a.parts, part = blockIdx.x - g * a.parts;
+  const int n = a.n, deg = n - 2, t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int64_t state = g % a.E;
+  if (t < RECV_MAX_LINKS) s_recv[t] = t < n ? a.recv[state * n + t] : -1;
+  __syncthreads();
+  const uint64_t m0 = __ballot(s_recv[lane] == lane), m1 = __ballot(s_recv[lane + 64] == lane + 64);
+  const int q0 = part * RECV_ROWS_PER_WG, q1 = min(q0 + RECV_ROWS_PER_WG, n);
+  const int base = a.edge_base ? a.edge_base[g] : g * n * deg;
+  const int most = (g + 1) * n * (n - 1);                                  // (fits int32: the entry point checked G n (n - 1))
+  const int limit = a.edge_base ? min(a.edge_base[g + 1], most) : base + n * deg;
+  if (w == 2) {
+    const int q = q0 + lane;
+    if (q < q1) a.row_ptr[(int64_t)g * n + q] = base + q * deg + recv_own_before(q, m0, m1);
+  } else if (t == 0 && g == a.G - 1 && part == a.parts - 1) {
+    a.row_ptr[(int64_t)a.G * n] = base + n * deg + recv_own_before(n, m0, m1);
   }
+  recv_write_cols(s_recv, m0, m1, q0, q1, w, lane, n, base, limit, a.col_idx);
 }
 
 // Contract check of a device-resident batch (include/v2xgnn.h "Data layout"): every graph has 1..max_nodes rows and at

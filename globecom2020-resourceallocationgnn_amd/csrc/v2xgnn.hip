@@ -2749,6 +2749,24 @@ int v2x_replay_gather_recv(const v2x_replay_recv* src, const v2x_mixed_batch* ou
   return V2X_OK;
 }
 
+int v2x_csr_from_recv(int32_t G, int32_t E, int32_t n, const int32_t* recv, const int32_t* edge_base, int32_t* row_ptr,
+                      int32_t* col_idx, void* stream) {
+  v2x_model* nullm = nullptr;
+  if (n < 3 || n > RECV_MAX_LINKS) FAIL(nullm, V2X_EINVAL, "csr_from_recv: n %d outside 3..%d", n, RECV_MAX_LINKS);
+  if (G < 1 || E < 1) FAIL(nullm, V2X_EINVAL, "csr_from_recv: G = %d graphs over E = %d states, at least 1 of each", G, E);
+  if (!recv || !row_ptr || !col_idx) FAIL(nullm, V2X_EINVAL, "csr_from_recv: a null pointer (only edge_base may be null)");
+  if ((int64_t)G * n >= INT32_MAX || (int64_t)G * n * (n - 1) > INT32_MAX)
+    FAIL(nullm, V2X_EINVAL, "csr_from_recv: the batch's rows (%lld) or edges (up to %lld) do not fit int32", (long long)G * n,
+         (long long)G * n * (n - 1));
+  CsrRecvArgs a;
+  a.recv = recv; a.edge_base = edge_base; a.row_ptr = row_ptr; a.col_idx = col_idx;
+  a.n = n; a.G = G; a.E = E; a.parts = (n + RECV_ROWS_PER_WG - 1) / RECV_ROWS_PER_WG;
+  hipLaunchKernelGGL(k_csr_from_recv, dim3((unsigned)((int64_t)G * a.parts)), dim3(256), 0, (hipStream_t)stream, a);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) FAIL(nullm, V2X_EHIP, "csr_from_recv launch failed: %s", hipGetErrorString(e));
+  return V2X_OK;
+}
+
 // ---------------------------------------------------------------------------- dict payload -> packed host batch
 int v2x_pack_feed(const v2x_feed* f, int check_kron, float* xe_out, int32_t* row_ptr_out, int32_t* col_idx_out,
                   float* nbr_out, int32_t* info_out) {

@@ -94,6 +94,17 @@ class RolloutTraj(C.Structure):
         [(k, C.c_void_p) for k in ("traj_xe", "traj_col", "traj_mask", "traj_regular", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs")]
 
 
+class RolloutRecv(C.Structure):
+    """v2x_rollout_recv of include/v2xgnn.h"""
+    _fields_ = [("model", C.c_void_p), ("batch", Batch)] + \
+        [(k, C.c_void_p) for k in ("q", "explore", "random_actions", "actions")] + \
+        [("step", SimStep), ("recv", C.c_void_p), ("flags", C.c_void_p), ("w_v2v", C.c_double), ("w_v2i", C.c_double),
+         ("T", C.c_int32), ("pad_", C.c_int32)] + \
+        [(k, C.c_void_p) for k in ("traj_xe", "traj_recv", "traj_flags", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs", "row_ptr",
+                                   "col_idx", "edge_base", "rep_xe", "rep_xe_next", "rep_recv", "rep_action", "rep_reward")] + \
+        [("head", C.c_int64), ("capacity", C.c_int64), ("result_reward", C.c_void_p), ("result_flags", C.c_void_p)]
+
+
 class RolloutMixed(C.Structure):
     """v2x_rollout_mixed of include/v2xgnn.h"""
     _fields_ = [("n_pools", C.c_int32), ("T", C.c_int32), ("pools", C.POINTER(RolloutTraj)), ("model", C.c_void_p)] + \
@@ -262,6 +273,10 @@ SYMBOLS = [
     ("v2x_eval_steps_mixed_wide", C.c_int, [C.POINTER(EvalMixed), C.POINTER(TrajWs), _P]),
     ("v2x_eval_sweep_result_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_eval_sweep_mixed", C.c_int, [C.POINTER(EvalSweep), C.POINTER(TrajWs), _P]),
+    ("v2x_sim_observe_recv", C.c_int, [_I, _I, _I, _P, _P, _P] + [C.c_double] * 5 + [_P] * 6),
+    ("v2x_csr_from_recv", C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P]),
+    ("v2x_rollout_recv_workspace_bytes", _L, [_I, _I, _I, _I]),
+    ("v2x_rollout_steps_recv", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P]),
 ]
 
 

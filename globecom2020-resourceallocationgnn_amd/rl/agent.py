@@ -105,7 +105,9 @@ class Agent(object):
         device_replay: keep the replay memory in HBM (rl/replay.py) and run replay() without the minibatch
         visiting the host; 'auto' = whenever the brain runs on the gfx950 engine and the scenario has at most 31 links.
         'receivers' (opt-in): the HBM memory that stores a transition's adjacency as its receivers (ReceiverReplay), 3..128
-        links, one v2x_replay_gather_recv launch per minibatch; rollout_backend='host' only, the rollouts take the array path.
+        links, one v2x_replay_gather_recv launch per minibatch.  With rollout_backend='host' the rollouts take the array path;
+        with rollout_backend='trajectory' on a DeviceBatchedEnviron with streams='device' every rollout that fits the ring is ONE
+        call on the resident state (v2x_rollout_steps_recv: the wide walk, chain stream phase), own-receiver states included.
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
           'replicated'  every rank steps the SAME seeded simulator and draws the same minibatch, of which it fits its
@@ -166,16 +168,22 @@ class Agent(object):
                 raise ValueError("device_replay needs a brain on the gfx950 engine")
             if not 3 <= self.num_D2D <= ReceiverReplay.MAX_LINKS:
                 raise ValueError("device_replay='receivers': 3..%d links (got %d)" % (ReceiverReplay.MAX_LINKS, self.num_D2D))
-            if rollout_backend != 'host':
-                raise ValueError("device_replay='receivers' takes rollout_backend='host' (got %r): the resident rollouts hold "
-                                 "3..31 links and write DeviceReplay's layout" % (rollout_backend,))
-            self.device_replay = ReceiverReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device)
+            resident = (rollout_backend == 'trajectory' and hasattr(self.env, 'rollout_steps_recv')
+                        and getattr(self.env, 'stream_backend', None) == 'device')
+            if rollout_backend != 'host' and not resident:
+                raise ValueError("device_replay='receivers' takes rollout_backend='host', or 'trajectory' on a DeviceBatchedEnviron "
+                                 "with streams='device' (got %r on %s): the other resident rollouts hold 3..31 links and write "
+                                 "DeviceReplay's layout" % (rollout_backend, type(self.env).__name__))
+            self.device_replay = ReceiverReplay(MEMORY_CAPACITY, self.num_D2D, device=engine.device, device_writes=resident)
         self._check_rollout_backend(rollout_backend, on_gpu)
         self.rollout_backend = rollout_backend
         self._check_trajectory_walk(trajectory_walk)
         self.trajectory_walk = trajectory_walk
         self._check_trajectory_streams(trajectory_streams)
         self.trajectory_streams = trajectory_streams
+        if getattr(self.device_replay, 'RECEIVERS', False) and rollout_backend == 'trajectory' and trajectory_streams != 'chain':
+            raise ValueError("device_replay='receivers' with rollout_backend='trajectory' walks wide with the chain stream phase "
+                             "(v2x_rollout_steps_recv); trajectory_streams=%r holds 3..31 links" % (trajectory_streams,))
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
@@ -388,7 +396,15 @@ class Agent(object):
         packed = self._packed_rollouts()
         if packed and E == 1 and self._native_rollout_ok():
             return self._rollout_one_simulator(num_transitions)
-        if self.rollout_backend in ('device', 'trajectory'):
+        if self.rollout_backend == 'trajectory' and getattr(self.device_replay, 'RECEIVERS', False):
+            if n_iter * E <= self.device_replay.capacity:  # (a rollout larger than the ring: the array path below, its own draws)
+                block = self._resident_rollout_recv(self._draw_rollout_ahead(n_iter))
+                out = rewards[:num_transitions] if n_iter * E == num_transitions else rewards
+                self._lazy_rewards = (out, rewards, [(0, block)], E)
+                if not getattr(self, '_predraw_ok', False):
+                    self._resolve_rewards()
+                return out
+        elif self.rollout_backend in ('device', 'trajectory'):
             if not packed:
                 raise RuntimeError("rollout_backend=%r takes the packed observation of the simulator (n_channels == n_RB, "
                                    "3..31 links, V2X_RL_PACKED unset)" % self.rollout_backend)
@@ -519,6 +535,30 @@ class Agent(object):
         result = call(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
                       engine=self.brain.model.engine if anybody else None, row_ptr=rep.row_ptr(K) if anybody else None, **walk)
         rep.commit(K, result)
+        self.num_step += K
+        samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
+        samples.extend([None] * K)
+        if len(samples) > self.memory.capacity:
+            del samples[:len(samples) - self.memory.capacity]
+        return result
+
+    def _resident_rollout_recv(self, drawn):
+        """_resident_rollout(whole=True) on a ReceiverReplay (3..128 links): one reserve, one DeviceBatchedEnviron.rollout_steps_recv,
+        one commit with the own-receiver counts the simulator's host-side receivers give -- so there is no result row to wait
+        for and no fallback: a state with an own-receiver link is scored from the closed-form CSR like any other.  The same
+        numpy draws in the same order as the per-iteration paths.  -> the RecvRolloutResult."""
+        env, rep = self.env, self.device_replay
+        E, n, T = env.E, self.num_D2D, len(drawn)
+        K = T * E
+        anybody = any(len(g) > 0 for _, g in drawn)
+        explore = np.ones((T, E), np.uint8)
+        for row, (_, greedy) in zip(explore, drawn):
+            row[greedy] = 0
+        actions = np.stack([a for a, _ in drawn]).reshape(T, E, n)
+        head = rep.reserve(K)
+        result = env.rollout_steps_recv(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
+                                        engine=self.brain.model.engine if anybody else None)
+        rep.commit(K, np.tile(env.own_receivers(), T))
         self.num_step += K
         samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
         samples.extend([None] * K)

@@ -86,18 +86,25 @@ interference, the observation and the rates run on the device; mobility and the 
 (libv2xsim.so) by default and move to the device with streams='device'.
 The host simulator stays the default and the definition; the two agree to the rounding of the two math libraries
 (tests/test_gpu_device_sim.py).  There is no CPU fallback: without a GPU every device call raises.
+
+Beyond the 31 links of the packed observation (one 32-bit source mask per link) the resident observation is kept in RECEIVER
+form -- `observe_recv`: xe as before, the links' receivers and one flag byte per state in place of mask / col / regular -- and
+`rollout_steps_recv` is the whole rollout of 3..128-link simulators in one call (v2x_rollout_steps_recv), stored in
+rl/replay.py ReceiverReplay's layout; `DeviceBatchedEnviron(streams='device')` serves 32..128 links on it.
 """
 import ctypes as C
 
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutTraj,
-                   SimReset, SimStep, TrajWs, check, load_library)
+from ..lib import (Eval, EvalMixed, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutRecv,
+                   RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
 OBSERVE_MIN_LINKS, OBSERVE_MAX_LINKS, XE_WIDTH = 3, 31, 16
+RECV_MAX_LINKS = 128                                     # v2x_sim_observe_recv / v2x_rollout_steps_recv: receivers, no source masks
+FLAG_OWN, FLAG_BAD = 1, 2                                # the bits of their flag bytes
 MT_WORDS, MAX_LANES = 624, 64                            # v2x_sim_stream
 
 # the radio constants of BatchedEnviron (Environment.py:183-212)
@@ -171,6 +178,32 @@ def wide_workspace_layout(E, n, rb, T):
         offs.append(o)
         o += _align(b, 256)
     return dict(zip(('u_all', 'xy_all', 'pl', 'gs', 'ob_state', 'ob_interf'), offs)), o
+
+
+RECV_SECTIONS = ('traj_xe', 'traj_recv', 'traj_flags', 'traj_v2v_ff', 'traj_v2i_ff', 'traj_v2i_abs', 'row_ptr', 'col_idx')
+
+
+def recv_workspace_layout(E, n, rb, T):
+    """-> (the byte offsets of RECV_SECTIONS and, under 'wide', of the wide walk's own part in the ONE workspace of
+    v2x_rollout_steps_recv, its size): the formula of include/v2xgnn.h, every array rounded up to 256 bytes"""
+    parts = (4 * (T + 1) * E * n * XE_WIDTH, 4 * (T + 1) * E * n, (T + 1) * E, 8 * T * E * n * n * rb, 8 * T * E * n * rb,
+             8 * T * E * n, 4 * (T * E * n + 1), 4 * T * E * n * (n - 1))
+    offs, o = [], 0
+    for b in parts:
+        offs.append(o)
+        o += _align(b, 256)
+    d = dict(zip(RECV_SECTIONS, offs))
+    d['wide'] = o
+    return d, o + wide_workspace_layout(E, n, rb, T)[1]
+
+
+def own_receiver_counts(dest):
+    """dest [E, n] host integers -> (own [E] int32: links of the state that are their own receiver, bad [E] bool: some receiver
+    outside [0, n)): what the host knows about the receivers before they go up (the rule of ReceiverReplay.sample: the
+    own-receiver counts decide whether a batch needs edge_base)"""
+    d = np.asarray(dest)
+    n = d.shape[-1]
+    return (d == np.arange(n)).sum(axis=-1).astype(np.int32), ((d < 0) | (d >= n)).any(axis=-1)
 
 
 WALKS = ('serial', 'wide')                               # how a trajectory call walks a state's T steps (v2x_*_steps / v2x_*_steps_wide)
@@ -345,6 +378,20 @@ class RolloutResult(object):
         return self.resolve().regular.reshape(-1, 2, self.E)[-1, 1]
 
 
+class RecvRolloutResult(RolloutResult):
+    """RolloutResult of rollout_steps_recv: the same bytes, read as flag bytes (.flags [T, 2, E] uint8: FLAG_OWN, FLAG_BAD);
+    .regular is flags == 0"""
+
+    def resolve(self):
+        if self._pin is not None:
+            K = self.T * self.E
+            self._event.synchronize()
+            self.flags = self._pin.numpy()[8 * K:10 * K].reshape(self.T, 2, self.E).copy()
+            RolloutResult.resolve(self)
+            self.regular = self.flags == 0
+        return self
+
+
 def _block_length(explore):
     """T of the explore flags [T, E] of a block (0: not a block, refused by the check)"""
     shape = np.shape(explore)
@@ -375,6 +422,7 @@ class DeviceChannels(object):
         self.torch = None
         self._t = {}                                     # name -> device tensor
         self._obs_ready = False
+        self._own = None                                 # own_receiver_counts of the receivers the device holds, when the host sent them
         self._h2d_done = None
         self._grid = None                                # set_grid(): (lanes [4, n_lanes] float64, width, height, timestep)
         self._grid_sent = False
@@ -384,6 +432,17 @@ class DeviceChannels(object):
         self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
         self.stream_phase_calls = {p: 0 for p in STREAM_PHASES}     # the wide ones among them, by the form of the stream phase
 
+    # the packed observation (xe / mask / col / regular) is current; any assignment -- a step, another observation, a reset --
+    # also says that the receiver form (observe_recv: xe / recv / flags) no longer is: observe_recv sets its own flag after it
+    def _get_obs_ready(self):
+        return self.__dict__.get('_packed_ready', False)
+
+    def _set_obs_ready(self, value):
+        self.__dict__['_packed_ready'] = bool(value)
+        self._recv_ready = False
+
+    _obs_ready = property(_get_obs_ready, _set_obs_ready)
+
     # ------------------------------------------------------------------ shapes and checks
     def shapes(self):
         E, n, rb, m = self.E, self.n, self.rb, min(self.rb, self.n)
@@ -391,7 +450,8 @@ class DeviceChannels(object):
                 'v2v_abs': (E, n, n), 'v2i_abs': (E, n), 'v2v_ff': (E, n, n, rb), 'v2i_ff': (E, n, rb), 'dest': (E, n),
                 'actions': (E, n), 'interf_db': (E, n, rb), 'state': (E, n, 3 * rb + 1), 'xe': (E, n, XE_WIDTH), 'mask': (E, n),
                 'col': (E, n * max(n - 2, 0)), 'regular': (E,), 'v2v_rate': (E, n), 'v2i_rate': (E, m), 'interference': (E, rb),
-                'v2i_interf': (E, rb), 'v2v_interf': (E, n), 'keys': (E, MT_WORDS), 'mtpos': (E,), 'dirs': (E, n), 'status': (E,)}
+                'v2i_interf': (E, rb), 'v2v_interf': (E, n), 'keys': (E, MT_WORDS), 'mtpos': (E,), 'dirs': (E, n), 'status': (E,),
+                'recv': (E, n), 'flags': (E,)}
 
     @staticmethod
     def check_observe(n, C, rb=None):
@@ -475,6 +535,8 @@ class DeviceChannels(object):
                                                                    ('regular', t.uint8)))
         self._rates_dev, self._rates_host, self._rates_np = self._group(tuple(
             (k, f64) for k in ('v2v_rate', 'v2i_rate', 'interference', 'v2i_interf', 'v2v_interf')))
+        # the receiver form's own small outputs (observe_recv; xe is shared with the packed form)
+        self._recv_dev, self._recv_host, self._recv_np = self._group((('recv', t.int32), ('flags', t.uint8)))
 
     def _group(self, fields):
         t, sh = self.torch, self.shapes()
@@ -525,6 +587,8 @@ class DeviceChannels(object):
         """host array -> the device tensor `name` (shadowing states, channel arrays, dest, keys, mtpos, dirs, ...)"""
         where, a = self._check_input(name, array, self._KINDS.get(name, 'f'))
         self._init_device()
+        if name == 'dest':
+            self._own = own_receiver_counts(a) if where == 'host' else None
         if where == 'dev':
             self._t[name].copy_(a)
         else:
@@ -588,8 +652,10 @@ class DeviceChannels(object):
         self._init_device()
         if where == 'dev':
             self._t['dest'].copy_(d)
+            self._own = None
         elif where is not None:
             self._up(self._t['dest'], d)
+            self._own = own_receiver_counts(d)
         T, c = self._t, self.constants
         check(self._lib, self._lib.v2x_sim_observe(
             self.E, self.n, self.rb, T['dest'].data_ptr(), T['v2v_ff'].data_ptr(), T['v2i_ff'].data_ptr(), c['p_v2i'],
@@ -621,8 +687,10 @@ class DeviceChannels(object):
         self._init_device()
         if dwhere == 'dev':
             self._t['dest'].copy_(d)
+            self._own = None
         elif dwhere is not None:
             self._up(self._t['dest'], d)
+            self._own = own_receiver_counts(d)
         if where == 'host':
             self._up(self._t['actions'], a)
             a = self._t['actions']
@@ -1055,6 +1123,227 @@ class DeviceChannels(object):
         counts the wide calls by it."""
         return self._rollout("rollout_steps", _block_length(explore), explore, random_actions, storage, head, capacity, v2v_weight,
                              v2i_weight, engine, row_ptr, power, walk, stream_phase)
+
+    # ------------------------------------------------------------------ 3..128 links: the receiver form (ReceiverReplay's layout)
+    @staticmethod
+    def check_observe_recv(n, C, rb=None):
+        """The limits of v2x_sim_observe_recv / v2x_rollout_steps_recv: check_observe's with 128 links in place of 31."""
+        if not OBSERVE_MIN_LINKS <= n <= RECV_MAX_LINKS:
+            raise ValueError("the device observation in receiver form supports %d..%d links, got %d"
+                             % (OBSERVE_MIN_LINKS, RECV_MAX_LINKS, n))
+        DeviceChannels.check_observe(min(n, OBSERVE_MAX_LINKS), C, rb)
+
+    def observe_recv(self, dest=None, power=None):
+        """observe() for 3..128 links (v2x_sim_observe_recv): interf_db, state and xe as observe() leaves them, and in place of
+        mask / col / regular the receivers (tensor('recv') [E, n] int32, recv[q] == q: link q is its own receiver) and one flag
+        byte per state (tensor('flags'): FLAG_OWN some link is its own receiver, FLAG_BAD some receiver outside [0, n): NaN
+        rows, recv[q] = q throughout).  Host receivers are looked at before they go up (own_receiver_counts): that is where
+        rollout_steps_recv learns whether its batch needs edge_base."""
+        self.check_observe_recv(self.n, self.rb)
+        where = None
+        if dest is not None:
+            where, d = self._check_input('dest', dest, 'i')
+        self._init_device()
+        if where == 'dev':
+            self._t['dest'].copy_(d)
+            self._own = None
+        elif where is not None:
+            self._up(self._t['dest'], d)
+            self._own = own_receiver_counts(d)
+        T, c = self._t, self.constants
+        check(self._lib, self._lib.v2x_sim_observe_recv(
+            self.E, self.n, self.rb, T['dest'].data_ptr(), T['v2v_ff'].data_ptr(), T['v2i_ff'].data_ptr(), c['p_v2i'],
+            c['veh_gain'], c['veh_nf'], c['sig2'], float(c['p_v2v'] if power is None else power), T['interf_db'].data_ptr(),
+            T['state'].data_ptr(), T['xe'].data_ptr(), T['recv'].data_ptr(), T['flags'].data_ptr(), self._stream()))
+        self._obs_ready = False                          # (xe is shared: the packed form's mask / col / regular are not of it)
+        self._recv_ready = True
+
+    def fetch_observation_recv(self):
+        """-> (xe [E, n, 16] float32, recv [E, n] int32, flags [E] uint8) of the last observe_recv(): fresh host arrays"""
+        self._init_device()
+        if not self._recv_ready:
+            raise RuntimeError("fetch_observation_recv: no observe_recv() since the last step()")
+        xe = self._t['xe'].cpu().numpy()
+        self._recv_host.copy_(self._recv_dev, non_blocking=True)
+        self.traffic['bytes_down'] += xe.nbytes + self._recv_host.numel()
+        self._sync()
+        return xe, self._recv_np['recv'].copy(), self._recv_np['flags'].copy()
+
+    def csr_from_recv(self, G, row_ptr, col_idx, edge_base=None):
+        """row_ptr [G n + 1] / col_idx (int32 device tensors) of G graphs on the resident receivers of the last observe_recv(),
+        graph g on state g % E (v2x_csr_from_recv); edge_base: an int32 tensor [G + 1] the device can read, or None (every
+        graph regular)"""
+        self._init_device()
+        if not self._recv_ready:
+            raise RuntimeError("csr_from_recv: no observe_recv() since the last step()")
+        n, G = self.n, int(G)
+        need = n * (n - 2) * G if edge_base is None else None
+        if row_ptr.numel() < G * n + 1 or (need is not None and col_idx.numel() < need):
+            raise ValueError("csr_from_recv: row_ptr of %d and col_idx of %d entries needed" % (G * n + 1, need))
+        check(self._lib, self._lib.v2x_csr_from_recv(G, self.E, n, self._t['recv'].data_ptr(),
+                                                     None if edge_base is None else edge_base.data_ptr(), row_ptr.data_ptr(),
+                                                     col_idx.data_ptr(), self._stream()))
+
+    def check_rollout_steps_recv(self, explore, random_actions, storage, head, capacity, own=None):
+        """ValueError unless the arguments of rollout_steps_recv() fit this object; -> (T, explore [T, E] uint8, random_actions
+        [T, E, n] int32, own [E] int32)"""
+        who, E, n = "rollout_steps_recv", self.E, self.n
+        T = _block_length(explore)
+        self.check_observe_recv(n, self.rb)
+        self._check_mobility(who, True)
+        ex = np.asarray(explore)
+        if T < 1 or ex.shape != (T, E) or ex.dtype.kind not in 'biu':
+            raise ValueError("explore: [T, %d] flags with T >= 1 expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
+        ra = np.asarray(random_actions)
+        if ra.dtype.kind not in 'iu':
+            raise ValueError("random_actions must be integers, got dtype %s" % ra.dtype)
+        if ra.shape == (T, E, n, 1):
+            ra = ra.reshape(T, E, n)
+        if ra.shape != (T, E, n):
+            raise ValueError("random_actions: an array of shape %s expected, got %s" % ([T, E, n], list(ra.shape)))
+        head, capacity, K = int(head), int(capacity), T * E
+        if not K <= capacity or not 0 <= head < capacity:
+            raise ValueError("%s: T E <= capacity and 0 <= head < capacity needed, got T = %d, E = %d, head = %d, capacity = %d"
+                             % (who, T, E, head, capacity))
+        if K * n * (n - 1) > 2 ** 31 - 1:
+            raise ValueError("%s: T E = %d graphs of %d links exceed the 32-bit sizes of a batch" % (who, K, n))
+        want = {'xe': (n, XE_WIDTH), 'xe_next': (n, XE_WIDTH), 'recv': (n,), 'action': (n,), 'reward': ()}
+        for k, tail in want.items():
+            t = storage.get(k)
+            if t is None or tuple(t.shape[1:]) != tail or not t.is_contiguous():
+                raise ValueError("%s: replay storage %r of shape [slots] + %s expected" % (who, k, list(tail)))
+            if t.shape[0] < (capacity if head + K > capacity else head + K):      # (a block that wraps touches the last slot)
+                raise ValueError("%s: replay storage %r has %d slots, the block at %d needs more" % (who, k, t.shape[0], head))
+        if own is None:
+            if self._own is None:
+                raise ValueError("%s: the receivers went up as a device tensor: pass own, the states' own-receiver counts [E] (the "
+                                 "host decides whether the batch needs edge_base)" % who)
+            own, bad = self._own
+            if bad.any():
+                raise ValueError("%s: state(s) %s hold a receiver outside [0, %d)" % (who, np.nonzero(bad)[0].tolist(), n))
+        own = np.asarray(own, np.int32).reshape(-1)
+        if own.shape != (E,) or (own < 0).any() or (own > n).any():
+            raise ValueError("%s: own: %d own-receiver counts in [0, %d] expected" % (who, E, n))
+        return T, ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32), own
+
+    def _recv_io(self, T):
+        """the buffers of rollout_steps_recv() for blocks of T, made once per T: the policy ring and the result block of
+        _rollout_io, q, the ONE workspace (recv_workspace_layout) and a ring of four page-locked edge_base [T E + 1]"""
+        self._init_device()
+        io = self._roll.get(('recv', T))
+        if io is None:
+            t, E, n, rb = self.torch, self.E, self.n, self.rb
+            K = T * E
+            nb = self.rollout_steps_policy_bytes(T)
+            offs, size = recv_workspace_layout(E, n, rb, T)
+            need = self._lib.v2x_rollout_recv_workspace_bytes(E, n, rb, T)
+            if need != size:
+                raise ValueError("rollout_steps_recv: the library sizes the workspace of E = %d, n = %d, rb = %d, T = %d at %d bytes, "
+                                 "the documented layout at %d" % (E, n, rb, T, need, size))
+            ws = t.zeros(size, dtype=t.uint8, device=self.device)
+            if ws.data_ptr() % 256:
+                raise RuntimeError("rollout_steps_recv: the allocator returned a workspace that is not 256-byte aligned")
+            io = self._roll[('recv', T)] = {
+                'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
+                'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
+                'result_dev': t.zeros(self.rollout_steps_result_bytes(T), dtype=t.uint8, device=self.device), 'free': [],
+                'q': t.zeros((K * n, rb), dtype=t.float32, device=self.device), 'graphs': K, 'workspace': ws, 'offsets': offs,
+                'eb_pin': [t.zeros(K + 1, dtype=t.int32, pin_memory=self._pin) for _ in range(4)], 'eb_ev': [None] * 4, 'eb_next': 0,
+                'eb_dev': t.zeros(K + 1, dtype=t.int32, device=self.device)}
+            view = lambda k, count, dt: ws[offs[k]:offs[k] + count * t.empty(0, dtype=dt).element_size()].view(dt)   # noqa: E731
+            io['xe'] = view('traj_xe', K * n * XE_WIDTH, t.float32).view(K * n, XE_WIDTH)
+            io['row_ptr'] = view('row_ptr', K * n + 1, t.int32)
+            io['col_any'] = view('col_idx', K * n * (n - 1), t.int32)
+        return io
+
+    def rollout_steps_recv_buffers(self, T):
+        """the device buffers of rollout_steps_recv() for blocks of T: workspace (carved by recv_workspace_layout: offsets),
+        policy_dev, result_dev (reward [T, E] float64 | flags [T, 2, E] bytes), q [T E n, rb] float32"""
+        return self._recv_io(T)
+
+    def _edge_base(self, io, own, T):
+        """own [E] -> (edge_base pointer or None, n_edges, max_edges) of the T E graphs of a trajectory: every state regular
+        needs none; otherwise the cumulative sum of n (n - 2) + own[g % E] goes up through the next of four page-locked copies"""
+        n, K = self.n, io['graphs']
+        if not own.any():
+            return None, K * n * (n - 2), n * (n - 2)
+        eb = np.zeros(K + 1, np.int64)
+        np.cumsum(n * (n - 2) + np.tile(own.astype(np.int64), T), out=eb[1:])
+        i = io['eb_next']
+        io['eb_next'] = (i + 1) % 4
+        if io['eb_ev'][i] is not None:
+            io['eb_ev'][i].synchronize()
+        io['eb_pin'][i].numpy()[:] = eb
+        io['eb_dev'].copy_(io['eb_pin'][i], non_blocking=True)
+        self.traffic['bytes_up'] += 4 * (K + 1)
+        if io['eb_ev'][i] is None:
+            io['eb_ev'][i] = self.torch.cuda.Event()
+        io['eb_ev'][i].record(self.torch.cuda.current_stream(self.device))
+        return io['eb_dev'].data_ptr(), int(eb[-1]), n * (n - 1)
+
+    def rollout_steps_recv_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine=None, edge_base=None,
+                                  n_edges=None, max_edges=None, power=None):
+        """the v2x_rollout_recv of the resident tensors and rollout_steps_recv_buffers(T) (what rollout_steps_recv() passes to
+        the library); edge_base: a device-readable pointer or None, with the batch's n_edges / max_edges it implies (None:
+        every graph regular)"""
+        io = self._recv_io(T)
+        self._send_grid()
+        t, K, n = self._t, io['graphs'], self.n
+        base, res, ws = io['policy_dev'].data_ptr(), io['result_dev'].data_ptr(), io['workspace'].data_ptr()
+        step = self._sim_step(t['actions'].data_ptr(), power)
+        step.mask = step.col = step.regular = None           # (not read: the receiver form has recv / flags)
+        r = RolloutRecv(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * n, random_actions=base, actions=t['actions'].data_ptr(),
+                        step=step, recv=t['recv'].data_ptr(), flags=t['flags'].data_ptr(), w_v2v=float(v2v_weight),
+                        w_v2i=float(v2i_weight), T=T, pad_=0, edge_base=edge_base, rep_xe=storage['xe'].data_ptr(),
+                        rep_xe_next=storage['xe_next'].data_ptr(), rep_recv=storage['recv'].data_ptr(),
+                        rep_action=storage['action'].data_ptr(), rep_reward=storage['reward'].data_ptr(), head=int(head),
+                        capacity=int(capacity), result_reward=res, result_flags=res + 8 * K,
+                        **{k: ws + io['offsets'][k] for k in RECV_SECTIONS})
+        if engine is not None:
+            from ..engine import DeviceBatch, _batch_struct
+            if edge_base is None:
+                n_edges, max_edges = K * n * (n - 2), n * (n - 2)
+            key = (n_edges, max_edges)
+            db = io.get('batch', {}).get(key)
+            if db is None:
+                db = DeviceBatch.from_tensors(K, n, io['xe'], io['row_ptr'], io['col_any'][:n_edges], max_edges)
+                io['batch'] = {key: db}
+            r.model = engine._h
+            r.batch = _batch_struct(db)
+        return r
+
+    def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, own=None,
+                           power=None):
+        """rollout_steps(walk='wide') for 3..128 links into ReceiverReplay's layout, ONE call (v2x_rollout_steps_recv): the wide
+        walk, the observations of entries 1..T in receiver form, the closed-form CSR of the T E graphs, one forward (engine
+        given), and the finish that picks, pays and stores xe / xe_next / recv / action / reward into slots
+        (head + t E + e) % capacity of `storage` (the tensors of ReceiverReplay.storage()).  States with an own-receiver link
+        are scored and stored like the others.  own: the states' own-receiver counts [E]; None: those of the receivers this
+        object last sent up from the host.  The current observation must be resident in receiver form (observe_recv() or a
+        previous rollout_steps_recv()).  -> a RecvRolloutResult whose download is in flight."""
+        who = "rollout_steps_recv"
+        T, ex, ra, own = self.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own)
+        self._init_device()
+        if not self._recv_ready:
+            raise RuntimeError("%s: no observe_recv() since the last step()" % who)
+        io = self._recv_io(T)
+        self._upload_policy(io, ra, ex)
+        eb, n_edges, max_edges = self._edge_base(io, own, T) if engine is not None else (None, None, None)
+        r = self.rollout_steps_recv_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, eb, n_edges, max_edges, power)
+        self._keep_actions = self._t['actions']
+        ws = io['workspace']
+        check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+        self.walk_calls['wide'] += 1
+        self.stream_phase_calls['chain'] += 1
+        self._obs_ready = False
+        self._recv_ready = True
+        t, free = self.torch, io['free']
+        pinned = free.pop() if free else t.zeros(io['result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
+        pinned.copy_(io['result_dev'], non_blocking=True)
+        self.traffic['bytes_down'] += pinned.numel()
+        ev = t.cuda.Event()
+        ev.record(t.cuda.current_stream(self.device))
+        return RecvRolloutResult(free, ev, pinned, self.E, T)
 
     # ------------------------------------------------------------------ an evaluation episode on the resident state
     def eval_steps_policy_bytes(self, T, baseline=True):
@@ -1773,9 +2062,20 @@ class DeviceBatchedEnviron(BatchedEnviron):
     def _one_call_step(self):
         return False
 
+    def _wide(self, n=None):
+        """more links than the packed observation holds (32..128): the resident observation is kept in receiver form"""
+        return int(self.n_Veh if n is None else n) > OBSERVE_MAX_LINKS
+
     def _check_sizes(self, n=None):
         n = self.n_Veh if n is None else n
-        DeviceChannels.check_observe(int(n), int(self.n_RB))
+        if self._wide(n):
+            if self.stream_backend != 'device':
+                raise ValueError("DeviceBatchedEnviron serves %d..%d links with streams='device' only (the resident observation "
+                                 "is then kept in receiver form), got %d links with streams=%r"
+                                 % (OBSERVE_MAX_LINKS + 1, RECV_MAX_LINKS, n, self.stream_backend))
+            DeviceChannels.check_observe_recv(int(n), int(self.n_RB))
+        else:
+            DeviceChannels.check_observe(int(n), int(self.n_RB))
         if uniforms_per_step(n, self.n_RB) & 1:
             raise NotImplementedError("odd number of draws per step")
 
@@ -1854,7 +2154,9 @@ class DeviceBatchedEnviron(BatchedEnviron):
         cached Gaussian, which only the host's generator objects can hand out"""
         self._check_sizes(n_Veh if n_Veh > 0 else self.n_Veh)
         if self.reset_backend == 'device':
-            if n_Veh > 0 and n_Veh != self.n_Veh:
+            if (n_Veh if n_Veh > 0 else self.n_Veh) > RESET_MAX_LINKS:      # (the device reset holds up to 28 links: the host's runs)
+                self.reset_stats['host'] += 1
+            elif n_Veh > 0 and n_Veh != self.n_Veh:
                 self.reset_stats['host_links_changed'] += 1
             elif any(s.gauss_next is not None for s in self.streams):
                 self.reset_stats['host_cached_gauss'] += 1
@@ -1966,13 +2268,19 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._obs = None
         self._resident_row = None
         dc = self._flush()
-        dc.advance(a.reshape(E, n))
+        if self._wide():                                       # v2x_sim_advance's four launches, the observation in receiver form
+            dc.rates(a.reshape(E, n))
+            dc.stream(mobility=True)
+            dc.step(dc.tensor('u'))
+            dc.observe_recv()
+        else:
+            dc.advance(a.reshape(E, n))
         self._streams_ahead = True
         self._channels_updated()
         self._on_device.add('V2V_Interference_all')
         r = dc.fetch_rates()
         self._rates_pending = False
-        self._dev_obs = dc.fetch_observation()
+        self._dev_obs = None if self._wide() else dc.fetch_observation()
         self.V2I_Interference = r['v2i_interf']
         self.V2V_Interference = r['v2v_interf'].reshape(E, n, 1)
         return r['v2v_rate'].reshape(E, n, 1), r['v2i_rate'], r['interference']
@@ -2047,6 +2355,36 @@ class DeviceBatchedEnviron(BatchedEnviron):
         return self._resident_rollout(True, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine,
                                       row_ptr, walk, stream_phase)
 
+    def own_receivers(self):
+        """[E] int32: the links of every state that are their own receiver, from the host's receivers (0 everywhere unless two
+        vehicles stand on one spot); ValueError for a receiver outside [0, n) -- the look the host takes before dest goes up"""
+        own, bad = own_receiver_counts(self.dest)
+        if bad.any():
+            raise ValueError("dest of environment(s) %s holds a receiver outside [0, %d)" % (np.nonzero(bad)[0].tolist(), self.n_Veh))
+        return own
+
+    def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None):
+        """rollout_steps() for 3..128 links into a ReceiverReplay's storage (DeviceChannels.rollout_steps_recv: the wide walk,
+        the closed-form CSR, one forward, one finish -- ONE call), with the same bookkeeping around it.  The resident
+        observation is brought into receiver form first when it is not (after a reset, or after a packed-form call).
+        -> the RecvRolloutResult of the block, its download in flight."""
+        who = 'rollout_steps_recv'
+        if self.stream_backend != 'device':
+            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
+        self.finish_step()
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        own = self.own_receivers()
+        stale = bool(self._dirty)
+        dc = self._flush()
+        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own)
+        if stale or not dc._recv_ready:
+            dc.observe_recv(self.dest)
+        self._obs = None
+        return self._resident_after(dc.rollout_steps_recv(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight,
+                                                          engine=engine, own=own))
+
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                        walk='serial', stream_phase='chain'):
         """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
@@ -2090,6 +2428,12 @@ class DeviceBatchedEnviron(BatchedEnviron):
 
     def _observe_device(self):
         dc = self._flush()
+        if self._wide():                                       # 32..128 links: receivers and flags stay on the device, no packed copy
+            dc.observe_recv(self.dest)
+            self._host.pop('V2V_Interference_all', None)
+            self._on_device.add('V2V_Interference_all')
+            self._dev_obs = None
+            return None
         dc.observe(self.dest)
         self._host.pop('V2V_Interference_all', None)
         self._on_device.add('V2V_Interference_all')
@@ -2103,6 +2447,8 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._observe_device()
 
     def observe_packed(self, n_channels=4):
+        """(3..31 links, as packed_ok() says: beyond them the resident observation is in receiver form and the agent's view is
+        the inherited observe())"""
         self.finish_step()
         DeviceChannels.check_observe(self.n_Veh, int(n_channels), self.n_RB)
         if self._dev_obs is None or self._dirty:

@@ -481,15 +481,19 @@ class ReceiverReplay(DeviceReplay):
     link the adjacency is a function of the receivers alone, so a sampled minibatch's CSR is closed-form and ONE launch
     (v2x_replay_gather_recv, csrc/kernels.hpp k_replay_gather_recv) gathers the rows and emits row_ptr / col_idx of regular
     and own-receiver graphs alike.  A 100-link transition is 13.6 KB (52 KB with the columns).  Same ring, growth rule,
-    staging and sampling interface as DeviceReplay; the methods that let a DEVICE call write transitions (the resident
-    rollouts hold 3..31 links) raise."""
+    staging and sampling interface as DeviceReplay.  device_writes=True (opt-in, like everything that lets a device call
+    write transitions: Agent asks for it with rollout_backend='trajectory') opens storage() / reserve() / commit(), through
+    which v2x_rollout_steps_recv writes whole blocks in this layout (rl/device_sim.py rollout_steps_recv); a memory built
+    without it takes add / add_many only and refuses the three as before.  What belongs to the packed 31-link observation
+    (add_many_packed, stage_early, prefetch_indices) raises either way."""
     MAX_LINKS = _lib.RECV_MAX_LINKS
     RECEIVERS = True
 
-    def __init__(self, capacity, n_nodes, device=0):
+    def __init__(self, capacity, n_nodes, device=0, device_writes=False):
         if not 3 <= int(n_nodes) <= self.MAX_LINKS:
             raise ValueError("ReceiverReplay holds 3..%d links, got %d" % (self.MAX_LINKS, n_nodes))
         super(ReceiverReplay, self).__init__(capacity, n_nodes, device=device)
+        self.device_writes = bool(device_writes)   # storage / reserve / commit are open (the resident rollout of 3..128 links)
         self.n_edges = self.n * (self.n - 2)
         self._own = np.zeros(0, np.int32)          # host-side: own-receiver links of the graph in the slot (0: regular)
         self._eb_in_use = None
@@ -538,8 +542,16 @@ class ReceiverReplay(DeviceReplay):
         self._n_staged += K
 
     def _resident_only(self, what):
-        raise NotImplementedError("ReceiverReplay.%s: transitions written by a device call (the resident rollouts, the packed "
-                                  "observation) hold 3..31 links in DeviceReplay's layout; this memory takes add / add_many" % what)
+        raise NotImplementedError("ReceiverReplay.%s: the packed observation and the calls that write DeviceReplay's layout hold "
+                                  "3..31 links; this memory takes add / add_many%s" % (
+                                      what, " and, built with device_writes=True, storage / reserve / commit"))
+
+    def _device_writer(self, what):
+        """storage / reserve / commit belong to a memory opened for device calls"""
+        if not self.device_writes:
+            raise NotImplementedError("ReceiverReplay.%s: this memory was built without device_writes=True and takes add / add_many "
+                                      "(the calls that write DeviceReplay's layout hold 3..31 links; v2x_rollout_steps_recv writes "
+                                      "this one: Agent(device_replay='receivers', rollout_backend='trajectory'))" % what)
 
     def add_many_packed(self, *args, **kwargs):
         self._resident_only("add_many_packed")
@@ -547,14 +559,37 @@ class ReceiverReplay(DeviceReplay):
     def stage_early(self, *args, **kwargs):
         self._resident_only("stage_early")
 
+    # ------------------------------------------------------------------ transitions written by the device (v2x_rollout_steps_recv)
     def storage(self):
-        self._resident_only("storage")
+        """the storage tensors by name, for a call that writes transitions in this layout into their slots on the device"""
+        self._device_writer("storage")
+        return {'xe': self.xe, 'xe_next': self.xe_next, 'recv': self.recv, 'action': self.action, 'reward': self.reward}
 
     def reserve(self, K):
-        self._resident_only("reserve")
+        """-> the first slot of a block of K transitions the DEVICE is about to write (slot (head + e) % capacity for
+        transition e: a block may wrap).  Flushes anything staged and grows the storage; nothing is stored until commit()."""
+        self._device_writer("reserve")
+        K = int(K)
+        if not 1 <= K <= self.capacity:
+            raise ValueError("reserve: 1..%d transitions, got %d" % (self.capacity, K))
+        self.flush()
+        self._grow(min(self.capacity, self.size + K))
+        return self.head
 
-    def commit(self, K, row):
-        self._resident_only("commit")
+    def commit(self, K, own):
+        """The block reserve(K) handed out has been enqueued: head and size advance at once.  own [K]: the own-receiver counts
+        of the block's graphs in slot order -- the host knows them before the call (it validated the receivers it uploaded), so
+        they go straight into the per-slot table sample() reads: nothing is pending on a result row."""
+        self._device_writer("commit")
+        K = int(K)
+        own = np.asarray(own, np.int32).reshape(-1)
+        if own.shape != (K,):
+            raise ValueError("commit: %d own-receiver counts expected, got %s" % (K, list(own.shape)))
+        if not 1 <= K <= self.capacity or self.size + K > self._alloc and self._alloc < self.capacity:
+            raise ValueError("commit: no reserved block of %d transitions" % K)
+        self._own[(self.head + np.arange(K)) % self.capacity] = own
+        self.head = (self.head + K) % self.capacity
+        self.size = min(self.capacity, self.size + K)
 
     def prefetch_indices(self, idx, K):
         self._resident_only("prefetch_indices")

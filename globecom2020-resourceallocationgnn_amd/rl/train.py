@@ -126,7 +126,8 @@ def build_parser():
     ap.add_argument("--replay", choices=["auto", "receivers"], default="auto",
                     help="the replay memory: 'auto' (the default: in HBM up to 31 links, the reference's host memory beyond) or "
                          "'receivers' (rl/replay.py ReceiverReplay: in HBM for 3..128 links, the adjacency stored as the links' "
-                         "receivers, one gather launch and one replay-step call per train step; --rollout host, one GPU)")
+                         "receivers, one gather launch and one replay-step call per train step; one GPU; --rollout host, or --rollout "
+                         "trajectory with --sim-backend device --sim-streams device: the whole rollout as one resident call)")
     ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
                     help="train ONE shared-weight network on scenarios of these link counts at once (rl/mixed.py: MixedAgent), "
                          "--envs simulators per size; distinct multiples of 4 up to 28, at most 8 of them.  Host simulators, host "
@@ -219,9 +220,15 @@ def parse_args(argv=None):
     if args.replay == "receivers":
         if args.mixed_links is not None:
             ap.error("--replay receivers holds one link count: --mixed-links keeps one DeviceReplay per link count (4..28 links)")
-        if args.rollout != "host":
-            ap.error("--replay receivers needs --rollout host: the resident rollouts (--rollout %s) hold 3..31 links and write "
-                     "the other memory's layout" % args.rollout)
+        if args.rollout == "device":
+            ap.error("--replay receivers needs --rollout host or --rollout trajectory: the one-iteration resident rollout "
+                     "(--rollout device) holds 3..31 links and writes the other memory's layout")
+        if args.rollout == "trajectory" and (args.sim_backend != "device" or args.sim_streams != "device"):
+            ap.error("--replay receivers needs --rollout host, or --rollout trajectory with --sim-backend device --sim-streams "
+                     "device (the whole rollout is then one call on the state resident in HBM, 3..128 links)")
+        if args.rollout == "trajectory" and args.trajectory_streams != "chain":
+            ap.error("--replay receivers --rollout trajectory walks wide with the chain stream phase: --trajectory-streams split "
+                     "holds 3..31 links")
     if args.mixed_links is not None:
         # the single-size options hold one link count and stay refused; the device simulators and the resident rollout of ALL
         # link counts are asked for by --mixed-sim-backend / --mixed-sim-streams / --mixed-rollout

@@ -883,6 +883,91 @@ int  v2x_rollout_steps_split(const v2x_rollout_traj* r, void* wide_ws, int64_t w
 int  v2x_eval_steps_split(const v2x_eval* r, void* wide_ws, int64_t wide_ws_bytes, void* split_ws, int64_t split_ws_bytes,
                           void* stream);
 
+/* ---- resident rollouts of 3..128 links on the receiver replay (csrc/v2xsimdev.hip, csrc/kernels.hpp) --------------------------
+ * The observation's mask / col outputs keep one 32-bit source mask per link and the one-wave observe and finish kernels need
+ * n + rb <= 64: both stop the calls above at 31 links.  With one receiver per link the receivers ARE the adjacency
+ * (v2x_replay_recv above), so these forms write receivers where the others write mask / col / regular, and the CSR of a
+ * resident batch is one closed-form launch.  Same rules as every v2x_sim_* call: all pointers [dev], asynchronous on `stream`,
+ * no allocation, no synchronisation, no environment variable read; a refusal is V2X_EINVAL with text in v2x_last_error(NULL),
+ * made before anything is launched.
+ *
+ * v2x_sim_observe_recv: v2x_sim_observe for 3 <= n <= 128 (1 <= C <= n, 3 C + 1 <= 16).  interf_db, state and xe are
+ * v2x_sim_observe's, bit for bit (one __device__ function computes the rows of both).  In place of mask / col / regular:
+ * recv[E][n] int32, recv[e][q] = dest[e][q], the encoding of v2x_replay_recv (recv[q] == q: link q is its own receiver), and
+ * flags[E] bytes: bit 0 -- some link of the state is its own receiver; bit 1 -- some receiver lies outside [0, n).  A state
+ * with bit 1 gets NaN rows, recv[q] = q for EVERY q and bit 0 as well (that is what its recv row says), so nothing downstream
+ * ever indexes with the bad receiver.  One workgroup of 128 threads per state, thread k = link k, the receivers in LDS.      */
+int  v2x_sim_observe_recv(int32_t E, int32_t n, int32_t C, const int64_t* dest, const double* v2v_ff, const double* v2i_ff,
+                          double p_v2i, double veh_gain, double veh_nf, double sig2, double power, double* interf_db,
+                          double* state, float* xe, int32_t* recv, uint8_t* flags, void* stream);
+/* v2x_csr_from_recv: row_ptr[G n + 1] and col_idx of G resident graphs of n links, nothing else.  Graph g takes the receivers
+ * of state g % E of recv[E][n] (the T E observations of a trajectory share their states' receivers).  The closed form, the
+ * order (packing.adj_to_csr's) and the meaning of edge_base[G + 1] (NULL: every graph regular) are v2x_replay_gather_recv's,
+ * written by the same __device__ column writer; so are the bounds: no store below 0, at or beyond edge_base[g + 1] or beyond
+ * (g + 1) n (n - 1); recv is compared, never used as an index.  One launch.  V2X_EINVAL: n outside 3..128, G or E < 1, a
+ * null pointer other than edge_base, G n or G n (n - 1) beyond int32.                                                         */
+int  v2x_csr_from_recv(int32_t G, int32_t E, int32_t n, const int32_t* recv /*[E][n]*/, const int32_t* edge_base /*[G + 1] or NULL*/,
+                       int32_t* row_ptr /*[G n + 1]*/, int32_t* col_idx, void* stream);
+/* v2x_rollout_steps_recv: v2x_rollout_steps_wide for 3 <= n <= 128 links (rb <= n, 3 rb + 1 <= 16, T >= 1, T E <= capacity,
+ * T E n (n - 1) < 2^31), storing into ReceiverReplay's layout.  Enqueues, in this order on one stream, no parallel branches:
+ *   1. the wide walk: k_traj_stream (entry 0 copied in the receiver form: xe, recv, flags; snapshot 0 unchanged), k_traj_terms
+ *      and k_traj_scan -- the device functions of v2x_rollout_steps_wide, so the same bits in every stream, position and
+ *      channel array;
+ *   2. k_traj_observe_recv, one workgroup of 128 threads per (t, e): v2x_sim_observe_recv for entries 1..T;
+ *   3. v2x_csr_from_recv for the G = T E graphs of entries 0..T-1 from the resident recv (skipped without a model);
+ *   4. v2x_forward of those graphs into q (skipped without a model);
+ *   5. k_rollout_finish_recv, one workgroup of 192 threads per transition (n + rb <= 144 of them compute a rate): the pick,
+ *      rates, summation and reward functions of k_rollout_finish; xe of entry t and xe' of entry t + 1 (16-byte words), recv,
+ *      action and reward into slot (head + t E + e) % capacity; the transitions of t = T - 1 also leave the resident actions
+ *      and rate arrays.
+ * A state with an own-receiver link is scored and stored like any other (its CSR is closed-form): there is no fallback.
+ * The caller validates dest on the host, and, only when some state has an own-receiver link, passes edge_base[T E + 1] (the
+ * cumulative sum of n (n - 2) + own(g % E)) and sizes batch.n_edges / batch.max_edges by it (v2x_replay_gather_recv's rule).
+ * In `r`: `step` is a v2x_sim_step whose mask / col / regular are not read (the resident observation is xe / state /
+ * interf_db of `step` plus recv / flags here); batch: on_device, T E graphs of n rows, max_nodes = n, xe = traj_xe, row_ptr /
+ * col_idx those of this struct, n_edges = T E n (n - 2) and max_edges = n (n - 2) without edge_base, else T E n (n - 2) <=
+ * n_edges <= T E n (n - 1) and max_edges = n (n - 1); explore [T][E], random_actions [T][E][n], q [T E n][rb]; result_reward
+ * [T][E], result_flags [T][2][E] (row t: the flags of the stored observation, then of the next one).
+ * ws: ONE allocation of v2x_rollout_recv_workspace_bytes(E, n, rb, T) bytes, fourteen arrays back to back, each rounded up
+ * to a multiple of 256 bytes -- first the eight the struct points into, which MUST be these sections in this order,
+ *   traj_xe, traj_recv, traj_flags, traj_v2v_ff, traj_v2i_ff, traj_v2i_abs, row_ptr, col_idx,
+ * then the wide walk's own six (v2x_traj_wide_workspace_bytes), contents undefined afterwards:
+ *   A(4 (T+1) E n 16) + A(4 (T+1) E n) + A((T+1) E) + A(8 T E n n rb) + A(8 T E n rb) + A(8 T E n) + A(4 (T E n + 1))
+ *   + A(4 T E n (n-1)) + A(8 T E n_u) + A(16 T E n) + A(8 T E n_el) + A(8 T E n_el) + A(8 (T-1) E n (3 rb + 1))
+ *   + A(8 (T-1) E n rb),   n_u = n + n^2 + 2 n rb + 2 n^2 rb, n_el = n + n^2, A(x) = ceil(x / 256) * 256.
+ * v2x_rollout_recv_workspace_bytes: that sum, or a negative V2X_E* code outside the limits.  ws must be 256-byte aligned;
+ * rep_xe / rep_xe_next 16-byte aligned.  A refused call leaves state and storage alone.                                      */
+typedef struct v2x_rollout_recv {
+  v2x_model* model;                /* the online network, or NULL: nobody is greedy */
+  v2x_batch batch;
+  float* q;                        /* [T E n][rb] Q workspace (required with a model) */
+  const uint8_t* explore;          /* [T][E]    */
+  const int32_t* random_actions;   /* [T][E][n] */
+  int32_t* actions;                /* [E][n]: the resident actions (those of step T - 1) */
+  v2x_sim_step step;               /* mask / col / regular not read; actions NULL or `actions` */
+  int32_t* recv;                   /* [E][n]  the resident observation's receivers */
+  uint8_t* flags;                  /* [E]     and flag bytes */
+  double w_v2v, w_v2i;
+  int32_t T, pad_;
+  float* traj_xe;                  /* [T+1][E][n][16]  */
+  int32_t* traj_recv;              /* [T+1][E][n]      */
+  uint8_t* traj_flags;             /* [T+1][E]         */
+  double* traj_v2v_ff;             /* [T][E][n][n][rb] */
+  double* traj_v2i_ff;             /* [T][E][n][rb]    */
+  double* traj_v2i_abs;            /* [T][E][n]        */
+  int32_t* row_ptr;                /* [T E n + 1]      */
+  int32_t* col_idx;                /* [T E n (n - 1)]  */
+  const int32_t* edge_base;        /* [T E + 1] device-addressable, or NULL: every state regular */
+  float *rep_xe, *rep_xe_next;     /* [capacity][n][16] */
+  int32_t *rep_recv, *rep_action;  /* [capacity][n]     */
+  double* rep_reward;              /* [capacity]        */
+  int64_t head, capacity;
+  double* result_reward;           /* [T][E]    */
+  uint8_t* result_flags;           /* [T][2][E] */
+} v2x_rollout_recv;
+int64_t v2x_rollout_recv_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
+int  v2x_rollout_steps_recv(const v2x_rollout_recv* r, void* ws, int64_t ws_bytes, void* stream);
+
 /* The mixed wide walk: v2x_rollout_steps_mixed and v2x_eval_steps_mixed with every pool's trajectory spread over the chip --
  * the wide walk with the split stream phase, for all link counts at once.  Both calls enqueue, on the one stream with no
  * parallel branches, exactly what their serial siblings enqueue, with six launches in k_sim_trajectory_mixed's place; each is
