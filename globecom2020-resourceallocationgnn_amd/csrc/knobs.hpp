@@ -31,8 +31,9 @@ struct Knobs {
   int wide_fold = 1;              // V2X_WIDE_FOLD=0: the [x | e] segment of a wide layer as a K tile of its own
   int wide_adam = 1;              // V2X_WIDE_ADAM=0: Adam never in the wide weight-gradient epilogues
   int wide_tail = 1;              // V2X_WIDE_TAIL: 0 whole 128-row tiles only, 2 half tiles for a launch below one round
+  int wide_slots = 0;             // V2X_WIDE_SLOTS: resident slots the half-tile rule plans for (0: five per CU; tests)
   // ---- launch sizes
-  int wg_embed_merge = 1;         // V2X_WG_EMBED_MERGE=0: the embed layer's gradient as a role of its own
+  int wg_embed_merge = 1;        // V2X_WG_EMBED_MERGE=0: the embed layer's gradient as a role of its own
   int wg_rounds = 0;              // V2X_WG_ROUNDS: > 0 work-proportional chunk counts, so many rounds of the chip
   int wg_chunk = 0;               // V2X_WG_CHUNK: rows per weight-gradient workgroup, every role (0: per-role defaults)
   int wg_chunk_gnn = 0;           // V2X_WG_CHUNK_GNN: ... of the graph layers' roles (0: 896, wide 1024)
@@ -79,6 +80,7 @@ inline Knobs read_knobs() {
   num("V2X_WIDE_FOLD", k.wide_fold);
   num("V2X_WIDE_ADAM", k.wide_adam);
   num("V2X_WIDE_TAIL", k.wide_tail);
+  num("V2X_WIDE_SLOTS", k.wide_slots);
   num("V2X_WG_EMBED_MERGE", k.wg_embed_merge);
   num("V2X_WG_ROUNDS", k.wg_rounds);
   num("V2X_WG_CHUNK", k.wg_chunk);

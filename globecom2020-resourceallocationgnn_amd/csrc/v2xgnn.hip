@@ -80,6 +80,9 @@ struct v2x_model {
   float* zero_buf = nullptr;   // 4 KiB of zeros
   float* slab = nullptr; int slab_cap = 0;
   int reduce_groups = 0;        // AdamArgs::groups of the last launch_reduce_adam (v2x_debug_layer_slabs)
+  // v2x_debug_wide_tiling: {ny, mbs, n_full_rb, n_rb} of the k_wide_gemm launches and {kt, nt, sp, folded} of the wide
+  // weight-gradient roles enqueued since it was last read (the first WIDE_REC_LAUNCHES / WIDE_REC_ROLES of them)
+  std::vector<int32_t> wide_rec_tiles, wide_rec_roles;
   // staging for host-side inputs
   DevBuf st_xe, st_nbr, st_goff, st_rp, st_ci, st_y, st_q;
   DevBuf adj_mask;              // adjacency bit masks of the current batch (dense-graph aggregation)
@@ -704,22 +707,33 @@ void set_idx(WideGemmArgs& a, const IdxMap& x) {
 // Dense-0's 80 columns are one 5-tile strip instead of a 64 + 16 split (154 -> 110 us).
 int wide_nt(int n_out) { return n_out <= 80 ? 5 : 4; }
 
-int launch_wide_gemm(v2x_model* m, hipStream_t st, WideGemmArgs& a, int grid_z, bool trans, const char* name) {
-  const int nt = wide_nt(a.n_out);
-  // Tiling (kernels_wide.hpp, WideTiling): 128-row tiles; when the launch is more than one round of the chip's resident
-  // workgroups (five per CU) and its last round would be less than three quarters full, the row blocks of that last round run
-  // as two 64-row tiles each, dispatched last (V2X_WIDE_TAIL=0: whole tiles only)
-  const int tail = m->knobs.wide_tail;
+// Tiling of one k_wide_gemm launch (kernels_wide.hpp, WideTiling) over `slots` resident workgroups, host arithmetic only:
+// 128-row tiles; when the launch is more than one round of the slots (the chip's: five per CU) and its last round would be
+// less than three quarters full, the row blocks of that last round run as two 64-row tiles each, dispatched last
+// (tail = V2X_WIDE_TAIL; 0: whole tiles only)
+WideTiling wide_tiling_plan(int n_idx, int grid_z, int n_out, int slots, int tail) {
+  const int nt = wide_nt(n_out);
   WideTiling t;
-  t.ny = (a.n_out + 16 * nt - 1) / (16 * nt);
-  t.mbs = (a.n_idx + WD_TM - 1) / WD_TM;
+  t.ny = (n_out + 16 * nt - 1) / (16 * nt);
+  t.mbs = (n_idx + WD_TM - 1) / WD_TM;
   t.n_rb = t.mbs * grid_z;
   t.n_full_rb = t.n_rb;
-  const int T = t.n_rb * t.ny, C = 5 * n_cus(), rem = T % C;
+  const int T = t.n_rb * t.ny, C = slots, rem = T % C;
   if (tail && T > C && rem > 0 && 4 * rem < 3 * C) t.n_full_rb = t.n_rb - rem / t.ny;
-  // a launch that does not fill the chip's resident slots at all (Dense-0 at configs[3]'s share: 800 tiles of 128 x 80 on 1,280
+  // a launch that does not fill the resident slots at all (Dense-0 at configs[3]'s share: 800 tiles of 128 x 80 on 1,280
   // slots, three workgroups per CU instead of five): every row block as two half tiles (V2X_WIDE_TAIL=2 only: measured)
   if (tail == 2 && T < C && 2 * T > C) t.n_full_rb = 0;
+  return t;
+}
+
+constexpr int WIDE_REC_LAUNCHES = 32, WIDE_REC_ROLES = 16;      // what v2x_debug_wide_tiling keeps between two reads
+
+int launch_wide_gemm(v2x_model* m, hipStream_t st, WideGemmArgs& a, int grid_z, bool trans, const char* name) {
+  const int nt = wide_nt(a.n_out);
+  // V2X_WIDE_SLOTS: the rule plans for so many slots instead of the chip's (which row blocks run as half tiles, nothing else)
+  const int slots = m->knobs.wide_slots > 0 ? m->knobs.wide_slots : 5 * n_cus();
+  const WideTiling t = wide_tiling_plan(a.n_idx, grid_z, a.n_out, slots, m->knobs.wide_tail);
+  if ((int)m->wide_rec_tiles.size() < 4 * WIDE_REC_LAUNCHES) m->wide_rec_tiles.insert(m->wide_rec_tiles.end(), {t.ny, t.mbs, t.n_full_rb, t.n_rb});
   const dim3 grid(t.n_full_rb * t.ny + 2 * (t.n_rb - t.n_full_rb) * t.ny);
 #define V2X_WIDE_GEMM(T_, NTV) { auto k = k_wide_gemm<T_, NTV>; LAUNCH(m, name, k, grid, 256, 0, st, a, t); return V2X_OK; }
   if (!trans) {
@@ -816,6 +830,7 @@ int wide_wgrad_plan(v2x_model* m, hipStream_t st, LayerDesc& ld, const IdxMap& x
     }
   }
   out->kt = kt; out->nt = nt; out->ntw = ntw; out->sp = sp;
+  if ((int)m->wide_rec_roles.size() < 4 * WIDE_REC_ROLES) m->wide_rec_roles.insert(m->wide_rec_roles.end(), {kt, nt, sp, a.xseg.ptr != nullptr ? 1 : 0});
   return V2X_OK;
 }
 
@@ -2873,6 +2888,28 @@ int v2x_debug_layer_slabs(v2x_model* m, int32_t* out, int n) {
     for (const LayerDesc& ld : *v) out[k++] = ld.n_slabs;
   out[k++] = m->reduce_groups;
   return k;
+}
+
+int v2x_wide_tiling_plan(int32_t n_idx, int32_t grid_z, int32_t n_out, int32_t slots, int32_t tail, int32_t out[4]) {
+  v2x_model* m = nullptr;
+  if (!out) FAIL(m, V2X_EINVAL, "wide_tiling_plan: null output");
+  if (n_idx < 1 || grid_z < 1 || n_out < 1 || slots < 1 || tail < 0 || tail > 2) FAIL(m, V2X_EINVAL, "wide_tiling_plan: n_idx, grid_z, n_out, slots >= 1 and tail in 0..2");
+  if (slots > (1 << 28) || ((int64_t)n_idx + WD_TM - 1) / WD_TM * grid_z * (((int64_t)n_out + 63) / 64) > (1 << 28))
+    FAIL(m, V2X_EINVAL, "wide_tiling_plan: more than 2^28 slots or tiles");
+  const WideTiling t = wide_tiling_plan(n_idx, grid_z, n_out, slots, tail);
+  out[0] = t.ny; out[1] = t.mbs; out[2] = t.n_full_rb; out[3] = t.n_rb;
+  return V2X_OK;
+}
+
+int v2x_debug_wide_tiling(v2x_model* m, int32_t* out, int n) {
+  if (!m || !out || n < 0) FAIL(m, V2X_EINVAL, "null argument");
+  const int nl = (int)m->wide_rec_tiles.size(), nr = (int)m->wide_rec_roles.size(), want = 2 + nl + nr;
+  if (n < want) FAIL(m, V2X_EINVAL, "wide_tiling: room for %d values needed", want);
+  out[0] = nl / 4; out[1] = nr / 4;
+  std::copy(m->wide_rec_tiles.begin(), m->wide_rec_tiles.end(), out + 2);
+  std::copy(m->wide_rec_roles.begin(), m->wide_rec_roles.end(), out + 2 + nl);
+  m->wide_rec_tiles.clear(); m->wide_rec_roles.clear();
+  return want;
 }
 
 int v2x_profile_enable(v2x_model* m, int enable) {

@@ -337,6 +337,18 @@ class GnnEngine(object):
         self._check(self._lib.v2x_path_info(self._h, C.byref(s), buf, 256))
         return dict(kv.split("=", 1) for kv in buf.value.decode().split())
 
+    def wide_tiling(self):
+        """([(ny, mbs, n_full_rb, n_rb) per wide GEMM launch], [(K tiles, column tiles, row splits, folded) per wide weight-gradient
+        role]) enqueued since the previous call (v2x_debug_wide_tiling); a replayed hipGraph records nothing."""
+        buf = (C.c_int32 * 194)()
+        k = self._lib.v2x_debug_wide_tiling(self._h, buf, 194)
+        if k < 0:
+            self._check(k)
+        v = [int(t) for t in buf[:k]]
+        a, b = v[0], v[1]
+        four = lambda w: [tuple(w[i:i + 4]) for i in range(0, len(w), 4)]
+        return four(v[2:2 + 4 * a]), four(v[2 + 4 * a:2 + 4 * a + 4 * b])
+
     def profile(self, enable):
         self._check(self._lib.v2x_profile_enable(self._h, 1 if enable else 0))
 

@@ -1052,6 +1052,18 @@ int  v2x_debug_ragged_plan(v2x_model* m, int32_t* out, int n);
  * column (1, 4 or 16) of the last slab sum / Adam launch.  n >= L + 6; returns the number of values written (L + 6) or a
  * negative error code.  Launches nothing.  [host] out. */
 int  v2x_debug_layer_slabs(v2x_model* m, int32_t* out, int n);
+/* Tests: how a wide GEMM launch (feat_dim >= 128: node update, Dense-0 and their data gradients) of n_idx rows per weight slot,
+ * grid_z slots and n_out output columns is cut for `slots` resident workgroups -- out = {ny column tiles, mbs 128-row blocks per
+ * slot, n_full_rb, n_rb}: row blocks [0, n_full_rb) of the slot-major enumeration run as one 128-row tile per column tile, the
+ * other n_rb - n_full_rb as two 64-row half tiles.  tail = V2X_WIDE_TAIL (0, 1 or 2).  The rule the launches themselves use,
+ * with slots = five per compute unit unless V2X_WIDE_SLOTS says otherwise.  Host arithmetic: no model, no GPU.  [host] out. */
+int  v2x_wide_tiling_plan(int32_t n_idx, int32_t grid_z, int32_t n_out, int32_t slots, int32_t tail, int32_t out[4]);
+/* Tests: what the model's wide launches were since the previous call of this function -- out[0] = A wide GEMM launches kept (the
+ * first 32), out[1] = B wide weight-gradient roles kept (the first 16), then A x {ny, mbs, n_full_rb, n_rb} (v2x_wide_tiling_plan)
+ * in launch order, then B x {K tiles, column tiles, row splits, 1 if the [x | e] segment rides on K tile 0} in the order the roles
+ * were planned.  Recorded where the launches are enqueued: a hipGraph capture records, its replays do not.  n >= 2 + 4 A + 4 B
+ * (194 is always enough); returns the number of values written or a negative error code.  Launches nothing.  [host] out. */
+int  v2x_debug_wide_tiling(v2x_model* m, int32_t* out, int n);
 int  v2x_profile_read(v2x_model* m, char* names_out, int names_cap, double* ms_out, int64_t* calls_out,
                       int max_entries);   /* returns number of entries, names '\n'-separated */
 
