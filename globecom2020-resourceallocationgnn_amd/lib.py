@@ -279,6 +279,8 @@ SYMBOLS = [
     ("v2x_csr_from_recv", C.c_int, [_I, _I, _I, _P, _P, _P, _P, _P]),
     ("v2x_rollout_recv_workspace_bytes", _L, [_I, _I, _I, _I]),
     ("v2x_rollout_steps_recv", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P]),
+    ("v2x_rollout_recv_split_workspace_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_rollout_steps_recv_split", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P, _L, _P]),
 ]
 
 

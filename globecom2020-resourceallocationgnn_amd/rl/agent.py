@@ -80,7 +80,7 @@ class Memory(object):
 class Agent(object):
     def __init__(self, num_d2d, num_ch, num_neighbor, num_d2d_feedback, environment, curr_rl_config, brain=None,
                  device_replay='auto', rollouts='replicated', rollout_backend='host', trajectory_walk='serial', trajectory_streams='chain',
-                 **brain_kwargs):
+                 receiver_streams='chain', **brain_kwargs):
         """rollout_backend: 'host' (the default: _packed_iteration -- the observation comes down, is scored, the actions go up,
         the transitions go up again) or 'device': a whole rollout iteration is ONE call on the resident state (v2x_rollout_step:
         score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
@@ -108,6 +108,11 @@ class Agent(object):
         links, one v2x_replay_gather_recv launch per minibatch.  With rollout_backend='host' the rollouts take the array path;
         with rollout_backend='trajectory' on a DeviceBatchedEnviron with streams='device' every rollout that fits the ring is ONE
         call on the resident state (v2x_rollout_steps_recv: the wide walk, chain stream phase), own-receiver states included.
+
+        receiver_streams: the stream phase of those receiver-form rollouts: 'chain' (the default) or 'split'
+        (v2x_rollout_steps_recv_split: the raw words, the offset walk for up to 128 vehicles and the conversion as three
+        launches) -- the same bits (tests/test_gpu_rollout_recv_split.py), opt-in.  'split' needs device_replay='receivers' and
+        rollout_backend='trajectory'; anything else is a ValueError here.  (trajectory_streams stays the 3..31-link option.)
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
           'replicated'  every rank steps the SAME seeded simulator and draws the same minibatch, of which it fits its
@@ -184,6 +189,13 @@ class Agent(object):
         if getattr(self.device_replay, 'RECEIVERS', False) and rollout_backend == 'trajectory' and trajectory_streams != 'chain':
             raise ValueError("device_replay='receivers' with rollout_backend='trajectory' walks wide with the chain stream phase "
                              "(v2x_rollout_steps_recv); trajectory_streams=%r holds 3..31 links" % (trajectory_streams,))
+        if receiver_streams not in TRAJECTORY_STREAMS:
+            raise ValueError("receiver_streams must be one of %s, got %r" % (TRAJECTORY_STREAMS, receiver_streams))
+        if receiver_streams == 'split' and not (getattr(self.device_replay, 'RECEIVERS', False) and rollout_backend == 'trajectory'):
+            raise ValueError("receiver_streams='split' needs device_replay='receivers' and rollout_backend='trajectory' (it is a form "
+                             "of the stream phase of v2x_rollout_steps_recv): device_replay is %r, rollout_backend is %r"
+                             % (device_replay, rollout_backend))
+        self.receiver_streams = receiver_streams
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
@@ -557,7 +569,7 @@ class Agent(object):
         actions = np.stack([a for a, _ in drawn]).reshape(T, E, n)
         head = rep.reserve(K)
         result = env.rollout_steps_recv(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
-                                        engine=self.brain.model.engine if anybody else None)
+                                        engine=self.brain.model.engine if anybody else None, stream_phase=self.receiver_streams)
         rep.commit(K, np.tile(env.own_receivers(), T))
         self.num_step += K
         samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)

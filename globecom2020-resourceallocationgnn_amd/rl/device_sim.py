@@ -90,7 +90,10 @@ The host simulator stays the default and the definition; the two agree to the ro
 Beyond the 31 links of the packed observation (one 32-bit source mask per link) the resident observation is kept in RECEIVER
 form -- `observe_recv`: xe as before, the links' receivers and one flag byte per state in place of mask / col / regular -- and
 `rollout_steps_recv` is the whole rollout of 3..128-link simulators in one call (v2x_rollout_steps_recv), stored in
-rl/replay.py ReceiverReplay's layout; `DeviceBatchedEnviron(streams='device')` serves 32..128 links on it.
+rl/replay.py ReceiverReplay's layout; `DeviceBatchedEnviron(streams='device')` serves 32..128 links on it.  It takes
+stream_phase='chain' (the default) or 'split' too (v2x_rollout_steps_recv_split: raw words, an offset walk with two vehicles
+per lane and the conversion in three launches on a second workspace made once per T; the same bits, 2.5-2.7x faster at
+32..128 links, profiles/rollout_recv_split_timing.json).
 """
 import ctypes as C
 
@@ -1184,10 +1187,11 @@ class DeviceChannels(object):
                                                      None if edge_base is None else edge_base.data_ptr(), row_ptr.data_ptr(),
                                                      col_idx.data_ptr(), self._stream()))
 
-    def check_rollout_steps_recv(self, explore, random_actions, storage, head, capacity, own=None):
+    def check_rollout_steps_recv(self, explore, random_actions, storage, head, capacity, own=None, stream_phase='chain'):
         """ValueError unless the arguments of rollout_steps_recv() fit this object; -> (T, explore [T, E] uint8, random_actions
         [T, E, n] int32, own [E] int32)"""
         who, E, n = "rollout_steps_recv", self.E, self.n
+        check_stream_phase(who, stream_phase)
         T = _block_length(explore)
         self.check_observe_recv(n, self.rb)
         self._check_mobility(who, True)
@@ -1256,6 +1260,25 @@ class DeviceChannels(object):
             io['col_any'] = view('col_idx', K * n * (n - 1), t.int32)
         return io
 
+    def _recv_split_workspace(self, T):
+        """the second workspace of a rollout_steps_recv() whose stream phase is split, for blocks of T on the current lane grid:
+        made at the first split call of that T (again when set_grid() changes the number of lanes) and kept next to
+        _recv_io(T)'s buffers; it never crosses the bus"""
+        io = self._recv_io(T)
+        E, n, rb, n_lanes = self.E, self.n, self.rb, self._grid[0].shape[1]
+        ws = io.get('split_workspace')
+        if ws is None or io.get('split_lanes') != n_lanes:
+            _, size = split_workspace_layout(E, n, rb, T, n_lanes)
+            need = self._lib.v2x_rollout_recv_split_workspace_bytes(E, n, rb, T, n_lanes)
+            if need != size:
+                raise ValueError("rollout_steps_recv: the library sizes the split-stream workspace of E = %d, n = %d, rb = %d, T = %d, "
+                                 "n_lanes = %d at %d bytes, the documented layout at %d" % (E, n, rb, T, n_lanes, need, size))
+            ws = self.torch.zeros(size, dtype=self.torch.uint8, device=self.device)
+            if ws.data_ptr() % 256:
+                raise RuntimeError("rollout_steps_recv: the allocator returned a split-stream workspace that is not 256-byte aligned")
+            io['split_workspace'], io['split_lanes'] = ws, n_lanes
+        return ws
+
     def rollout_steps_recv_buffers(self, T):
         """the device buffers of rollout_steps_recv() for blocks of T: workspace (carved by recv_workspace_layout: offsets),
         policy_dev, result_dev (reward [T, E] float64 | flags [T, 2, E] bytes), q [T E n, rb] float32"""
@@ -1313,16 +1336,18 @@ class DeviceChannels(object):
         return r
 
     def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, own=None,
-                           power=None):
+                           power=None, stream_phase='chain'):
         """rollout_steps(walk='wide') for 3..128 links into ReceiverReplay's layout, ONE call (v2x_rollout_steps_recv): the wide
         walk, the observations of entries 1..T in receiver form, the closed-form CSR of the T E graphs, one forward (engine
         given), and the finish that picks, pays and stores xe / xe_next / recv / action / reward into slots
         (head + t E + e) % capacity of `storage` (the tensors of ReceiverReplay.storage()).  States with an own-receiver link
         are scored and stored like the others.  own: the states' own-receiver counts [E]; None: those of the receivers this
         object last sent up from the host.  The current observation must be resident in receiver form (observe_recv() or a
-        previous rollout_steps_recv()).  -> a RecvRolloutResult whose download is in flight."""
+        previous rollout_steps_recv()).  stream_phase: 'chain' (the first launch draws the streams of all T steps) or 'split'
+        (v2x_rollout_steps_recv_split: raw words, offset walk and conversion as three launches on a second workspace made once
+        per T, the same bits); stream_phase_calls counts the calls by it.  -> a RecvRolloutResult whose download is in flight."""
         who = "rollout_steps_recv"
-        T, ex, ra, own = self.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own)
+        T, ex, ra, own = self.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase)
         self._init_device()
         if not self._recv_ready:
             raise RuntimeError("%s: no observe_recv() since the last step()" % who)
@@ -1332,9 +1357,14 @@ class DeviceChannels(object):
         r = self.rollout_steps_recv_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, eb, n_edges, max_edges, power)
         self._keep_actions = self._t['actions']
         ws = io['workspace']
-        check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+        if stream_phase == 'split':
+            sws = self._recv_split_workspace(T)
+            check(self._lib, self._lib.v2x_rollout_steps_recv_split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
+                                                                    self._stream()))
+        else:
+            check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
         self.walk_calls['wide'] += 1
-        self.stream_phase_calls['chain'] += 1
+        self.stream_phase_calls[stream_phase] += 1
         self._obs_ready = False
         self._recv_ready = True
         t, free = self.torch, io['free']
@@ -2363,10 +2393,12 @@ class DeviceBatchedEnviron(BatchedEnviron):
             raise ValueError("dest of environment(s) %s holds a receiver outside [0, %d)" % (np.nonzero(bad)[0].tolist(), self.n_Veh))
         return own
 
-    def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None):
+    def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None,
+                           stream_phase='chain'):
         """rollout_steps() for 3..128 links into a ReceiverReplay's storage (DeviceChannels.rollout_steps_recv: the wide walk,
         the closed-form CSR, one forward, one finish -- ONE call), with the same bookkeeping around it.  The resident
         observation is brought into receiver form first when it is not (after a reset, or after a packed-form call).
+        stream_phase: 'chain' or 'split', the form of the walk's stream phase (the same bits either way).
         -> the RecvRolloutResult of the block, its download in flight."""
         who = 'rollout_steps_recv'
         if self.stream_backend != 'device':
@@ -2378,12 +2410,12 @@ class DeviceBatchedEnviron(BatchedEnviron):
         own = self.own_receivers()
         stale = bool(self._dirty)
         dc = self._flush()
-        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own)
+        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase)
         if stale or not dc._recv_ready:
             dc.observe_recv(self.dest)
         self._obs = None
         return self._resident_after(dc.rollout_steps_recv(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight,
-                                                          engine=engine, own=own))
+                                                          engine=engine, own=own, stream_phase=stream_phase))
 
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                        walk='serial', stream_phase='chain'):

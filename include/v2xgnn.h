@@ -967,6 +967,25 @@ typedef struct v2x_rollout_recv {
 } v2x_rollout_recv;
 int64_t v2x_rollout_recv_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T);
 int  v2x_rollout_steps_recv(const v2x_rollout_recv* r, void* ws, int64_t ws_bytes, void* stream);
+/* v2x_rollout_steps_recv_split: v2x_rollout_steps_recv with the split stream phase -- step 1's k_traj_stream as three launches,
+ *   k_traj_words_recv  grid (E), 256 threads: k_traj_words with entry 0 copied in the receiver form (xe, recv, flags);
+ *   k_traj_walk_recv   grid (E), one wave, lane l = vehicles l and l + 64: k_traj_walk's walk for up to 128 vehicles, walkers
+ *                      in vehicle index order (the low half, then the high half), the same word reads, draws and arithmetic;
+ *   k_traj_uniforms    as in v2x_rollout_steps_split;
+ * then k_traj_terms, k_traj_scan and steps 2..5 of v2x_rollout_steps_recv with the same arguments.  Integer and exactly rounded
+ * arithmetic only: every byte the call leaves (state, workspace sections, storage, results) is v2x_rollout_steps_recv's, and
+ * the two forms mix freely on one state.  `r`, ws, ws_bytes: as there.
+ * split_ws [dev]: the call's own second workspace, 256-byte aligned, contents undefined afterwards: the words [E][NB][624]
+ * (uint32) and the offsets [T + 1][E] (int64) of v2x_traj_split_workspace_bytes, the same formula for 3..128 links,
+ *   NB = 1 + ceil(T (2 n_u + 4 n n_lanes) / 624),   A(4 E NB 624) + A(8 (T + 1) E),   A(x) = ceil(x / 256) * 256
+ * (about 36 MB per state at 100 links, rb = 4, T = 50, 59.9 MB at 128 links with 2 lanes per direction; linear in E).
+ * v2x_rollout_recv_split_workspace_bytes: that sum, or a negative V2X_E* code on sizes outside the limits of
+ * v2x_rollout_recv_workspace_bytes or n_lanes outside 1..64.  The call sizes its need by the step's own n_lanes.
+ * Checks: every check of v2x_rollout_steps_recv, then split_ws non-NULL, 256-byte aligned and split_ws_bytes >= the need, all
+ * before the first launch (V2X_EINVAL, text in v2x_last_error(NULL)); a refused call leaves state and storage alone.          */
+int64_t v2x_rollout_recv_split_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t n_lanes);
+int  v2x_rollout_steps_recv_split(const v2x_rollout_recv* r, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                                  void* stream);
 
 /* The mixed wide walk: v2x_rollout_steps_mixed and v2x_eval_steps_mixed with every pool's trajectory spread over the chip --
  * the wide walk with the split stream phase, for all link counts at once.  Both calls enqueue, on the one stream with no
