@@ -105,6 +105,17 @@ class RolloutRecv(C.Structure):
         [("head", C.c_int64), ("capacity", C.c_int64), ("result_reward", C.c_void_p), ("result_flags", C.c_void_p)]
 
 
+class EvalRecv(C.Structure):
+    """v2x_eval_recv of include/v2xgnn.h"""
+    _fields_ = [("model", C.c_void_p), ("batch", Batch)] + \
+        [(k, C.c_void_p) for k in ("q", "explore", "random_actions", "baseline_actions", "actions")] + \
+        [("step", SimStep), ("recv", C.c_void_p), ("flags", C.c_void_p), ("w_v2v", C.c_double), ("w_v2i", C.c_double),
+         ("T", C.c_int32), ("pad_", C.c_int32)] + \
+        [(k, C.c_void_p) for k in ("traj_xe", "traj_recv", "traj_flags", "traj_v2v_ff", "traj_v2i_ff", "traj_v2i_abs", "row_ptr",
+                                   "col_idx", "edge_base", "result_actions", "result_v2v_rate", "result_v2i_rate",
+                                   "result_interference", "result_reward", "result_flags")]
+
+
 class RolloutMixed(C.Structure):
     """v2x_rollout_mixed of include/v2xgnn.h"""
     _fields_ = [("n_pools", C.c_int32), ("T", C.c_int32), ("pools", C.POINTER(RolloutTraj)), ("model", C.c_void_p)] + \
@@ -281,6 +292,9 @@ SYMBOLS = [
     ("v2x_rollout_steps_recv", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P]),
     ("v2x_rollout_recv_split_workspace_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_rollout_steps_recv_split", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P, _L, _P]),
+    ("v2x_eval_recv_result_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_eval_steps_recv", C.c_int, [C.POINTER(EvalRecv), _P, _L, _P]),
+    ("v2x_eval_steps_recv_split", C.c_int, [C.POINTER(EvalRecv), _P, _L, _P, _L, _P]),
 ]
 
 

@@ -111,8 +111,10 @@ class Agent(object):
 
         receiver_streams: the stream phase of those receiver-form rollouts: 'chain' (the default) or 'split'
         (v2x_rollout_steps_recv_split: the raw words, the offset walk for up to 128 vehicles and the conversion as three
-        launches) -- the same bits (tests/test_gpu_rollout_recv_split.py), opt-in.  'split' needs device_replay='receivers' and
-        rollout_backend='trajectory'; anything else is a ValueError here.  (trajectory_streams stays the 3..31-link option.)
+        launches) -- the same bits (tests/test_gpu_rollout_recv_split.py), opt-in.  It is also the stream phase of the
+        evaluation episodes of eval_backend='device' beyond 31 links (v2x_eval_steps_recv / _split, which walk wide whatever
+        trajectory_walk says).  'split' needs device_replay='receivers' and rollout_backend='trajectory', or an agent that
+        eval_backend='device' can run on; anything else is a ValueError here.  (trajectory_streams stays the 3..31-link option.)
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
           'replicated'  every rank steps the SAME seeded simulator and draws the same minibatch, of which it fits its
@@ -192,9 +194,15 @@ class Agent(object):
         if receiver_streams not in TRAJECTORY_STREAMS:
             raise ValueError("receiver_streams must be one of %s, got %r" % (TRAJECTORY_STREAMS, receiver_streams))
         if receiver_streams == 'split' and not (getattr(self.device_replay, 'RECEIVERS', False) and rollout_backend == 'trajectory'):
-            raise ValueError("receiver_streams='split' needs device_replay='receivers' and rollout_backend='trajectory' (it is a form "
-                             "of the stream phase of v2x_rollout_steps_recv): device_replay is %r, rollout_backend is %r"
-                             % (device_replay, rollout_backend))
+            try:                                       # no receiver-form rollouts: an evaluation in receiver form is what is left
+                if not self._receiver_form():
+                    raise ValueError("the receiver form evaluates more than 31 links, the scenario has %d" % self.num_D2D)
+                self._check_eval_backend('device')
+            except ValueError as exc:
+                raise ValueError("receiver_streams='split' needs device_replay='receivers' and rollout_backend='trajectory' (it is a "
+                                 "form of the stream phase of v2x_rollout_steps_recv) or an agent that eval_backend='device' can run "
+                                 "on (v2x_eval_steps_recv): device_replay is %r, rollout_backend is %r, and %s"
+                                 % (device_replay, rollout_backend, exc))
         self.receiver_streams = receiver_streams
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
@@ -1235,9 +1243,12 @@ class Agent(object):
         T, n = len(explore), self.num_D2D
         explore = np.asarray(explore, np.uint8)
         engine = None if explore.all() else self.brain.model.engine
+        walk, stream_phase = self.trajectory_walk, self.trajectory_streams
+        if self._receiver_form():                      # beyond 31 links: the receiver form, wide, its own stream-phase option
+            walk, stream_phase = 'wide', self.receiver_streams
         res = self.env.evaluate_steps(explore.reshape(T, 1), np.asarray(policy_random).reshape(T, 1, n),
                                       np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine,
-                                      walk=self.trajectory_walk, stream_phase=self.trajectory_streams)
+                                      walk=walk, stream_phase=stream_phase)
         out = {'res': res.resolve()}
         if optimum is not None or rank:
             states = self.env.trajectory_states(T)
@@ -1254,9 +1265,18 @@ class Agent(object):
         self.eval_stats['device_episodes'] += 1
         return out
 
+    def _receiver_form(self):
+        """the environment keeps this scenario's resident observation in receiver form (more than 31 links)"""
+        wide = getattr(self.env, '_wide', None)
+        return bool(wide(self.num_D2D)) if wide is not None else False
+
     def _device_episode_possible(self):
         """after the reset of an episode: the new graph is regular (receivers are fixed within an episode, so one look is
-        enough); otherwise the episode runs through the host loop -- nothing has been drawn yet"""
+        enough); otherwise the episode runs through the host loop -- nothing has been drawn yet.  Beyond 31 links every graph
+        runs on the device, own-receiver links included (a receiver outside [0, n) is a ValueError)"""
+        if self._receiver_form():
+            self.env.own_receivers()
+            return True
         return bool(np.all(self.env.resident_regular(self.num_CH)))
 
     def test_run(self, num_episodes, num_test_step, opt_flag=False, opt_backend='host', opt_restarts=None, opt_rank=False,

@@ -93,14 +93,17 @@ form -- `observe_recv`: xe as before, the links' receivers and one flag byte per
 rl/replay.py ReceiverReplay's layout; `DeviceBatchedEnviron(streams='device')` serves 32..128 links on it.  It takes
 stream_phase='chain' (the default) or 'split' too (v2x_rollout_steps_recv_split: raw words, an offset walk with two vehicles
 per lane and the conversion in three launches on a second workspace made once per T; the same bits, 2.5-2.7x faster at
-32..128 links, profiles/rollout_recv_split_timing.json).
+32..128 links, profiles/rollout_recv_split_timing.json).  `eval_steps_recv` is the evaluation episode of that form
+(v2x_eval_steps_recv / _split: the same front, then k_eval_finish_recv paying the policy and the baseline on every step's
+snapshot; -> RecvEvalResult), on the same buffers; `DeviceBatchedEnviron.evaluate_steps` goes through it beyond 31 links, and
+trajectory_states(T) serves the snapshots of whichever form ran last (profiles/eval_recv_timing.json).
 """
 import ctypes as C
 
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutRecv,
+from ..lib import (Eval, EvalMixed, EvalRecv, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutRecv,
                    RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
 from .batched_env import BatchedEnviron
 
@@ -299,6 +302,20 @@ class EvalResult(object):
         return self.resolve().regular[-1]
 
 
+class RecvEvalResult(EvalResult):
+    """EvalResult of eval_steps_recv: the same block, its last section read as flag bytes (.flags [T + 1, E] uint8: FLAG_OWN,
+    FLAG_BAD, of the observation at entry and after every step); .regular is flags == 0"""
+
+    def resolve(self):
+        if self._pin is not None:
+            self._event.synchronize()
+            o = eval_result_layout(self.E, self.n, self.rb, self.T, self.schemes)[0]['regular']
+            self.flags = self._pin.numpy()[o:o + (self.T + 1) * self.E].reshape(self.T + 1, self.E).copy()
+            EvalResult.resolve(self)
+            self.regular = self.flags == 0
+        return self
+
+
 class TrajectoryStates(object):
     """The T snapshots a trajectory call (rollout_steps / eval_steps) of block length T left in its workspace, as ONE stacked
     problem of T E states for OptimalAllocation (state t E + e: simulator e before its step t).  The channel arrays are views
@@ -431,6 +448,7 @@ class DeviceChannels(object):
         self._grid_sent = False
         self.traffic = {'bytes_up': 0, 'bytes_down': 0}  # every host <-> device copy this object issues
         self._roll = {}                                  # _rollout_io(): None (rollout_step) or T (rollout_steps) -> its buffers
+        self._traj_form = {}                             # T -> 'recv' when the last trajectory call of that T ran in receiver form
         self._mixed = {}                                 # mixed_rollout_buffers(): ((E_k, n_k)..., T) of the pools this one leads
         self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
         self.stream_phase_calls = {p: 0 for p in STREAM_PHASES}     # the wide ones among them, by the form of the stream phase
@@ -1098,6 +1116,7 @@ class DeviceChannels(object):
         else:
             check(self._lib, serial(C.byref(r), self._stream()))
         self.walk_calls[walk] += 1
+        self._traj_form.pop(T, None)
 
     def rollout_step(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                      power=None):
@@ -1323,16 +1342,11 @@ class DeviceChannels(object):
                         capacity=int(capacity), result_reward=res, result_flags=res + 8 * K,
                         **{k: ws + io['offsets'][k] for k in RECV_SECTIONS})
         if engine is not None:
-            from ..engine import DeviceBatch, _batch_struct
+            from ..engine import _batch_struct
             if edge_base is None:
                 n_edges, max_edges = K * n * (n - 2), n * (n - 2)
-            key = (n_edges, max_edges)
-            db = io.get('batch', {}).get(key)
-            if db is None:
-                db = DeviceBatch.from_tensors(K, n, io['xe'], io['row_ptr'], io['col_any'][:n_edges], max_edges)
-                io['batch'] = {key: db}
             r.model = engine._h
-            r.batch = _batch_struct(db)
+            r.batch = _batch_struct(self._recv_batch(io, n_edges, max_edges))
         return r
 
     def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, own=None,
@@ -1365,6 +1379,7 @@ class DeviceChannels(object):
             check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
         self.walk_calls['wide'] += 1
         self.stream_phase_calls[stream_phase] += 1
+        self._traj_form[T] = 'recv'
         self._obs_ready = False
         self._recv_ready = True
         t, free = self.torch, io['free']
@@ -1389,16 +1404,21 @@ class DeviceChannels(object):
     def check_eval_steps(self, explore, policy_random, baseline_actions):
         """ValueError unless the arguments of eval_steps() fit this object; -> (T, explore [T, E] uint8, policy_random [T, E, n]
         int32, baseline_actions [T, E, n] int32 or None)"""
+        self.check_observe(self.n, self.rb)
+        # (called unbound by _PoolShape, the shape-only stand-in of the mixed calls: it has E, n and _check_mobility)
+        return DeviceChannels._check_eval_arrays(self, "eval_steps", explore, policy_random, baseline_actions)
+
+    def _check_eval_arrays(self, who, explore, policy_random, baseline_actions):
+        """what check_eval_steps and check_eval_steps_recv ask of the draws of an evaluation block"""
         E, n = self.E, self.n
-        self.check_observe(n, self.rb)
-        self._check_mobility("eval_steps", True)
+        self._check_mobility(who, True)
         T = _block_length(explore)
         ex = np.asarray(explore)
         if T < 1 or ex.shape != (T, E) or ex.dtype.kind not in 'biu':
             raise ValueError("explore: [T, %d] flags with T >= 1 expected, got shape %s of dtype %s" % (E, list(ex.shape), ex.dtype))
         if T * E > MAX_STATES:
-            raise ValueError("eval_steps: T E <= %d needed (the snapshots are one stacked search problem), got T = %d, E = %d"
-                             % (MAX_STATES, T, E))
+            raise ValueError("%s: T E <= %d needed (the snapshots are one stacked search problem), got T = %d, E = %d"
+                             % (who, MAX_STATES, T, E))
         out = []
         for name, a in (('policy_random', policy_random), ('baseline_actions', baseline_actions)):
             if a is None and name == 'baseline_actions':
@@ -1417,7 +1437,10 @@ class DeviceChannels(object):
     def _eval_io(self, T):
         """_rollout_io(T) -- the trajectory workspace, q and the cached T E-graph batch are shared with rollout_steps() -- with
         the evaluation's own policy buffer (ring of four page-locked copies) and result block added at the first use"""
-        io = self._rollout_io(T)
+        return self._add_eval_buffers(self._rollout_io(T), T)
+
+    def _add_eval_buffers(self, io, T):
+        """the evaluation's own policy ring and result block in the buffers `io` of blocks of T, made at the first use"""
         if 'eval_policy_dev' not in io:
             t, nb = self.torch, self.eval_steps_policy_bytes(T)
             io['eval_policy_dev'] = t.zeros(nb, dtype=t.uint8, device=self.device)
@@ -1446,9 +1469,9 @@ class DeviceChannels(object):
             io['eval_policy_ev'][i] = t.cuda.Event()
         io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
 
-    def _eval_download(self, io, T, S):
+    def _eval_download(self, io, T, S, cls=EvalResult):
         """the result block of S schemes in io['eval_result_dev'] -> a page-locked copy (a returned one, or a new one); -> the
-        EvalResult, its download in flight"""
+        EvalResult (cls), its download in flight"""
         t = self.torch
         size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
         pinned = free.pop() if free else t.zeros(io['eval_result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
@@ -1456,7 +1479,7 @@ class DeviceChannels(object):
         self.traffic['bytes_down'] += size
         ev = t.cuda.Event()
         ev.record(t.cuda.current_stream(self.device))
-        return EvalResult(free, ev, pinned, self.E, self.n, self.rb, T, S)
+        return cls(free, ev, pinned, self.E, self.n, self.rb, T, S)
 
     def _sweep_io(self, T, S):
         """-> (_eval_io(T), the result block of a sweep of S schemes (eval_sweep_mixed): its device block 'dev' and the
@@ -1526,16 +1549,125 @@ class DeviceChannels(object):
         self._obs_ready = True
         return self._eval_download(io, T, 2 if ba is not None else 1)
 
+    # ------------------------------------------------------------------ an evaluation episode of 3..128 links (receiver form)
+    def check_eval_steps_recv(self, explore, policy_random, baseline_actions, own=None, stream_phase='chain'):
+        """ValueError unless the arguments of eval_steps_recv() fit this object; -> (T, explore [T, E] uint8, policy_random
+        [T, E, n] int32, baseline_actions [T, E, n] int32 or None, own [E] int32)"""
+        who, E, n = "eval_steps_recv", self.E, self.n
+        check_stream_phase(who, stream_phase)
+        self.check_observe_recv(n, self.rb)
+        T, ex, ra, ba = self._check_eval_arrays(who, explore, policy_random, baseline_actions)
+        if T * E * n * (n - 1) > 2 ** 31 - 1:
+            raise ValueError("%s: T E = %d graphs of %d links exceed the 32-bit sizes of a batch" % (who, T * E, n))
+        if own is None:
+            if self._own is None:
+                raise ValueError("%s: the receivers went up as a device tensor: pass own, the states' own-receiver counts [E] (the "
+                                 "host decides whether the batch needs edge_base)" % who)
+            own, bad = self._own
+            if bad.any():
+                raise ValueError("%s: state(s) %s hold a receiver outside [0, %d)" % (who, np.nonzero(bad)[0].tolist(), n))
+        own = np.asarray(own)
+        if own.dtype.kind not in 'iu' or own.reshape(-1).shape != (E,) or (own < 0).any() or (own > n).any():
+            raise ValueError("%s: own: %d integer own-receiver counts in [0, %d] expected" % (who, E, n))
+        return T, ex, ra, ba, own.reshape(-1).astype(np.int32)
+
+    def _recv_eval_io(self, T):
+        """_recv_io(T) -- the ONE workspace, q, the cached batches and the edge_base ring are shared with rollout_steps_recv() --
+        with the evaluation's own policy ring and result block added at the first use"""
+        io = self._recv_io(T)
+        if 'eval_policy_dev' not in io:
+            need = self._lib.v2x_eval_recv_result_bytes(self.E, self.n, self.rb, T, 2)
+            if need != self.eval_steps_result_bytes(T, 2):
+                raise ValueError("eval_steps_recv: the library sizes the result block of E = %d, n = %d, rb = %d, T = %d at %d bytes, "
+                                 "the documented layout at %d" % (self.E, self.n, self.rb, T, need, self.eval_steps_result_bytes(T, 2)))
+        return self._add_eval_buffers(io, T)
+
+    def eval_steps_recv_buffers(self, T):
+        """the device buffers of eval_steps_recv() for blocks of T: those of rollout_steps_recv_buffers(T) (workspace, q) with
+        eval_policy_dev and eval_result_dev (the result block of two schemes, carved by eval_result_layout)"""
+        return self._recv_eval_io(T)
+
+    def _recv_batch(self, io, n_edges, max_edges):
+        """the cached DeviceBatch of the T E graphs of io's workspace with that many edges"""
+        from ..engine import DeviceBatch
+        key = (n_edges, max_edges)
+        db = io.get('batch', {}).get(key)
+        if db is None:
+            db = DeviceBatch.from_tensors(io['graphs'], self.n, io['xe'], io['row_ptr'], io['col_any'][:n_edges], max_edges)
+            io['batch'] = {key: db}
+        return db
+
+    def eval_steps_recv_struct(self, T, v2v_weight, v2i_weight, engine=None, edge_base=None, n_edges=None, max_edges=None, power=None,
+                               baseline=True):
+        """the v2x_eval_recv of the resident tensors and the buffers of _recv_eval_io(T) (what eval_steps_recv() passes to the
+        library); edge_base, n_edges, max_edges: as for rollout_steps_recv_struct"""
+        io = self._recv_eval_io(T)
+        self._send_grid()
+        t, K, n = self._t, io['graphs'], self.n
+        base, res, ws = io['eval_policy_dev'].data_ptr(), io['eval_result_dev'].data_ptr(), io['workspace'].data_ptr()
+        offs, _ = eval_result_layout(self.E, n, self.rb, T, 2 if baseline else 1)
+        step = self._sim_step(t['actions'].data_ptr(), power)
+        step.mask = step.col = step.regular = None           # (not read: the receiver form has recv / flags)
+        r = EvalRecv(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * n, random_actions=base,
+                     baseline_actions=base + _align(4 * K * n + K, 4) if baseline else None, actions=t['actions'].data_ptr(),
+                     step=step, recv=t['recv'].data_ptr(), flags=t['flags'].data_ptr(), w_v2v=float(v2v_weight),
+                     w_v2i=float(v2i_weight), T=T, pad_=0, edge_base=edge_base,
+                     **{k: ws + io['offsets'][k] for k in RECV_SECTIONS},
+                     **{'result_' + ('flags' if k == 'regular' else k): res + o for k, o in offs.items()})
+        if engine is not None:
+            from ..engine import _batch_struct
+            if edge_base is None:
+                n_edges, max_edges = K * n * (n - 2), n * (n - 2)
+            r.model = engine._h
+            r.batch = _batch_struct(self._recv_batch(io, n_edges, max_edges))
+        return r
+
+    def eval_steps_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, own=None, power=None,
+                        stream_phase='chain'):
+        """eval_steps(walk='wide') for 3..128 links on the receiver-form resident state, ONE call (v2x_eval_steps_recv): the wide
+        walk, the observations of entries 1..T in receiver form, the closed-form CSR of the T E graphs, one forward (engine
+        given; None: nobody is greedy, no forward) and the finish that pays the policy and, when given, the baseline on every
+        step's snapshot.  It runs on the buffers of rollout_steps_recv() of that T (workspace, q, cached batches, edge_base
+        ring) with a policy ring and a result block of its own; no replay memory is touched.  States with an own-receiver link
+        are scored like the others.  own, stream_phase: as for rollout_steps_recv().  The current observation must be resident
+        in receiver form.  -> a RecvEvalResult whose download is in flight; afterwards the resident state is what T advance()
+        calls under the policy's actions leave, and trajectory_states(T) holds the T snapshots."""
+        who = "eval_steps_recv"
+        T, ex, ra, ba, own = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+        self._init_device()
+        if not self._recv_ready:
+            raise RuntimeError("%s: no observe_recv() since the last step()" % who)
+        io = self._recv_eval_io(T)
+        self._eval_upload(io, T, ex, ra, ba)
+        eb, n_edges, max_edges = self._edge_base(io, own, T) if engine is not None else (None, None, None)
+        r = self.eval_steps_recv_struct(T, v2v_weight, v2i_weight, engine, eb, n_edges, max_edges, power, ba is not None)
+        self._keep_actions = self._t['actions']
+        ws = io['workspace']
+        if stream_phase == 'split':
+            sws = self._recv_split_workspace(T)
+            check(self._lib, self._lib.v2x_eval_steps_recv_split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
+                                                                 self._stream()))
+        else:
+            check(self._lib, self._lib.v2x_eval_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
+        self.walk_calls['wide'] += 1
+        self.stream_phase_calls[stream_phase] += 1
+        self._traj_form[T] = 'recv'
+        self._obs_ready = False
+        self._recv_ready = True
+        return self._eval_download(io, T, 2 if ba is not None else 1, RecvEvalResult)
+
     def trajectory_states(self, T):
-        """-> TrajectoryStates: the T snapshots the last rollout_steps() / eval_steps() of block length T left in its workspace,
+        """-> TrajectoryStates: the T snapshots the last rollout_steps() / eval_steps() of block length T (or their receiver
+        forms, rollout_steps_recv() / eval_steps_recv(): whichever ran last at that T) left in its workspace,
         as one stacked problem of T E states (E = T self.E, n_Veh, n_RB, problem_tensors(), rates()) for OptimalAllocation.
         Views over the workspace, no copy: valid until the next trajectory call of that T."""
         T = int(T)
         if T < 1 or T * self.E > MAX_STATES:
             raise ValueError("trajectory_states: 1 <= T and T E <= %d needed, got T = %d, E = %d" % (MAX_STATES, T, self.E))
-        if self.torch is None or T not in self._roll:
+        key = ('recv', T) if self._traj_form.get(T) == 'recv' else T     # (the form of the last trajectory call of that T)
+        if self.torch is None or key not in self._roll:
             raise RuntimeError("trajectory_states: no trajectory call of T = %d has run on this object" % T)
-        return TrajectoryStates(self, T, self._roll[T])
+        return TrajectoryStates(self, T, self._roll[key])
 
     # ------------------------------------------------------------------ for OptimalAllocation
     def problem(self, v2v_weight=0.0, v2i_weight=0.0):
@@ -1619,6 +1751,7 @@ def _mixed_trajectory_call(serial, wide, m, channels, T, walk):
         check(dc0._lib, serial(C.byref(m), dc0._stream()))
     for dc in channels:
         dc.walk_calls[walk] += 1
+        dc._traj_form.pop(T, None)
         if walk == 'wide':
             dc.stream_phase_calls['split'] += 1
 
@@ -1871,6 +2004,7 @@ def eval_sweep_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
     out = []
     for dc, sw in zip(channels, blocks):
         dc.walk_calls[walk] += 1
+        dc._traj_form.pop(T, None)
         if walk == 'wide':
             dc.stream_phase_calls['split'] += 1
         dc._obs_ready = True
@@ -2418,12 +2552,20 @@ class DeviceBatchedEnviron(BatchedEnviron):
                                                           engine=engine, own=own, stream_phase=stream_phase))
 
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                       walk='serial', stream_phase='chain'):
+                       walk='serial', stream_phase='chain', receiver_form=None):
         """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
         bookkeeping of rollout_steps() around it: explore [T, E], policy_random [T, E, n], baseline_actions [T, E, n] or None.
         walk: 'serial' or 'wide', the form of the trajectory; stream_phase: 'chain' or 'split', the form of a wide walk's stream
         phase (the same bits all).
-        -> the EvalResult, its download in flight.  trajectory_states(T) then holds the T snapshots."""
+        Beyond 31 links the call goes through the receiver form (DeviceChannels.eval_steps_recv, the bookkeeping of
+        rollout_steps_recv()): walk must then be 'wide' and row_ptr None; receiver_form=True asks for that form at any size
+        (None: by the link count).
+        -> the EvalResult (receiver form: RecvEvalResult), its download in flight.  trajectory_states(T) then holds the T
+        snapshots."""
+        if self._wide() if receiver_form is None else receiver_form:
+            return self._evaluate_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine, row_ptr, walk,
+                                             stream_phase)
+
         def check_args(dc):
             check_walk('evaluate_steps', walk)
             check_stream_phase('evaluate_steps', stream_phase, walk)
@@ -2433,6 +2575,31 @@ class DeviceBatchedEnviron(BatchedEnviron):
             'evaluate_steps', check_args,
             lambda dc: dc.eval_steps(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, row_ptr=row_ptr,
                                      walk=walk, stream_phase=stream_phase))
+
+    def _evaluate_steps_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine, row_ptr, walk,
+                             stream_phase):
+        """evaluate_steps() in receiver form: rollout_steps_recv()'s bookkeeping around DeviceChannels.eval_steps_recv"""
+        who = 'evaluate_steps'
+        if walk != 'wide':
+            raise ValueError("%s: the receiver form (more than %d links, or receiver_form=True) walks wide only: pass walk='wide', "
+                             "got walk=%r" % (who, OBSERVE_MAX_LINKS, walk))
+        if row_ptr is not None:
+            raise ValueError("%s: the receiver form writes its own CSR (row_ptr must be None)" % who)
+        if self.stream_backend != 'device':
+            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
+        self.finish_step()
+        self._check_sizes()
+        if any(s.gauss_next is not None for s in self.streams):
+            raise RuntimeError("a stream holds a cached gauss value")
+        own = self.own_receivers()
+        stale = bool(self._dirty)
+        dc = self._flush()
+        dc.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+        if stale or not dc._recv_ready:
+            dc.observe_recv(self.dest)
+        self._obs = None
+        return self._resident_after(dc.eval_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight,
+                                                       engine=engine, own=own, stream_phase=stream_phase))
 
     def trajectory_states(self, T):
         """the T snapshots of the last evaluate_steps() / rollout_steps() of block length T as one stacked search problem

@@ -24,7 +24,7 @@ import numpy as np
 
 from .agent import Agent
 from .sim_config import RL_Config
-from .run import add_sim_arguments, evaluation_env
+from .run import add_sim_arguments, check_receiver_arguments, evaluation_env
 
 
 def build_parser():
@@ -76,8 +76,12 @@ def parse_args(argv=None):
             ap.error("--mixed-trajectory-walk %s needs --mixed-links" % args.mixed_trajectory_walk)
         if args.opt_backend is None:
             args.opt_backend = "host"
+        check_receiver_arguments(ap, args)
         return ap, args
     # the mixed network is scored as one ragged batch of all link counts: what holds one link count stays refused
+    if args.receiver_streams != "chain":
+        ap.error("--mixed-links holds 3..31 links: --receiver-streams is the stream phase of one link count beyond 31 "
+                 "(rl.evaluate --links)")
     if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
         ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
                  "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
@@ -166,7 +170,8 @@ def main(argv=None):
     cfg.set_train_value(args.feedback, args.gamma, args.batch, 1, 0.1)
     env = evaluation_env(ap, args)
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False,
-                  trajectory_walk=args.trajectory_walk, trajectory_streams=args.trajectory_streams)
+                  trajectory_walk=args.trajectory_walk, trajectory_streams=args.trajectory_streams,
+                  receiver_streams=args.receiver_streams)
     out = agent.evaluate_training_diff_trials(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials,
                                               model_dir=args.save_dir, num_train_steps=args.train_steps,
                                               opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,

@@ -8,6 +8,8 @@
                               [--opt-rank [--opt-rank-backend bound [--opt-rank-max-nodes N]]] \\
                               [--sim-backend device --sim-streams device --eval-backend device
                                [--trajectory-walk wide [--trajectory-streams split]]]
+    python -m v2xgnn.rl.run   --links 100 --save-dir runs/b --opt --opt-backend local \\
+                              --sim-backend device --sim-streams device --eval-backend device [--receiver-streams split]
 
 A shared-weight network trained on several link counts at once (rl.train --mixed-links ... --save-dir D) is evaluated per link
 count, on the training sizes or on others, --envs parallel episodes per size (rl/mixed.py MixedAgent.test_run):
@@ -43,9 +45,12 @@ def load_trained_model(env, cfg, model_dir, brain=None, **brain_kwargs):
     return agent
 
 
+RECEIVER_FORM_ABOVE = 31                                 # the packed observation's links (rl/device_sim.py OBSERVE_MAX_LINKS)
+
+
 def add_sim_arguments(ap):
-    """--sim-backend / --sim-streams / --sim-reset / --eval-backend / --trajectory-walk / --trajectory-streams of the two
-    evaluation drivers"""
+    """--sim-backend / --sim-streams / --sim-reset / --eval-backend / --trajectory-walk / --trajectory-streams /
+    --receiver-streams of the two evaluation drivers"""
     ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
                     help="where the simulator's channel update, observation and rates run: the single host simulator (the "
                          "default) or ONE batched simulator on the GPU (rl/device_sim.py)")
@@ -63,6 +68,24 @@ def add_sim_arguments(ap):
     ap.add_argument("--trajectory-streams", choices=["chain", "split"], default="chain",
                     help="with --trajectory-walk wide: the stream phase of the wide walk -- 'chain' (the default: one launch draws "
                          "the streams of all steps) or 'split' (raw words, offset walk and conversion in three launches; the same bits)")
+    ap.add_argument("--receiver-streams", choices=["chain", "split"], default="chain",
+                    help="with --eval-backend device beyond %d links (the episode then runs in receiver form and walks wide): its "
+                         "stream phase -- 'chain' (the default) or 'split' (three launches on a second workspace; the same bits)"
+                         % RECEIVER_FORM_ABOVE)
+
+
+def check_receiver_arguments(ap, args):
+    """the checks of one link count (--links) that concern the receiver form: beyond 31 links --eval-backend device runs the
+    episode as v2x_eval_steps_recv, whose stream phase is --receiver-streams; what that form cannot honour is refused with
+    the option to use instead"""
+    wide = args.links > RECEIVER_FORM_ABOVE
+    if args.receiver_streams != "chain" and not (wide and args.eval_backend == "device"):
+        ap.error("--receiver-streams %s needs --eval-backend device and more than %d links (the receiver form); at %d links the "
+                 "option is --trajectory-walk wide --trajectory-streams %s"
+                 % (args.receiver_streams, RECEIVER_FORM_ABOVE, args.links, args.receiver_streams))
+    if wide and args.eval_backend == "device" and args.trajectory_streams != "chain":
+        ap.error("--trajectory-streams %s holds 3..%d links: at %d links the episode runs in receiver form, use "
+                 "--receiver-streams %s" % (args.trajectory_streams, RECEIVER_FORM_ABOVE, args.links, args.trajectory_streams))
 
 
 def evaluation_env(ap, args):
@@ -179,10 +202,13 @@ def parse_args(argv=None):
             ap.error("--mixed-trajectory-walk %s needs --mixed-links" % args.mixed_trajectory_walk)
         if args.opt_backend is None:
             args.opt_backend = "host"
+        check_receiver_arguments(ap, args)
         return ap, args
     # the mixed network is scored as one ragged batch of all link counts: what holds one link count stays refused
     if args.opt_rank:
         ap.error("--mixed-links has no ranks: --opt-rank ranks the actions of one link count (rl.run --links)")
+    if args.receiver_streams != "chain":
+        ap.error("--mixed-links holds 3..31 links: --receiver-streams is the stream phase of one link count beyond 31 (rl.run --links)")
     if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
         ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
                  "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
@@ -259,7 +285,7 @@ def main(argv=None):
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = evaluation_env(ap, args)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed, trajectory_walk=args.trajectory_walk,
-                               trajectory_streams=args.trajectory_streams)
+                               trajectory_streams=args.trajectory_streams, receiver_streams=args.receiver_streams)
     res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank,
                    eval_backend=args.eval_backend, rank_backend=args.opt_rank_backend, rank_max_nodes=args.opt_rank_max_nodes)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,

@@ -986,6 +986,66 @@ int  v2x_rollout_steps_recv(const v2x_rollout_recv* r, void* ws, int64_t ws_byte
 int64_t v2x_rollout_recv_split_workspace_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t n_lanes);
 int  v2x_rollout_steps_recv_split(const v2x_rollout_recv* r, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
                                   void* stream);
+/* v2x_eval_steps_recv: v2x_eval_steps for 3 <= n <= 128 links -- the T steps of an EVALUATION episode in one call on the
+ * receiver-form resident state, no replay memory.  Enqueues, in this order on one stream, no parallel branches: steps 1..4 of
+ * v2x_rollout_steps_recv with the same arguments (the wide walk, k_traj_observe_recv, v2x_csr_from_recv and v2x_forward, the
+ * last two skipped without a model: one body serves both calls), then
+ *   5. k_eval_finish_recv, grid (S T E), scheme major, one workgroup of 192 threads per (scheme, t, e), S = 2 with
+ *      baseline_actions, else 1: the body of k_eval_finish (one __device__ function, called by both), so the pick, the rates of
+ *      v2x_sim_rates on snapshot t, the summation and the reward of v2x_eval_steps, scheme 0 the policy, scheme 1 the baseline;
+ *      the policy scheme at t = T - 1 leaves actions / v2v_rate / v2i_rate / interference / v2i_interf / v2v_interf in the
+ *      resident arrays.
+ * After the call the resident state (streams, positions, channel arrays, xe / state / interf_db / recv / flags of entry T,
+ * actions and rates) is what T calls of v2x_sim_advance under the policy's actions leave.  A state with an own-receiver link is
+ * scored like any other: edge_base and the batch's n_edges / max_edges follow v2x_rollout_steps_recv's rule; no fallback.
+ * Results, scheme major, the layout and section order of v2x_eval_steps: result_v2v_rate [S][T][E][n], result_v2i_rate
+ * [S][T][E][min(rb, n)], result_interference [S][T][E][rb], result_reward [S][T][E] (doubles), result_actions [S][T][E][n]
+ * (int32), then result_flags [T+1][E], the FLAG BYTES of entries 0..T (v2x_sim_observe_recv's bits) where v2x_eval_steps has
+ * result_regular.  v2x_eval_recv_result_bytes(E, n, rb, T, S): 8 S T E (n + min(rb, n) + rb + 1) + 4 S T E n + (T + 1) E rounded
+ * up to a multiple of 8, or a negative V2X_E* code outside the limits of v2x_rollout_recv_workspace_bytes, S outside {1, 2} or
+ * T E > 65535 (the stacked searches of v2x_opt_* take the T E snapshots as one problem).
+ * ws, ws_bytes: the workspace of v2x_rollout_recv_workspace_bytes(E, n, rb, T), its first eight sections checked as there (a
+ * rollout and an evaluation of one T may share it).  Same rules: all pointers [dev], asynchronous, no allocation, no
+ * synchronisation, no environment variable read; every check before the first launch (V2X_EINVAL, text in
+ * v2x_last_error(NULL)); a refused call leaves the resident state and the result block alone.                              */
+typedef struct v2x_eval_recv {
+  v2x_model* model;                /* the network, or NULL: the policy takes random_actions everywhere, explore is not read */
+  v2x_batch batch;
+  float* q;                        /* [T E n][rb] Q workspace (required with a model) */
+  const uint8_t* explore;          /* [T][E] (required with a model) */
+  const int32_t* random_actions;   /* [T][E][n]: the policy's random actions */
+  const int32_t* baseline_actions; /* [T][E][n], or NULL: no baseline scheme */
+  int32_t* actions;                /* [E][n]: the resident actions (written: the policy's of t = T - 1) */
+  v2x_sim_step step;               /* mask / col / regular not read; actions NULL or `actions` */
+  int32_t* recv;                   /* [E][n]  the resident observation's receivers */
+  uint8_t* flags;                  /* [E]     and flag bytes */
+  double w_v2v, w_v2i;
+  int32_t T, pad_;
+  float* traj_xe;                  /* [T+1][E][n][16]  */
+  int32_t* traj_recv;              /* [T+1][E][n]      */
+  uint8_t* traj_flags;             /* [T+1][E]         */
+  double* traj_v2v_ff;             /* [T][E][n][n][rb] */
+  double* traj_v2i_ff;             /* [T][E][n][rb]    */
+  double* traj_v2i_abs;            /* [T][E][n]        */
+  int32_t* row_ptr;                /* [T E n + 1]      */
+  int32_t* col_idx;                /* [T E n (n - 1)]  */
+  const int32_t* edge_base;        /* [T E + 1] device-addressable, or NULL: every state regular */
+  int32_t* result_actions;         /* [S][T][E][n]         */
+  double* result_v2v_rate;         /* [S][T][E][n]         */
+  double* result_v2i_rate;         /* [S][T][E][min(rb,n)] */
+  double* result_interference;     /* [S][T][E][rb]        */
+  double* result_reward;           /* [S][T][E]            */
+  uint8_t* result_flags;           /* [T+1][E]             */
+} v2x_eval_recv;
+int64_t v2x_eval_recv_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
+int  v2x_eval_steps_recv(const v2x_eval_recv* r, void* ws, int64_t ws_bytes, void* stream);
+/* v2x_eval_steps_recv_split: v2x_eval_steps_recv with the split stream phase of v2x_rollout_steps_recv_split (k_traj_words_recv,
+ * k_traj_walk_recv, k_traj_uniforms in k_traj_stream's place) on the second workspace of
+ * v2x_rollout_recv_split_workspace_bytes.  Every byte the call leaves is v2x_eval_steps_recv's; the forms mix freely on one
+ * state.  Checks: every check of v2x_eval_steps_recv first, then split_ws non-NULL, 256-byte aligned and split_ws_bytes >= the
+ * need, all before the first launch.                                                                                        */
+int  v2x_eval_steps_recv_split(const v2x_eval_recv* r, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                               void* stream);
 
 /* The mixed wide walk: v2x_rollout_steps_mixed and v2x_eval_steps_mixed with every pool's trajectory spread over the chip --
  * the wide walk with the split stream phase, for all link counts at once.  Both calls enqueue, on the one stream with no
