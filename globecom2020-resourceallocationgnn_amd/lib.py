@@ -153,6 +153,11 @@ class EvalSweep(C.Structure):
 SWEEP_MAX_MODELS = 64
 
 
+class EvalSweepRecv(C.Structure):
+    """struct v2x_eval_sweep_recv of include/v2xgnn.h"""
+    _fields_ = [("base", EvalRecv), ("K", C.c_int32), ("pad_", C.c_int32), ("models", C.POINTER(C.c_void_p)), ("q", C.c_void_p)]
+
+
 class ReplayPool(C.Structure):
     """v2x_replay_pool of include/v2xgnn.h"""
     _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
@@ -295,6 +300,9 @@ SYMBOLS = [
     ("v2x_eval_recv_result_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_eval_steps_recv", C.c_int, [C.POINTER(EvalRecv), _P, _L, _P]),
     ("v2x_eval_steps_recv_split", C.c_int, [C.POINTER(EvalRecv), _P, _L, _P, _L, _P]),
+    ("v2x_eval_sweep_recv_result_bytes", _L, [_I, _I, _I, _I, _I]),
+    ("v2x_eval_sweep_recv", C.c_int, [C.POINTER(EvalSweepRecv), _P, _L, _P]),
+    ("v2x_eval_sweep_recv_split", C.c_int, [C.POINTER(EvalSweepRecv), _P, _L, _P, _L, _P]),
 ]
 
 

@@ -1461,3 +1461,138 @@ class Agent(object):
         if opt_flag:
             return ret, rew, ra_return, ra_reward, opt_return, opt_reward, opt_v2v, opt_v2i, opt_intf
         return ev_opt_return, ret, rew, ra_return, ra_reward
+
+    def _checkpoint_engine(self, path):
+        """a new engine of the brain's spec with the weights of the checkpoint file `path`"""
+        from ..bs_brain import load_weight_file
+        factory = getattr(self.brain, '_engine_factory', None)
+        if factory is not None:
+            engine = factory(self.brain.model.spec)
+        else:
+            from ..engine import GnnEngine
+            engine = GnnEngine(self.brain.model.spec, device=getattr(self.brain, '_device', 0))
+        try:
+            engine.set_weights(load_weight_file(path))
+        except Exception:
+            close = getattr(engine, 'close', None)
+            if close is not None:
+                close()
+            raise
+        return engine
+
+    def evaluate_training_sweep(self, num_episodes, num_test_step, opt_flag, fixed_epsilon, num_evaluate_trials, model_dir=None,
+                                num_train_steps=20, engines=None, opt_backend='host', opt_restarts=None, eval_backend='host'):
+        """evaluate_training_diff_trials with ONE walked episode per trial on which all K = num_episodes // 5 checkpoints are
+        scored (MixedAgent.evaluate_training's construction for the fixed-size network): nothing in a simulator step depends on
+        the actions except the rates paid for them, so the walk, the observations, the random scheme and the optimum are shared
+        and only the forward and the pick differ between checkpoints.  The checkpoints are loaded once into K engines of the
+        brain's spec (closed again at the end), or engines: K loaded engines.  Same return tuples and shapes as
+        evaluate_training_diff_trials (9 arrays with opt_flag, 5 without); the random scheme's and the optimum's rows are the
+        same for every checkpoint of a trial.
+        Trial t: random.seed(t + 1), np.random.seed(t + 1), one new_random_game, one _draw_trial_ahead(T, fixed_epsilon).
+        eval_backend='host' is the definition, at every link count.  Per step: the random scheme's rates (dump_act); one optimum
+        search (the first checkpoint's ground truth, booked again under opt_flag); for k = 0 .. K - 1 the greedy action of
+        engine k on the one observation where the step is greedy, and the rates of its action without stepping; then one act()
+        under network K - 1's action.
+        eval_backend='device' (what test_run(eval_backend='device') needs, and more than 31 links: the receiver form; anything
+        else is a ValueError before any draw or reset): per trial ONE evaluate_sweep call (v2x_eval_sweep_recv, the stream phase
+        receiver_streams) and one stacked search on trajectory_states(T).  Same arrays, generator states, num_step and resident
+        simulator state as 'host', bit for bit (tests/test_gpu_eval_sweep_recv.py)."""
+        import random
+        from ..packing import PackedBatch
+        _check_opt_backend(opt_backend)
+        self._check_eval_backend(eval_backend)
+        if eval_backend == 'device' and not self._receiver_form():
+            raise ValueError("eval_backend='device' needs the receiver form (more than 31 links, got %d) in evaluate_training_sweep: "
+                             "MixedAgent.evaluate_training scores the checkpoints of a shared-weight network at 3..31 links"
+                             % self.num_D2D)
+        n, C, nn = self.num_D2D, self.num_CH, self.num_Neighbor
+        if nn != 1:
+            raise ValueError("evaluate_training_sweep supports one receiver per link (num_Neighbor = 1), got %d" % nn)
+        engines = None if engines is None else list(engines)
+        K = int(num_episodes // 5) if engines is None else len(engines)
+        if K < 1:
+            raise ValueError("evaluate_training_sweep: no checkpoint to score (num_episodes = %d, one per 5 episodes)" % num_episodes)
+        self.num_Episodes = K
+        self.num_Test_Step = num_test_step
+        n_st, n_tr = num_test_step, num_evaluate_trials
+        w_v2v, w_v2i = self.v2v_weight, self.v2i_weight
+        ev_opt_return, ev_opt_reward = np.zeros(n_tr), np.zeros((n_tr, n_st))
+        ra_return, ra_reward = np.zeros((n_tr, K)), np.zeros((n_tr, K, n_st))
+        opt_return, opt_reward = np.zeros((n_tr, K)), np.zeros((n_tr, K, n_st))
+        opt_v2v, opt_v2i, opt_intf = np.zeros((n_tr, K, n_st, n)), np.zeros((n_tr, K, n_st, C)), np.zeros((n_tr, K, n_st, C))
+        ret, rew = np.zeros((n_tr, K)), np.zeros((n_tr, K, n_st))
+        optimum = self._optimum_search(opt_backend, opt_restarts)
+
+        def book_shared(trial, st, random_rates, reward, v2v, v2i, intf):
+            """the random scheme and the optimum of step st, the same for every checkpoint (v2v: per link [n])"""
+            if reward > 0:
+                ev_opt_reward[trial, st] = reward
+                ev_opt_return[trial] += reward
+            ra_reward[trial, :, st] = w_v2v * np.sum(random_rates[0]) + w_v2i * np.sum(random_rates[1])
+            ra_return[trial, :] += ra_reward[trial, :, st]
+            if opt_flag and reward > 0:
+                opt_reward[trial, :, st] = reward
+                opt_return[trial, :] += reward
+                opt_v2v[trial, :, st, :] = v2v
+                opt_v2i[trial, :, st, :] = v2i
+                opt_intf[trial, :, st, :] = intf
+
+        loaded = []
+        if engines is None:
+            folder = model_dir if model_dir is not None else self.checkpoint_dir()
+            paths = [os.path.join(folder, 'Q-Network_model_weights-Episode-%d-Step-%d-Batch-%d.h5'
+                                  % ((k + 1) * 5, num_train_steps, self.batch_size)) for k in range(K)]
+            for path in paths:
+                if not os.path.exists(path):
+                    raise ValueError("evaluate_training_sweep: no checkpoint %s" % path)
+        try:
+            if engines is None:
+                for path in paths:
+                    loaded.append(self._checkpoint_engine(path))
+                engines = loaded
+            for trial in range(n_tr):
+                random.seed(trial + 1)
+                np.random.seed(trial + 1)
+                self.env.new_random_game(self.num_D2D)
+                baseline, explore, rand = self._draw_trial_ahead(n_st, fixed_epsilon)
+                if eval_backend == 'device' and n_st > 0 and self._device_episode_possible():
+                    r = self.env.evaluate_sweep(explore.reshape(n_st, 1), rand.reshape(n_st, 1, n), baseline.reshape(n_st, 1, n),
+                                                w_v2v, w_v2i, engines=None if explore.all() else engines, K=K,
+                                                stream_phase=self.receiver_streams).resolve()
+                    _, o_reward, o_rates = self._stacked_optimum(self.env.trajectory_states(n_st), opt_backend, opt_restarts)
+                    for st in range(n_st):
+                        book_shared(trial, st, (r.v2v_rate[K, st, 0], r.v2i_rate[K, st, 0]), o_reward[st], *(a[st] for a in o_rates))
+                        for k in range(K):
+                            rew[trial, k, st] = w_v2v * np.sum(r.v2v_rate[k, st, 0]) + w_v2i * np.sum(r.v2i_rate[k, st, 0])
+                            ret[trial, k] += rew[trial, k, st]
+                    self.num_step += n_st
+                    self.eval_stats['device_episodes'] += 1
+                    continue
+                self.eval_stats['host_episodes'] += 1
+                for st in range(n_st):
+                    random_rates = self.dump_act(baseline[st].reshape(n, 1))
+                    _, reward, (v2v, v2i, intf) = optimum()
+                    book_shared(trial, st, random_rates, reward, np.sum(v2v, axis=1), v2i, intf)
+                    if not explore[st]:
+                        d2d_state, adj = self.observe()
+                        dn = self.brain.num_One_Node_Input
+                        pb = PackedBatch.from_dense(d2d_state[None][:, :, :dn], d2d_state[None][:, :, dn:], adj[None])
+                    for k, engine in enumerate(engines):
+                        if explore[st]:
+                            action = rand[st].reshape(n, 1)
+                        else:
+                            q = np.asarray(engine.forward(pb)).reshape(n, C)
+                            action = np.argmax(q, axis=1).reshape(n, nn).astype(int)
+                        v2v, v2i, _ = self.dump_act(action)
+                        rew[trial, k, st] = w_v2v * np.sum(v2v) + w_v2i * np.sum(v2i)
+                        ret[trial, k] += rew[trial, k, st]
+                    self.act(action)
+        finally:
+            for engine in loaded:
+                close = getattr(engine, 'close', None)
+                if close is not None:
+                    close()
+        if opt_flag:
+            return ret, rew, ra_return, ra_reward, opt_return, opt_reward, opt_v2v, opt_v2i, opt_intf
+        return ev_opt_return, ret, rew, ra_return, ra_reward

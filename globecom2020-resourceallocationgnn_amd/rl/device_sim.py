@@ -96,15 +96,18 @@ per lane and the conversion in three launches on a second workspace made once pe
 32..128 links, profiles/rollout_recv_split_timing.json).  `eval_steps_recv` is the evaluation episode of that form
 (v2x_eval_steps_recv / _split: the same front, then k_eval_finish_recv paying the policy and the baseline on every step's
 snapshot; -> RecvEvalResult), on the same buffers; `DeviceBatchedEnviron.evaluate_steps` goes through it beyond 31 links, and
-trajectory_states(T) serves the snapshots of whichever form ran last (profiles/eval_recv_timing.json).
+trajectory_states(T) serves the snapshots of whichever form ran last (profiles/eval_recv_timing.json).  `eval_sweep_recv`
+scores K fixed-size networks on those same steps in one call (v2x_eval_sweep_recv / _split: that front once, K - 1 further
+forwards of the one batch, k_eval_finish_sweep_recv; -> RecvEvalResult of K (+ 1) schemes); `DeviceBatchedEnviron.evaluate_sweep`
+is its resident form, Agent.evaluate_training_sweep its caller (profiles/eval_sweep_recv_timing.json).
 """
 import ctypes as C
 
 import numpy as np
 
 from . import native_sim
-from ..lib import (Eval, EvalMixed, EvalRecv, EvalSweep, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout, RolloutMixed, RolloutRecv,
-                   RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
+from ..lib import (Eval, EvalMixed, EvalRecv, EvalSweep, EvalSweepRecv, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout,
+                   RolloutMixed, RolloutRecv, RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -1491,7 +1494,7 @@ class DeviceChannels(object):
             sw = io['sweep'][S] = {'dev': t.zeros(self.eval_steps_result_bytes(T, S), dtype=t.uint8, device=self.device), 'free': []}
         return io, sw
 
-    def _sweep_download(self, sw, T, S):
+    def _sweep_download(self, sw, T, S, cls=EvalResult):
         """_eval_download for the result block of a sweep"""
         t = self.torch
         size, free = sw['dev'].numel(), sw['free']
@@ -1500,7 +1503,7 @@ class DeviceChannels(object):
         self.traffic['bytes_down'] += size
         ev = t.cuda.Event()
         ev.record(t.cuda.current_stream(self.device))
-        return EvalResult(free, ev, pinned, self.E, self.n, self.rb, T, S)
+        return cls(free, ev, pinned, self.E, self.n, self.rb, T, S)
 
     def eval_steps_struct(self, T, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None, baseline=True):
         """the v2x_eval of the resident tensors and the buffers of _eval_io(T) (what eval_steps() passes to the library)"""
@@ -1655,6 +1658,106 @@ class DeviceChannels(object):
         self._obs_ready = False
         self._recv_ready = True
         return self._eval_download(io, T, 2 if ba is not None else 1, RecvEvalResult)
+
+    # ------------------------------------------------------------------ K networks on one walked episode (receiver form)
+    def check_eval_sweep_recv(self, explore, policy_random, baseline_actions, engines=None, K=None, own=None, stream_phase='chain'):
+        """ValueError unless the arguments of eval_sweep_recv() fit this object; -> (T, explore, policy_random, baseline_actions,
+        own) as check_eval_steps_recv returns them, and K"""
+        who = "eval_sweep_recv"
+        try:
+            checked = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+        except ValueError as err:
+            raise ValueError(str(err).replace("eval_steps_recv", who))
+        if engines is None:
+            K = 1 if K is None else int(K)
+        else:
+            engines = list(engines)
+            if K is not None and int(K) != len(engines):
+                raise ValueError("%s: K = %d, but %d engines" % (who, K, len(engines)))
+            K = len(engines)
+        if not 1 <= K <= SWEEP_MAX_MODELS:
+            raise ValueError("%s: 1..%d networks, got %d" % (who, SWEEP_MAX_MODELS, K))
+        for k, engine in enumerate(engines or ()):
+            spec = None if engine is None else engine.spec
+            if spec is None or spec.variable_graphs or spec.n_nodes != self.n or spec.n_channels != self.rb:
+                raise ValueError("%s: scoring needs fixed-size engines of %d links and %d channels (engine %d)" % (who, self.n, self.rb, k))
+            if spec != engines[0].spec:
+                raise ValueError("%s: engine %d has another spec than engine 0: the networks of a sweep are checkpoints of one network"
+                                 % (who, k))
+        return checked + (K,)
+
+    def _recv_sweep_io(self, T, S, K):
+        """-> (_recv_eval_io(T), the sweep's own buffers: the result block of S schemes 'dev' with the page-locked copies that
+        came back 'free', made at the first use of (T, S), and the Q workspace [K, T E n, rb] of (T, K))"""
+        io = self._recv_eval_io(T)
+        t = self.torch
+        sw = io.setdefault('sweep', {}).get(S)
+        if sw is None:
+            size = self.eval_steps_result_bytes(T, S)
+            need = self._lib.v2x_eval_sweep_recv_result_bytes(self.E, self.n, self.rb, T, S)
+            if need != size:
+                raise ValueError("eval_sweep_recv: the library sizes the result block of E = %d, n = %d, rb = %d, T = %d, %d schemes at "
+                                 "%d bytes, the documented layout at %d" % (self.E, self.n, self.rb, T, S, need, size))
+            sw = io['sweep'][S] = {'dev': t.zeros(size, dtype=t.uint8, device=self.device), 'free': []}
+        q = io.setdefault('sweep_q', {}).get(K)
+        if q is None:
+            q = io['sweep_q'][K] = t.zeros((K, io['graphs'] * self.n, self.rb), dtype=t.float32, device=self.device)
+        return io, sw, q
+
+    def eval_sweep_recv_struct(self, T, K, v2v_weight, v2i_weight, engines=None, edge_base=None, n_edges=None, max_edges=None,
+                               power=None, baseline=True):
+        """the v2x_eval_sweep_recv of the resident tensors and the buffers of _recv_sweep_io (what eval_sweep_recv() passes to
+        the library): eval_steps_recv_struct with engine 0's batch, the result pointers in the sweep's own block of S schemes"""
+        S = K + (1 if baseline else 0)
+        io, sw, q = self._recv_sweep_io(T, S, K)
+        base = self.eval_steps_recv_struct(T, v2v_weight, v2i_weight, engines[0] if engines else None, edge_base, n_edges, max_edges,
+                                           power, baseline)
+        base.model = base.q = None
+        offs, _ = eval_result_layout(self.E, self.n, self.rb, T, S)
+        for name, o in offs.items():
+            setattr(base, 'result_' + ('flags' if name == 'regular' else name), sw['dev'].data_ptr() + o)
+        s = EvalSweepRecv(base=base, K=K, pad_=0, models=None, q=None)
+        if engines:
+            s._handles = (C.c_void_p * K)(*[engine._h for engine in engines])     # (kept alive with the struct)
+            s.models = s._handles
+            s.q = q.data_ptr()
+        return s
+
+    def eval_sweep_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None, own=None,
+                        power=None, stream_phase='chain'):
+        """eval_steps_recv() for K networks on the SAME steps in ONE call (v2x_eval_sweep_recv / _split): its arguments with a
+        list of K fixed-size `engines` of one spec in the engine's place (None: nobody is greedy anywhere, no CSR, no forward; K
+        then says how many identical policy schemes the result holds, default 1).  One walk, one observation pass, one CSR, K
+        forwards of the one batch, one finish: scheme k < K is engine k's policy on the shared explore flags and random actions,
+        scheme K the baseline (when given).  It runs on the buffers of eval_steps_recv() of that T with a result block per
+        (T, S) and a Q workspace per (T, K) of its own.  The resident state afterwards is the one engine K - 1's own
+        eval_steps_recv() leaves, and trajectory_states(T) holds the T snapshots.
+        -> a RecvEvalResult of K (+ 1) schemes, its download in flight."""
+        who = "eval_sweep_recv"
+        T, ex, ra, ba, own, K = self.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase)
+        engines = None if engines is None else list(engines)
+        self._init_device()
+        if not self._recv_ready:
+            raise RuntimeError("%s: no observe_recv() since the last step()" % who)
+        S = K + (1 if ba is not None else 0)
+        io, sw, _ = self._recv_sweep_io(T, S, K)
+        self._eval_upload(io, T, ex, ra, ba)
+        eb, n_edges, max_edges = self._edge_base(io, own, T) if engines is not None else (None, None, None)
+        s = self.eval_sweep_recv_struct(T, K, v2v_weight, v2i_weight, engines, eb, n_edges, max_edges, power, ba is not None)
+        self._keep_actions = self._t['actions']
+        ws = io['workspace']
+        if stream_phase == 'split':
+            sws = self._recv_split_workspace(T)
+            check(self._lib, self._lib.v2x_eval_sweep_recv_split(C.byref(s), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
+                                                                 self._stream()))
+        else:
+            check(self._lib, self._lib.v2x_eval_sweep_recv(C.byref(s), ws.data_ptr(), ws.numel(), self._stream()))
+        self.walk_calls['wide'] += 1
+        self.stream_phase_calls[stream_phase] += 1
+        self._traj_form[T] = 'recv'
+        self._obs_ready = False
+        self._recv_ready = True
+        return self._sweep_download(sw, T, S, RecvEvalResult)
 
     def trajectory_states(self, T):
         """-> TrajectoryStates: the T snapshots the last rollout_steps() / eval_steps() of block length T (or their receiver
@@ -2468,17 +2571,17 @@ class DeviceBatchedEnviron(BatchedEnviron):
 
         return self._resident_call('rollout_steps' if steps else 'rollout_step', check_args, call)
 
-    def _resident_call(self, who, check_args, call):
+    def _resident_call(self, who, check_args, call, receiver_form=False):
         """the bookkeeping every call that steps the resident state shares (rollout_step / rollout_steps / evaluate_steps):
         check_args(dc) raises ValueError before any device work of the call, call(dc) makes it -> its result object.  The two
         halves around the call are methods of their own for a call that steps several environments at once
         (resident_rollout_steps_mixed): every environment's first half, the one call, every environment's second half."""
-        dc = self._resident_before(who, check_args)
+        dc = self._resident_before(who, check_args, receiver_form)
         return self._resident_after(call(dc))
 
-    def _resident_before(self, who, check_args):
+    def _resident_before(self, who, check_args, receiver_form=False):
         """_resident_call up to the library call: everything the device needs is on it, the arguments are checked, the
-        observation is resident -> the DeviceChannels"""
+        observation is resident (receiver_form: in receiver form, as rollout_steps_recv() brings it) -> the DeviceChannels"""
         if self.stream_backend != 'device':
             raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
         self.finish_step()
@@ -2488,7 +2591,10 @@ class DeviceBatchedEnviron(BatchedEnviron):
         stale = bool(self._dirty)
         dc = self._flush()
         check_args(dc)
-        if stale or not dc._obs_ready:                         # (after a reset: the observation of the new channels, left on the device)
+        if receiver_form:
+            if stale or not dc._recv_ready:
+                dc.observe_recv(self.dest)
+        elif stale or not dc._obs_ready:                       # (after a reset: the observation of the new channels, left on the device)
             dc.observe(self.dest)
         self._obs = None
         return dc
@@ -2600,6 +2706,25 @@ class DeviceBatchedEnviron(BatchedEnviron):
         self._obs = None
         return self._resident_after(dc.eval_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight,
                                                        engine=engine, own=own, stream_phase=stream_phase))
+
+    def evaluate_sweep(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None,
+                       stream_phase='chain'):
+        """K networks scored on the SAME T steps of an evaluation episode in one call (streams='device', more than 31 links:
+        DeviceChannels.eval_sweep_recv) with the bookkeeping of evaluate_steps() in receiver form around it: explore [T, E],
+        policy_random [T, E, n], baseline_actions [T, E, n] or None, engines: K fixed-size engines of one spec (None: nobody is
+        greedy, K identical policy schemes).  Afterwards the resident state is what engine K - 1's own evaluate_steps() leaves.
+        -> the RecvEvalResult of K (+ 1) schemes, its download in flight.  trajectory_states(T) then holds the T snapshots."""
+        who = 'evaluate_sweep'
+        if not self._wide():
+            raise ValueError("%s serves the receiver form only (more than %d links, got %d): MixedAgent.evaluate_training scores the "
+                             "checkpoints of a shared-weight network at 3..%d links" % (who, OBSERVE_MAX_LINKS, self.n_Veh,
+                                                                                        OBSERVE_MAX_LINKS))
+        own = self.own_receivers()
+        return self._resident_call(
+            who, lambda dc: dc.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase),
+            lambda dc: dc.eval_sweep_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=engines, K=K,
+                                          own=own, stream_phase=stream_phase),
+            receiver_form=True)
 
     def trajectory_states(self, T):
         """the T snapshots of the last evaluate_steps() / rollout_steps() of block length T as one stacked search problem

@@ -6,6 +6,11 @@ baseline and the brute-force optimum.
     python -m v2xgnn.rl.train    --links 4 --episodes 10 --train-steps 20 --batch 512 --save-dir runs/a
     python -m v2xgnn.rl.evaluate --links 4 --episodes 10 --batch 512 --save-dir runs/a --test-steps 100 --trials 10
 
+--sweep scores all checkpoints of a trial on ONE walked episode (Agent.evaluate_training_sweep); beyond 31 links on the GPU:
+
+    python -m v2xgnn.rl.evaluate --links 100 --feedback 64 --episodes 40 --save-dir runs/b --test-steps 50 --trials 10 --sweep \
+                                 --opt-backend local --sim-backend device --sim-streams device --eval-backend device
+
 The checkpoints of a shared-weight network trained on several link counts at once (rl.train --mixed-links ... --save-interval 5
 --save-dir D) are evaluated per link count, on the training sizes or on others -- every trial ONE re-seeded episode on which
 all checkpoints are scored (rl/mixed.py MixedAgent.evaluate_training):
@@ -48,6 +53,10 @@ def build_parser():
     ap.add_argument("--opt-restarts", type=int, default=None,
                     help="restarts per state of --opt-backend local (default: rl/optimum.py DEFAULT_LOCAL_RESTARTS)")
     ap.add_argument("--seed", type=int, default=1)                # :22
+    ap.add_argument("--sweep", action="store_true",
+                    help="with --links: score all checkpoints on ONE walked episode per trial (Agent.evaluate_training_sweep; with "
+                         "--eval-backend device beyond 31 links one library call per trial) instead of one episode per "
+                         "(trial, checkpoint)")
     ap.add_argument("--mixed-links", default=None, metavar="N1,N2,...",
                     help="evaluate the checkpoints rl.train --mixed-links N1,N2,... --save-interval K saved (rl/mixed.py): the "
                          "training sizes, used only to find the files; --links is ignored")
@@ -161,7 +170,12 @@ def run_mixed(ap, args):
 def main(argv=None):
     ap, args = parse_args(argv)
     if args.mixed_links is not None:
+        if args.sweep:
+            ap.error("--sweep is the single-size path's (--links): --mixed-links always scores all checkpoints on one episode")
         return run_mixed(ap, args)
+    if args.sweep and args.eval_backend == "device" and args.links <= 31:
+        ap.error("--sweep --eval-backend device needs more than 31 links (the receiver form); --mixed-links scores the checkpoints "
+                 "of a shared-weight network at 3..31 links on the GPU")
     if args.links < 4 or args.links % 4:
         ap.error("--links must be a multiple of 4 and at least 4 (got %d)" % args.links)
     random.seed(args.seed)
@@ -172,10 +186,10 @@ def main(argv=None):
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False,
                   trajectory_walk=args.trajectory_walk, trajectory_streams=args.trajectory_streams,
                   receiver_streams=args.receiver_streams)
-    out = agent.evaluate_training_diff_trials(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials,
-                                              model_dir=args.save_dir, num_train_steps=args.train_steps,
-                                              opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,
-                                              eval_backend=args.eval_backend)
+    evaluate = agent.evaluate_training_sweep if args.sweep else agent.evaluate_training_diff_trials
+    out = evaluate(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials, model_dir=args.save_dir,
+                   num_train_steps=args.train_steps, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,
+                   eval_backend=args.eval_backend)
     ret, ra = (out[0], out[2]) if args.opt else (out[1], out[3])
     summary = {"links": args.links, "checkpoints": int(ret.shape[1]), "trials": args.trials,
                "mean_return_per_checkpoint": [round(float(v), 4) for v in ret.mean(axis=0)],

@@ -1108,6 +1108,41 @@ typedef struct v2x_eval_sweep {
 int64_t v2x_eval_sweep_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
 int  v2x_eval_sweep_mixed(const v2x_eval_sweep* s, const v2x_traj_ws* ws /*[host][n_pools] or NULL*/, void* stream);
 
+/* v2x_eval_sweep_recv: v2x_eval_sweep_mixed's idea for 3 <= n <= 128 links on the receiver-form resident state -- K fixed-size
+ * networks (the checkpoints of a training run, rl/agent.py Agent.evaluate_training_sweep) scored on the SAME T steps.  Enqueues,
+ * in this order on one stream with no parallel branches,
+ *   the front of v2x_eval_steps_recv   once, unchanged, with model = models[0] and q = this struct's q: the wide walk (chain
+ *                                      stream phase), k_traj_observe_recv and, with models, v2x_csr_from_recv and models[0]'s forward;
+ *   v2x_forward                        K - 1 times, of that one batch (same CSR, same edge_base): models[k] into q + k T E n rb;
+ *   k_eval_finish_sweep_recv           grid (S T E), scheme major, S = K + 1 with base.baseline_actions, else K; 192 threads per
+ *                                      (scheme, t, e): the body of k_eval_finish_recv on the block's view.  Scheme k < K is the
+ *                                      policy of network k on the shared explore / random_actions, scheme K the baseline.  Only
+ *                                      network K - 1 at t = T - 1 leaves the resident actions, rates and interference.
+ * Results: the layout of v2x_eval_steps_recv with S in place of its 1 or 2, [S][T][E][..] sections in the same order, then
+ * result_flags [T+1][E]; v2x_eval_sweep_recv_result_bytes(E, n, rb, T, S) is the formula of v2x_eval_recv_result_bytes for
+ * 1 <= S <= 65 (negative outside, and for T E > 65535 or outside the limits of v2x_rollout_recv_workspace_bytes).  Scheme k
+ * holds the bits of scheme 0 of v2x_eval_steps_recv with models[k] from the state before the call, scheme K those of its scheme
+ * 1; every byte of resident state and of the workspace's eight sections afterwards is what v2x_eval_steps_recv with
+ * models[K - 1] leaves.  v2x_eval_sweep_recv_split: the same with the split stream phase on the second workspace of
+ * v2x_rollout_recv_split_workspace_bytes; every byte it leaves is the chain form's.
+ * Same rules as v2x_eval_steps_recv: all pointers [dev] except `models` ([host]), asynchronous, no allocation, no
+ * synchronisation, no environment variable read; every check before the first launch.  V2X_EINVAL (text in
+ * v2x_last_error(NULL)), nothing launched or written: a null s, K outside 1..64, a NULL entry of models, models that are not
+ * fixed-size models of n links and rb channels or differ in feature width, depth or weight sharing, a null q with models, and
+ * everything v2x_eval_steps_recv / _split refuses of base, ws and split_ws.  (An error v2x_forward itself returns for
+ * models[k], k >= 1 -- none is known for a model that passed these checks, its shape being models[0]'s -- comes back after the
+ * front has run: the walk is made, the results are not; the same holds for v2x_eval_sweep_mixed.)                            */
+struct v2x_eval_sweep_recv {         /* (a tag, not a typedef: the call below bears the same name) */
+  v2x_eval_recv base;               /* as for v2x_eval_steps_recv; base.model and base.q are ignored */
+  int32_t K, pad_;                  /* 1..64 networks */
+  v2x_model* const* models;         /* [host][K], or NULL: everybody explores, no CSR, no forward */
+  float* q;                         /* [dev] [K][T E n][rb] (required with models) */
+};
+int64_t v2x_eval_sweep_recv_result_bytes(int32_t E, int32_t n, int32_t rb, int32_t T, int32_t schemes);
+int  v2x_eval_sweep_recv(const struct v2x_eval_sweep_recv* s, void* ws, int64_t ws_bytes, void* stream);
+int  v2x_eval_sweep_recv_split(const struct v2x_eval_sweep_recv* s, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                               void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */
