@@ -4,7 +4,8 @@ run on a GPU box:
 Every case is one seeded draw, judged exactly as tests/test_gpu_shapes.py judges its permanent subset: plain rounding
 tolerances, ReLU gates at fp32 rounding distance of 0 identified explicitly and taken the kernels' way (tests/util.py),
 nothing redrawn.  The grid: 7 link counts x 4 feature widths x 5 depths (1, 2, 4, 6, 8) x shared / per-node weights x
-3 batch sizes = 840 shapes, reference topology or a random adjacency."""
+3 batch sizes = 840 shapes, and 64, 100 and 128 links at F = 64, L = 2 (x weights x batch sizes = 18 more: the layer-wise
+model beyond 40 links, tests/test_gpu_links_41_128.py), reference topology or a random adjacency."""
 import itertools, os, sys, traceback
 import numpy as np
 sys.path.insert(0, '.'); sys.path.insert(0, 'tests')
@@ -15,6 +16,7 @@ from util import f32_params, random_inputs, oracle_step, assert_fwd_close, asser
 
 rng = np.random.default_rng(7)
 cases = list(itertools.product([1, 2, 3, 7, 20, 33, 40], [16, 32, 64, 128], [1, 2, 4, 6, 8], [False, True], [1, 17, 130]))
+cases += list(itertools.product([64, 100, 128], [64], [2], [False, True], [1, 17, 130]))
 rng.shuffle(cases)
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 60
 bad = flips = 0

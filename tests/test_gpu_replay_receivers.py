@@ -148,23 +148,33 @@ def test_receiver_memory_beyond_31_links_is_the_host_packer(n, K):
     _check_against_packer(rep, kept, rng.choice(regular, size=K))        # and regular again, in the same buffers
 
 
-@pytest.mark.parametrize("n,feat,layers", [(33, 32, 1), (40, 16, 2)])
+@pytest.mark.parametrize("n,feat,layers", [(33, 32, 1), (40, 16, 2), (65, 64, 2), (128, 64, 2)])
 def test_forward_of_a_sampled_batch_is_the_forward_of_the_host_batch(n, feat, layers):
+    """(65 and 128 links at F = 64: the CSR v2x_csr_from_recv builds on the device feeds k_adj_masks and the dense
+    aggregation, own-receiver rows of in-degree n - 1 included; the forward is also held to the float64 oracle)"""
     from v2xgnn import GnnEngine, GnnSpec
     from v2xgnn.rl.replay import ReceiverReplay
     from oracle import compact as oc
-    from util import f32_params
+    from util import f32_params, ospec, assert_fwd_close
     rng = np.random.default_rng(n)
     log = [_transition(rng, n, (5,) if i == 6 else ()) for i in range(12)]
+    assert log[6]['adj'][:, 5].sum() == n - 1 and all(t['adj'].sum() == n * (n - 2) for i, t in enumerate(log) if i != 6)
     rep = ReceiverReplay(32, n)
     _feed((rep,), log, lambda i: False)
     spec = GnnSpec(n_nodes=n, feat_dim=feat, n_mp_layers=layers)
     eng = GnnEngine(spec)
-    eng.set_weights(oc.params_to_list(f32_params(spec, np.random.default_rng(1))))
+    P = f32_params(spec, np.random.default_rng(1))
+    eng.set_weights(oc.params_to_list(P))
     for idx in (np.array([0, 1, 2, 3, 3, 11, 9]), np.array([4, 6, 6, 0, 10])):      # regular; with an own-receiver graph
         ref = _check_against_packer(rep, log, idx)
         sb = rep.sample(idx)[0]
-        assert np.array_equal(eng.forward(sb).cpu().numpy(), eng.forward(ref))
+        q = eng.forward(sb).cpu().numpy()
+        assert np.array_equal(q, eng.forward(ref))
+        if n > 40:
+            assert eng.path_info(sb)["aggregation"].startswith("dense"), eng.path_info(sb)
+        f32 = lambda k: np.concatenate([log[i][k] for i in idx]).astype(np.float32).astype(np.float64)
+        M = oc.csr_to_matrix(*oc.adj_to_csr(np.stack([log[i]['adj'] for i in idx])), dtype=np.float64)
+        assert_fwd_close(q, oc.forward(ospec(spec), P, f32('x'), f32('e'), M)[0], "forward of the sampled batch against the oracle")
     eng.close()
 
 

@@ -1,7 +1,8 @@
 """GPU: whole-model parity (forward, per-output loss, every gradient array) against the float64 oracle over a spread of
-shapes -- link counts 1..40 (1 and 2 links: graphs without edges), all feature widths incl. the wide path, 1..4
-message-passing layers, per-node and shared weights, batches that are not multiples of any tile (1, 17, 130), the
-reference topology and random adjacencies.  `tests/sweep_shapes.py` runs the full 840-shape grid
+shapes -- link counts 1..40 (1 and 2 links: graphs without edges; 41 to 128 links: tests/test_gpu_links_41_128.py), all
+feature widths incl. the wide path, 1..4 message-passing layers, per-node and shared weights, batches that are not
+multiples of any tile (1, 17, 130), the reference topology and random adjacencies.  `tests/sweep_shapes.py` runs the full
+840-shape grid and 64, 100 and 128 links at F = 64, L = 2
 (depths 1, 2, 4, 6, 8; tests/test_gpu_depth.py covers the paths whose plan changes above 4 layers).
 
 Every shape is ONE seeded draw and that draw counts.  A ReLU whose pre-activation lies within fp32 rounding of 0 is gated
