@@ -158,6 +158,12 @@ class EvalSweepRecv(C.Structure):
     _fields_ = [("base", EvalRecv), ("K", C.c_int32), ("pad_", C.c_int32), ("models", C.POINTER(C.c_void_p)), ("q", C.c_void_p)]
 
 
+class MtJump(C.Structure):
+    """v2x_mt_jump of include/v2xgnn.h"""
+    _fields_ = [("first", C.c_int64), ("stride", C.c_int64), ("count", C.c_int32), ("pad_", C.c_int32), ("polys", C.c_void_p),
+                ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
 class ReplayPool(C.Structure):
     """v2x_replay_pool of include/v2xgnn.h"""
     _fields_ = [("n_nodes", C.c_int32), ("count", C.c_int32)] + \
@@ -303,6 +309,11 @@ SYMBOLS = [
     ("v2x_eval_sweep_recv_result_bytes", _L, [_I, _I, _I, _I, _I]),
     ("v2x_eval_sweep_recv", C.c_int, [C.POINTER(EvalSweepRecv), _P, _L, _P]),
     ("v2x_eval_sweep_recv_split", C.c_int, [C.POINTER(EvalSweepRecv), _P, _L, _P, _L, _P]),
+    ("v2x_mt_jump_polys", C.c_int, [_L, _L, _I, _P]),
+    ("v2x_mt_jump_scratch_bytes", _L, [_I, _I]),
+    ("v2x_rollout_steps_recv_jump", C.c_int, [C.POINTER(RolloutRecv), _P, _L, _P, _L, C.POINTER(MtJump), _P]),
+    ("v2x_eval_steps_recv_jump", C.c_int, [C.POINTER(EvalRecv), _P, _L, _P, _L, C.POINTER(MtJump), _P]),
+    ("v2x_eval_sweep_recv_jump", C.c_int, [C.POINTER(EvalSweepRecv), _P, _L, _P, _L, C.POINTER(MtJump), _P]),
 ]
 
 

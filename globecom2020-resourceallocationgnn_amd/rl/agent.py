@@ -29,6 +29,7 @@ ROLLOUT_BACKENDS = ('host', 'device', 'trajectory')
 EVAL_BACKENDS = ('host', 'device')
 TRAJECTORY_WALKS = ('serial', 'wide')
 TRAJECTORY_STREAMS = ('chain', 'split')
+RECEIVER_WORDS = ('serial', 'jump')
 
 
 def _check_opt_backend(opt_backend):
@@ -80,7 +81,7 @@ class Memory(object):
 class Agent(object):
     def __init__(self, num_d2d, num_ch, num_neighbor, num_d2d_feedback, environment, curr_rl_config, brain=None,
                  device_replay='auto', rollouts='replicated', rollout_backend='host', trajectory_walk='serial', trajectory_streams='chain',
-                 receiver_streams='chain', **brain_kwargs):
+                 receiver_streams='chain', receiver_words='serial', **brain_kwargs):
         """rollout_backend: 'host' (the default: _packed_iteration -- the observation comes down, is scored, the actions go up,
         the transitions go up again) or 'device': a whole rollout iteration is ONE call on the resident state (v2x_rollout_step:
         score, pick, step, reward, store); the host contributes the epsilon-greedy draws and reads one result row.  'device'
@@ -115,6 +116,11 @@ class Agent(object):
         evaluation episodes of eval_backend='device' beyond 31 links (v2x_eval_steps_recv / _split, which walk wide whatever
         trajectory_walk says).  'split' needs device_replay='receivers' and rollout_backend='trajectory', or an agent that
         eval_backend='device' can run on; anything else is a ValueError here.  (trajectory_streams stays the 3..31-link option.)
+
+        receiver_words: how receiver_streams='split' draws its raw words: 'serial' (the default: one workgroup per simulator) or
+        'jump' (v2x_rollout_steps_recv_jump / v2x_eval_steps_recv_jump / v2x_eval_sweep_recv_jump: the words beyond a prefix in
+        chunks entered by jump-ahead polynomials of MT19937, spread over the chip) -- the same bits
+        (tests/test_gpu_mt_jump.py), opt-in.  'jump' needs receiver_streams='split'; anything else is a ValueError here.
 
         rollouts (data-parallel runs only; north_star: "RL rollouts from Environment.py are the natural shard"):
           'replicated'  every rank steps the SAME seeded simulator and draws the same minibatch, of which it fits its
@@ -204,6 +210,12 @@ class Agent(object):
                                  "on (v2x_eval_steps_recv): device_replay is %r, rollout_backend is %r, and %s"
                                  % (device_replay, rollout_backend, exc))
         self.receiver_streams = receiver_streams
+        if receiver_words not in RECEIVER_WORDS:
+            raise ValueError("receiver_words must be one of %s, got %r" % (RECEIVER_WORDS, receiver_words))
+        if receiver_words == 'jump' and receiver_streams != 'split':
+            raise ValueError("receiver_words='jump' needs receiver_streams='split' (it draws the split stream phase's words in chunks), "
+                             "got receiver_streams=%r" % (receiver_streams,))
+        self.receiver_words = receiver_words
         self._lazy_rewards = None
         self.eval_stats = {'device_episodes': 0, 'host_episodes': 0}      # which path the evaluation episodes took
 
@@ -577,7 +589,8 @@ class Agent(object):
         actions = np.stack([a for a, _ in drawn]).reshape(T, E, n)
         head = rep.reserve(K)
         result = env.rollout_steps_recv(explore, actions, rep.storage(), head, rep.capacity, self.v2v_weight, self.v2i_weight,
-                                        engine=self.brain.model.engine if anybody else None, stream_phase=self.receiver_streams)
+                                        engine=self.brain.model.engine if anybody else None, stream_phase=self.receiver_streams,
+                                        **self._receiver_words_kw())
         rep.commit(K, np.tile(env.own_receivers(), T))
         self.num_step += K
         samples = self.memory.samples                  # the host list only keeps the FIFO bookkeeping (train_observe(None) x K)
@@ -1243,12 +1256,12 @@ class Agent(object):
         T, n = len(explore), self.num_D2D
         explore = np.asarray(explore, np.uint8)
         engine = None if explore.all() else self.brain.model.engine
-        walk, stream_phase = self.trajectory_walk, self.trajectory_streams
-        if self._receiver_form():                      # beyond 31 links: the receiver form, wide, its own stream-phase option
-            walk, stream_phase = 'wide', self.receiver_streams
+        walk, stream_phase, stream_words = self.trajectory_walk, self.trajectory_streams, 'serial'
+        if self._receiver_form():                      # beyond 31 links: the receiver form, wide, its own stream-phase options
+            walk, stream_phase, stream_words = 'wide', self.receiver_streams, self.receiver_words
         res = self.env.evaluate_steps(explore.reshape(T, 1), np.asarray(policy_random).reshape(T, 1, n),
                                       np.asarray(baseline).reshape(T, 1, n), self.v2v_weight, self.v2i_weight, engine=engine,
-                                      walk=walk, stream_phase=stream_phase)
+                                      walk=walk, stream_phase=stream_phase, **self._receiver_words_kw(stream_words))
         out = {'res': res.resolve()}
         if optimum is not None or rank:
             states = self.env.trajectory_states(T)
@@ -1264,6 +1277,11 @@ class Agent(object):
         self.num_step += T
         self.eval_stats['device_episodes'] += 1
         return out
+
+    def _receiver_words_kw(self, words=None):
+        """the stream_words argument of a receiver-form call, only where it differs from the call's default"""
+        words = self.receiver_words if words is None else words
+        return {} if words == 'serial' else {'stream_words': words}
 
     def _receiver_form(self):
         """the environment keeps this scenario's resident observation in receiver form (more than 31 links)"""
@@ -1559,7 +1577,7 @@ class Agent(object):
                 if eval_backend == 'device' and n_st > 0 and self._device_episode_possible():
                     r = self.env.evaluate_sweep(explore.reshape(n_st, 1), rand.reshape(n_st, 1, n), baseline.reshape(n_st, 1, n),
                                                 w_v2v, w_v2i, engines=None if explore.all() else engines, K=K,
-                                                stream_phase=self.receiver_streams).resolve()
+                                                stream_phase=self.receiver_streams, **self._receiver_words_kw()).resolve()
                     _, o_reward, o_rates = self._stacked_optimum(self.env.trajectory_states(n_st), opt_backend, opt_restarts)
                     for st in range(n_st):
                         book_shared(trial, st, (r.v2v_rate[K, st, 0], r.v2i_rate[K, st, 0]), o_reward[st], *(a[st] for a in o_rates))

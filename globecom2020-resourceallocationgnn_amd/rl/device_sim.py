@@ -93,7 +93,10 @@ form -- `observe_recv`: xe as before, the links' receivers and one flag byte per
 rl/replay.py ReceiverReplay's layout; `DeviceBatchedEnviron(streams='device')` serves 32..128 links on it.  It takes
 stream_phase='chain' (the default) or 'split' too (v2x_rollout_steps_recv_split: raw words, an offset walk with two vehicles
 per lane and the conversion in three launches on a second workspace made once per T; the same bits, 2.5-2.7x faster at
-32..128 links, profiles/rollout_recv_split_timing.json).  `eval_steps_recv` is the evaluation episode of that form
+32..128 links, profiles/rollout_recv_split_timing.json), and with 'split' stream_words='serial' (the default) or 'jump'
+(v2x_rollout_steps_recv_jump: the raw words beyond a prefix drawn in chunks that jump-ahead polynomials of MT19937 enter --
+`jump_plan`, a table and a scratch made once; the same word array, the call 2-10.7x faster again at 32..128 links,
+profiles/rollout_recv_jump_timing.json; the evaluation and sweep calls below take it too).  `eval_steps_recv` is the evaluation episode of that form
 (v2x_eval_steps_recv / _split: the same front, then k_eval_finish_recv paying the policy and the baseline on every step's
 snapshot; -> RecvEvalResult), on the same buffers; `DeviceBatchedEnviron.evaluate_steps` goes through it beyond 31 links, and
 trajectory_states(T) serves the snapshots of whichever form ran last (profiles/eval_recv_timing.json).  `eval_sweep_recv`
@@ -107,7 +110,7 @@ import numpy as np
 
 from . import native_sim
 from ..lib import (Eval, EvalMixed, EvalRecv, EvalSweep, EvalSweepRecv, MIXED_MAX_POOLS, SWEEP_MAX_MODELS, OptProblem, Rollout,
-                   RolloutMixed, RolloutRecv, RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
+                   MtJump, RolloutMixed, RolloutRecv, RolloutTraj, SimReset, SimStep, TrajWs, check, load_library)
 from .batched_env import BatchedEnviron
 
 MAX_LINKS, MAX_RB, MAX_STATES = 128, 16, 65535          # v2x_sim_channels / v2x_sim_rates
@@ -236,6 +239,31 @@ def check_stream_phase(who, stream_phase, walk='wide'):
         raise ValueError("%s: stream_phase='split' needs walk='wide' (it is a form of the wide walk's stream phase), got walk=%r"
                          % (who, walk))
     return stream_phase
+
+
+STREAM_WORDS = ('serial', 'jump')                         # the words launch of a receiver-form split stream phase: one chain, or chunks
+JUMP_FIRST = MT_WORDS + 88 * 227                         # 20600 >= 20561: the prefix every chunk's seeds are made from, in whole rounds
+JUMP_STRIDE = 227 * 256                                  # words per chunk (the measured strides)
+JUMP_SLICES = 8                                          # the slices of a polynomial in the scratch of v2x_mt_jump_scratch_bytes
+
+
+def check_stream_words(who, stream_words, stream_phase):
+    """ValueError unless stream_words names a form of the words launch, and 'jump' comes with stream_phase='split'"""
+    if stream_words not in STREAM_WORDS:
+        raise ValueError("%s: stream_words must be one of %s, got %r" % (who, ", ".join(repr(w) for w in STREAM_WORDS), stream_words))
+    if stream_words == 'jump' and stream_phase != 'split':
+        raise ValueError("%s: stream_words='jump' needs stream_phase='split' (it draws the split stream phase's words in chunks), got "
+                         "stream_phase=%r" % (who, stream_phase))
+    return stream_words
+
+
+def jump_plan(nbw):
+    """-> (first, stride, count) of v2x_mt_jump for a word array of nbw words per state: the prefix [0, first) is drawn serially,
+    chunk p = 1 .. count begins at first + (p - 1) stride and the last one ends at nbw; count = 0 (the serial words launch) when
+    the prefix covers the array"""
+    nbw = int(nbw)
+    count = -(-(nbw - JUMP_FIRST) // JUMP_STRIDE) if nbw > JUMP_FIRST else 0
+    return JUMP_FIRST, JUMP_STRIDE, count
 
 
 def split_stream_blocks(n, rb, T, n_lanes):
@@ -455,6 +483,8 @@ class DeviceChannels(object):
         self._mixed = {}                                 # mixed_rollout_buffers(): ((E_k, n_k)..., T) of the pools this one leads
         self.walk_calls = {w: 0 for w in WALKS}          # trajectory calls made (rollout_steps / eval_steps), by the walk that ran
         self.stream_phase_calls = {p: 0 for p in STREAM_PHASES}     # the wide ones among them, by the form of the stream phase
+        self.stream_words_calls = {w: 0 for w in STREAM_WORDS}      # the receiver-form split ones among those, by the words launch
+        self._jump_tables = {}                                      # (first, stride, count) -> the uploaded polynomials
 
     # the packed observation (xe / mask / col / regular) is current; any assignment -- a step, another observation, a reset --
     # also says that the receiver form (observe_recv: xe / recv / flags) no longer is: observe_recv sets its own flag after it
@@ -1209,11 +1239,13 @@ class DeviceChannels(object):
                                                      None if edge_base is None else edge_base.data_ptr(), row_ptr.data_ptr(),
                                                      col_idx.data_ptr(), self._stream()))
 
-    def check_rollout_steps_recv(self, explore, random_actions, storage, head, capacity, own=None, stream_phase='chain'):
+    def check_rollout_steps_recv(self, explore, random_actions, storage, head, capacity, own=None, stream_phase='chain',
+                                 stream_words='serial'):
         """ValueError unless the arguments of rollout_steps_recv() fit this object; -> (T, explore [T, E] uint8, random_actions
         [T, E, n] int32, own [E] int32)"""
         who, E, n = "rollout_steps_recv", self.E, self.n
         check_stream_phase(who, stream_phase)
+        check_stream_words(who, stream_words, stream_phase)
         T = _block_length(explore)
         self.check_observe_recv(n, self.rb)
         self._check_mobility(who, True)
@@ -1301,6 +1333,51 @@ class DeviceChannels(object):
             io['split_workspace'], io['split_lanes'] = ws, n_lanes
         return ws
 
+    jump_plan = staticmethod(jump_plan)
+
+    def _recv_jump_table(self, T):
+        """the v2x_mt_jump of a receiver-form split call whose words are drawn in chunks (stream_words='jump'), for blocks of T
+        on the current lane grid: jump_plan() of the word array's length, the polynomials of v2x_mt_jump_polys uploaded once per
+        (first, stride, count) of this object -- they depend on the chunk positions alone, not on T, the states or the seeds --
+        and the scratch of v2x_mt_jump_scratch_bytes kept next to _recv_io(T)'s buffers; built once, never per call"""
+        io = self._recv_io(T)
+        E, n, rb, n_lanes = self.E, self.n, self.rb, self._grid[0].shape[1]
+        jump = io.get('jump')
+        if jump is None or io.get('jump_lanes') != n_lanes:
+            t = self.torch
+            plan = first, stride, count = self.jump_plan(split_stream_blocks(n, rb, T, n_lanes) * MT_WORDS)
+            polys = scratch = None
+            if count:
+                polys = self._jump_tables.get(plan)
+                if polys is None:
+                    host = np.zeros((count, MT_WORDS), np.uint32)
+                    check(self._lib, self._lib.v2x_mt_jump_polys(first, stride, count, host.ctypes.data))
+                    polys = self._jump_tables[plan] = t.from_numpy(host.view(np.int32)).to(self.device)
+                    self.traffic['bytes_up'] += host.nbytes
+                need = self._lib.v2x_mt_jump_scratch_bytes(E, count)
+                if need != _align(4 * E * count * JUMP_SLICES * MT_WORDS, 256):
+                    raise ValueError("rollout_steps_recv: the library sizes the jump scratch of E = %d, count = %d at %d bytes, the "
+                                     "documented formula at %d" % (E, count, need, _align(4 * E * count * JUMP_SLICES * MT_WORDS, 256)))
+                scratch = t.zeros(need, dtype=t.uint8, device=self.device)
+                if polys.data_ptr() % 256 or scratch.data_ptr() % 256:
+                    raise RuntimeError("rollout_steps_recv: the allocator returned a jump table or scratch that is not 256-byte aligned")
+            jump = MtJump(first=first, stride=stride, count=count, pad_=0, polys=None if polys is None else polys.data_ptr(),
+                          scratch=None if scratch is None else scratch.data_ptr(), scratch_bytes=0 if scratch is None else scratch.numel())
+            jump._keep = (polys, scratch)                    # (kept alive with the struct)
+            io['jump'], io['jump_lanes'] = jump, n_lanes
+        return jump
+
+    def _recv_split_call(self, split, jump, r, ws, T, stream_words):
+        """the library call of a receiver-form struct r with the split stream phase: `split`, or with stream_words='jump' its
+        _jump form on the cached table of _recv_jump_table(T); counted in stream_words_calls"""
+        sws = self._recv_split_workspace(T)
+        if stream_words == 'jump':
+            check(self._lib, jump(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(), C.byref(self._recv_jump_table(T)),
+                                  self._stream()))
+        else:
+            check(self._lib, split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(), self._stream()))
+        self.stream_words_calls[stream_words] += 1
+
     def rollout_steps_recv_buffers(self, T):
         """the device buffers of rollout_steps_recv() for blocks of T: workspace (carved by recv_workspace_layout: offsets),
         policy_dev, result_dev (reward [T, E] float64 | flags [T, 2, E] bytes), q [T E n, rb] float32"""
@@ -1353,7 +1430,7 @@ class DeviceChannels(object):
         return r
 
     def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None, own=None,
-                           power=None, stream_phase='chain'):
+                           power=None, stream_phase='chain', stream_words='serial'):
         """rollout_steps(walk='wide') for 3..128 links into ReceiverReplay's layout, ONE call (v2x_rollout_steps_recv): the wide
         walk, the observations of entries 1..T in receiver form, the closed-form CSR of the T E graphs, one forward (engine
         given), and the finish that picks, pays and stores xe / xe_next / recv / action / reward into slots
@@ -1362,9 +1439,13 @@ class DeviceChannels(object):
         object last sent up from the host.  The current observation must be resident in receiver form (observe_recv() or a
         previous rollout_steps_recv()).  stream_phase: 'chain' (the first launch draws the streams of all T steps) or 'split'
         (v2x_rollout_steps_recv_split: raw words, offset walk and conversion as three launches on a second workspace made once
-        per T, the same bits); stream_phase_calls counts the calls by it.  -> a RecvRolloutResult whose download is in flight."""
+        per T, the same bits); stream_phase_calls counts the calls by it.  stream_words (stream_phase='split' only): 'serial'
+        (one workgroup per state draws all its words) or 'jump' (v2x_rollout_steps_recv_jump: the words beyond a prefix drawn in
+        chunks entered by jump-ahead polynomials, the same bits; the table and a scratch are made once per T);
+        stream_words_calls counts the split calls by it.  -> a RecvRolloutResult whose download is in flight."""
         who = "rollout_steps_recv"
-        T, ex, ra, own = self.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase)
+        T, ex, ra, own = self.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase,
+                                                       stream_words)
         self._init_device()
         if not self._recv_ready:
             raise RuntimeError("%s: no observe_recv() since the last step()" % who)
@@ -1375,9 +1456,7 @@ class DeviceChannels(object):
         self._keep_actions = self._t['actions']
         ws = io['workspace']
         if stream_phase == 'split':
-            sws = self._recv_split_workspace(T)
-            check(self._lib, self._lib.v2x_rollout_steps_recv_split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
-                                                                    self._stream()))
+            self._recv_split_call(self._lib.v2x_rollout_steps_recv_split, self._lib.v2x_rollout_steps_recv_jump, r, ws, T, stream_words)
         else:
             check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
         self.walk_calls['wide'] += 1
@@ -1553,11 +1632,12 @@ class DeviceChannels(object):
         return self._eval_download(io, T, 2 if ba is not None else 1)
 
     # ------------------------------------------------------------------ an evaluation episode of 3..128 links (receiver form)
-    def check_eval_steps_recv(self, explore, policy_random, baseline_actions, own=None, stream_phase='chain'):
+    def check_eval_steps_recv(self, explore, policy_random, baseline_actions, own=None, stream_phase='chain', stream_words='serial'):
         """ValueError unless the arguments of eval_steps_recv() fit this object; -> (T, explore [T, E] uint8, policy_random
         [T, E, n] int32, baseline_actions [T, E, n] int32 or None, own [E] int32)"""
         who, E, n = "eval_steps_recv", self.E, self.n
         check_stream_phase(who, stream_phase)
+        check_stream_words(who, stream_words, stream_phase)
         self.check_observe_recv(n, self.rb)
         T, ex, ra, ba = self._check_eval_arrays(who, explore, policy_random, baseline_actions)
         if T * E * n * (n - 1) > 2 ** 31 - 1:
@@ -1626,17 +1706,18 @@ class DeviceChannels(object):
         return r
 
     def eval_steps_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, own=None, power=None,
-                        stream_phase='chain'):
+                        stream_phase='chain', stream_words='serial'):
         """eval_steps(walk='wide') for 3..128 links on the receiver-form resident state, ONE call (v2x_eval_steps_recv): the wide
         walk, the observations of entries 1..T in receiver form, the closed-form CSR of the T E graphs, one forward (engine
         given; None: nobody is greedy, no forward) and the finish that pays the policy and, when given, the baseline on every
         step's snapshot.  It runs on the buffers of rollout_steps_recv() of that T (workspace, q, cached batches, edge_base
         ring) with a policy ring and a result block of its own; no replay memory is touched.  States with an own-receiver link
-        are scored like the others.  own, stream_phase: as for rollout_steps_recv().  The current observation must be resident
+        are scored like the others.  own, stream_phase, stream_words: as for rollout_steps_recv() (v2x_eval_steps_recv_split /
+        _jump).  The current observation must be resident
         in receiver form.  -> a RecvEvalResult whose download is in flight; afterwards the resident state is what T advance()
         calls under the policy's actions leave, and trajectory_states(T) holds the T snapshots."""
         who = "eval_steps_recv"
-        T, ex, ra, ba, own = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+        T, ex, ra, ba, own = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words)
         self._init_device()
         if not self._recv_ready:
             raise RuntimeError("%s: no observe_recv() since the last step()" % who)
@@ -1647,9 +1728,7 @@ class DeviceChannels(object):
         self._keep_actions = self._t['actions']
         ws = io['workspace']
         if stream_phase == 'split':
-            sws = self._recv_split_workspace(T)
-            check(self._lib, self._lib.v2x_eval_steps_recv_split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
-                                                                 self._stream()))
+            self._recv_split_call(self._lib.v2x_eval_steps_recv_split, self._lib.v2x_eval_steps_recv_jump, r, ws, T, stream_words)
         else:
             check(self._lib, self._lib.v2x_eval_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
         self.walk_calls['wide'] += 1
@@ -1660,12 +1739,13 @@ class DeviceChannels(object):
         return self._eval_download(io, T, 2 if ba is not None else 1, RecvEvalResult)
 
     # ------------------------------------------------------------------ K networks on one walked episode (receiver form)
-    def check_eval_sweep_recv(self, explore, policy_random, baseline_actions, engines=None, K=None, own=None, stream_phase='chain'):
+    def check_eval_sweep_recv(self, explore, policy_random, baseline_actions, engines=None, K=None, own=None, stream_phase='chain',
+                              stream_words='serial'):
         """ValueError unless the arguments of eval_sweep_recv() fit this object; -> (T, explore, policy_random, baseline_actions,
         own) as check_eval_steps_recv returns them, and K"""
         who = "eval_sweep_recv"
         try:
-            checked = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+            checked = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words)
         except ValueError as err:
             raise ValueError(str(err).replace("eval_steps_recv", who))
         if engines is None:
@@ -1724,17 +1804,19 @@ class DeviceChannels(object):
         return s
 
     def eval_sweep_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None, own=None,
-                        power=None, stream_phase='chain'):
+                        power=None, stream_phase='chain', stream_words='serial'):
         """eval_steps_recv() for K networks on the SAME steps in ONE call (v2x_eval_sweep_recv / _split): its arguments with a
         list of K fixed-size `engines` of one spec in the engine's place (None: nobody is greedy anywhere, no CSR, no forward; K
         then says how many identical policy schemes the result holds, default 1).  One walk, one observation pass, one CSR, K
         forwards of the one batch, one finish: scheme k < K is engine k's policy on the shared explore flags and random actions,
         scheme K the baseline (when given).  It runs on the buffers of eval_steps_recv() of that T with a result block per
         (T, S) and a Q workspace per (T, K) of its own.  The resident state afterwards is the one engine K - 1's own
-        eval_steps_recv() leaves, and trajectory_states(T) holds the T snapshots.
+        eval_steps_recv() leaves, and trajectory_states(T) holds the T snapshots.  stream_phase, stream_words: as for
+        rollout_steps_recv() (v2x_eval_sweep_recv_split / _jump).
         -> a RecvEvalResult of K (+ 1) schemes, its download in flight."""
         who = "eval_sweep_recv"
-        T, ex, ra, ba, own, K = self.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase)
+        T, ex, ra, ba, own, K = self.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase,
+                                                           stream_words)
         engines = None if engines is None else list(engines)
         self._init_device()
         if not self._recv_ready:
@@ -1747,9 +1829,7 @@ class DeviceChannels(object):
         self._keep_actions = self._t['actions']
         ws = io['workspace']
         if stream_phase == 'split':
-            sws = self._recv_split_workspace(T)
-            check(self._lib, self._lib.v2x_eval_sweep_recv_split(C.byref(s), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
-                                                                 self._stream()))
+            self._recv_split_call(self._lib.v2x_eval_sweep_recv_split, self._lib.v2x_eval_sweep_recv_jump, s, ws, T, stream_words)
         else:
             check(self._lib, self._lib.v2x_eval_sweep_recv(C.byref(s), ws.data_ptr(), ws.numel(), self._stream()))
         self.walk_calls['wide'] += 1
@@ -2634,11 +2714,12 @@ class DeviceBatchedEnviron(BatchedEnviron):
         return own
 
     def rollout_steps_recv(self, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine=None,
-                           stream_phase='chain'):
+                           stream_phase='chain', stream_words='serial'):
         """rollout_steps() for 3..128 links into a ReceiverReplay's storage (DeviceChannels.rollout_steps_recv: the wide walk,
         the closed-form CSR, one forward, one finish -- ONE call), with the same bookkeeping around it.  The resident
         observation is brought into receiver form first when it is not (after a reset, or after a packed-form call).
-        stream_phase: 'chain' or 'split', the form of the walk's stream phase (the same bits either way).
+        stream_phase: 'chain' or 'split', the form of the walk's stream phase (the same bits either way); stream_words: 'serial' or
+        'jump', how a split stream phase draws its words (DeviceChannels.rollout_steps_recv; the same bits either way).
         -> the RecvRolloutResult of the block, its download in flight."""
         who = 'rollout_steps_recv'
         if self.stream_backend != 'device':
@@ -2650,27 +2731,32 @@ class DeviceBatchedEnviron(BatchedEnviron):
         own = self.own_receivers()
         stale = bool(self._dirty)
         dc = self._flush()
-        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase)
+        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase, stream_words)
         if stale or not dc._recv_ready:
             dc.observe_recv(self.dest)
         self._obs = None
         return self._resident_after(dc.rollout_steps_recv(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight,
-                                                          engine=engine, own=own, stream_phase=stream_phase))
+                                                          engine=engine, own=own, stream_phase=stream_phase,
+                                                          stream_words=stream_words))
 
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
-                       walk='serial', stream_phase='chain', receiver_form=None):
+                       walk='serial', stream_phase='chain', receiver_form=None, stream_words='serial'):
         """The T steps of an evaluation episode in one call (streams='device' only; DeviceChannels.eval_steps) with the
         bookkeeping of rollout_steps() around it: explore [T, E], policy_random [T, E, n], baseline_actions [T, E, n] or None.
         walk: 'serial' or 'wide', the form of the trajectory; stream_phase: 'chain' or 'split', the form of a wide walk's stream
         phase (the same bits all).
         Beyond 31 links the call goes through the receiver form (DeviceChannels.eval_steps_recv, the bookkeeping of
         rollout_steps_recv()): walk must then be 'wide' and row_ptr None; receiver_form=True asks for that form at any size
-        (None: by the link count).
+        (None: by the link count); stream_words: 'serial' or 'jump', how the receiver form's split stream phase draws its words.
         -> the EvalResult (receiver form: RecvEvalResult), its download in flight.  trajectory_states(T) then holds the T
         snapshots."""
         if self._wide() if receiver_form is None else receiver_form:
             return self._evaluate_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine, row_ptr, walk,
-                                             stream_phase)
+                                             stream_phase, stream_words)
+        if stream_words != 'serial':
+            check_stream_words('evaluate_steps', stream_words, stream_phase)
+            raise ValueError("evaluate_steps: stream_words=%r serves the receiver form only (more than %d links, or receiver_form=True)"
+                             % (stream_words, OBSERVE_MAX_LINKS))
 
         def check_args(dc):
             check_walk('evaluate_steps', walk)
@@ -2683,7 +2769,7 @@ class DeviceBatchedEnviron(BatchedEnviron):
                                      walk=walk, stream_phase=stream_phase))
 
     def _evaluate_steps_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine, row_ptr, walk,
-                             stream_phase):
+                             stream_phase, stream_words='serial'):
         """evaluate_steps() in receiver form: rollout_steps_recv()'s bookkeeping around DeviceChannels.eval_steps_recv"""
         who = 'evaluate_steps'
         if walk != 'wide':
@@ -2700,15 +2786,16 @@ class DeviceBatchedEnviron(BatchedEnviron):
         own = self.own_receivers()
         stale = bool(self._dirty)
         dc = self._flush()
-        dc.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase)
+        dc.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words)
         if stale or not dc._recv_ready:
             dc.observe_recv(self.dest)
         self._obs = None
         return self._resident_after(dc.eval_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight,
-                                                       engine=engine, own=own, stream_phase=stream_phase))
+                                                       engine=engine, own=own, stream_phase=stream_phase,
+                                                       stream_words=stream_words))
 
     def evaluate_sweep(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None,
-                       stream_phase='chain'):
+                       stream_phase='chain', stream_words='serial'):
         """K networks scored on the SAME T steps of an evaluation episode in one call (streams='device', more than 31 links:
         DeviceChannels.eval_sweep_recv) with the bookkeeping of evaluate_steps() in receiver form around it: explore [T, E],
         policy_random [T, E, n], baseline_actions [T, E, n] or None, engines: K fixed-size engines of one spec (None: nobody is
@@ -2721,9 +2808,9 @@ class DeviceBatchedEnviron(BatchedEnviron):
                                                                                         OBSERVE_MAX_LINKS))
         own = self.own_receivers()
         return self._resident_call(
-            who, lambda dc: dc.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase),
+            who, lambda dc: dc.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase, stream_words),
             lambda dc: dc.eval_sweep_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=engines, K=K,
-                                          own=own, stream_phase=stream_phase),
+                                          own=own, stream_phase=stream_phase, stream_words=stream_words),
             receiver_form=True)
 
     def trajectory_states(self, T):

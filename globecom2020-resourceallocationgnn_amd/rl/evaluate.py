@@ -91,6 +91,8 @@ def parse_args(argv=None):
     if args.receiver_streams != "chain":
         ap.error("--mixed-links holds 3..31 links: --receiver-streams is the stream phase of one link count beyond 31 "
                  "(rl.evaluate --links)")
+    if args.receiver_words != "serial":
+        ap.error("--mixed-links holds 3..31 links: --receiver-words draws the words of one link count beyond 31 (rl.evaluate --links)")
     if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
         ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
                  "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
@@ -185,7 +187,7 @@ def main(argv=None):
     env = evaluation_env(ap, args)
     agent = Agent(env.n_Veh, env.n_RB, env.n_Neighbor, cfg.Num_Feedback, env, cfg, seed=args.seed, device_replay=False,
                   trajectory_walk=args.trajectory_walk, trajectory_streams=args.trajectory_streams,
-                  receiver_streams=args.receiver_streams)
+                  receiver_streams=args.receiver_streams, receiver_words=args.receiver_words)
     evaluate = agent.evaluate_training_sweep if args.sweep else agent.evaluate_training_diff_trials
     out = evaluate(args.episodes, args.test_steps, args.opt, args.epsilon, args.trials, model_dir=args.save_dir,
                    num_train_steps=args.train_steps, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts,

@@ -9,7 +9,7 @@
                               [--sim-backend device --sim-streams device --eval-backend device
                                [--trajectory-walk wide [--trajectory-streams split]]]
     python -m v2xgnn.rl.run   --links 100 --save-dir runs/b --opt --opt-backend local \\
-                              --sim-backend device --sim-streams device --eval-backend device [--receiver-streams split]
+                              --sim-backend device --sim-streams device --eval-backend device [--receiver-streams split [--receiver-words jump]]
 
 A shared-weight network trained on several link counts at once (rl.train --mixed-links ... --save-dir D) is evaluated per link
 count, on the training sizes or on others, --envs parallel episodes per size (rl/mixed.py MixedAgent.test_run):
@@ -50,7 +50,7 @@ RECEIVER_FORM_ABOVE = 31                                 # the packed observatio
 
 def add_sim_arguments(ap):
     """--sim-backend / --sim-streams / --sim-reset / --eval-backend / --trajectory-walk / --trajectory-streams /
-    --receiver-streams of the two evaluation drivers"""
+    --receiver-streams / --receiver-words of the two evaluation drivers"""
     ap.add_argument("--sim-backend", choices=["host", "device"], default="host",
                     help="where the simulator's channel update, observation and rates run: the single host simulator (the "
                          "default) or ONE batched simulator on the GPU (rl/device_sim.py)")
@@ -72,6 +72,10 @@ def add_sim_arguments(ap):
                     help="with --eval-backend device beyond %d links (the episode then runs in receiver form and walks wide): its "
                          "stream phase -- 'chain' (the default) or 'split' (three launches on a second workspace; the same bits)"
                          % RECEIVER_FORM_ABOVE)
+    ap.add_argument("--receiver-words", choices=["serial", "jump"], default="serial",
+                    help="with --receiver-streams split: how the raw words are drawn -- 'serial' (the default: one workgroup per "
+                         "simulator) or 'jump' (the words beyond a prefix in chunks entered by jump-ahead polynomials of MT19937, "
+                         "spread over the chip; the same bits)")
 
 
 def check_receiver_arguments(ap, args):
@@ -83,6 +87,9 @@ def check_receiver_arguments(ap, args):
         ap.error("--receiver-streams %s needs --eval-backend device and more than %d links (the receiver form); at %d links the "
                  "option is --trajectory-walk wide --trajectory-streams %s"
                  % (args.receiver_streams, RECEIVER_FORM_ABOVE, args.links, args.receiver_streams))
+    if args.receiver_words != "serial" and args.receiver_streams != "split":
+        ap.error("--receiver-words %s needs --receiver-streams split (it draws the split stream phase's words in chunks)"
+                 % args.receiver_words)
     if wide and args.eval_backend == "device" and args.trajectory_streams != "chain":
         ap.error("--trajectory-streams %s holds 3..%d links: at %d links the episode runs in receiver form, use "
                  "--receiver-streams %s" % (args.trajectory_streams, RECEIVER_FORM_ABOVE, args.links, args.trajectory_streams))
@@ -209,6 +216,8 @@ def parse_args(argv=None):
         ap.error("--mixed-links has no ranks: --opt-rank ranks the actions of one link count (rl.run --links)")
     if args.receiver_streams != "chain":
         ap.error("--mixed-links holds 3..31 links: --receiver-streams is the stream phase of one link count beyond 31 (rl.run --links)")
+    if args.receiver_words != "serial":
+        ap.error("--mixed-links holds 3..31 links: --receiver-words draws the words of one link count beyond 31 (rl.run --links)")
     if args.trajectory_walk != "serial" or args.trajectory_streams != "chain":
         ap.error("--mixed-links walks serially: the wide and split walks (--trajectory-walk / --trajectory-streams) hold one "
                  "link count (--mixed-trajectory-walk wide spreads the steps of all link counts over the chip)")
@@ -285,7 +294,8 @@ def main(argv=None):
     cfg.set_test_values(args.test_episodes, args.test_steps, args.opt, 1, 0.1)
     env = evaluation_env(ap, args)
     agent = load_trained_model(env, cfg, args.save_dir, seed=args.seed, trajectory_walk=args.trajectory_walk,
-                               trajectory_streams=args.trajectory_streams, receiver_streams=args.receiver_streams)
+                               trajectory_streams=args.trajectory_streams, receiver_streams=args.receiver_streams,
+                               receiver_words=args.receiver_words)
     res = run_test(cfg, agent, opt_backend=args.opt_backend, opt_restarts=args.opt_restarts, opt_rank=args.opt_rank,
                    eval_backend=args.eval_backend, rank_backend=args.opt_rank_backend, rank_max_nodes=args.opt_rank_max_nodes)
     summary = {"links": args.links, "test_episodes": args.test_episodes, "test_steps": args.test_steps,

@@ -127,6 +127,10 @@ def build_parser():
                     help="with --replay receivers --rollout trajectory: the stream phase of the resident rollout of 3..128 links -- "
                          "'chain' (the default: one launch draws the streams of all steps) or 'split' (raw words, the offset walk "
                          "for up to 128 vehicles and the conversion in three launches; the same bits)")
+    ap.add_argument("--receiver-words", choices=["serial", "jump"], default="serial",
+                    help="with --receiver-streams split: how the raw words are drawn -- 'serial' (the default: one workgroup per "
+                         "simulator) or 'jump' (the words beyond a prefix in chunks entered by jump-ahead polynomials of MT19937, "
+                         "spread over the chip; the same bits; DESIGN.md section 6 says at which sizes it pays)")
     ap.add_argument("--replay", choices=["auto", "receivers"], default="auto",
                     help="the replay memory: 'auto' (the default: in HBM up to 31 links, the reference's host memory beyond) or "
                          "'receivers' (rl/replay.py ReceiverReplay: in HBM for 3..128 links, the adjacency stored as the links' "
@@ -236,6 +240,9 @@ def parse_args(argv=None):
     if args.receiver_streams != "chain" and (args.replay != "receivers" or args.rollout != "trajectory"):
         ap.error("--receiver-streams %s needs --replay receivers --rollout trajectory (it is a form of the stream phase of the "
                  "resident rollout of 3..128 links)" % args.receiver_streams)
+    if args.receiver_words != "serial" and args.receiver_streams != "split":
+        ap.error("--receiver-words %s needs --receiver-streams split (it draws the split stream phase's words in chunks)"
+                 % args.receiver_words)
     if args.mixed_links is not None:
         # the single-size options hold one link count and stay refused; the device simulators and the resident rollout of ALL
         # link counts are asked for by --mixed-sim-backend / --mixed-sim-streams / --mixed-rollout
@@ -335,7 +342,8 @@ def main(argv=None):
             env, cfg, save_dir=args.save_dir if rank == 0 else None, verbose=rank == 0,
             device=local, seed=args.seed, use_graph=args.use_graph, data_parallel=world > 1 or force_dp,
             rollouts=args.rollouts, rollout_backend=args.rollout, trajectory_walk=args.trajectory_walk,
-            trajectory_streams=args.trajectory_streams, receiver_streams=args.receiver_streams, device_replay=args.replay)
+            trajectory_streams=args.trajectory_streams, receiver_streams=args.receiver_streams, receiver_words=args.receiver_words,
+            device_replay=args.replay)
     dt = time.perf_counter() - t0
     if rank == 0:
         n_fit = args.episodes * args.train_steps

@@ -1143,6 +1143,53 @@ int  v2x_eval_sweep_recv(const struct v2x_eval_sweep_recv* s, void* ws, int64_t 
 int  v2x_eval_sweep_recv_split(const struct v2x_eval_sweep_recv* s, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
                                void* stream);
 
+/* ---- jump-ahead MT19937: the words of the split stream phase drawn in chunks ---------------------------------------------
+ * MT19937 is linear over GF(2).  Let w[0..623] be a key array and w[i + 624] = twist(w[i], w[i + 1], w[i + 397]) -- the raw word
+ * stream k_traj_words_recv writes.  Let phi be the characteristic polynomial of that recurrence (degree 19937), and for J >= 0
+ * g = x^J mod phi with coefficients g_0 .. g_19936.  Then for every m >= 1, on all 32 bits,
+ *     w[J + m] = XOR over { i : g_i = 1 } of w[i + m]
+ * (m = 0 holds on bit 31 only: the low 31 bits of w[0] are not part of the generator's state).  So the 624 words from stream
+ * index c on are   w[c + k] = XOR_i g_i w[1 + i + k],  k = 0..623,  g = x^(c - 1) mod phi:   they need the prefix w[1 .. 20560]
+ * and a polynomial that depends on c alone, not on the seed or the simulator.
+ * v2x_mt_jump_polys [host, no GPU call]: out[p] = the coefficients of x^(first - 1 + p stride) mod phi, p = 0 .. count - 1,
+ * coefficient i in bit i & 31 of word i >> 5 (the 31 unused top bits of word 623 are zero).  phi comes from Berlekamp-Massey on
+ * the library's own word stream (once per process); the first power by square-and-reduce, each further one by a product with
+ * x^stride mod phi.  V2X_EINVAL (text in v2x_last_error(NULL)): first < 20561, stride < 624, count < 1, a null out.
+ *
+ * v2x_rollout_steps_recv_jump / v2x_eval_steps_recv_jump / v2x_eval_sweep_recv_jump: the _split forms with k_traj_words_recv's
+ * work cut into chunks.  Chunk 0 is [0, first); chunk p = 1 .. count is [c_p, c_p+1) with c_p = first + (p - 1) stride and the
+ * last one running to nbw = 624 NB.  Three launches stand in k_traj_words_recv's place:
+ *   k_traj_words_recv   grid (E): unchanged, with its loop bound at `first` instead of nbw (entry 0 copied as before);
+ *   k_traj_jump_seeds   grid (8, count, E), 256 threads: slice s of polynomial p against the prefix of state e -- the prefix words
+ *                       the slice needs staged in LDS, three k per thread, the coefficient bits walked on the scalar side --
+ *                       into scratch[e][p][s][624];
+ *   k_traj_jump_chunks  grid (count, E), 256 threads: the XOR of the eight slices is words[c_p .. c_p + 624), stored and loaded
+ *                       into the ring at the slots k_traj_words_recv uses for those indices, then the same round loop (one
+ *                       function) up to the chunk's end.
+ * Every word of the array has one writer, and the array is k_traj_words_recv's bit for bit, so k_traj_walk_recv, k_traj_uniforms
+ * and everything after them run unchanged: every byte the calls leave is the _split form's.
+ * jump->polys [dev]: the table of v2x_mt_jump_polys(first, stride, count); jump->scratch [dev]: v2x_mt_jump_scratch_bytes(E,
+ * count) = A(4 E count 8 624) bytes (0 for count = 0; negative V2X_EINVAL for E < 1 or count < 0), contents undefined afterwards.
+ * count = 0, or first >= nbw, is legal and runs the _split form's launches.  Checks, after every check of the _split form and
+ * before the first launch (V2X_EINVAL, text in v2x_last_error(NULL), nothing written): a null jump; first < 20561; stride < 624;
+ * count < 0; with chunks to run, polys or scratch null or not 256-byte aligned, first + (count - 1) stride >= nbw (an empty last
+ * chunk), scratch_bytes below the need.                                                                                      */
+typedef struct v2x_mt_jump {
+  int64_t first, stride;            /* chunk p >= 1 begins at first + (p - 1) stride */
+  int32_t count, pad_;              /* polynomials = chunks after the prefix */
+  const uint32_t* polys;            /* [dev] [count][624] */
+  void* scratch;                    /* [dev] v2x_mt_jump_scratch_bytes(E, count) */
+  int64_t scratch_bytes;
+} v2x_mt_jump;
+int  v2x_mt_jump_polys(int64_t first, int64_t stride, int32_t count, uint32_t* out /* [host] [count][624] */);
+int64_t v2x_mt_jump_scratch_bytes(int32_t E, int32_t count);
+int  v2x_rollout_steps_recv_jump(const v2x_rollout_recv* r, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                                 const v2x_mt_jump* jump, void* stream);
+int  v2x_eval_steps_recv_jump(const v2x_eval_recv* r, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                              const v2x_mt_jump* jump, void* stream);
+int  v2x_eval_sweep_recv_jump(const struct v2x_eval_sweep_recv* s, void* ws, int64_t ws_bytes, void* split_ws, int64_t split_ws_bytes,
+                              const v2x_mt_jump* jump, void* stream);
+
 /* ---- measurement ------------------------------------------------------------------------ */
 /* When enabled, every kernel launch of this model is bracketed by HIP events on its stream
  * (eager, no graph); v2x_profile_read returns per-kernel-name call counts and total ms.    */
