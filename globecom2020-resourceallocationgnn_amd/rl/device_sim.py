@@ -986,16 +986,26 @@ class DeviceChannels(object):
                 io['xe'], io['col'] = self._t['xe'].view(E * n, XE_WIDTH), self._t['col'].view(-1)
             else:
                 offs, size = trajectory_workspace_layout(E, n, rb, T)
-                need = self._lib.v2x_rollout_steps_workspace_bytes(E, n, rb, T)
-                if need != size:
-                    raise ValueError("rollout_steps: the library sizes the trajectory workspace of E = %d, n = %d, rb = %d, T = %d at "
-                                     "%d bytes, the documented layout at %d" % (E, n, rb, T, need, size))
-                ws = io['workspace'] = t.zeros(size, dtype=t.uint8, device=self.device)
+                ws = io['workspace'] = self._sized_workspace("trajectory workspace", T, self._lib.v2x_rollout_steps_workspace_bytes(E, n, rb, T),
+                                                             size, who="rollout_steps")
                 io['offsets'] = offs
                 # entries 0..T-1 of the trajectory, where k_sim_trajectory writes them
                 io['xe'] = ws[offs['traj_xe']:offs['traj_xe'] + 4 * K * n * XE_WIDTH].view(t.float32).view(K * n, XE_WIDTH)
                 io['col'] = ws[offs['traj_col']:offs['traj_col'] + 4 * K * n * (n - 2)].view(t.int32)
         return io
+
+    def _sized_workspace(self, name, T, need, size, who=None, n_lanes=None, aligned=False, least=0):
+        """a zeroed device workspace `name` for blocks of T, of the `size` bytes its documented layout gives (`least` at least):
+        ValueError unless the library's size `need` is the same; aligned: RuntimeError unless the allocator returned it 256-byte
+        aligned.  who: the call both refusals name"""
+        if need != size:
+            dims = "E = %d, n = %d, rb = %d, T = %d" % (self.E, self.n, self.rb, T) + ("" if n_lanes is None else ", n_lanes = %d" % n_lanes)
+            raise ValueError("%sthe library sizes the %s of %s at %d bytes, the documented layout at %d"
+                             % (who + ": " if who else "", name, dims, need, size))
+        ws = self.torch.zeros(max(size, least), dtype=self.torch.uint8, device=self.device)
+        if aligned and ws.data_ptr() % 256:
+            raise RuntimeError("%s: the allocator returned a %s that is not 256-byte aligned" % (who, name))
+        return ws
 
     def _wide_workspace(self, T):
         """the workspace of the wide walk for blocks of T, made at the first wide call of that T and kept in _rollout_io(T) next
@@ -1004,12 +1014,8 @@ class DeviceChannels(object):
         ws = io.get('wide_workspace')
         if ws is None:
             E, n, rb = self.E, self.n, self.rb
-            _, size = wide_workspace_layout(E, n, rb, T)
-            need = self._lib.v2x_traj_wide_workspace_bytes(E, n, rb, T)
-            if need != size:
-                raise ValueError("the library sizes the wide-walk workspace of E = %d, n = %d, rb = %d, T = %d at %d bytes, the "
-                                 "documented layout at %d" % (E, n, rb, T, need, size))
-            ws = io['wide_workspace'] = self.torch.zeros(max(size, 256), dtype=self.torch.uint8, device=self.device)
+            ws = io['wide_workspace'] = self._sized_workspace("wide-walk workspace", T, self._lib.v2x_traj_wide_workspace_bytes(E, n, rb, T),
+                                                              wide_workspace_layout(E, n, rb, T)[1], least=256)
         return ws
 
     def _split_workspace(self, T):
@@ -1020,12 +1026,9 @@ class DeviceChannels(object):
         E, n, rb, n_lanes = self.E, self.n, self.rb, self._grid[0].shape[1]
         ws = io.get('split_workspace')
         if ws is None or io.get('split_lanes') != n_lanes:
-            _, size = split_workspace_layout(E, n, rb, T, n_lanes)
-            need = self._lib.v2x_traj_split_workspace_bytes(E, n, rb, T, n_lanes)
-            if need != size:
-                raise ValueError("the library sizes the split-stream workspace of E = %d, n = %d, rb = %d, T = %d, n_lanes = %d at %d "
-                                 "bytes, the documented layout at %d" % (E, n, rb, T, n_lanes, need, size))
-            ws = io['split_workspace'] = self.torch.zeros(size, dtype=self.torch.uint8, device=self.device)
+            ws = io['split_workspace'] = self._sized_workspace(
+                "split-stream workspace", T, self._lib.v2x_traj_split_workspace_bytes(E, n, rb, T, n_lanes),
+                split_workspace_layout(E, n, rb, T, n_lanes)[1], n_lanes=n_lanes)
             io['split_lanes'] = n_lanes
         return ws
 
@@ -1089,28 +1092,50 @@ class DeviceChannels(object):
 
     def _upload_policy(self, io, random_actions, explore):
         """the host's draws -> io['policy_dev'] through the next of the four page-locked copies (its event guards the reuse)"""
-        t, i = self.torch, io['next']
-        io['next'] = (i + 1) % 4
-        if io['policy_ev'][i] is not None:
-            io['policy_ev'][i].synchronize()
-        pin, nb = io['policy_pin'][i].numpy(), 4 * random_actions.size
+        pin, nb = self._ring_next(io, 'policy_', 'next'), 4 * random_actions.size
         pin[:nb].view(np.int32)[:] = random_actions.reshape(-1)
         pin[nb:nb + explore.size] = explore.reshape(-1)
-        io['policy_dev'].copy_(io['policy_pin'][i], non_blocking=True)
-        self.traffic['bytes_up'] += io['policy_dev'].numel()
-        if io['policy_ev'][i] is None:
-            io['policy_ev'][i] = t.cuda.Event()
-        io['policy_ev'][i].record(t.cuda.current_stream(self.device))
+        self._ring_send(io, 'policy_', 'next')
 
-    def _download_result(self, io, T):
-        """io['result_dev'] -> a page-locked copy (a returned one, or a new one); -> the RolloutResult, its download in flight"""
-        t, free = self.torch, io['free']
-        pinned = free.pop() if free else t.zeros(io['result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
-        pinned.copy_(io['result_dev'], non_blocking=True)
-        self.traffic['bytes_down'] += pinned.numel()
+    def _ring_next(self, io, ring, next_key):
+        """-> the numpy view of the next of the four page-locked copies io[ring + 'pin'], once the upload that last read it is
+        through (its event guards the reuse); the caller fills it and hands it to _ring_send"""
+        i = io[next_key]
+        if io[ring + 'ev'][i] is not None:
+            io[ring + 'ev'][i].synchronize()
+        return io[ring + 'pin'][i].numpy()
+
+    def _ring_send(self, io, ring, next_key, size=None):
+        """the copy _ring_next gave out -> io[ring + 'dev'] (their first `size` elements; None: all), counted in traffic"""
+        t, i = self.torch, io[next_key]
+        io[next_key] = (i + 1) % 4
+        pin, dev, ev = io[ring + 'pin'][i], io[ring + 'dev'], io[ring + 'ev']
+        if size is None:
+            dev.copy_(pin, non_blocking=True)
+        else:
+            dev[:size].copy_(pin[:size], non_blocking=True)
+        self.traffic['bytes_up'] += (dev.numel() if size is None else size) * dev.element_size()
+        if ev[i] is None:
+            ev[i] = t.cuda.Event()
+        ev[i].record(t.cuda.current_stream(self.device))
+
+    def _download(self, dev, free, size=None):
+        """the block `dev` (its first `size` bytes; None: all of it) -> a page-locked copy (a returned one of `free`, or a new
+        one), counted in traffic; -> (free, event, copy): what every result class takes first, the download in flight"""
+        t = self.torch
+        pinned = free.pop() if free else t.zeros(dev.numel(), dtype=t.uint8, pin_memory=self._pin)
+        if size is None:
+            pinned.copy_(dev, non_blocking=True)
+        else:
+            pinned[:size].copy_(dev[:size], non_blocking=True)
+        self.traffic['bytes_down'] += dev.numel() if size is None else size
         ev = t.cuda.Event()
         ev.record(t.cuda.current_stream(self.device))
-        return RolloutResult(free, ev, pinned, self.E, T)
+        return free, ev, pinned
+
+    def _download_result(self, io, T, cls=RolloutResult):
+        """io['result_dev'] -> the RolloutResult (cls), its download in flight"""
+        return cls(*self._download(io['result_dev'], io['free']), self.E, T)
 
     def _rollout(self, who, T, explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight, engine, row_ptr, power,
                  walk='serial', stream_phase='chain'):
@@ -1272,6 +1297,14 @@ class DeviceChannels(object):
                 raise ValueError("%s: replay storage %r of shape [slots] + %s expected" % (who, k, list(tail)))
             if t.shape[0] < (capacity if head + K > capacity else head + K):      # (a block that wraps touches the last slot)
                 raise ValueError("%s: replay storage %r has %d slots, the block at %d needs more" % (who, k, t.shape[0], head))
+        if own is not None:
+            own = np.asarray(own, np.int32)                  # (the rollout casts what it is given; the evaluation refuses floats)
+        return T, ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32), self._own_counts(who, own, "")
+
+    def _own_counts(self, who, own, word):
+        """own, the states' own-receiver counts of a receiver-form call -- None: those of the receivers this object last sent up
+        from the host -> [E] int32; ValueError unless they are E integers in [0, n] (word: how the refusal qualifies them)"""
+        E, n = self.E, self.n
         if own is None:
             if self._own is None:
                 raise ValueError("%s: the receivers went up as a device tensor: pass own, the states' own-receiver counts [E] (the "
@@ -1279,10 +1312,10 @@ class DeviceChannels(object):
             own, bad = self._own
             if bad.any():
                 raise ValueError("%s: state(s) %s hold a receiver outside [0, %d)" % (who, np.nonzero(bad)[0].tolist(), n))
-        own = np.asarray(own, np.int32).reshape(-1)
-        if own.shape != (E,) or (own < 0).any() or (own > n).any():
-            raise ValueError("%s: own: %d own-receiver counts in [0, %d] expected" % (who, E, n))
-        return T, ex.astype(np.uint8), np.ascontiguousarray(ra, np.int32), own
+        own = np.asarray(own)
+        if own.dtype.kind not in 'iu' or own.reshape(-1).shape != (E,) or (own < 0).any() or (own > n).any():
+            raise ValueError("%s: own: %d %sown-receiver counts in [0, %d] expected" % (who, E, word, n))
+        return own.reshape(-1).astype(np.int32)
 
     def _recv_io(self, T):
         """the buffers of rollout_steps_recv() for blocks of T, made once per T: the policy ring and the result block of
@@ -1294,13 +1327,8 @@ class DeviceChannels(object):
             K = T * E
             nb = self.rollout_steps_policy_bytes(T)
             offs, size = recv_workspace_layout(E, n, rb, T)
-            need = self._lib.v2x_rollout_recv_workspace_bytes(E, n, rb, T)
-            if need != size:
-                raise ValueError("rollout_steps_recv: the library sizes the workspace of E = %d, n = %d, rb = %d, T = %d at %d bytes, "
-                                 "the documented layout at %d" % (E, n, rb, T, need, size))
-            ws = t.zeros(size, dtype=t.uint8, device=self.device)
-            if ws.data_ptr() % 256:
-                raise RuntimeError("rollout_steps_recv: the allocator returned a workspace that is not 256-byte aligned")
+            ws = self._sized_workspace("workspace", T, self._lib.v2x_rollout_recv_workspace_bytes(E, n, rb, T), size,
+                                       who="rollout_steps_recv", aligned=True)
             io = self._roll[('recv', T)] = {
                 'policy_dev': t.zeros(nb, dtype=t.uint8, device=self.device),
                 'policy_pin': [t.zeros(nb, dtype=t.uint8, pin_memory=self._pin) for _ in range(4)], 'policy_ev': [None] * 4, 'next': 0,
@@ -1322,14 +1350,9 @@ class DeviceChannels(object):
         E, n, rb, n_lanes = self.E, self.n, self.rb, self._grid[0].shape[1]
         ws = io.get('split_workspace')
         if ws is None or io.get('split_lanes') != n_lanes:
-            _, size = split_workspace_layout(E, n, rb, T, n_lanes)
-            need = self._lib.v2x_rollout_recv_split_workspace_bytes(E, n, rb, T, n_lanes)
-            if need != size:
-                raise ValueError("rollout_steps_recv: the library sizes the split-stream workspace of E = %d, n = %d, rb = %d, T = %d, "
-                                 "n_lanes = %d at %d bytes, the documented layout at %d" % (E, n, rb, T, n_lanes, need, size))
-            ws = self.torch.zeros(size, dtype=self.torch.uint8, device=self.device)
-            if ws.data_ptr() % 256:
-                raise RuntimeError("rollout_steps_recv: the allocator returned a split-stream workspace that is not 256-byte aligned")
+            ws = self._sized_workspace("split-stream workspace", T, self._lib.v2x_rollout_recv_split_workspace_bytes(E, n, rb, T, n_lanes),
+                                       split_workspace_layout(E, n, rb, T, n_lanes)[1], who="rollout_steps_recv", n_lanes=n_lanes,
+                                       aligned=True)
             io['split_workspace'], io['split_lanes'] = ws, n_lanes
         return ws
 
@@ -1367,16 +1390,28 @@ class DeviceChannels(object):
             io['jump'], io['jump_lanes'] = jump, n_lanes
         return jump
 
-    def _recv_split_call(self, split, jump, r, ws, T, stream_words):
-        """the library call of a receiver-form struct r with the split stream phase: `split`, or with stream_words='jump' its
-        _jump form on the cached table of _recv_jump_table(T); counted in stream_words_calls"""
-        sws = self._recv_split_workspace(T)
-        if stream_words == 'jump':
-            check(self._lib, jump(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(), C.byref(self._recv_jump_table(T)),
-                                  self._stream()))
+    def _recv_call(self, family, r, io, T, stream_phase, stream_words):
+        """the one library call of the receiver-form struct r on io's workspace: v2x_<family>_recv ('rollout_steps', 'eval_steps'
+        or 'eval_sweep'), with stream_phase='split' its _split form on _recv_split_workspace(T) or, stream_words='jump', its _jump
+        form on the cached table of _recv_jump_table(T) as well; counted in walk_calls (a wide walk), stream_phase_calls and, the
+        split ones, stream_words_calls.  Afterwards the resident observation and trajectory T are in receiver form."""
+        lib, ws, name = self._lib, io['workspace'], 'v2x_%s_recv' % family
+        self._keep_actions = self._t['actions']
+        if stream_phase != 'split':
+            check(lib, getattr(lib, name)(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
         else:
-            check(self._lib, split(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(), self._stream()))
-        self.stream_words_calls[stream_words] += 1
+            sws = self._recv_split_workspace(T)
+            if stream_words == 'jump':
+                check(lib, getattr(lib, name + '_jump')(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(),
+                                                        C.byref(self._recv_jump_table(T)), self._stream()))
+            else:
+                check(lib, getattr(lib, name + '_split')(C.byref(r), ws.data_ptr(), ws.numel(), sws.data_ptr(), sws.numel(), self._stream()))
+            self.stream_words_calls[stream_words] += 1
+        self.walk_calls['wide'] += 1
+        self.stream_phase_calls[stream_phase] += 1
+        self._traj_form[T] = 'recv'
+        self._obs_ready = False
+        self._recv_ready = True
 
     def rollout_steps_recv_buffers(self, T):
         """the device buffers of rollout_steps_recv() for blocks of T: workspace (carved by recv_workspace_layout: offsets),
@@ -1391,16 +1426,8 @@ class DeviceChannels(object):
             return None, K * n * (n - 2), n * (n - 2)
         eb = np.zeros(K + 1, np.int64)
         np.cumsum(n * (n - 2) + np.tile(own.astype(np.int64), T), out=eb[1:])
-        i = io['eb_next']
-        io['eb_next'] = (i + 1) % 4
-        if io['eb_ev'][i] is not None:
-            io['eb_ev'][i].synchronize()
-        io['eb_pin'][i].numpy()[:] = eb
-        io['eb_dev'].copy_(io['eb_pin'][i], non_blocking=True)
-        self.traffic['bytes_up'] += 4 * (K + 1)
-        if io['eb_ev'][i] is None:
-            io['eb_ev'][i] = self.torch.cuda.Event()
-        io['eb_ev'][i].record(self.torch.cuda.current_stream(self.device))
+        self._ring_next(io, 'eb_', 'eb_next')[:] = eb
+        self._ring_send(io, 'eb_', 'eb_next')
         return io['eb_dev'].data_ptr(), int(eb[-1]), n * (n - 1)
 
     def rollout_steps_recv_struct(self, T, storage, head, capacity, v2v_weight, v2i_weight, engine=None, edge_base=None,
@@ -1412,8 +1439,7 @@ class DeviceChannels(object):
         self._send_grid()
         t, K, n = self._t, io['graphs'], self.n
         base, res, ws = io['policy_dev'].data_ptr(), io['result_dev'].data_ptr(), io['workspace'].data_ptr()
-        step = self._sim_step(t['actions'].data_ptr(), power)
-        step.mask = step.col = step.regular = None           # (not read: the receiver form has recv / flags)
+        step = self._recv_step(power)
         r = RolloutRecv(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * n, random_actions=base, actions=t['actions'].data_ptr(),
                         step=step, recv=t['recv'].data_ptr(), flags=t['flags'].data_ptr(), w_v2v=float(v2v_weight),
                         w_v2i=float(v2i_weight), T=T, pad_=0, edge_base=edge_base, rep_xe=storage['xe'].data_ptr(),
@@ -1421,10 +1447,21 @@ class DeviceChannels(object):
                         rep_action=storage['action'].data_ptr(), rep_reward=storage['reward'].data_ptr(), head=int(head),
                         capacity=int(capacity), result_reward=res, result_flags=res + 8 * K,
                         **{k: ws + io['offsets'][k] for k in RECV_SECTIONS})
+        return self._recv_scored(r, io, engine, edge_base, n_edges, max_edges)
+
+    def _recv_step(self, power):
+        """the v2x_sim_step of a receiver-form struct: _sim_step with the action buffer in it and the packed form's fields empty"""
+        step = self._sim_step(self._t['actions'].data_ptr(), power)
+        step.mask = step.col = step.regular = None           # (not read: the receiver form has recv / flags)
+        return step
+
+    def _recv_scored(self, r, io, engine, edge_base, n_edges, max_edges):
+        """-> the receiver-form struct r, with `engine` (when given) and the cached batch of io's T E graphs attached: n_edges /
+        max_edges as edge_base implies them, or those of regular graphs without one"""
         if engine is not None:
             from ..engine import _batch_struct
             if edge_base is None:
-                n_edges, max_edges = K * n * (n - 2), n * (n - 2)
+                n_edges, max_edges = io['graphs'] * self.n * (self.n - 2), self.n * (self.n - 2)
             r.model = engine._h
             r.batch = _batch_struct(self._recv_batch(io, n_edges, max_edges))
         return r
@@ -1453,24 +1490,8 @@ class DeviceChannels(object):
         self._upload_policy(io, ra, ex)
         eb, n_edges, max_edges = self._edge_base(io, own, T) if engine is not None else (None, None, None)
         r = self.rollout_steps_recv_struct(T, storage, head, capacity, v2v_weight, v2i_weight, engine, eb, n_edges, max_edges, power)
-        self._keep_actions = self._t['actions']
-        ws = io['workspace']
-        if stream_phase == 'split':
-            self._recv_split_call(self._lib.v2x_rollout_steps_recv_split, self._lib.v2x_rollout_steps_recv_jump, r, ws, T, stream_words)
-        else:
-            check(self._lib, self._lib.v2x_rollout_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
-        self.walk_calls['wide'] += 1
-        self.stream_phase_calls[stream_phase] += 1
-        self._traj_form[T] = 'recv'
-        self._obs_ready = False
-        self._recv_ready = True
-        t, free = self.torch, io['free']
-        pinned = free.pop() if free else t.zeros(io['result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
-        pinned.copy_(io['result_dev'], non_blocking=True)
-        self.traffic['bytes_down'] += pinned.numel()
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return RecvRolloutResult(free, ev, pinned, self.E, T)
+        self._recv_call('rollout_steps', r, io, T, stream_phase, stream_words)
+        return self._download_result(io, T, RecvRolloutResult)
 
     # ------------------------------------------------------------------ an evaluation episode on the resident state
     def eval_steps_policy_bytes(self, T, baseline=True):
@@ -1535,33 +1556,18 @@ class DeviceChannels(object):
     def _eval_upload(self, io, T, ex, ra, ba):
         """the host's draws of an evaluation block -> io['eval_policy_dev'] through the next of the four page-locked copies (its
         event guards the reuse)"""
-        t, i = self.torch, io['eval_next']
-        io['eval_next'] = (i + 1) % 4
-        if io['eval_policy_ev'][i] is not None:
-            io['eval_policy_ev'][i].synchronize()
-        pin, K, n = io['eval_policy_pin'][i].numpy(), T * self.E, self.n
+        pin, K, n = self._ring_next(io, 'eval_policy_', 'eval_next'), T * self.E, self.n
         nb = self.eval_steps_policy_bytes(T, ba is not None)
         pin[:4 * K * n].view(np.int32)[:] = ra.reshape(-1)
         pin[4 * K * n:4 * K * n + K] = ex.reshape(-1)
         if ba is not None:
             pin[nb - 4 * K * n:nb].view(np.int32)[:] = ba.reshape(-1)
-        io['eval_policy_dev'][:nb].copy_(io['eval_policy_pin'][i][:nb], non_blocking=True)
-        self.traffic['bytes_up'] += nb
-        if io['eval_policy_ev'][i] is None:
-            io['eval_policy_ev'][i] = t.cuda.Event()
-        io['eval_policy_ev'][i].record(t.cuda.current_stream(self.device))
+        self._ring_send(io, 'eval_policy_', 'eval_next', nb)
 
     def _eval_download(self, io, T, S, cls=EvalResult):
-        """the result block of S schemes in io['eval_result_dev'] -> a page-locked copy (a returned one, or a new one); -> the
-        EvalResult (cls), its download in flight"""
-        t = self.torch
-        size, free = self.eval_steps_result_bytes(T, S), io['eval_free']
-        pinned = free.pop() if free else t.zeros(io['eval_result_dev'].numel(), dtype=t.uint8, pin_memory=self._pin)
-        pinned[:size].copy_(io['eval_result_dev'][:size], non_blocking=True)
-        self.traffic['bytes_down'] += size
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return cls(free, ev, pinned, self.E, self.n, self.rb, T, S)
+        """the result block of S schemes in io['eval_result_dev'] (a block of two schemes: only the S there are come down) ->
+        the EvalResult (cls), its download in flight"""
+        return cls(*self._download(io['eval_result_dev'], io['eval_free'], self.eval_steps_result_bytes(T, S)), self.E, self.n, self.rb, T, S)
 
     def _sweep_io(self, T, S):
         """-> (_eval_io(T), the result block of a sweep of S schemes (eval_sweep_mixed): its device block 'dev' and the
@@ -1575,14 +1581,7 @@ class DeviceChannels(object):
 
     def _sweep_download(self, sw, T, S, cls=EvalResult):
         """_eval_download for the result block of a sweep"""
-        t = self.torch
-        size, free = sw['dev'].numel(), sw['free']
-        pinned = free.pop() if free else t.zeros(size, dtype=t.uint8, pin_memory=self._pin)
-        pinned.copy_(sw['dev'], non_blocking=True)
-        self.traffic['bytes_down'] += size
-        ev = t.cuda.Event()
-        ev.record(t.cuda.current_stream(self.device))
-        return cls(free, ev, pinned, self.E, self.n, self.rb, T, S)
+        return cls(*self._download(sw['dev'], sw['free']), self.E, self.n, self.rb, T, S)
 
     def eval_steps_struct(self, T, v2v_weight, v2i_weight, engine=None, row_ptr=None, power=None, baseline=True):
         """the v2x_eval of the resident tensors and the buffers of _eval_io(T) (what eval_steps() passes to the library)"""
@@ -1642,17 +1641,7 @@ class DeviceChannels(object):
         T, ex, ra, ba = self._check_eval_arrays(who, explore, policy_random, baseline_actions)
         if T * E * n * (n - 1) > 2 ** 31 - 1:
             raise ValueError("%s: T E = %d graphs of %d links exceed the 32-bit sizes of a batch" % (who, T * E, n))
-        if own is None:
-            if self._own is None:
-                raise ValueError("%s: the receivers went up as a device tensor: pass own, the states' own-receiver counts [E] (the "
-                                 "host decides whether the batch needs edge_base)" % who)
-            own, bad = self._own
-            if bad.any():
-                raise ValueError("%s: state(s) %s hold a receiver outside [0, %d)" % (who, np.nonzero(bad)[0].tolist(), n))
-        own = np.asarray(own)
-        if own.dtype.kind not in 'iu' or own.reshape(-1).shape != (E,) or (own < 0).any() or (own > n).any():
-            raise ValueError("%s: own: %d integer own-receiver counts in [0, %d] expected" % (who, E, n))
-        return T, ex, ra, ba, own.reshape(-1).astype(np.int32)
+        return T, ex, ra, ba, self._own_counts(who, own, "integer ")
 
     def _recv_eval_io(self, T):
         """_recv_io(T) -- the ONE workspace, q, the cached batches and the edge_base ring are shared with rollout_steps_recv() --
@@ -1689,21 +1678,14 @@ class DeviceChannels(object):
         t, K, n = self._t, io['graphs'], self.n
         base, res, ws = io['eval_policy_dev'].data_ptr(), io['eval_result_dev'].data_ptr(), io['workspace'].data_ptr()
         offs, _ = eval_result_layout(self.E, n, self.rb, T, 2 if baseline else 1)
-        step = self._sim_step(t['actions'].data_ptr(), power)
-        step.mask = step.col = step.regular = None           # (not read: the receiver form has recv / flags)
+        step = self._recv_step(power)
         r = EvalRecv(model=None, q=io['q'].data_ptr(), explore=base + 4 * K * n, random_actions=base,
                      baseline_actions=base + _align(4 * K * n + K, 4) if baseline else None, actions=t['actions'].data_ptr(),
                      step=step, recv=t['recv'].data_ptr(), flags=t['flags'].data_ptr(), w_v2v=float(v2v_weight),
                      w_v2i=float(v2i_weight), T=T, pad_=0, edge_base=edge_base,
                      **{k: ws + io['offsets'][k] for k in RECV_SECTIONS},
                      **{'result_' + ('flags' if k == 'regular' else k): res + o for k, o in offs.items()})
-        if engine is not None:
-            from ..engine import _batch_struct
-            if edge_base is None:
-                n_edges, max_edges = K * n * (n - 2), n * (n - 2)
-            r.model = engine._h
-            r.batch = _batch_struct(self._recv_batch(io, n_edges, max_edges))
-        return r
+        return self._recv_scored(r, io, engine, edge_base, n_edges, max_edges)
 
     def eval_steps_recv(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, own=None, power=None,
                         stream_phase='chain', stream_words='serial'):
@@ -1725,17 +1707,7 @@ class DeviceChannels(object):
         self._eval_upload(io, T, ex, ra, ba)
         eb, n_edges, max_edges = self._edge_base(io, own, T) if engine is not None else (None, None, None)
         r = self.eval_steps_recv_struct(T, v2v_weight, v2i_weight, engine, eb, n_edges, max_edges, power, ba is not None)
-        self._keep_actions = self._t['actions']
-        ws = io['workspace']
-        if stream_phase == 'split':
-            self._recv_split_call(self._lib.v2x_eval_steps_recv_split, self._lib.v2x_eval_steps_recv_jump, r, ws, T, stream_words)
-        else:
-            check(self._lib, self._lib.v2x_eval_steps_recv(C.byref(r), ws.data_ptr(), ws.numel(), self._stream()))
-        self.walk_calls['wide'] += 1
-        self.stream_phase_calls[stream_phase] += 1
-        self._traj_form[T] = 'recv'
-        self._obs_ready = False
-        self._recv_ready = True
+        self._recv_call('eval_steps', r, io, T, stream_phase, stream_words)
         return self._eval_download(io, T, 2 if ba is not None else 1, RecvEvalResult)
 
     # ------------------------------------------------------------------ K networks on one walked episode (receiver form)
@@ -1748,23 +1720,7 @@ class DeviceChannels(object):
             checked = self.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words)
         except ValueError as err:
             raise ValueError(str(err).replace("eval_steps_recv", who))
-        if engines is None:
-            K = 1 if K is None else int(K)
-        else:
-            engines = list(engines)
-            if K is not None and int(K) != len(engines):
-                raise ValueError("%s: K = %d, but %d engines" % (who, K, len(engines)))
-            K = len(engines)
-        if not 1 <= K <= SWEEP_MAX_MODELS:
-            raise ValueError("%s: 1..%d networks, got %d" % (who, SWEEP_MAX_MODELS, K))
-        for k, engine in enumerate(engines or ()):
-            spec = None if engine is None else engine.spec
-            if spec is None or spec.variable_graphs or spec.n_nodes != self.n or spec.n_channels != self.rb:
-                raise ValueError("%s: scoring needs fixed-size engines of %d links and %d channels (engine %d)" % (who, self.n, self.rb, k))
-            if spec != engines[0].spec:
-                raise ValueError("%s: engine %d has another spec than engine 0: the networks of a sweep are checkpoints of one network"
-                                 % (who, k))
-        return checked + (K,)
+        return checked + (_check_sweep_engines(who, engines, K, self.rb, self.n),)
 
     def _recv_sweep_io(self, T, S, K):
         """-> (_recv_eval_io(T), the sweep's own buffers: the result block of S schemes 'dev' with the page-locked copies that
@@ -1826,17 +1782,7 @@ class DeviceChannels(object):
         self._eval_upload(io, T, ex, ra, ba)
         eb, n_edges, max_edges = self._edge_base(io, own, T) if engines is not None else (None, None, None)
         s = self.eval_sweep_recv_struct(T, K, v2v_weight, v2i_weight, engines, eb, n_edges, max_edges, power, ba is not None)
-        self._keep_actions = self._t['actions']
-        ws = io['workspace']
-        if stream_phase == 'split':
-            self._recv_split_call(self._lib.v2x_eval_sweep_recv_split, self._lib.v2x_eval_sweep_recv_jump, s, ws, T, stream_words)
-        else:
-            check(self._lib, self._lib.v2x_eval_sweep_recv(C.byref(s), ws.data_ptr(), ws.numel(), self._stream()))
-        self.walk_calls['wide'] += 1
-        self.stream_phase_calls[stream_phase] += 1
-        self._traj_form[T] = 'recv'
-        self._obs_ready = False
-        self._recv_ready = True
+        self._recv_call('eval_sweep', s, io, T, stream_phase, stream_words)
         return self._sweep_download(sw, T, S, RecvEvalResult)
 
     def trajectory_states(self, T):
@@ -1919,17 +1865,42 @@ def _check_mixed_pools(who, channels, per_pool):
     return channels
 
 
+def _mixed_pools_ready(who, channels):
+    """every pool of a mixed call initialised, all on one device, every observation resident"""
+    for dc in channels:
+        dc._init_device()
+        if dc.device != channels[0].device:
+            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
+        if not dc._obs_ready:
+            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+
+
+def _mixed_batch_pointers(m, channels, T, names=('xe', 'graph_off', 'row_ptr', 'col_idx', 'q')):
+    """the ragged batch of mixed_rollout_buffers(channels, T) (and its Q rows) into the fields `names` of the mixed struct m"""
+    buf = mixed_rollout_buffers(channels, T)
+    for name in names:
+        setattr(m, name, buf[name].data_ptr())
+
+
+def _mixed_traj_ws(channels, T):
+    """the v2x_traj_ws table of a mixed wide walk: every pool supplies the wide and split workspaces its own single-size calls
+    use (cached in the pool's _rollout_io(T): they outlive the call)"""
+    table = (TrajWs * len(channels))()
+    for k, dc in enumerate(channels):
+        ws, ss = dc._wide_workspace(T), dc._split_workspace(T)
+        table[k] = TrajWs(ws.data_ptr(), ws.numel(), ss.data_ptr(), ss.numel())
+    return table
+
+
 def _mixed_trajectory_call(serial, wide, m, channels, T, walk):
-    """the library call of a mixed trajectory struct m in the form `walk` names: with 'wide' every pool supplies the wide and
-    split workspaces its own single-size calls use (v2x_traj_ws per pool).  Counted per pool as _trajectory_call counts: the
-    mixed wide walk is a wide call whose stream phase is split."""
+    """the library call of a mixed trajectory struct m in the form `walk` names: serial(m, stream), or with 'wide'
+    wide(m, _mixed_traj_ws, stream).  Counted per pool as _trajectory_call counts: the mixed wide walk is a wide call whose stream
+    phase is split.  Afterwards every pool's observation is resident."""
     dc0 = channels[0]
+    for dc in channels:
+        dc._keep_actions = dc._t['actions']
     if walk == 'wide':
-        table = (TrajWs * len(channels))()
-        for k, dc in enumerate(channels):
-            ws, ss = dc._wide_workspace(T), dc._split_workspace(T)       # (cached in the pool's _rollout_io(T): they outlive the call)
-            table[k] = TrajWs(ws.data_ptr(), ws.numel(), ss.data_ptr(), ss.numel())
-        check(dc0._lib, wide(C.byref(m), table, dc0._stream()))
+        check(dc0._lib, wide(C.byref(m), _mixed_traj_ws(channels, T), dc0._stream()))
     else:
         check(dc0._lib, serial(C.byref(m), dc0._stream()))
     for dc in channels:
@@ -1937,6 +1908,21 @@ def _mixed_trajectory_call(serial, wide, m, channels, T, walk):
         dc._traj_form.pop(T, None)
         if walk == 'wide':
             dc.stream_phase_calls['split'] += 1
+        dc._obs_ready = True
+
+
+def _check_mixed_envs(who, envs, per_pool, streams_first=True):
+    """what the resident_*_mixed wrappers refuse of their lists before anything else -> envs; streams_first: the evaluation
+    wrappers ask streams='device' of every environment here, before their shape checks"""
+    envs = list(envs)
+    for name, arg in per_pool.items():
+        if len(arg) != len(envs):
+            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
+    for env in envs if streams_first else ():
+        if getattr(env, 'stream_backend', None) != 'device':
+            raise ValueError("%s needs streams='device' in every environment (mobility and the MT19937 streams advance inside the "
+                             "call)" % who)
+    return envs
 
 
 def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None,
@@ -1962,12 +1948,7 @@ def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capa
         checked.append(dc._check_rollout(who, T, explore[k], random_actions[k], storages[k], heads[k], capacities[k]))
     if engine is not None and not (engine.spec.variable_graphs and engine.spec.n_channels == channels[0].rb):
         raise ValueError("%s: scoring needs a variable_graphs engine of %d channels" % (who, channels[0].rb))
-    for dc in channels:
-        dc._init_device()
-        if dc.device != channels[0].device:
-            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
-        if not dc._obs_ready:
-            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    _mixed_pools_ready(who, channels)
     table = (RolloutTraj * len(channels))()
     ios = []
     for k, (dc, (ex, ra)) in enumerate(zip(channels, checked)):
@@ -1977,19 +1958,11 @@ def rollout_steps_mixed(channels, explore, random_actions, storages, heads, capa
         ios.append(io)
     m = RolloutMixed(n_pools=len(channels), T=T, pools=table, model=None)
     if engine is not None:
-        buf = mixed_rollout_buffers(channels, T)
         m.model = engine._h
-        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx', 'q'):
-            setattr(m, name, buf[name].data_ptr())
-    for dc in channels:
-        dc._keep_actions = dc._t['actions']
+        _mixed_batch_pointers(m, channels, T)
     lib = channels[0]._lib
     _mixed_trajectory_call(lib.v2x_rollout_steps_mixed, lib.v2x_rollout_steps_mixed_wide, m, channels, T, walk)
-    out = []
-    for dc, io in zip(channels, ios):
-        dc._obs_ready = True
-        out.append(dc._download_result(io, T))
-    return out
+    return [dc._download_result(io, T) for dc, io in zip(channels, ios)]
 
 
 def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads, capacities, v2v_weight, v2i_weight, engine=None,
@@ -1999,11 +1972,8 @@ def resident_rollout_steps_mixed(envs, explore, random_actions, storages, heads,
     -> [RolloutResult] per environment, the downloads in flight."""
     who = "rollout_steps_mixed"
     check_walk(who, walk)
-    envs = list(envs)
     per_pool = dict(explore=explore, random_actions=random_actions, storages=storages, heads=heads, capacities=capacities)
-    for name, arg in per_pool.items():
-        if len(arg) != len(envs):
-            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
+    envs = _check_mixed_envs(who, envs, per_pool, streams_first=False)     # (each environment's _resident_before asks it)
     channels = [env._resident_before(who, lambda dc, k=k: dc.check_rollout_steps(explore[k], random_actions[k], storages[k], heads[k],
                                                                                  capacities[k]))
                 for k, env in enumerate(envs)]
@@ -2048,12 +2018,7 @@ def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
     channels, T, checked = _check_eval_mixed(who, channels, explore, policy_random, baseline_actions)
     if engine is not None and not (engine.spec.variable_graphs and engine.spec.n_channels == channels[0].rb):
         raise ValueError("%s: scoring needs a variable_graphs engine of %d channels" % (who, channels[0].rb))
-    for dc in channels:
-        dc._init_device()
-        if dc.device != channels[0].device:
-            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
-        if not dc._obs_ready:
-            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    _mixed_pools_ready(who, channels)
     baseline = checked[0][3] is not None
     table = (Eval * len(channels))()
     ios = []
@@ -2064,19 +2029,11 @@ def eval_steps_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
         ios.append(io)
     m = EvalMixed(n_pools=len(channels), T=T, pools=table, model=None)
     if engine is not None:
-        buf = mixed_rollout_buffers(channels, T)
         m.model = engine._h
-        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx', 'q'):
-            setattr(m, name, buf[name].data_ptr())
-    for dc in channels:
-        dc._keep_actions = dc._t['actions']
+        _mixed_batch_pointers(m, channels, T)
     lib = channels[0]._lib
     _mixed_trajectory_call(lib.v2x_eval_steps_mixed, lib.v2x_eval_steps_mixed_wide, m, channels, T, walk)
-    out = []
-    for dc, io in zip(channels, ios):
-        dc._obs_ready = True
-        out.append(dc._eval_download(io, T, 2 if baseline else 1))
-    return out
+    return [dc._eval_download(io, T, 2 if baseline else 1) for dc, io in zip(channels, ios)]
 
 
 def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None,
@@ -2087,14 +2044,7 @@ def resident_evaluate_steps_mixed(envs, explore, policy_random, baseline_actions
     -> [EvalResult] per environment, the downloads in flight."""
     who = "eval_steps_mixed"
     check_walk(who, walk)
-    envs = list(envs)
-    for name, arg in dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions).items():
-        if len(arg) != len(envs):
-            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
-    for env in envs:
-        if getattr(env, 'stream_backend', None) != 'device':
-            raise ValueError("%s needs streams='device' in every environment (mobility and the MT19937 streams advance inside the "
-                             "call)" % who)
+    envs = _check_mixed_envs(who, envs, dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions))
     _check_eval_mixed(who, [_PoolShape(env) for env in envs], explore, policy_random, baseline_actions)   # before any device work
     channels = [env._resident_before(who, lambda dc, k=k: dc.check_eval_steps(explore[k], policy_random[k], baseline_actions[k]))
                 for k, env in enumerate(envs)]
@@ -2115,8 +2065,9 @@ def mixed_sweep_q(channels, T, K):
     return q
 
 
-def _check_sweep_engines(who, engines, K, rb):
-    """what a sweep refuses of its networks, before any device work -> K"""
+def _check_sweep_engines(who, engines, K, rb, n=None):
+    """what a sweep refuses of its networks, before any device work -> K.  n None: variable_graphs engines of rb channels (the
+    mixed sweep); n given: fixed-size engines of n links and rb channels (the receiver-form sweep)"""
     if engines is None:
         K = 1 if K is None else int(K)
     else:
@@ -2127,8 +2078,11 @@ def _check_sweep_engines(who, engines, K, rb):
     if not 1 <= K <= SWEEP_MAX_MODELS:
         raise ValueError("%s: 1..%d networks, got %d" % (who, SWEEP_MAX_MODELS, K))
     for k, engine in enumerate(engines or ()):
-        if engine is None or not (engine.spec.variable_graphs and engine.spec.n_channels == rb):
+        spec = None if engine is None else engine.spec
+        if n is None and (spec is None or not (spec.variable_graphs and spec.n_channels == rb)):
             raise ValueError("%s: scoring needs variable_graphs engines of %d channels (engine %d)" % (who, rb, k))
+        if n is not None and (spec is None or spec.variable_graphs or spec.n_nodes != n or spec.n_channels != rb):
+            raise ValueError("%s: scoring needs fixed-size engines of %d links and %d channels (engine %d)" % (who, n, rb, k))
         if engine.spec != engines[0].spec:
             raise ValueError("%s: engine %d has another spec than engine 0: the networks of a sweep are checkpoints of one network"
                              % (who, k))
@@ -2148,12 +2102,7 @@ def eval_sweep_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
     check_walk(who, walk)
     channels, T, checked = _check_eval_mixed(who, channels, explore, policy_random, baseline_actions)
     K = _check_sweep_engines(who, engines, K, channels[0].rb)
-    for dc in channels:
-        dc._init_device()
-        if dc.device != channels[0].device:
-            raise ValueError("%s: the pools live on %s and %s" % (who, channels[0].device, dc.device))
-        if not dc._obs_ready:
-            raise RuntimeError("%s: no observe() since the last step() (pool of %d links)" % (who, dc.n))
+    _mixed_pools_ready(who, channels)
     baseline = checked[0][3] is not None
     S = K + (1 if baseline else 0)
     table = (Eval * len(channels))()
@@ -2168,31 +2117,13 @@ def eval_sweep_mixed(channels, explore, policy_random, baseline_actions, v2v_wei
         blocks.append(sw)
     m = EvalSweep(base=EvalMixed(n_pools=len(channels), T=T, pools=table, model=None), K=K, pad_=0, models=None, q=None)
     if engines is not None:
-        buf = mixed_rollout_buffers(channels, T)
-        for name in ('xe', 'graph_off', 'row_ptr', 'col_idx'):
-            setattr(m.base, name, buf[name].data_ptr())
+        _mixed_batch_pointers(m.base, channels, T, ('xe', 'graph_off', 'row_ptr', 'col_idx'))
         handles = (C.c_void_p * K)(*[engine._h for engine in engines])
         m.models = handles
         m.q = mixed_sweep_q(channels, T, K).data_ptr()
-    for dc in channels:
-        dc._keep_actions = dc._t['actions']
-    dc0 = channels[0]
-    ws = None
-    if walk == 'wide':
-        ws = (TrajWs * len(channels))()
-        for k, dc in enumerate(channels):
-            wide, split = dc._wide_workspace(T), dc._split_workspace(T)
-            ws[k] = TrajWs(wide.data_ptr(), wide.numel(), split.data_ptr(), split.numel())
-    check(dc0._lib, dc0._lib.v2x_eval_sweep_mixed(C.byref(m), ws, dc0._stream()))
-    out = []
-    for dc, sw in zip(channels, blocks):
-        dc.walk_calls[walk] += 1
-        dc._traj_form.pop(T, None)
-        if walk == 'wide':
-            dc.stream_phase_calls['split'] += 1
-        dc._obs_ready = True
-        out.append(dc._sweep_download(sw, T, S))
-    return out
+    sweep = channels[0]._lib.v2x_eval_sweep_mixed            # (one entry point: a null workspace table asks for the serial walk)
+    _mixed_trajectory_call(lambda s, stream: sweep(s, None, stream), sweep, m, channels, T, walk)
+    return [dc._sweep_download(sw, T, S) for dc, sw in zip(channels, blocks)]
 
 
 def resident_evaluate_sweep_mixed(envs, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None,
@@ -2203,14 +2134,7 @@ def resident_evaluate_sweep_mixed(envs, explore, policy_random, baseline_actions
     -> [EvalResult] per environment with K (+ 1) schemes, the downloads in flight."""
     who = "eval_sweep_mixed"
     check_walk(who, walk)
-    envs = list(envs)
-    for name, arg in dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions).items():
-        if len(arg) != len(envs):
-            raise ValueError("%s: one %s per environment expected, got %d for %d environments" % (who, name, len(arg), len(envs)))
-    for env in envs:
-        if getattr(env, 'stream_backend', None) != 'device':
-            raise ValueError("%s needs streams='device' in every environment (mobility and the MT19937 streams advance inside the "
-                             "call)" % who)
+    envs = _check_mixed_envs(who, envs, dict(explore=explore, policy_random=policy_random, baseline_actions=baseline_actions))
     _check_eval_mixed(who, [_PoolShape(env) for env in envs], explore, policy_random, baseline_actions)   # before any device work
     if envs:
         _check_sweep_engines(who, engines, K, envs[0].n_RB)
@@ -2655,29 +2579,39 @@ class DeviceBatchedEnviron(BatchedEnviron):
         """the bookkeeping every call that steps the resident state shares (rollout_step / rollout_steps / evaluate_steps):
         check_args(dc) raises ValueError before any device work of the call, call(dc) makes it -> its result object.  The two
         halves around the call are methods of their own for a call that steps several environments at once
-        (resident_rollout_steps_mixed): every environment's first half, the one call, every environment's second half."""
-        dc = self._resident_before(who, check_args, receiver_form)
-        return self._resident_after(call(dc))
+        (resident_rollout_steps_mixed): every environment's first half, the one call, every environment's second half.
+        In receiver form (rollout_steps_recv / evaluate_steps / evaluate_sweep) both get own_receivers() as their second
+        argument, as _resident_before took them."""
+        if receiver_form:
+            dc, own = self._resident_before(who, check_args, True)
+            return self._resident_after(call(dc, own))
+        return self._resident_after(call(self._resident_before(who, check_args)))
 
     def _resident_before(self, who, check_args, receiver_form=False):
         """_resident_call up to the library call: everything the device needs is on it, the arguments are checked, the
-        observation is resident (receiver_form: in receiver form, as rollout_steps_recv() brings it) -> the DeviceChannels"""
+        observation is resident (receiver_form: in receiver form, as rollout_steps_recv() brings it; the host's look at the
+        receivers, own_receivers(), is then taken before they go up and handed to check_args) -> the DeviceChannels; in receiver
+        form (the DeviceChannels, own)"""
         if self.stream_backend != 'device':
             raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
         self.finish_step()
         self._check_sizes()
         if any(s.gauss_next is not None for s in self.streams):
             raise RuntimeError("a stream holds a cached gauss value")
+        if receiver_form:
+            own = self.own_receivers()
         stale = bool(self._dirty)
         dc = self._flush()
-        check_args(dc)
         if receiver_form:
+            check_args(dc, own)
             if stale or not dc._recv_ready:
                 dc.observe_recv(self.dest)
-        elif stale or not dc._obs_ready:                       # (after a reset: the observation of the new channels, left on the device)
-            dc.observe(self.dest)
+        else:
+            check_args(dc)
+            if stale or not dc._obs_ready:                     # (after a reset: the observation of the new channels, left on the device)
+                dc.observe(self.dest)
         self._obs = None
-        return dc
+        return (dc, own) if receiver_form else dc
 
     def _resident_after(self, result):
         """_resident_call after the library call: who holds the newer copy of what -> result"""
@@ -2721,23 +2655,12 @@ class DeviceBatchedEnviron(BatchedEnviron):
         stream_phase: 'chain' or 'split', the form of the walk's stream phase (the same bits either way); stream_words: 'serial' or
         'jump', how a split stream phase draws its words (DeviceChannels.rollout_steps_recv; the same bits either way).
         -> the RecvRolloutResult of the block, its download in flight."""
-        who = 'rollout_steps_recv'
-        if self.stream_backend != 'device':
-            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
-        self.finish_step()
-        self._check_sizes()
-        if any(s.gauss_next is not None for s in self.streams):
-            raise RuntimeError("a stream holds a cached gauss value")
-        own = self.own_receivers()
-        stale = bool(self._dirty)
-        dc = self._flush()
-        dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase, stream_words)
-        if stale or not dc._recv_ready:
-            dc.observe_recv(self.dest)
-        self._obs = None
-        return self._resident_after(dc.rollout_steps_recv(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight,
-                                                          engine=engine, own=own, stream_phase=stream_phase,
-                                                          stream_words=stream_words))
+        return self._resident_call(
+            'rollout_steps_recv',
+            lambda dc, own: dc.check_rollout_steps_recv(explore, random_actions, storage, head, capacity, own, stream_phase, stream_words),
+            lambda dc, own: dc.rollout_steps_recv(explore, random_actions, storage, head, capacity, v2v_weight, v2i_weight,
+                                                  engine=engine, own=own, stream_phase=stream_phase, stream_words=stream_words),
+            receiver_form=True)
 
     def evaluate_steps(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=None, row_ptr=None,
                        walk='serial', stream_phase='chain', receiver_form=None, stream_words='serial'):
@@ -2777,22 +2700,11 @@ class DeviceBatchedEnviron(BatchedEnviron):
                              "got walk=%r" % (who, OBSERVE_MAX_LINKS, walk))
         if row_ptr is not None:
             raise ValueError("%s: the receiver form writes its own CSR (row_ptr must be None)" % who)
-        if self.stream_backend != 'device':
-            raise ValueError("%s needs streams='device' (mobility and the MT19937 streams advance inside the call)" % who)
-        self.finish_step()
-        self._check_sizes()
-        if any(s.gauss_next is not None for s in self.streams):
-            raise RuntimeError("a stream holds a cached gauss value")
-        own = self.own_receivers()
-        stale = bool(self._dirty)
-        dc = self._flush()
-        dc.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words)
-        if stale or not dc._recv_ready:
-            dc.observe_recv(self.dest)
-        self._obs = None
-        return self._resident_after(dc.eval_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight,
-                                                       engine=engine, own=own, stream_phase=stream_phase,
-                                                       stream_words=stream_words))
+        return self._resident_call(
+            who, lambda dc, own: dc.check_eval_steps_recv(explore, policy_random, baseline_actions, own, stream_phase, stream_words),
+            lambda dc, own: dc.eval_steps_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engine=engine, own=own,
+                                               stream_phase=stream_phase, stream_words=stream_words),
+            receiver_form=True)
 
     def evaluate_sweep(self, explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=None, K=None,
                        stream_phase='chain', stream_words='serial'):
@@ -2806,10 +2718,10 @@ class DeviceBatchedEnviron(BatchedEnviron):
             raise ValueError("%s serves the receiver form only (more than %d links, got %d): MixedAgent.evaluate_training scores the "
                              "checkpoints of a shared-weight network at 3..%d links" % (who, OBSERVE_MAX_LINKS, self.n_Veh,
                                                                                         OBSERVE_MAX_LINKS))
-        own = self.own_receivers()
         return self._resident_call(
-            who, lambda dc: dc.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase, stream_words),
-            lambda dc: dc.eval_sweep_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=engines, K=K,
+            who,
+            lambda dc, own: dc.check_eval_sweep_recv(explore, policy_random, baseline_actions, engines, K, own, stream_phase, stream_words),
+            lambda dc, own: dc.eval_sweep_recv(explore, policy_random, baseline_actions, v2v_weight, v2i_weight, engines=engines, K=K,
                                           own=own, stream_phase=stream_phase, stream_words=stream_words),
             receiver_form=True)
 
