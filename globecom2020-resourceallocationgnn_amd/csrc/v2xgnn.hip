@@ -103,7 +103,8 @@ struct v2x_model {
   int xchg_cap_tiles = 0;
   int* flag_host = nullptr;     // pinned, device-mapped word the kernels raise on a contract violation (tile guards,
   int* flag_dev = nullptr;      // k_validate_batch); read by the host after any synchronising call
-  bool have_fwd = false;
+  bool phase0_done = false;                     // phase 0 of v2x_forward_backward_phase left its activations and dz / gha for the later
+                                                // phases; every other call that runs a forward clears it
   std::string err;
   // profiling
   bool prof = false;
@@ -2210,7 +2211,7 @@ int v2x_forward(v2x_model* m, const v2x_batch* b, float* q_out, int q_on_device,
       hd.ci = reinterpret_cast<const int32_t*>(m->pin_d + PIN_CI);
       float* qd = reinterpret_cast<float*>(m->pin_d + PIN_Q);
       CHK(run_maybe_graph(m, st, make_key(8, hd, qd, 0), [&]() { return launch_small_forward(m, st, hd, qd); }));
-      m->have_fwd = false;
+      m->phase0_done = false;
       HIPCHK(m, hipStreamSynchronize(st));
       CHK(check_flag(m));
       memcpy(q_out, m->pin_h + PIN_Q, (size_t)hd.R * m->C * sizeof(float));
@@ -2225,7 +2226,7 @@ int v2x_forward(v2x_model* m, const v2x_batch* b, float* q_out, int q_on_device,
   const bool small = p.small_predict;
   if (small) CHK(run_maybe_graph(m, st, make_key(7, d, nullptr, 0), [&]() { return launch_small_forward(m, st, d); }));
   else CHK(run_maybe_graph(m, st, make_key(1, d, nullptr, 0), [&]() { return run_forward(m, st, d, p); }));
-  m->have_fwd = !small;
+  m->phase0_done = false;
   const size_t qb = (size_t)d.R * m->C * sizeof(float);
   if (q_on_device) {
     HIPCHK(m, hipMemcpyAsync(q_out, m->q, qb, hipMemcpyDeviceToDevice, st));
@@ -2269,7 +2270,7 @@ static int fwd_bwd(v2x_model* m, const v2x_batch* b, const float* y, int y_on_de
       return launch_reduce_adam(m, st, 1, false, nullptr, loss_job(m, d, n_global));
     }));
   }
-  m->have_fwd = true;
+  m->phase0_done = false;
   return emit_loss(m, loss_out, loss_on_device, st);
 }
 
@@ -2296,7 +2297,7 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
     // one weight-gradient launch per layer: phase 0 = forward, decision MLP backward, the Dense layers' gradients; phase k =
     // the data gradient handed down by stage s + 1 (not before: the all-reduce of the bucket a phase completes starts when the
     // phase's LAST launch is done), the transposed aggregation and the weight gradient of stage s = L + 1 - k
-    if (phase > 0 && !m->have_fwd) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase %d before phase 0", phase);
+    if (phase > 0 && !m->phase0_done) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase %d before phase 0", phase);
     BwdCall c;
     c.bucketed = c.phased = true;
     CHK(run_maybe_graph(m, st, make_key(20 + phase, d, yd, n_global), [&]() -> int {
@@ -2316,7 +2317,7 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
         return launch_reduce_adam(m, st, 1, false, nullptr, last ? loss_job(m, d, n_global) : LossJob{0, 0, 0, 0.f, 0}, -1, false, rb, re);
       return V2X_OK;
     }));
-    if (phase == 0) m->have_fwd = true;
+    if (phase == 0) m->phase0_done = true;
     return phase == n_phase_buckets(m) - 1 ? emit_loss(m, loss_out, loss_on_device, st) : V2X_OK;
   }
   BwdCall c;
@@ -2327,10 +2328,10 @@ int v2x_forward_backward_phase(v2x_model* m, const v2x_batch* b, const float* y,
       CHK(backward_mlp(m, st, d, p, c, yd, n_global));
       return launch_reduce_adam(m, st, 1, false, nullptr, LossJob{0, 0, 0, 0.f, 0}, 0);
     }));
-    m->have_fwd = true;
+    m->phase0_done = true;
     return V2X_OK;
   }
-  if (!m->have_fwd) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase 1 before phase 0");
+  if (!m->phase0_done) FAIL(m, V2X_ESTATE, "forward_backward_phase: phase 1 before phase 0");
   CHK(run_maybe_graph(m, st, make_key(6, d, yd, n_global), [&]() -> int {
     CHK(backward_graph_layers(m, st, d, p, c));
     return launch_reduce_adam(m, st, 1, false, nullptr, loss_job(m, d, n_global), 1);
@@ -2459,7 +2460,7 @@ static int dqn_step(v2x_model* online, v2x_model* target, const v2x_batch* s, co
     CHK(dp_dqn_collectives(online, comm, loss_out != nullptr, st));
     CHK(launch_reduce_adam(online, st, 0, true, nullptr));
   }
-  online->have_fwd = target->have_fwd = true;
+  online->phase0_done = target->phase0_done = false;
   return emit_loss(online, loss_out, loss_on_device, st);
 }
 

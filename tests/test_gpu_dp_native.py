@@ -44,7 +44,7 @@ def _case(name):
     from oracle import compact as oc
     from util import f32_params, random_inputs
     rng = np.random.default_rng(31)
-    if name == "ragged":
+    if name in ("ragged", "ragged_dev"):             # one draw; "ragged_dev" is moved to the device by _run_pair
         spec = GnnSpec(n_nodes=1, feat_dim=64, share_weights=True, variable_graphs=True)
         sizes = rng.integers(8, 41, size=48)
         offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
@@ -77,8 +77,9 @@ def _host(loss):
     return loss.cpu().numpy() if hasattr(loss, "cpu") else np.asarray(loss)
 
 
-def _run_pair(spec, P, pb, y, n_global, kw, comm, steps=3):
-    """the Python trainer and the native one, each on its own engine with the same weights: -> [(weights, losses, m, v, it)]"""
+def _run_pair(spec, P, pb, y, n_global, kw, comm, steps=3, on_device=None):
+    """the Python trainer and the native one, each on its own engine with the same weights: -> [(weights, losses, m, v, it)]
+    on_device: the batch and its targets are moved to the device first (default: every batch but a ragged one)"""
     import torch
     from v2xgnn import GnnEngine
     from v2xgnn.dp import DataParallelTrainer
@@ -88,7 +89,7 @@ def _run_pair(spec, P, pb, y, n_global, kw, comm, steps=3):
         eng.set_weights(P)
         tr = DataParallelTrainer(eng, force=True, native=native, comm=comm if native else None, **kw)
         sb, sy = tr.shard(pb, y)
-        if pb.graph_off is None:
+        if (pb.graph_off is None) if on_device is None else on_device:
             db, yd = eng.to_device(sb), torch.from_numpy(np.ascontiguousarray(sy)).cuda()
         else:
             db, yd = sb, sy          # the ragged batch stays on the host: the trainers' unphased forms
@@ -110,10 +111,10 @@ def _rccl_worker(rank, world, port, ret):
         comm = RcclComm()
         res = {}
         with torch.cuda.stream(torch.cuda.Stream()):
-            for name in ("b512", "b4096", "wide", "ragged"):
+            for name in ("b512", "b4096", "wide", "ragged", "ragged_dev"):
                 spec, P, pb, y, n_global = _case(name)
                 for form, kw in FORMS:
-                    res[(name, form)] = _run_pair(spec, P, pb, y, n_global, kw, comm)
+                    res[(name, form)] = _run_pair(spec, P, pb, y, n_global, kw, comm, on_device=(name != "ragged"))
         comm.close()
         ret[rank] = res
     finally:
@@ -122,14 +123,16 @@ def _rccl_worker(rank, world, port, ret):
 
 def test_world1_rccl_table_equals_python_trainer_bit_for_bit():
     """The library's RCCL table (one rank) against DataParallelTrainer(force=True) on the nccl backend: three steps of each
-    form at 512 and 4096 graphs, a wide model (one bucket per layer: L + 2 = 4) and a ragged batch (host-resident: the
-    forms without phases).  Weights, losses and Adam moments equal bit for bit.  (Models are made and freed one after the
+    form at 512 and 4096 graphs, a wide model (one bucket per layer: L + 2 = 4) and a ragged batch, host-resident
+    (the forms without phases) and device-resident (ragged_dev: both trainers run the phased ragged step in the forms
+    `buckets` and `sharded` -- the one-launch ragged forward with a layer-wise backward; against the oracle in
+    tests/test_gpu_phased_forms.py).  Weights, losses and Adam moments equal bit for bit.  (Models are made and freed one after the
     other in one process: v2x_create's zeroing must not land on the weights a side-stream set_weights writes next.)"""
     import torch.multiprocessing as mp
     ret = mp.Manager().dict()
     mp.spawn(_rccl_worker, args=(1, _port(), ret), nprocs=1, join=True)
     res = ret[0]
-    assert len(res) == 12
+    assert len(res) == 15
     for key, (py, nat) in res.items():
         assert np.all(np.isfinite(py[0])) and py[4] == nat[4] == 3, key
         for i, what in enumerate(("weights", "losses", "m", "v")):

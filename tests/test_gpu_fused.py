@@ -8,7 +8,7 @@ import pytest
 import v2xgnn
 from v2xgnn import GnnSpec, PackedBatch, GnnEngine
 from util import (ospec, random_inputs, fixed_indegree_adj, f32_params, assert_fwd_close, assert_grad_close, assert_close, oracle_step,
-                  assert_grads_match_oracle)
+                  assert_grads_match_oracle, _ragged_batch)
 from oracle import compact as oc
 
 pytestmark = pytest.mark.gpu
@@ -439,44 +439,6 @@ def test_two_phase_step_equals_single_call(N, F, B, use_graph, monkeypatch):
             one.apply_gradients()
             two.apply_gradients()
     assert np.allclose(one.get_flat(), two.get_flat(), rtol=1e-6, atol=1e-8)
-
-
-def _ragged_batch(rng, sizes, kind):
-    """kind: 'ref' = the reference topology (in-degree n - 2), 'mixed' = per graph one of: reference, half-dense random,
-    sparse random; a few rows of the larger graphs lose ALL their in-edges (isolated destinations); a float = every edge
-    p -> q (p == q included) present with that probability."""
-    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
-    R = int(offs[-1])
-    row_ptr, cols, max_e = [0], [], 0
-    for gi, n in enumerate(sizes):
-        mode = 0 if kind == 'ref' else gi % 3
-        if isinstance(kind, float):
-            adj = rng.uniform(size=(n, n)) < kind
-        elif mode == 0:
-            adj = ~np.eye(n, dtype=bool)
-            if n > 1:
-                dest = rng.integers(0, n - 1, size=n)
-                dest = dest + (dest >= np.arange(n))
-                adj[dest, np.arange(n)] = False
-        elif mode == 1:
-            adj = rng.uniform(size=(n, n)) < 0.55
-        else:
-            adj = rng.uniform(size=(n, n)) < 0.3
-        if kind == 'mixed' and n >= 20:
-            adj[:, rng.integers(0, n, size=2)] = False        # destinations with no in-neighbour at all
-            adj[rng.integers(0, n)] = False                   # a source nobody hears
-        e_g = 0
-        for q in range(n):
-            src = np.nonzero(adj[:, q])[0]
-            cols.append(src)
-            row_ptr.append(row_ptr[-1] + len(src))
-            e_g += len(src)
-        max_e = max(max_e, e_g)
-    col_idx = np.concatenate(cols).astype(np.int32) if row_ptr[-1] else np.zeros(0, np.int32)
-    x = np.concatenate([rng.normal(0.84, 0.39, size=(R, 4)), rng.normal(0.6, 0.21, size=(R, 4)), np.full((R, 1), 10.0)], 1).astype(np.float32)
-    e = rng.normal(0.88, 0.11, size=(R, 4)).astype(np.float32)
-    return PackedBatch(len(sizes), 0, v2xgnn.pack_xe(x, e), np.array(row_ptr, np.int32), col_idx, max_e, graph_off=offs,
-                       max_nodes=int(max(sizes))), x, e, offs
 
 
 RAGGED = [  # feat_dim, layers, topology, sizes

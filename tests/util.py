@@ -6,6 +6,8 @@ import numpy as np
 
 from oracle.spec import GnnSpec as OSpec
 from oracle import compact as oc
+import v2xgnn
+from v2xgnn import PackedBatch
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
@@ -43,6 +45,44 @@ def fixed_indegree_adj(rng, B, N, degree):
             others = np.delete(np.arange(N), q)
             adj[b, rng.choice(others, size=min(degree, N - 1), replace=False), q] = 1.0
     return adj
+
+
+def _ragged_batch(rng, sizes, kind):
+    """kind: 'ref' = the reference topology (in-degree n - 2), 'mixed' = per graph one of: reference, half-dense random,
+    sparse random; a few rows of the larger graphs lose ALL their in-edges (isolated destinations); a float = every edge
+    p -> q (p == q included) present with that probability."""
+    offs = np.concatenate([[0], np.cumsum(sizes)]).astype(np.int32)
+    R = int(offs[-1])
+    row_ptr, cols, max_e = [0], [], 0
+    for gi, n in enumerate(sizes):
+        mode = 0 if kind == 'ref' else gi % 3
+        if isinstance(kind, float):
+            adj = rng.uniform(size=(n, n)) < kind
+        elif mode == 0:
+            adj = ~np.eye(n, dtype=bool)
+            if n > 1:
+                dest = rng.integers(0, n - 1, size=n)
+                dest = dest + (dest >= np.arange(n))
+                adj[dest, np.arange(n)] = False
+        elif mode == 1:
+            adj = rng.uniform(size=(n, n)) < 0.55
+        else:
+            adj = rng.uniform(size=(n, n)) < 0.3
+        if kind == 'mixed' and n >= 20:
+            adj[:, rng.integers(0, n, size=2)] = False        # destinations with no in-neighbour at all
+            adj[rng.integers(0, n)] = False                   # a source nobody hears
+        e_g = 0
+        for q in range(n):
+            src = np.nonzero(adj[:, q])[0]
+            cols.append(src)
+            row_ptr.append(row_ptr[-1] + len(src))
+            e_g += len(src)
+        max_e = max(max_e, e_g)
+    col_idx = np.concatenate(cols).astype(np.int32) if row_ptr[-1] else np.zeros(0, np.int32)
+    x = np.concatenate([rng.normal(0.84, 0.39, size=(R, 4)), rng.normal(0.6, 0.21, size=(R, 4)), np.full((R, 1), 10.0)], 1).astype(np.float32)
+    e = rng.normal(0.88, 0.11, size=(R, 4)).astype(np.float32)
+    return PackedBatch(len(sizes), 0, v2xgnn.pack_xe(x, e), np.array(row_ptr, np.int32), col_idx, max_e, graph_off=offs,
+                       max_nodes=int(max(sizes))), x, e, offs
 
 
 def f32_params(spec, rng, random_bias=True):
